@@ -7,6 +7,8 @@
                                              launcher whose WORLD_SIZE differs from --gpus)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...      (the driver's form)
     python bench.py --dist-fft L [--gpus N] (ONE transform of 2^L points over the ranks, every stage timed: SURVEY 8 f-3)
+    python bench.py ... --dump-outputs DIR  (after the timed steps: what the last one computed, DIR/<name>.npy, for comparing
+                                             two builds output for output)
 
 Metric (BASELINE.json): GSamples/s of the f64 forward planar FFT at N=2^20 and 2^26 (and % of the HBM roofline),
 complex samples transformed per second over the whole job, inputs resident in HBM when the timed region starts.
@@ -15,7 +17,9 @@ complex samples transformed per second over the whole job, inputs resident in HB
     `fft_64_dit_with_planner` (the _dev entry point of the C ABI) on one 16 MiB transform.  Every step uses a fresh
     buffer of a pre-filled ring (values never overflow; the ring, > 512 MiB, defeats the 256 MiB Infinity Cache);
     the K steps are captured once into a HIP graph and replayed inside the timed region so that the host launch
-    path (Python + ctypes) is not what is measured.
+    path (Python + ctypes) is not what is measured.  A --steps beyond RING_MAX buffers cycles through the ring (at most
+    RING_REUSE_MAX transforms of one buffer per region); more than GRAPH_STEPS steps are captured as several graphs of at
+    most GRAPH_STEPS steps each, replayed in order.
     After the timed region four buffers of that ring are compared, every bin, with the CPU oracle's fft_64_dit of the
     same seeded inputs (`config.result_check`; the oracle is the checker, never the thing measured).
     `config.results` (round 5: the driver's record keeps the top-level keys and `config`) holds the WHOLE metric in
@@ -61,6 +65,10 @@ N = 1 << LOG_N
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 BYTES_PER_SAMPLE = 32          # planar C2C f64 = 4 * sizeof(f64) per complex sample
 SHARD = 1024                   # transforms per GPU in the multi-GPU workload (configs[4])
+RING_MAX = 4096                # buffers of the headline's ring at most (16 MiB each, 64 GiB): a long --steps cycles through it
+RING_REUSE_MAX = 90            # transforms of one buffer per timed region at most: values grow 2^10-fold per in-place transform
+                               # (f64 overflows near 100; 13 measured: max 3.9e39 = 2.9 x 2^130)
+GRAPH_STEPS = 200              # steps per captured HIP graph at most: a longer --steps is captured into several (GraphChain)
 
 
 def parse():
@@ -84,6 +92,10 @@ def parse():
     ap.add_argument("--sharded", action="store_true",
                     help="run the N > 1 code path (process group, sharded batch, digest gather) even with WORLD_SIZE=1: on "
                          "a one-GPU box this is what puts RCCL init and the device collectives on real hardware")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64; the "
+                         "whole 2^20 transform for --gpus 1, a fixed seeded sample of rank 0's shard for N > 1): two builds "
+                         "run with the same arguments can be compared output for output")
     return ap.parse_args()
 
 
@@ -316,11 +328,24 @@ def event_ms(torch, fn):
     return e0.elapsed_time(e1)
 
 
+class GraphChain:
+    """Captured graphs replayed back to back on the current stream: K steps as graphs of at most GRAPH_STEPS steps each
+    (`--steps 50000` captured as one graph, 150000 chained kernel nodes, ended the process with a segmentation fault on the
+    host; 200 steps per graph is the default K of every earlier run)."""
+
+    def __init__(self, graphs):
+        self.graphs = graphs
+
+    def replay(self):
+        for g in self.graphs:
+            g.replay()
+
+
 def capture_steps(torch, P, step, first: int, steps: int, touch=None):
-    """The K timed steps step(first) .. step(first + K - 1) captured into one HIP graph, instantiated and UPLOADED
-    (hipGraphUpload), so that the replay inside the timed region is the launch of a resident executable graph: the
-    Python + ctypes launch path is not the product, and neither is the one-time upload of the graph.  Returns
-    (graph or None, description)."""
+    """The K timed steps step(first) .. step(first + K - 1) captured into one HIP graph (K > GRAPH_STEPS: a GraphChain of
+    several), instantiated and UPLOADED (hipGraphUpload), so that the replay inside the timed region is the launch of a
+    resident executable graph: the Python + ctypes launch path is not the product, and neither is the one-time upload of the
+    graph.  Returns (graph or None, description)."""
     try:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -329,13 +354,16 @@ def capture_steps(torch, P, step, first: int, steps: int, touch=None):
                 touch()  # first use of the planner on the side stream happens outside the capture
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            for i in range(steps):
-                step(first + i)
+        graphs = []
+        for c0 in range(0, steps, GRAPH_STEPS):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for i in range(c0, min(steps, c0 + GRAPH_STEPS)):
+                    step(first + i)
+            graphs.append(g)
         uploaded = False
         try:
-            uploaded = P.graph_upload(g)
+            uploaded = all([P.graph_upload(g) for g in graphs])
         except Exception as e:  # the upload is an optimisation of the first launch only
             print(f"note: hipGraphUpload unavailable ({e})", file=sys.stderr)
         # ... and replayed once, untimed: the first launch of an executable graph still pays one-time work that the
@@ -343,10 +371,13 @@ def capture_steps(torch, P, step, first: int, steps: int, touch=None):
         # cold, 27.0 uploaded, 25.9 after one replay; K = 200: 24.3 / 24.3 / 23.2).  The ring is larger than the Infinity
         # Cache, so the timed replay finds every buffer as cold as the first one did; values grow by <= 2^10 per
         # transform, far from overflow.
-        g.replay()
+        for g in graphs:
+            g.replay()
         torch.cuda.synchronize()
-        return g, ("hipGraph replay of the K steps (graph " + ("uploaded and " if uploaded else "") +
-                   "replayed once, untimed, before the timed region)")
+        chain = f" in {len(graphs)} graphs of <= {GRAPH_STEPS} steps" if len(graphs) > 1 else ""
+        return (graphs[0] if len(graphs) == 1 else GraphChain(graphs)), (
+            f"hipGraph replay of the K steps{chain} (graph " + ("uploaded and " if uploaded else "") +
+            "replayed once, untimed, before the timed region)")
     except Exception as e:  # capture is an optimisation of the launch path only
         print(f"note: HIP graph capture unavailable ({e}); launching eagerly", file=sys.stderr)
         torch.cuda.synchronize()
@@ -728,6 +759,29 @@ def check_headline(P, torch, views, planner, ids, already: int):
             "what": "ring buffers of the timed workload, every bin, against the CPU oracle's fft_64_dit of the same seeded input"}
 
 
+DUMP_SAMPLE = 1 << 21   # elements per array of a sampled dump: 2 x 16 MiB of float64, inside the 64 MB a dump may hold
+
+
+def dump_sample_index(size: int, count: int = DUMP_SAMPLE, seed: int = 0xD0):
+    """Sorted distinct indices into an array of `size` elements: every element when it is small enough, else a fixed seeded
+    sample -- the same indices in every run with the same arguments."""
+    import numpy as np
+
+    if size <= count:
+        return np.arange(size, dtype=np.int64)
+    return np.unique(np.random.default_rng(seed).integers(0, size, count, dtype=np.int64))
+
+
+def dump_outputs(dirname: str, arrays: dict):
+    """--dump-outputs: every device tensor of `arrays` as dirname/<name>.npy (float32 stays float32, the rest float64)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
+
+
 def fail(msg: str, rc: int = 2):
     """bench.py never prints a number for a job other than the one it was asked to measure: refuse, loudly, rc != 0"""
     print(f"bench.py: error: {msg}", file=sys.stderr, flush=True)
@@ -856,6 +910,8 @@ def dist_fft_mode(args, P, torch, dev, rank, world):
 
 def main():
     args = parse()
+    if args.dist_fft and args.dump_outputs:
+        fail("--dump-outputs covers the batch workloads; --dist-fft has no dump")
     # the host driver of this pool only supports dmabuf IPC: without this RCCL / device-tensor sharing across the ranks
     # fails with `hipIpcGetMemHandle: invalid argument` (already exported on the boxes; kept here for any other launcher)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -923,7 +979,13 @@ def main():
     if not multi:
         steps = args.steps if args.steps is not None else 200
         warmup = args.warmup if args.warmup is not None else 20
-        ring = max(steps + warmup, 40)  # >= 640 MiB of distinct transforms; no buffer is transformed twice
+        # >= 640 MiB of distinct transforms; no buffer is transformed twice -- unless the K steps outnumber RING_MAX buffers: a
+        # --steps chosen from ms_per_step for a long timed region must not run the card out of memory, so the steps cycle
+        # through the ring (every buffer still HBM-cold when its turn comes: the ring is far larger than the Infinity Cache)
+        ring = max(min(steps + warmup, RING_MAX), 40)
+        if -(-steps // ring) > RING_REUSE_MAX:
+            fail(f"--steps {steps} would transform a buffer of the {ring}-buffer ring {-(-steps // ring)} times in one region "
+                 f"(at most {RING_REUSE_MAX}: the values would overflow)")
         re = torch.empty(ring * N, dtype=torch.float64, device=dev)
         im = torch.empty_like(re)
         P.fill_uniform(re, im, N, seed=0xCAFE, first_id=0)
@@ -963,6 +1025,9 @@ def main():
         torch.cuda.synchronize()
         elapsed_wall = time.perf_counter() - t0
         elapsed = ev0.elapsed_time(ev1) * 1e-3
+        if args.dump_outputs:   # the last timed step's buffer of the ring, as its caller holds it -- before the regions below re-fill it
+            r, m = views[(warmup + steps - 1) % ring]
+            dump_outputs(args.dump_outputs, {"n2p20_forward_re": r, "n2p20_forward_im": m})
         # SURVEY.md 8(d) "median and min": two more K-step regions after the contract's one (ring re-filled before each: the
         # steps work in place), reported beside ms_per_step, never instead of it
         head_stats = replay_stats(torch, graph.replay if graph is not None else (lambda: [step(warmup + i) for i in range(steps)]),
@@ -1036,6 +1101,10 @@ def main():
         dist.barrier()
         torch.cuda.synchronize()
         mine = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:   # a fixed seeded sample of rank 0's shard after the last timed step (16 GiB at --shard 1024)
+            idx = torch.from_numpy(dump_sample_index(re.numel())).to(dev)
+            dump_outputs(args.dump_outputs, {"shard_forward_re_sample": re[idx], "shard_forward_im_sample": im[idx]})
+            del idx
         elapsed = max_over_ranks(mine, dist, dev)
         rank_s = times_over_ranks(mine, dist, dev)   # every rank's own time: what makes a bad N-GPU point readable
         elapsed_wall = elapsed

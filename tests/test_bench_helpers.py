@@ -63,6 +63,60 @@ def test_roofline_arithmetic():
     assert abs(roof["frac_transform"] - 33554432 / 0.026e-3 / 1e9 / 8000.0) < 1e-9 and roof["passes"] == 3
 
 
+def test_dump_outputs_sample_and_files(tmp_path):
+    """--dump-outputs: the sample of a large output is the same in every run and inside the array; small outputs go whole;
+    the files are float64 / float32 .npy under the names given."""
+    import numpy as np
+    import torch
+
+    a, b = bench.dump_sample_index(1 << 30), bench.dump_sample_index(1 << 30)
+    assert np.array_equal(a, b) and 0 < len(a) <= bench.DUMP_SAMPLE and a[0] >= 0 and a[-1] < 1 << 30
+    assert np.all(np.diff(a) > 0)
+    assert np.array_equal(bench.dump_sample_index(1000), np.arange(1000))
+    assert 2 * bench.DUMP_SAMPLE * 8 <= 64 << 20   # two float64 samples stay inside a dump's 64 MB
+    x = torch.arange(8, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "d"), {"re": x, "im": x.float()})
+    re, im = np.load(tmp_path / "d" / "re.npy"), np.load(tmp_path / "d" / "im.npy")
+    assert re.dtype == np.float64 and im.dtype == np.float32 and np.array_equal(re, np.arange(8)) and np.array_equal(im, re)
+
+
+def test_long_capture_is_split_into_graphs_replayed_in_order():
+    """capture_steps: K <= GRAPH_STEPS stays ONE graph; a longer K becomes graphs of at most GRAPH_STEPS steps whose replay
+    runs exactly step(first) .. step(first + K - 1), in order (torch's graph API stood in for: no GPU here)."""
+    import contextlib
+    import types
+
+    ran, capturing = [], []
+
+    class Graph:
+        def __init__(self):
+            self.steps = []
+
+        def replay(self):
+            ran.extend(self.steps)
+
+    @contextlib.contextmanager
+    def graph(g):
+        capturing.append(g)
+        yield
+        capturing.pop()
+
+    stream = types.SimpleNamespace(wait_stream=lambda s: None)
+    cuda = types.SimpleNamespace(Stream=lambda: stream, current_stream=lambda: stream, stream=lambda s: contextlib.nullcontext(),
+                                 synchronize=lambda: None, CUDAGraph=Graph, graph=graph)
+    fake_torch, fake_P = types.SimpleNamespace(cuda=cuda), types.SimpleNamespace(graph_upload=lambda g: True)
+    step = lambda i: capturing[-1].steps.append(i)
+    k = 2 * bench.GRAPH_STEPS + 50
+    g, launch = bench.capture_steps(fake_torch, fake_P, step, 7, k)
+    assert isinstance(g, bench.GraphChain) and len(g.graphs) == 3 and max(len(x.steps) for x in g.graphs) <= bench.GRAPH_STEPS
+    assert ran == list(range(7, 7 + k)) and "3 graphs" in launch   # the untimed replay of capture_steps
+    ran.clear()
+    g.replay()
+    assert ran == list(range(7, 7 + k))
+    g, launch = bench.capture_steps(fake_torch, fake_P, step, 3, 20)
+    assert isinstance(g, Graph) and g.steps == list(range(3, 23)) and "graphs" not in launch
+
+
 # ---------------------------------------------------------------- round 4: `bench.py --gpus N` cannot mis-measure
 def _run_bench(argv, env_extra=None, drop=("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE")):
     import subprocess
