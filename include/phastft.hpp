@@ -15,6 +15,7 @@
 //   fft_*_interleaved[_with_planner[_and_opts]]     lib.rs:50,87,120 (feature complex-nums)
 //   bit_rev_bravo_f64/f32                           bravo.rs:303,317 (feature bench-internals)
 //   deinterleave[_complex64/32], combine_re_im      complex_nums.rs:11,25,37,47 (feature bench-internals)
+//   (none: powers of two only upstream)                      class PlannerAny64/32, fft_64/32_any[_with_planner] -- any N >= 1
 //
 // A Rust `&mut [T]` is a (pointer, length) pair here -- `Slice<T>` converts from std::vector / std::array /
 // raw pointer + length.  Where the reference panics (`assert!`), these functions throw `phastft::Panic` whose
@@ -287,6 +288,48 @@ inline void c2r_fft_f64(Slice<const double> input_re, Slice<const double> input_
 }
 inline void c2r_fft_f32(Slice<const float> input_re, Slice<const float> input_im, Slice<float> output) {
     check(phast_c2r_fft_f32(input_re.ptr, input_re.len, input_im.ptr, input_im.len, output.ptr, output.len));
+}
+
+// ---- complex transforms of any length N >= 1 (Bluestein; no reference counterpart: upstream takes powers of two only) ----
+#define PHASTFT_PLANNER_ANY(NAME, CT, SFX)                                                                       \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        explicit NAME(std::size_t n) { check(phast_planner_any##SFX##_new(n, &h_)); }                            \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }                                                   \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_any##SFX##_free(h_);                                                           \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_any##SFX##_describe(h_, &s[0], s.size()));                                       \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_any##SFX##_device_bytes(h_); }                   \
+        /* elements of T a _dev call of `batch` transforms works in (0 for a power of two) */                    \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_any##SFX##_workspace_len(h_, batch); } \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+    };
+PHASTFT_PLANNER_ANY(PlannerAny64, phast_planner_any64, 64)
+PHASTFT_PLANNER_ANY(PlannerAny32, phast_planner_any32, 32)
+#undef PHASTFT_PLANNER_ANY
+
+inline void fft_64_any_with_planner(Slice<double> reals, Slice<double> imags, Direction direction, const PlannerAny64 &planner) {
+    check(phast_fft_64_any_with_planner(reals.ptr, reals.len, imags.ptr, imags.len, static_cast<int>(direction), planner.get()));
+}
+inline void fft_32_any_with_planner(Slice<float> reals, Slice<float> imags, Direction direction, const PlannerAny32 &planner) {
+    check(phast_fft_32_any_with_planner(reals.ptr, reals.len, imags.ptr, imags.len, static_cast<int>(direction), planner.get()));
+}
+inline void fft_64_any(Slice<double> reals, Slice<double> imags, Direction direction) {
+    check(phast_fft_64_any(reals.ptr, reals.len, imags.ptr, imags.len, static_cast<int>(direction)));
+}
+inline void fft_32_any(Slice<float> reals, Slice<float> imags, Direction direction) {
+    check(phast_fft_32_any(reals.ptr, reals.len, imags.ptr, imags.len, static_cast<int>(direction)));
 }
 
 }  // namespace phastft

@@ -240,6 +240,48 @@ int phast_fft_64_interleaved_dev(double *d_signal, size_t n, size_t batch, size_
 int phast_fft_32_interleaved_dev(float *d_signal, size_t n, size_t batch, size_t dist, int direction,
                                  const phast_planner_dit32 *planner, void *stream);
 
+/* ---- complex transforms of ANY length N >= 1 (no reference counterpart: the reference takes powers of two only; its README
+ * names other lengths as its first planned feature).  Bluestein's algorithm: the length-N DFT as a cyclic convolution of
+ * M = 2^ceil(log2(2N - 1)) points on the power-of-two engine ("Arbitrary lengths").  N <= 2^29 for both types
+ * (N = 0 or more: PHAST_ERR_INVALID_ARG).  A power-of-two N calls the phast_fft_*_dit path itself: same bits, no workspace.
+ * Forward is unnormalised, the inverse scales by 1/N, as above.  A planner belongs to the device current at creation and
+ * is immutable after _new (its table is ready on any stream); share it between threads and streams freely.
+ *
+ * _dev calls take a caller-provided device workspace of work_len elements of T: phast_planner_any*_workspace_len(p, batch)
+ * = 2 M batch (0 for a power of two).  Any work_len >= 2 M is legal: the batch then runs in chunks of floor(work_len / 2M)
+ * transforms.  The planner holds no per-call state, so graph capture and concurrent streams are safe as long as no two
+ * calls in flight share a workspace.  The bits of a transform do not depend on the batch, the chunking or the form of the
+ * call.  Host-slice calls stage through the device (they block). */
+typedef struct phast_planner_any64 phast_planner_any64; /* PlannerAny64 */
+typedef struct phast_planner_any32 phast_planner_any32; /* PlannerAny32 */
+int phast_planner_any64_new(size_t n, phast_planner_any64 **out);
+int phast_planner_any32_new(size_t n, phast_planner_any32 **out);
+void phast_planner_any64_free(phast_planner_any64 *p);
+void phast_planner_any32_free(phast_planner_any32 *p);
+int phast_planner_any64_describe(const phast_planner_any64 *p, char *buf, size_t buf_len);
+int phast_planner_any32_describe(const phast_planner_any32 *p, char *buf, size_t buf_len);
+size_t phast_planner_any64_device_bytes(const phast_planner_any64 *p);
+size_t phast_planner_any32_device_bytes(const phast_planner_any32 *p);
+size_t phast_planner_any64_workspace_len(const phast_planner_any64 *p, size_t batch);
+size_t phast_planner_any32_workspace_len(const phast_planner_any32 *p, size_t batch);
+int phast_fft_64_any(double *reals, size_t reals_len, double *imags, size_t imags_len, int direction);
+int phast_fft_32_any(float *reals, size_t reals_len, float *imags, size_t imags_len, int direction);
+int phast_fft_64_any_with_planner(double *reals, size_t reals_len, double *imags, size_t imags_len, int direction,
+                                  const phast_planner_any64 *planner);
+int phast_fft_32_any_with_planner(float *reals, size_t reals_len, float *imags, size_t imags_len, int direction,
+                                  const phast_planner_any32 *planner);
+int phast_fft_64_any_dev(double *d_reals, double *d_imags, size_t n, size_t batch, size_t dist, int direction,
+                         const phast_planner_any64 *planner, double *d_work, size_t work_len, void *stream);
+int phast_fft_32_any_dev(float *d_reals, float *d_imags, size_t n, size_t batch, size_t dist, int direction,
+                         const phast_planner_any32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/any_len_rate.py): stage_ms[5] = average milliseconds of the chirp-pad sweep, the forward M-point
+ * engine call, the spectrum sweep, the inverse engine call and the chirp-post sweep over `reps` forward calls of the batch
+ * in ONE chunk (work_len >= 2 M batch); not for powers of two.  Blocks until done. */
+int phast_planner_any64_time_stages(const phast_planner_any64 *p, double *d_reals, double *d_imags, size_t batch, size_t dist,
+                                    double *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+int phast_planner_any32_time_stages(const phast_planner_any32 *p, float *d_reals, float *d_imags, size_t batch, size_t dist,
+                                    float *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+
 /* ---- bit reversal: algorithms/bravo.rs:303,317 (public with feature bench-internals, lib.rs:20-23) ---- */
 int phast_bit_rev_f64(double *data, size_t len, unsigned log_n); /* host slice */
 int phast_bit_rev_f32(float *data, size_t len, unsigned log_n);

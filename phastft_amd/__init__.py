@@ -17,6 +17,7 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
     bit_rev_bravo_f32/f64             bravo.rs:303   bit_rev_bravo_f32/f64(data, n)
     deinterleave[_complex64/32]       complex_nums.rs:11   deinterleave(data) -> (a, b)
     combine_re_im                     complex_nums.rs:47   combine_re_im(reals, imags) -> Complex<T> array
+    (none: powers of two only)                      PlannerAny64/32, fft_64/32_any[_with_planner], fft_any_batched
     ==============================================  ==========================================
 
 Slices are 1-D contiguous arrays: ``numpy.ndarray`` (host slices -- staged through device memory, the
@@ -50,6 +51,8 @@ __all__ = [
     "fft_64_interleaved_with_planner_and_opts", "fft_32_interleaved_with_planner_and_opts",
     "bit_rev_bravo_f64", "bit_rev_bravo_f32", "deinterleave", "deinterleave_complex64", "deinterleave_complex32", "combine_re_im", "fft_dit_batched", "r2c_fft_batched", "c2r_fft_batched", "fill_uniform", "digest", "device_info",
     "TwiddleGrid64", "TwiddleGrid32",
+    "PlannerAny64", "PlannerAny32", "fft_64_any", "fft_32_any", "fft_64_any_with_planner", "fft_32_any_with_planner",
+    "fft_any_batched",
 ]
 
 
@@ -533,6 +536,142 @@ def fft_dit_batched(reals, imags, n: int, direction: Direction, planner, dist: i
     batch = (re.len - n) // dist + 1
     _check(getattr(_lib.lib(), f"phast_fft_{sfx}_dit_dev")(re.ptr, im.ptr, C.c_size_t(n), C.c_size_t(batch),
                                                            C.c_size_t(dist), C.c_int(int(direction)), planner._h,
+                                                           _stream()))
+
+
+
+# ---------------------------------------------------------------------------------------------
+# any length N >= 1 (Bluestein on the power-of-two engine; no reference counterpart -- the reference takes powers of two only)
+# ---------------------------------------------------------------------------------------------
+class _PlannerAny:
+    _sfx = "64"
+    _dtype = np.float64
+
+    def __init__(self, n: int):
+        self._h = C.c_void_p()
+        _check(getattr(_lib.lib(), f"phast_planner_any{self._sfx}_new")(C.c_size_t(n), C.byref(self._h)))
+        self.n = n
+        # the convolution length: the smallest power of two >= 2N - 1 (N itself for a power of two)
+        self.m = n if n & (n - 1) == 0 else 1 << (2 * n - 2).bit_length()
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None and self._h.value and _lib is not None and _lib._lib is not None:
+                getattr(_lib._lib, f"phast_planner_any{self._sfx}_free")(self._h)
+                self._h.value = None
+        except Exception:  # interpreter shutdown: modules may already be gone
+            pass
+
+    def describe(self) -> str:
+        buf = C.create_string_buffer(16384)
+        _check(getattr(_lib.lib(), f"phast_planner_any{self._sfx}_describe")(self._h, buf, C.c_size_t(16384)))
+        return buf.value.decode()
+
+    def device_bytes(self) -> int:
+        return int(getattr(_lib.lib(), f"phast_planner_any{self._sfx}_device_bytes")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` transforms works in: 2 M batch (0 for a power of two).  A smaller
+        workspace of at least 2 M runs the batch in chunks."""
+        return int(getattr(_lib.lib(), f"phast_planner_any{self._sfx}_workspace_len")(self._h, C.c_size_t(batch)))
+
+    def time_stages(self, reals, imags, batch: int = 1, dist: int | None = None, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of the five stages of a forward call on device tensors -- chirp-pad sweep, forward
+        M-point transform, spectrum sweep, inverse M-point transform, chirp-post sweep (measurement hook)."""
+        re, im = _Slice(reals, self._dtype, "reals"), _Slice(imags, self._dtype, "imags")
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 5)()
+        _check(getattr(_lib.lib(), f"phast_planner_any{self._sfx}_time_stages")(
+            self._h, re.ptr, im.ptr, C.c_size_t(batch), C.c_size_t(self.n if dist is None else dist), ws.ptr,
+            C.c_size_t(ws.len), C.c_int(reps), ms, _stream()))
+        return [float(x) for x in ms]
+
+
+class PlannerAny64(_PlannerAny):
+    """f64 transforms of any length 1 <= N <= 2^29"""
+
+
+class PlannerAny32(_PlannerAny):
+    """f32 transforms of any length 1 <= N <= 2^29 (the table is built in f64 and rounded)"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def _any_workspace(planner, batch: int, workspace=None) -> _Slice:
+    """the caller's device workspace, or one from torch's allocator on the current stream (stream-ordered: free to reuse
+    once the call's work is done)"""
+    if workspace is None:
+        import torch
+
+        workspace = torch.empty(max(1, planner.workspace_len(batch)),
+                                dtype=torch.float64 if planner._dtype == np.float64 else torch.float32, device="cuda")
+    ws = _Slice(workspace, planner._dtype, "workspace")
+    if not ws.dev:
+        raise TypeError("workspace: need a device tensor")
+    return ws
+
+
+def _fft_any(sfx, dtype, reals, imags, direction, planner=None):
+    re, im = _Slice(reals, dtype, "reals"), _Slice(imags, dtype, "imags")
+    l = _lib.lib()
+    direction = C.c_int(int(direction))
+    if _same_place(re, im):
+        if re.len != im.len:
+            _check(2)
+        own = planner is None
+        if own:
+            planner = (PlannerAny64 if sfx == "64" else PlannerAny32)(re.len)
+        ws = _any_workspace(planner, 1)
+        _check(getattr(l, f"phast_fft_{sfx}_any_dev")(re.ptr, im.ptr, C.c_size_t(re.len), C.c_size_t(1), C.c_size_t(re.len),
+                                                      direction, planner._h, ws.ptr, C.c_size_t(ws.len), _stream()))
+        if own:
+            import torch
+
+            torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+        return
+    args = [re.ptr, C.c_size_t(re.len), im.ptr, C.c_size_t(im.len), direction]
+    if planner is None:
+        _check(getattr(l, f"phast_fft_{sfx}_any")(*args))
+    else:
+        _check(getattr(l, f"phast_fft_{sfx}_any_with_planner")(*args, planner._h))
+
+
+def fft_64_any(reals, imags, direction: Direction) -> None:
+    """In-place f64 DFT of any length N = len(reals) (Reverse scales by 1/N), as fft_64_dit for powers of two"""
+    _fft_any("64", np.float64, reals, imags, direction)
+
+
+def fft_32_any(reals, imags, direction: Direction) -> None:
+    """f32 twin of :func:`fft_64_any`"""
+    _fft_any("32", np.float32, reals, imags, direction)
+
+
+def fft_64_any_with_planner(reals, imags, direction: Direction, planner: PlannerAny64) -> None:
+    _fft_any("64", np.float64, reals, imags, direction, planner)
+
+
+def fft_32_any_with_planner(reals, imags, direction: Direction, planner: PlannerAny32) -> None:
+    _fft_any("32", np.float32, reals, imags, direction, planner)
+
+
+def fft_any_batched(reals, imags, n: int, direction: Direction, planner, dist: int | None = None, workspace=None) -> None:
+    """Device-resident batch of any-length transforms: transform b at ``[b*dist, b*dist + n)`` (``dist`` defaults to ``n``).
+    ``workspace``: a device tensor of the planner's type, at least ``planner.workspace_len(1)`` elements (fewer than
+    ``planner.workspace_len(batch)`` runs the batch in chunks); by default one from torch's allocator."""
+    dtype, sfx = planner._dtype, planner._sfx
+    re, im = _Slice(reals, dtype, "reals"), _Slice(imags, dtype, "imags")
+    if not _same_place(re, im):
+        raise TypeError("fft_any_batched needs device tensors")
+    if re.len != im.len:
+        _check(2)
+    dist = n if dist is None else dist
+    if n == 0 or dist < n or re.len < n or (re.len - n) % dist:
+        raise ValueError("length must be (batch-1)*dist + n")
+    batch = (re.len - n) // dist + 1
+    ws = _any_workspace(planner, batch, workspace)
+    _check(getattr(_lib.lib(), f"phast_fft_{sfx}_any_dev")(re.ptr, im.ptr, C.c_size_t(n), C.c_size_t(batch), C.c_size_t(dist),
+                                                           C.c_int(int(direction)), planner._h, ws.ptr, C.c_size_t(ws.len),
                                                            _stream()))
 
 

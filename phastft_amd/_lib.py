@@ -46,6 +46,10 @@ phast_planner_dit64_tune phast_planner_dit32_tune phast_planner_r2c64_tune phast
 phast_planner_r2c64_with_mode phast_planner_r2c32_with_mode
 phast_wisdom_export phast_wisdom_import phast_wisdom_forget phast_wisdom_builtin phast_wisdom_count phast_debug_throw
 phast_planner_dit64_describe_call phast_planner_dit32_describe_call phast_planner_r2c64_describe_call phast_planner_r2c32_describe_call
+phast_planner_any64_new phast_planner_any32_new phast_planner_any64_free phast_planner_any32_free
+phast_planner_any64_describe phast_planner_any32_describe phast_planner_any64_device_bytes phast_planner_any32_device_bytes
+phast_planner_any64_workspace_len phast_planner_any32_workspace_len phast_planner_any64_time_stages phast_planner_any32_time_stages
+phast_fft_64_any phast_fft_32_any phast_fft_64_any_with_planner phast_fft_32_any_with_planner phast_fft_64_any_dev phast_fft_32_any_dev
 """.split()
 
 
@@ -105,5 +109,8 @@ def lib() -> C.CDLL:
         getattr(l, f"phast_planner_dit{sfx}_free").restype = None
         getattr(l, f"phast_planner_r2c{sfx}_free").restype = None
         getattr(l, f"phast_twiddle_grid{sfx}_free").restype = None
+        getattr(l, f"phast_planner_any{sfx}_free").restype = None
+        getattr(l, f"phast_planner_any{sfx}_device_bytes").restype = C.c_size_t
+        getattr(l, f"phast_planner_any{sfx}_workspace_len").restype = C.c_size_t
     _lib = l
     return l

@@ -14,6 +14,7 @@
 #include "entry.hpp"
 #include "host_api.hpp"
 #include "tune.hpp"
+#include "planner_any.hpp"
 
 // ================================================================================================
 // C ABI
@@ -24,6 +25,8 @@ struct phast_planner_dit64 : Planner<double> {};
 struct phast_planner_dit32 : Planner<float> {};
 struct phast_planner_r2c64 : PlannerR2c<double> {};
 struct phast_planner_r2c32 : PlannerR2c<float> {};
+struct phast_planner_any64 : AnyPlanner<double> {};
+struct phast_planner_any32 : AnyPlanner<float> {};
 
 // W_N^(r*c) tables of a four-step split (twiddle.hip)
 template <typename T> struct TwiddleGrid {
@@ -476,5 +479,52 @@ PHAST_FFT_API(32, f32, float)
     } PHAST_CATCH_RC
 PHAST_TWIDDLE_API(64, double)
 PHAST_TWIDDLE_API(32, float)
+
+// Arbitrary lengths (Bluestein, planner_any.hpp): arguments are checked before the device is touched
+#define PHAST_ANY_API(SFX, T)                                                                                           \
+    int phast_planner_any##SFX##_new(size_t n, phast_planner_any##SFX **out) try {                                      \
+        return any_planner_new(n, out);                                                                                 \
+    } PHAST_CATCH_RC                                                                                                    \
+    void phast_planner_any##SFX##_free(phast_planner_any##SFX *p) try { delete p; } PHAST_CATCH_VOID                    \
+    int phast_planner_any##SFX##_describe(const phast_planner_any##SFX *p, char *buf, size_t len) try {                 \
+        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
+        std::snprintf(buf, len, "%s", p->describe().c_str());                                                          \
+        return PHAST_OK;                                                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_any##SFX##_device_bytes(const phast_planner_any##SFX *p) try {                                 \
+        return p ? p->device_bytes() : 0;                                                                               \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_any##SFX##_workspace_len(const phast_planner_any##SFX *p, size_t batch) try {                  \
+        return p ? p->workspace_len(batch) : 0;                                                                         \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_any##SFX##_time_stages(const phast_planner_any##SFX *p, T *d_re, T *d_im, size_t batch,           \
+                                             size_t dist, T *d_work, size_t work_len, int reps, float *stage_ms,        \
+                                             void *stream) try {                                                        \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(d_re, d_im, batch, dist, d_work, work_len, reps, stage_ms,                                \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_fft_##SFX##_any(T *re, size_t re_len, T *im, size_t im_len, int direction) try {                          \
+        if ((!re && re_len) || (!im && im_len)) return PHAST_ERR_INVALID_ARG;                                           \
+        if (direction != PHAST_FORWARD && direction != PHAST_REVERSE) return PHAST_ERR_INVALID_ARG;                     \
+        if (re_len != im_len) return PHAST_ERR_LEN_MISMATCH;                                                            \
+        std::shared_ptr<AnyPlanner<T>> pl; /* the planner from reals.len(), kept as fft_*_dit keeps its own */          \
+        int rc = PlannerCache<AnyPlanner<T>>::instance().get(                                                           \
+            re_len, sizeof(T), [](size_t m, AnyPlanner<T> **o) { return any_planner_new(m, o); }, &pl);                 \
+        if (rc) return rc;                                                                                              \
+        return pl->fft_host_any(re, re_len, im, im_len, direction);                                                     \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_fft_##SFX##_any_with_planner(T *re, size_t re_len, T *im, size_t im_len, int direction,                   \
+                                           const phast_planner_any##SFX *p) try {                                       \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->fft_host_any(re, re_len, im, im_len, direction);                                                      \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_fft_##SFX##_any_dev(T *d_re, T *d_im, size_t n, size_t batch, size_t dist, int direction,                 \
+                                  const phast_planner_any##SFX *p, T *d_work, size_t work_len, void *stream) try {      \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->fft_dev_any(d_re, d_im, n, batch, dist, direction, d_work, work_len, static_cast<hipStream_t>(stream)); \
+    } PHAST_CATCH_RC
+PHAST_ANY_API(64, double)
+PHAST_ANY_API(32, float)
 
 }  // extern "C"

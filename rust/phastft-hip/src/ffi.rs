@@ -76,6 +76,21 @@ extern "C" {
         planner: *const Opaque, opts: *const PhastOptions) -> c_int;
     pub(crate) fn phast_fft_32_interleaved_with_planner_and_opts(signal: *mut f32, n: usize, direction: c_int,
         planner: *const Opaque, opts: *const PhastOptions) -> c_int;
+    // any length (an extension beyond PhastFT 0.3.0: planner_any.rs / lib.rs)
+    pub(crate) fn phast_planner_any64_new(n: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_any32_new(n: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_any64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_any32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_any64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_any32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_fft_64_any_with_planner(re: *mut f64, re_len: usize, im: *mut f64, im_len: usize,
+        direction: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_fft_32_any_with_planner(re: *mut f32, re_len: usize, im: *mut f32, im_len: usize,
+        direction: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_fft_64_any_dev(re: *mut f64, im: *mut f64, n: usize, batch: usize, dist: usize,
+        direction: c_int, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_fft_32_any_dev(re: *mut f32, im: *mut f32, n: usize, batch: usize, dist: usize,
+        direction: c_int, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
 }
 
 /// Re-raises a library status as the reference's panic: `phast_strerror` returns the exact text of the

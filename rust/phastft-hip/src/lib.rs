@@ -39,7 +39,7 @@ pub use algorithms::r2c::{
 };
 
 use crate::options::Options;
-use crate::planner::{Direction, PlannerDit32, PlannerDit64};
+use crate::planner::{Direction, PlannerAny32, PlannerAny64, PlannerDit32, PlannerDit64};
 use std::ffi::{c_int, c_void};
 
 macro_rules! impl_fft {
@@ -70,6 +70,33 @@ pub unsafe fn fft_32_dit_dev(d_reals: *mut f32, d_imags: *mut f32, n: usize, bat
                              direction: Direction, planner: &PlannerDit32, stream: *mut c_void) {
     ffi::check(ffi::phast_fft_32_dit_dev(d_reals, d_imags, n, batch, dist, direction as c_int, planner.h, stream));
 }
+
+/// Complex transforms of ANY length N >= 1 -- an extension beyond PhastFT 0.3.0, which takes powers of two only (its README
+/// lists other lengths as planned).  Same calling convention as `fft_64_dit`: planar slices, in place, `Reverse` scales by
+/// 1/N, panics carry the library's message (`reals.len() != imags.len()`, a planner of another length, N = 0 or > 2^29).
+macro_rules! impl_fft_any {
+    ($t:ty, $planner:ident, $with_planner:ident, $plain:ident, $c_fn:ident, $dev:ident, $c_dev:ident) => {
+        pub fn $with_planner(reals: &mut [$t], imags: &mut [$t], direction: Direction, planner: &$planner) {
+            ffi::check(unsafe {
+                ffi::$c_fn(reals.as_mut_ptr(), reals.len(), imags.as_mut_ptr(), imags.len(), direction as c_int, planner.h)
+            });
+        }
+        pub fn $plain(reals: &mut [$t], imags: &mut [$t], direction: Direction) {
+            let planner = <$planner>::new(reals.len());
+            $with_planner(reals, imags, direction, &planner);
+        }
+        /// Device-resident, batched, asynchronous on `stream`: `d_work` is a device workspace of `work_len >= 2 M` elements
+        /// (`planner.workspace_len(batch)` runs the batch in one chunk; unused for a power of two)
+        pub unsafe fn $dev(d_reals: *mut $t, d_imags: *mut $t, n: usize, batch: usize, dist: usize, direction: Direction,
+                           planner: &$planner, d_work: *mut $t, work_len: usize, stream: *mut c_void) {
+            ffi::check(ffi::$c_dev(d_reals, d_imags, n, batch, dist, direction as c_int, planner.h, d_work, work_len, stream));
+        }
+    };
+}
+impl_fft_any!(f64, PlannerAny64, fft_64_any_with_planner, fft_64_any, phast_fft_64_any_with_planner, fft_64_any_dev,
+              phast_fft_64_any_dev);
+impl_fft_any!(f32, PlannerAny32, fft_32_any_with_planner, fft_32_any, phast_fft_32_any_with_planner, fft_32_any_dev,
+              phast_fft_32_any_dev);
 
 /// Interleaved `Complex<T>` signals (reference: feature `complex-nums`, lib.rs:41-140).  The reference copies into
 /// two planar Vecs, runs the planar path and copies back; the library fuses the (de)interleave into the first

@@ -123,3 +123,41 @@ macro_rules! impl_planner_r2c {
 }
 impl_planner_r2c!(PlannerR2c64, phast_planner_r2c64_with_mode, phast_planner_r2c64_free, phast_planner_r2c64_tune);
 impl_planner_r2c!(PlannerR2c32, phast_planner_r2c32_with_mode, phast_planner_r2c32_free, phast_planner_r2c32_tune);
+
+macro_rules! impl_planner_any {
+    ($any:ident, $new:ident, $free:ident, $ws_len:ident) => {
+        /// An extension beyond PhastFT 0.3.0, whose planners take powers of two only: complex transforms of any length
+        /// 1 <= N <= 2^29 (Bluestein's algorithm on the power-of-two engine; a power of two runs the `PlannerDit*` path
+        /// itself).  Immutable after `new`, like the reference's planners.
+        pub struct $any {
+            pub(crate) h: *mut Opaque,
+            pub(crate) n: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in a
+        // workspace of the library's own pool (host-slice calls)
+        unsafe impl Send for $any {}
+        unsafe impl Sync for $any {}
+        impl $any {
+            /// panics with "invalid argument" for N = 0 or N > 2^29
+            pub fn new(n: usize) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe { ffi::$new(n, &mut h) });
+                Self { h, n }
+            }
+            pub fn num_points(&self) -> usize {
+                self.n
+            }
+            /// elements of the workspace a device call of `batch` transforms works in (0 for a power of two)
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+        }
+        impl Drop for $any {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_any!(PlannerAny64, phast_planner_any64_new, phast_planner_any64_free, phast_planner_any64_workspace_len);
+impl_planner_any!(PlannerAny32, phast_planner_any32_new, phast_planner_any32_free, phast_planner_any32_workspace_len);
