@@ -16,6 +16,8 @@
 //   bit_rev_bravo_f64/f32                           bravo.rs:303,317 (feature bench-internals)
 //   deinterleave[_complex64/32], combine_re_im      complex_nums.rs:11,25,37,47 (feature bench-internals)
 //   (none: powers of two only upstream)                      class PlannerAny64/32, fft_64/32_any[_with_planner] -- any N >= 1
+//   (none: r2c.rs takes powers of two >= 4)                  class PlannerR2cAny64/32, r2c_fft_f64/f32_any[_with_planner],
+//                                                            c2r_fft_f64/f32_any[_with_planner] -- any N >= 1
 //
 // A Rust `&mut [T]` is a (pointer, length) pair here -- `Slice<T>` converts from std::vector / std::array /
 // raw pointer + length.  Where the reference panics (`assert!`), these functions throw `phastft::Panic` whose
@@ -330,6 +332,70 @@ inline void fft_64_any(Slice<double> reals, Slice<double> imags, Direction direc
 }
 inline void fft_32_any(Slice<float> reals, Slice<float> imags, Direction direction) {
     check(phast_fft_32_any(reals.ptr, reals.len, imags.ptr, imags.len, static_cast<int>(direction)));
+}
+
+// ---- real transforms of any length N >= 1 (no reference counterpart: r2c.rs takes powers of two >= 4) ----
+#define PHASTFT_PLANNER_R2C_ANY(NAME, CT, SFX)                                                                   \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        explicit NAME(std::size_t n) { check(phast_planner_r2c_any##SFX##_new(n, &h_)); }                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }                                                   \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_r2c_any##SFX##_free(h_);                                                       \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_r2c_any##SFX##_describe(h_, &s[0], s.size()));                                   \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_r2c_any##SFX##_device_bytes(h_); }               \
+        /* elements of T a _dev call of `batch` transforms works in (0 for a power of two, N = 1, 2) */          \
+        std::size_t workspace_len(std::size_t batch = 1) const {                                                 \
+            return phast_planner_r2c_any##SFX##_workspace_len(h_, batch);                                        \
+        }                                                                                                        \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+    };
+PHASTFT_PLANNER_R2C_ANY(PlannerR2cAny64, phast_planner_r2c_any64, 64)
+PHASTFT_PLANNER_R2C_ANY(PlannerR2cAny32, phast_planner_r2c_any32, 32)
+#undef PHASTFT_PLANNER_R2C_ANY
+
+inline void r2c_fft_f64_any_with_planner(Slice<const double> input, Slice<double> output_re, Slice<double> output_im,
+                                         const PlannerR2cAny64 &planner) {
+    check(phast_r2c_fft_f64_any_with_planner(input.ptr, input.len, output_re.ptr, output_re.len, output_im.ptr, output_im.len,
+                                             planner.get()));
+}
+inline void r2c_fft_f32_any_with_planner(Slice<const float> input, Slice<float> output_re, Slice<float> output_im,
+                                         const PlannerR2cAny32 &planner) {
+    check(phast_r2c_fft_f32_any_with_planner(input.ptr, input.len, output_re.ptr, output_re.len, output_im.ptr, output_im.len,
+                                             planner.get()));
+}
+inline void r2c_fft_f64_any(Slice<const double> input, Slice<double> output_re, Slice<double> output_im) {
+    check(phast_r2c_fft_f64_any(input.ptr, input.len, output_re.ptr, output_re.len, output_im.ptr, output_im.len));
+}
+inline void r2c_fft_f32_any(Slice<const float> input, Slice<float> output_re, Slice<float> output_im) {
+    check(phast_r2c_fft_f32_any(input.ptr, input.len, output_re.ptr, output_re.len, output_im.ptr, output_im.len));
+}
+inline void c2r_fft_f64_any_with_planner(Slice<const double> input_re, Slice<const double> input_im, Slice<double> output,
+                                         const PlannerR2cAny64 &planner) {
+    check(phast_c2r_fft_f64_any_with_planner(input_re.ptr, input_re.len, input_im.ptr, input_im.len, output.ptr, output.len,
+                                             planner.get()));
+}
+inline void c2r_fft_f32_any_with_planner(Slice<const float> input_re, Slice<const float> input_im, Slice<float> output,
+                                         const PlannerR2cAny32 &planner) {
+    check(phast_c2r_fft_f32_any_with_planner(input_re.ptr, input_re.len, input_im.ptr, input_im.len, output.ptr, output.len,
+                                             planner.get()));
+}
+inline void c2r_fft_f64_any(Slice<const double> input_re, Slice<const double> input_im, Slice<double> output) {
+    check(phast_c2r_fft_f64_any(input_re.ptr, input_re.len, input_im.ptr, input_im.len, output.ptr, output.len));
+}
+inline void c2r_fft_f32_any(Slice<const float> input_re, Slice<const float> input_im, Slice<float> output) {
+    check(phast_c2r_fft_f32_any(input_re.ptr, input_re.len, input_im.ptr, input_im.len, output.ptr, output.len));
 }
 
 }  // namespace phastft

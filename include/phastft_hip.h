@@ -282,6 +282,86 @@ int phast_planner_any64_time_stages(const phast_planner_any64 *p, double *d_real
 int phast_planner_any32_time_stages(const phast_planner_any32 *p, float *d_reals, float *d_imags, size_t batch, size_t dist,
                                     float *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
 
+/* ---- real transforms (R2C / C2R) of ANY length N >= 1 (no reference counterpart: r2c.rs takes powers of two >= 4).  NumPy
+ * rfft / irfft semantics with this library's conventions: R2C writes the half spectrum X[k], k = 0 .. floor(N/2), to two
+ * planes of floor(N/2) + 1 points (unnormalised; Im X[0] = 0 exactly, and Im X[N/2] = 0 exactly for even N); C2R reads them
+ * and writes the real signal of N points, scaled by 1/N (for a Hermitian spectrum, irfft(X, N)).  The length codes 5-10 of
+ * the power-of-two calls apply, with floor(N/2).  N <= 2^29 for both types (N = 0 or more: PHAST_ERR_INVALID_ARG, before the
+ * device is touched).  Algorithms: a power of two N >= 4 calls phast_r2c_fft_*_dev / phast_c2r_fft_*_dev
+ * itself (same bits, no workspace); an even N packs x[2n] + i x[2n+1] into an N/2-point Bluestein transform (the
+ * phast_planner_any* engine, table and spectrum sweep) and untangles -- C2R runs the power-of-two path's preprocess formula,
+ * so a non-Hermitian input gives what that formula gives; an odd N runs an N-point Bluestein transform on real data (C2R:
+ * Im X[0] is ignored, as irfft ignores it); N = 1 and 2 are direct (C2R: the imaginary parts are ignored).  R2C never writes
+ * its input, C2R never its input planes.
+ *
+ * _dev calls: asynchronous on `stream`; `batch` transforms, the real side `in_dist` (R2C) / `out_dist` (C2R) >= N elements
+ * apart, the complex side >= floor(N/2) + 1 apart; pointers need element alignment only.  One limit: a power of two N >= 4
+ * runs phast_r2c_fft_*_dev / phast_c2r_fft_*_dev, which read and write the real side as (even, odd) pairs, so there a batch
+ * needs an EVEN real-side distance (R2C in_dist, C2R out_dist); an odd one is PHAST_ERR_INVALID_ARG.  The caller's device workspace holds
+ * phast_planner_r2c_any*_workspace_len(p, batch) = 2 M batch elements of T (M: the inner convolution length; 0 for N a
+ * power of two, 1 or 2); any work_len >= 2 M runs the batch in chunks.  A null pointer, a short dist or a null / short
+ * workspace is PHAST_ERR_INVALID_ARG; an `n` that is not the planner's, PHAST_ERR_PLANNER_SIZE.  The planner is immutable
+ * and holds no per-call state (graph capture, threads and streams as for phast_planner_any*), and the bits of a transform
+ * do not depend on the batch, the chunking, the stream or the form of the call.  Host-slice calls stage through the device
+ * (they block). */
+typedef struct phast_planner_r2c_any64 phast_planner_r2c_any64; /* PlannerR2cAny64 */
+typedef struct phast_planner_r2c_any32 phast_planner_r2c_any32; /* PlannerR2cAny32 */
+int phast_planner_r2c_any64_new(size_t n, phast_planner_r2c_any64 **out);
+int phast_planner_r2c_any32_new(size_t n, phast_planner_r2c_any32 **out);
+void phast_planner_r2c_any64_free(phast_planner_r2c_any64 *p);
+void phast_planner_r2c_any32_free(phast_planner_r2c_any32 *p);
+int phast_planner_r2c_any64_describe(const phast_planner_r2c_any64 *p, char *buf, size_t buf_len);
+int phast_planner_r2c_any32_describe(const phast_planner_r2c_any32 *p, char *buf, size_t buf_len);
+size_t phast_planner_r2c_any64_device_bytes(const phast_planner_r2c_any64 *p);
+size_t phast_planner_r2c_any32_device_bytes(const phast_planner_r2c_any32 *p);
+size_t phast_planner_r2c_any64_workspace_len(const phast_planner_r2c_any64 *p, size_t batch);
+size_t phast_planner_r2c_any32_workspace_len(const phast_planner_r2c_any32 *p, size_t batch);
+int phast_r2c_fft_f64_any(const double *input, size_t input_len, double *output_re, size_t output_re_len, double *output_im,
+                          size_t output_im_len);
+int phast_r2c_fft_f32_any(const float *input, size_t input_len, float *output_re, size_t output_re_len, float *output_im,
+                          size_t output_im_len);
+int phast_r2c_fft_f64_any_with_planner(const double *input, size_t input_len, double *output_re, size_t output_re_len,
+                                       double *output_im, size_t output_im_len, const phast_planner_r2c_any64 *planner);
+int phast_r2c_fft_f32_any_with_planner(const float *input, size_t input_len, float *output_re, size_t output_re_len,
+                                       float *output_im, size_t output_im_len, const phast_planner_r2c_any32 *planner);
+int phast_r2c_fft_f64_any_dev(const double *d_input, double *d_output_re, double *d_output_im, size_t n, size_t batch,
+                              size_t in_dist, size_t out_dist, const phast_planner_r2c_any64 *planner, double *d_work,
+                              size_t work_len, void *stream);
+int phast_r2c_fft_f32_any_dev(const float *d_input, float *d_output_re, float *d_output_im, size_t n, size_t batch,
+                              size_t in_dist, size_t out_dist, const phast_planner_r2c_any32 *planner, float *d_work,
+                              size_t work_len, void *stream);
+int phast_c2r_fft_f64_any(const double *input_re, size_t input_re_len, const double *input_im, size_t input_im_len,
+                          double *output, size_t output_len);
+int phast_c2r_fft_f32_any(const float *input_re, size_t input_re_len, const float *input_im, size_t input_im_len,
+                          float *output, size_t output_len);
+int phast_c2r_fft_f64_any_with_planner(const double *input_re, size_t input_re_len, const double *input_im,
+                                       size_t input_im_len, double *output, size_t output_len,
+                                       const phast_planner_r2c_any64 *planner);
+int phast_c2r_fft_f32_any_with_planner(const float *input_re, size_t input_re_len, const float *input_im,
+                                       size_t input_im_len, float *output, size_t output_len,
+                                       const phast_planner_r2c_any32 *planner);
+int phast_c2r_fft_f64_any_dev(const double *d_input_re, const double *d_input_im, double *d_output, size_t n, size_t batch,
+                              size_t in_dist, size_t out_dist, const phast_planner_r2c_any64 *planner, double *d_work,
+                              size_t work_len, void *stream);
+int phast_c2r_fft_f32_any_dev(const float *d_input_re, const float *d_input_im, float *d_output, size_t n, size_t batch,
+                              size_t in_dist, size_t out_dist, const phast_planner_r2c_any32 *planner, float *d_work,
+                              size_t work_len, void *stream);
+/* measurement hooks (tools/any_real_rate.py): stage_ms[5] = average milliseconds of the pad sweep, the forward M-point engine
+ * call, the spectrum sweep, the inverse engine call and the post sweep over `reps` calls of the batch at the natural
+ * distances in ONE chunk (work_len >= 2 M batch); not for N a power of two, 1 or 2.  Block until done. */
+int phast_planner_r2c_any64_time_stages(const phast_planner_r2c_any64 *p, const double *d_input, double *d_output_re,
+                                        double *d_output_im, size_t batch, double *d_work, size_t work_len, int reps,
+                                        float *stage_ms, void *stream);
+int phast_planner_r2c_any32_time_stages(const phast_planner_r2c_any32 *p, const float *d_input, float *d_output_re,
+                                        float *d_output_im, size_t batch, float *d_work, size_t work_len, int reps,
+                                        float *stage_ms, void *stream);
+int phast_planner_r2c_any64_time_c2r_stages(const phast_planner_r2c_any64 *p, const double *d_input_re,
+                                            const double *d_input_im, double *d_output, size_t batch, double *d_work,
+                                            size_t work_len, int reps, float *stage_ms, void *stream);
+int phast_planner_r2c_any32_time_c2r_stages(const phast_planner_r2c_any32 *p, const float *d_input_re,
+                                            const float *d_input_im, float *d_output, size_t batch, float *d_work,
+                                            size_t work_len, int reps, float *stage_ms, void *stream);
+
 /* ---- bit reversal: algorithms/bravo.rs:303,317 (public with feature bench-internals, lib.rs:20-23) ---- */
 int phast_bit_rev_f64(double *data, size_t len, unsigned log_n); /* host slice */
 int phast_bit_rev_f32(float *data, size_t len, unsigned log_n);

@@ -18,6 +18,8 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
     deinterleave[_complex64/32]       complex_nums.rs:11   deinterleave(data) -> (a, b)
     combine_re_im                     complex_nums.rs:47   combine_re_im(reals, imags) -> Complex<T> array
     (none: powers of two only)                      PlannerAny64/32, fft_64/32_any[_with_planner], fft_any_batched
+    (none: r2c.rs takes powers of two >= 4)         PlannerR2cAny64/32, r2c_fft_f64/f32_any[_with_planner],
+                                                    c2r_fft_f64/f32_any[_with_planner], r2c_any_batched, c2r_any_batched
     ==============================================  ==========================================
 
 Slices are 1-D contiguous arrays: ``numpy.ndarray`` (host slices -- staged through device memory, the
@@ -53,6 +55,9 @@ __all__ = [
     "TwiddleGrid64", "TwiddleGrid32",
     "PlannerAny64", "PlannerAny32", "fft_64_any", "fft_32_any", "fft_64_any_with_planner", "fft_32_any_with_planner",
     "fft_any_batched",
+    "PlannerR2cAny64", "PlannerR2cAny32", "r2c_fft_f64_any", "r2c_fft_f32_any", "r2c_fft_f64_any_with_planner",
+    "r2c_fft_f32_any_with_planner", "c2r_fft_f64_any", "c2r_fft_f32_any", "c2r_fft_f64_any_with_planner",
+    "c2r_fft_f32_any_with_planner", "r2c_any_batched", "c2r_any_batched",
 ]
 
 
@@ -673,6 +678,215 @@ def fft_any_batched(reals, imags, n: int, direction: Direction, planner, dist: i
     _check(getattr(_lib.lib(), f"phast_fft_{sfx}_any_dev")(re.ptr, im.ptr, C.c_size_t(n), C.c_size_t(batch), C.c_size_t(dist),
                                                            C.c_int(int(direction)), planner._h, ws.ptr, C.c_size_t(ws.len),
                                                            _stream()))
+
+
+# ---------------------------------------------------------------------------------------------
+# real transforms of any length N >= 1 (no reference counterpart: r2c.rs takes powers of two >= 4)
+# ---------------------------------------------------------------------------------------------
+class _PlannerR2cAny:
+    _sfx = "64"
+    _dtype = np.float64
+
+    def __init__(self, n: int):
+        self._h = C.c_void_p()
+        _check(getattr(_lib.lib(), f"phast_planner_r2c_any{self._sfx}_new")(C.c_size_t(n), C.byref(self._h)))
+        self.n = n
+        self.half = n // 2
+        self.m = self.workspace_len(1) // 2  # the inner convolution length (0: a power of two >= 4, N = 1, 2)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None and self._h.value and _lib is not None and _lib._lib is not None:
+                getattr(_lib._lib, f"phast_planner_r2c_any{self._sfx}_free")(self._h)
+                self._h.value = None
+        except Exception:  # interpreter shutdown: modules may already be gone
+            pass
+
+    def describe(self) -> str:
+        buf = C.create_string_buffer(16384)
+        _check(getattr(_lib.lib(), f"phast_planner_r2c_any{self._sfx}_describe")(self._h, buf, C.c_size_t(16384)))
+        return buf.value.decode()
+
+    def device_bytes(self) -> int:
+        return int(getattr(_lib.lib(), f"phast_planner_r2c_any{self._sfx}_device_bytes")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` transforms works in: 2 M batch (0 for a power of two, N = 1 or 2).  A
+        smaller workspace of at least 2 M runs the batch in chunks."""
+        return int(getattr(_lib.lib(), f"phast_planner_r2c_any{self._sfx}_workspace_len")(self._h, C.c_size_t(batch)))
+
+    def time_stages(self, input_re, output_re, output_im, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of the five stages of an R2C call on device tensors -- pad sweep, forward M-point
+        transform, spectrum sweep, inverse M-point transform, post sweep (measurement hook)"""
+        i, ore, oim = (_Slice(x, self._dtype, w) for x, w in ((input_re, "input_re"), (output_re, "output_re"),
+                                                               (output_im, "output_im")))
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 5)()
+        _check(getattr(_lib.lib(), f"phast_planner_r2c_any{self._sfx}_time_stages")(
+            self._h, i.ptr, ore.ptr, oim.ptr, C.c_size_t(batch), ws.ptr, C.c_size_t(ws.len), C.c_int(reps), ms, _stream()))
+        return [float(x) for x in ms]
+
+    def time_c2r_stages(self, input_re, input_im, output, batch: int = 1, workspace=None, reps: int = 10):
+        """:meth:`time_stages` of a C2R call"""
+        ire, iim, out = (_Slice(x, self._dtype, w) for x, w in ((input_re, "input_re"), (input_im, "input_im"),
+                                                                 (output, "output")))
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 5)()
+        _check(getattr(_lib.lib(), f"phast_planner_r2c_any{self._sfx}_time_c2r_stages")(
+            self._h, ire.ptr, iim.ptr, out.ptr, C.c_size_t(batch), ws.ptr, C.c_size_t(ws.len), C.c_int(reps), ms, _stream()))
+        return [float(x) for x in ms]
+
+
+class PlannerR2cAny64(_PlannerR2cAny):
+    """f64 real transforms (R2C / C2R) of any length 1 <= N <= 2^29"""
+
+
+class PlannerR2cAny32(_PlannerR2cAny):
+    """f32 real transforms (R2C / C2R) of any length 1 <= N <= 2^29"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def _r2c_any(fs, dtype, input_re, output_re, output_im, planner=None):
+    i, ore, oim = _Slice(input_re, dtype, "input_re"), _Slice(output_re, dtype, "output_re"), _Slice(
+        output_im, dtype, "output_im")
+    l, sfx = _lib.lib(), fs[1:]
+    if _same_place(i, ore, oim):
+        own = planner is None
+        if own:
+            planner = (PlannerR2cAny64 if fs == "f64" else PlannerR2cAny32)(i.len)
+        n, half = planner.n, planner.n // 2
+        for code, got, want in ((5, i.len, n), (6, ore.len, half + 1), (7, oim.len, half + 1)):
+            if got != want:
+                _check(code)
+        ws = _any_workspace(planner, 1)
+        _check(getattr(l, f"phast_r2c_fft_{fs}_any_dev")(i.ptr, ore.ptr, oim.ptr, C.c_size_t(n), C.c_size_t(1), C.c_size_t(n),
+                                                         C.c_size_t(half + 1), planner._h, ws.ptr, C.c_size_t(ws.len),
+                                                         _stream()))
+        if own:
+            import torch
+
+            torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+        return
+    args = [i.ptr, C.c_size_t(i.len), ore.ptr, C.c_size_t(ore.len), oim.ptr, C.c_size_t(oim.len)]
+    if planner is None:
+        _check(getattr(l, f"phast_r2c_fft_{fs}_any")(*args))
+    else:
+        _check(getattr(l, f"phast_r2c_fft_{fs}_any_with_planner")(*args, planner._h))
+
+
+def _c2r_any(fs, dtype, input_re, input_im, output, planner=None):
+    ire, iim, out = _Slice(input_re, dtype, "input_re"), _Slice(input_im, dtype, "input_im"), _Slice(
+        output, dtype, "output")
+    l = _lib.lib()
+    if _same_place(ire, iim, out):
+        own = planner is None
+        if own:
+            planner = (PlannerR2cAny64 if fs == "f64" else PlannerR2cAny32)(out.len)
+        n, half = planner.n, planner.n // 2
+        for code, got, want in ((8, out.len, n), (9, ire.len, half + 1), (10, iim.len, half + 1)):
+            if got != want:
+                _check(code)
+        ws = _any_workspace(planner, 1)
+        _check(getattr(l, f"phast_c2r_fft_{fs}_any_dev")(ire.ptr, iim.ptr, out.ptr, C.c_size_t(n), C.c_size_t(1),
+                                                         C.c_size_t(half + 1), C.c_size_t(n), planner._h, ws.ptr,
+                                                         C.c_size_t(ws.len), _stream()))
+        if own:
+            import torch
+
+            torch.cuda.current_stream().synchronize()
+        return
+    args = [ire.ptr, C.c_size_t(ire.len), iim.ptr, C.c_size_t(iim.len), out.ptr, C.c_size_t(out.len)]
+    if planner is None:
+        _check(getattr(l, f"phast_c2r_fft_{fs}_any")(*args))
+    else:
+        _check(getattr(l, f"phast_c2r_fft_{fs}_any_with_planner")(*args, planner._h))
+
+
+def r2c_fft_f64_any(input_re, output_re, output_im) -> None:
+    """f64 R2C of any length N = len(input_re): X[k], k = 0 .. N // 2, into planes of N // 2 + 1 (numpy.fft.rfft)"""
+    _r2c_any("f64", np.float64, input_re, output_re, output_im)
+
+
+def r2c_fft_f32_any(input_re, output_re, output_im) -> None:
+    """f32 twin of :func:`r2c_fft_f64_any`"""
+    _r2c_any("f32", np.float32, input_re, output_re, output_im)
+
+
+def r2c_fft_f64_any_with_planner(input_re, output_re, output_im, planner: PlannerR2cAny64) -> None:
+    _r2c_any("f64", np.float64, input_re, output_re, output_im, planner)
+
+
+def r2c_fft_f32_any_with_planner(input_re, output_re, output_im, planner: PlannerR2cAny32) -> None:
+    _r2c_any("f32", np.float32, input_re, output_re, output_im, planner)
+
+
+def c2r_fft_f64_any(input_re, input_im, output) -> None:
+    """f64 C2R of any length N = len(output), scaled by 1/N (numpy.fft.irfft(X, N) for a Hermitian spectrum)"""
+    _c2r_any("f64", np.float64, input_re, input_im, output)
+
+
+def c2r_fft_f32_any(input_re, input_im, output) -> None:
+    """f32 twin of :func:`c2r_fft_f64_any`"""
+    _c2r_any("f32", np.float32, input_re, input_im, output)
+
+
+def c2r_fft_f64_any_with_planner(input_re, input_im, output, planner: PlannerR2cAny64) -> None:
+    _c2r_any("f64", np.float64, input_re, input_im, output, planner)
+
+
+def c2r_fft_f32_any_with_planner(input_re, input_im, output, planner: PlannerR2cAny32) -> None:
+    _c2r_any("f32", np.float32, input_re, input_im, output, planner)
+
+
+def _need(what: str, got: int, batch: int, dist: int, per: int) -> None:
+    if batch and got < (batch - 1) * dist + per:
+        raise ValueError(f"{what}: {got} elements, need (batch-1)*dist + {per} = {(batch - 1) * dist + per}")
+
+
+def r2c_any_batched(input_re, output_re, output_im, planner, batch: int, in_dist: int | None = None,
+                    out_dist: int | None = None, workspace=None) -> None:
+    """Device-resident batch of any-length R2C transforms: input b at ``b*in_dist`` (default N), its half spectrum at
+    ``b*out_dist`` (default N // 2 + 1); for N a power of two >= 4, ``in_dist`` must be even when ``batch > 1`` (the
+    power-of-two path reads the input as pairs).  ``workspace``: a device tensor of the planner's type, at least
+    ``planner.workspace_len(1)`` elements (fewer than ``planner.workspace_len(batch)`` runs the batch in chunks); by default
+    one from torch's allocator."""
+    dtype, fs = planner._dtype, "f64" if planner._dtype == np.float64 else "f32"
+    i, ore, oim = (_Slice(x, dtype, w) for x, w in ((input_re, "input_re"), (output_re, "output_re"), (output_im, "output_im")))
+    if not _same_place(i, ore, oim):
+        raise TypeError("r2c_any_batched needs device tensors")
+    n, h1 = planner.n, planner.n // 2 + 1
+    in_dist = n if in_dist is None else in_dist
+    out_dist = h1 if out_dist is None else out_dist
+    _need("input_re", i.len, batch, in_dist, n)
+    _need("output_re", ore.len, batch, out_dist, h1)
+    _need("output_im", oim.len, batch, out_dist, h1)
+    ws = _any_workspace(planner, batch, workspace)
+    _check(getattr(_lib.lib(), f"phast_r2c_fft_{fs}_any_dev")(i.ptr, ore.ptr, oim.ptr, C.c_size_t(n), C.c_size_t(batch),
+                                                              C.c_size_t(in_dist), C.c_size_t(out_dist), planner._h, ws.ptr,
+                                                              C.c_size_t(ws.len), _stream()))
+
+
+def c2r_any_batched(input_re, input_im, output, planner, batch: int, in_dist: int | None = None,
+                    out_dist: int | None = None, workspace=None) -> None:
+    """Device-resident batch of any-length C2R transforms: half spectrum b at ``b*in_dist`` (default N // 2 + 1), its real
+    signal at ``b*out_dist`` (default N; even when ``batch > 1`` for N a power of two >= 4); ``workspace`` as for
+    :func:`r2c_any_batched`."""
+    dtype, fs = planner._dtype, "f64" if planner._dtype == np.float64 else "f32"
+    ire, iim, out = (_Slice(x, dtype, w) for x, w in ((input_re, "input_re"), (input_im, "input_im"), (output, "output")))
+    if not _same_place(ire, iim, out):
+        raise TypeError("c2r_any_batched needs device tensors")
+    n, h1 = planner.n, planner.n // 2 + 1
+    in_dist = h1 if in_dist is None else in_dist
+    out_dist = n if out_dist is None else out_dist
+    _need("input_re", ire.len, batch, in_dist, h1)
+    _need("input_im", iim.len, batch, in_dist, h1)
+    _need("output", out.len, batch, out_dist, n)
+    ws = _any_workspace(planner, batch, workspace)
+    _check(getattr(_lib.lib(), f"phast_c2r_fft_{fs}_any_dev")(ire.ptr, iim.ptr, out.ptr, C.c_size_t(n), C.c_size_t(batch),
+                                                              C.c_size_t(in_dist), C.c_size_t(out_dist), planner._h, ws.ptr,
+                                                              C.c_size_t(ws.len), _stream()))
 
 
 class TransformList:

@@ -50,6 +50,12 @@ phast_planner_any64_new phast_planner_any32_new phast_planner_any64_free phast_p
 phast_planner_any64_describe phast_planner_any32_describe phast_planner_any64_device_bytes phast_planner_any32_device_bytes
 phast_planner_any64_workspace_len phast_planner_any32_workspace_len phast_planner_any64_time_stages phast_planner_any32_time_stages
 phast_fft_64_any phast_fft_32_any phast_fft_64_any_with_planner phast_fft_32_any_with_planner phast_fft_64_any_dev phast_fft_32_any_dev
+phast_planner_r2c_any64_new phast_planner_r2c_any32_new phast_planner_r2c_any64_free phast_planner_r2c_any32_free
+phast_planner_r2c_any64_describe phast_planner_r2c_any32_describe phast_planner_r2c_any64_device_bytes phast_planner_r2c_any32_device_bytes
+phast_planner_r2c_any64_workspace_len phast_planner_r2c_any32_workspace_len phast_planner_r2c_any64_time_stages phast_planner_r2c_any32_time_stages
+phast_planner_r2c_any64_time_c2r_stages phast_planner_r2c_any32_time_c2r_stages
+phast_r2c_fft_f64_any phast_r2c_fft_f32_any phast_r2c_fft_f64_any_with_planner phast_r2c_fft_f32_any_with_planner phast_r2c_fft_f64_any_dev phast_r2c_fft_f32_any_dev
+phast_c2r_fft_f64_any phast_c2r_fft_f32_any phast_c2r_fft_f64_any_with_planner phast_c2r_fft_f32_any_with_planner phast_c2r_fft_f64_any_dev phast_c2r_fft_f32_any_dev
 """.split()
 
 
@@ -112,5 +118,8 @@ def lib() -> C.CDLL:
         getattr(l, f"phast_planner_any{sfx}_free").restype = None
         getattr(l, f"phast_planner_any{sfx}_device_bytes").restype = C.c_size_t
         getattr(l, f"phast_planner_any{sfx}_workspace_len").restype = C.c_size_t
+        getattr(l, f"phast_planner_r2c_any{sfx}_free").restype = None
+        getattr(l, f"phast_planner_r2c_any{sfx}_device_bytes").restype = C.c_size_t
+        getattr(l, f"phast_planner_r2c_any{sfx}_workspace_len").restype = C.c_size_t
     _lib = l
     return l

@@ -15,6 +15,7 @@
 #include "host_api.hpp"
 #include "tune.hpp"
 #include "planner_any.hpp"
+#include "planner_any_real.hpp"
 
 // ================================================================================================
 // C ABI
@@ -27,6 +28,8 @@ struct phast_planner_r2c64 : PlannerR2c<double> {};
 struct phast_planner_r2c32 : PlannerR2c<float> {};
 struct phast_planner_any64 : AnyPlanner<double> {};
 struct phast_planner_any32 : AnyPlanner<float> {};
+struct phast_planner_r2c_any64 : AnyRealPlanner<double> {};
+struct phast_planner_r2c_any32 : AnyRealPlanner<float> {};
 
 // W_N^(r*c) tables of a four-step split (twiddle.hip)
 template <typename T> struct TwiddleGrid {
@@ -526,5 +529,83 @@ PHAST_TWIDDLE_API(32, float)
     } PHAST_CATCH_RC
 PHAST_ANY_API(64, double)
 PHAST_ANY_API(32, float)
+
+// Real transforms of arbitrary lengths (planner_any_real.hpp): arguments are checked before the device is touched
+#define PHAST_ANY_REAL_API(SFX, FS, T)                                                                                  \
+    int phast_planner_r2c_any##SFX##_new(size_t n, phast_planner_r2c_any##SFX **out) try {                              \
+        return any_planner_new(n, out);                                                                                 \
+    } PHAST_CATCH_RC                                                                                                    \
+    void phast_planner_r2c_any##SFX##_free(phast_planner_r2c_any##SFX *p) try { delete p; } PHAST_CATCH_VOID            \
+    int phast_planner_r2c_any##SFX##_describe(const phast_planner_r2c_any##SFX *p, char *buf, size_t len) try {         \
+        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
+        std::snprintf(buf, len, "%s", p->describe().c_str());                                                          \
+        return PHAST_OK;                                                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_r2c_any##SFX##_device_bytes(const phast_planner_r2c_any##SFX *p) try {                         \
+        return p ? p->device_bytes() : 0;                                                                               \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_r2c_any##SFX##_workspace_len(const phast_planner_r2c_any##SFX *p, size_t batch) try {          \
+        return p ? p->workspace_len(batch) : 0;                                                                         \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_r2c_any##SFX##_time_stages(const phast_planner_r2c_any##SFX *p, const T *d_in, T *d_out_re,       \
+                                                 T *d_out_im, size_t batch, T *d_work, size_t work_len, int reps,       \
+                                                 float *stage_ms, void *stream) try {                                   \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(false, d_in, nullptr, d_out_re, d_out_im, batch, d_work, work_len, reps, stage_ms,        \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_planner_r2c_any##SFX##_time_c2r_stages(const phast_planner_r2c_any##SFX *p, const T *d_in_re,             \
+                                                     const T *d_in_im, T *d_out, size_t batch, T *d_work,               \
+                                                     size_t work_len, int reps, float *stage_ms, void *stream) try {    \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(true, d_in_re, d_in_im, d_out, nullptr, batch, d_work, work_len, reps, stage_ms,          \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_r2c_fft_##FS##_any(const T *in, size_t in_len, T *ore, size_t ore_len, T *oim, size_t oim_len) try {      \
+        if (!in || !ore || !oim || in_len == 0 || in_len > kAnyMaxN) return PHAST_ERR_INVALID_ARG;                      \
+        if (ore_len != in_len / 2 + 1) return PHAST_ERR_R2C_OUT_RE_LEN; /* before the device is touched */             \
+        if (oim_len != in_len / 2 + 1) return PHAST_ERR_R2C_OUT_IM_LEN;                                                 \
+        std::shared_ptr<AnyRealPlanner<T>> pl; /* the planner from input.len(), as r2c_fft_* */                        \
+        int rc = PlannerCache<AnyRealPlanner<T>>::instance().get(                                                       \
+            in_len, sizeof(T), [](size_t m, AnyRealPlanner<T> **o) { return any_planner_new(m, o); }, &pl);             \
+        if (rc) return rc;                                                                                              \
+        return pl->host(false, in, in_len, nullptr, 0, ore, ore_len, oim, oim_len);                                     \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_r2c_fft_##FS##_any_with_planner(const T *in, size_t in_len, T *ore, size_t ore_len, T *oim,               \
+                                              size_t oim_len, const phast_planner_r2c_any##SFX *p) try {                \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(false, in, in_len, nullptr, 0, ore, ore_len, oim, oim_len);                                      \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_r2c_fft_##FS##_any_dev(const T *d_in, T *d_ore, T *d_oim, size_t n, size_t batch, size_t in_dist,         \
+                                     size_t out_dist, const phast_planner_r2c_any##SFX *p, T *d_work, size_t work_len,  \
+                                     void *stream) try {                                                                \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(false, d_in, nullptr, d_ore, d_oim, n, batch, in_dist, out_dist, d_work, work_len,                \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_c2r_fft_##FS##_any(const T *ire, size_t ire_len, const T *iim, size_t iim_len, T *out, size_t out_len) try { \
+        if (!ire || !iim || !out || out_len == 0 || out_len > kAnyMaxN) return PHAST_ERR_INVALID_ARG;                   \
+        if (ire_len != out_len / 2 + 1) return PHAST_ERR_C2R_IN_RE_LEN; /* before the device is touched */             \
+        if (iim_len != out_len / 2 + 1) return PHAST_ERR_C2R_IN_IM_LEN;                                                 \
+        std::shared_ptr<AnyRealPlanner<T>> pl; /* the planner from output.len(), as c2r_fft_* */                       \
+        int rc = PlannerCache<AnyRealPlanner<T>>::instance().get(                                                       \
+            out_len, sizeof(T), [](size_t m, AnyRealPlanner<T> **o) { return any_planner_new(m, o); }, &pl);            \
+        if (rc) return rc;                                                                                              \
+        return pl->host(true, ire, ire_len, iim, iim_len, out, out_len, nullptr, 0);                                    \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_c2r_fft_##FS##_any_with_planner(const T *ire, size_t ire_len, const T *iim, size_t iim_len, T *out,       \
+                                              size_t out_len, const phast_planner_r2c_any##SFX *p) try {                \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(true, ire, ire_len, iim, iim_len, out, out_len, nullptr, 0);                                     \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_c2r_fft_##FS##_any_dev(const T *d_ire, const T *d_iim, T *d_out, size_t n, size_t batch, size_t in_dist,  \
+                                     size_t out_dist, const phast_planner_r2c_any##SFX *p, T *d_work, size_t work_len,  \
+                                     void *stream) try {                                                                \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(true, d_ire, d_iim, d_out, nullptr, n, batch, in_dist, out_dist, d_work, work_len,                \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC
+PHAST_ANY_REAL_API(64, f64, double)
+PHAST_ANY_REAL_API(32, f32, float)
 
 }  // extern "C"

@@ -91,6 +91,29 @@ extern "C" {
         direction: c_int, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
     pub(crate) fn phast_fft_32_any_dev(re: *mut f32, im: *mut f32, n: usize, batch: usize, dist: usize,
         direction: c_int, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // real transforms of any length (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/r2c.rs)
+    pub(crate) fn phast_planner_r2c_any64_new(n: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_r2c_any32_new(n: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_r2c_any64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_r2c_any32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_r2c_any64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_r2c_any32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_r2c_fft_f64_any_with_planner(input: *const f64, n: usize, ore: *mut f64, ore_len: usize,
+        oim: *mut f64, oim_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_r2c_fft_f32_any_with_planner(input: *const f32, n: usize, ore: *mut f32, ore_len: usize,
+        oim: *mut f32, oim_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_r2c_fft_f64_any_dev(input: *const f64, ore: *mut f64, oim: *mut f64, n: usize, batch: usize,
+        in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_r2c_fft_f32_any_dev(input: *const f32, ore: *mut f32, oim: *mut f32, n: usize, batch: usize,
+        in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_c2r_fft_f64_any_with_planner(ire: *const f64, ire_len: usize, iim: *const f64, iim_len: usize,
+        out: *mut f64, n: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_c2r_fft_f32_any_with_planner(ire: *const f32, ire_len: usize, iim: *const f32, iim_len: usize,
+        out: *mut f32, n: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_c2r_fft_f64_any_dev(ire: *const f64, iim: *const f64, out: *mut f64, n: usize, batch: usize,
+        in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_c2r_fft_f32_any_dev(ire: *const f32, iim: *const f32, out: *mut f32, n: usize, batch: usize,
+        in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
 }
 
 /// Re-raises a library status as the reference's panic: `phast_strerror` returns the exact text of the

@@ -37,6 +37,12 @@ pub use algorithms::r2c::{
     c2r_fft_f64_with_planner, c2r_fft_f64_with_planner_and_scratch, r2c_fft_f32,
     r2c_fft_f32_with_planner, r2c_fft_f64, r2c_fft_f64_with_planner,
 };
+// real transforms of any length (an extension beyond PhastFT 0.3.0)
+pub use algorithms::r2c::{
+    c2r_fft_f32_any, c2r_fft_f32_any_dev, c2r_fft_f32_any_with_planner, c2r_fft_f64_any, c2r_fft_f64_any_dev,
+    c2r_fft_f64_any_with_planner, r2c_fft_f32_any, r2c_fft_f32_any_dev, r2c_fft_f32_any_with_planner, r2c_fft_f64_any,
+    r2c_fft_f64_any_dev, r2c_fft_f64_any_with_planner,
+};
 
 use crate::options::Options;
 use crate::planner::{Direction, PlannerAny32, PlannerAny64, PlannerDit32, PlannerDit64};

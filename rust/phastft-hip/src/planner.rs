@@ -161,3 +161,43 @@ macro_rules! impl_planner_any {
 }
 impl_planner_any!(PlannerAny64, phast_planner_any64_new, phast_planner_any64_free, phast_planner_any64_workspace_len);
 impl_planner_any!(PlannerAny32, phast_planner_any32_new, phast_planner_any32_free, phast_planner_any32_workspace_len);
+
+macro_rules! impl_planner_r2c_any {
+    ($any:ident, $new:ident, $free:ident, $ws_len:ident) => {
+        /// An extension beyond PhastFT 0.3.0, whose `PlannerR2c*` takes powers of two >= 4 only: real transforms (R2C / C2R)
+        /// of any length 1 <= N <= 2^29 (a power of two >= 4 runs the `PlannerR2c*` path itself, an even N packs into an
+        /// N/2-point Bluestein transform, an odd N runs an N-point one).  Immutable after `new`, like the reference's planners.
+        pub struct $any {
+            pub(crate) h: *mut Opaque,
+            pub(crate) n: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in a
+        // workspace of the library's own pool (host-slice calls)
+        unsafe impl Send for $any {}
+        unsafe impl Sync for $any {}
+        impl $any {
+            /// panics with "invalid argument" for N = 0 or N > 2^29
+            pub fn new(n: usize) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe { ffi::$new(n, &mut h) });
+                Self { h, n }
+            }
+            pub fn num_points(&self) -> usize {
+                self.n
+            }
+            /// elements of the workspace a device call of `batch` transforms works in (0 for a power of two, N = 1, 2)
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+        }
+        impl Drop for $any {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_r2c_any!(PlannerR2cAny64, phast_planner_r2c_any64_new, phast_planner_r2c_any64_free,
+                      phast_planner_r2c_any64_workspace_len);
+impl_planner_r2c_any!(PlannerR2cAny32, phast_planner_r2c_any32_new, phast_planner_r2c_any32_free,
+                      phast_planner_r2c_any32_workspace_len);
