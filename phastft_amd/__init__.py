@@ -548,48 +548,64 @@ def fft_dit_batched(reals, imags, n: int, direction: Direction, planner, dist: i
 # ---------------------------------------------------------------------------------------------
 # any length N >= 1 (Bluestein on the power-of-two engine; no reference counterpart -- the reference takes powers of two only)
 # ---------------------------------------------------------------------------------------------
-class _PlannerAny:
+class _AnyHandle:
+    """the handle of an any-length planner: phast_planner_{_prefix}{_sfx}_*"""
+    _prefix = "any"
     _sfx = "64"
     _dtype = np.float64
 
     def __init__(self, n: int):
         self._h = C.c_void_p()
-        _check(getattr(_lib.lib(), f"phast_planner_any{self._sfx}_new")(C.c_size_t(n), C.byref(self._h)))
+        _check(self._fn("new")(C.c_size_t(n), C.byref(self._h)))
         self.n = n
-        # the convolution length: the smallest power of two >= 2N - 1 (N itself for a power of two)
-        self.m = n if n & (n - 1) == 0 else 1 << (2 * n - 2).bit_length()
+
+    def _fn(self, name: str):
+        return getattr(_lib.lib(), f"phast_planner_{self._prefix}{self._sfx}_{name}")
 
     def __del__(self):
         try:
             if getattr(self, "_h", None) is not None and self._h.value and _lib is not None and _lib._lib is not None:
-                getattr(_lib._lib, f"phast_planner_any{self._sfx}_free")(self._h)
+                getattr(_lib._lib, f"phast_planner_{self._prefix}{self._sfx}_free")(self._h)
                 self._h.value = None
         except Exception:  # interpreter shutdown: modules may already be gone
             pass
 
     def describe(self) -> str:
         buf = C.create_string_buffer(16384)
-        _check(getattr(_lib.lib(), f"phast_planner_any{self._sfx}_describe")(self._h, buf, C.c_size_t(16384)))
+        _check(self._fn("describe")(self._h, buf, C.c_size_t(16384)))
         return buf.value.decode()
 
     def device_bytes(self) -> int:
-        return int(getattr(_lib.lib(), f"phast_planner_any{self._sfx}_device_bytes")(self._h))
+        return int(self._fn("device_bytes")(self._h))
+
+    def _workspace_len(self, batch: int) -> int:
+        return int(self._fn("workspace_len")(self._h, C.c_size_t(batch)))
+
+    def _time(self, name: str, bufs, counts, batch: int, workspace, reps: int):
+        """the five stage times of a *_time_*stages call: (handle, buffers, counts, workspace, reps, ms, stream)"""
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 5)()
+        _check(self._fn(name)(self._h, *(b.ptr for b in bufs), *(C.c_size_t(c) for c in counts), ws.ptr, C.c_size_t(ws.len),
+                              C.c_int(reps), ms, _stream()))
+        return [float(x) for x in ms]
+
+
+class _PlannerAny(_AnyHandle):
+    def __init__(self, n: int):
+        super().__init__(n)
+        # the convolution length: the smallest power of two >= 2N - 1 (N itself for a power of two)
+        self.m = n if n & (n - 1) == 0 else 1 << (2 * n - 2).bit_length()
 
     def workspace_len(self, batch: int = 1) -> int:
         """Elements of T a device call of ``batch`` transforms works in: 2 M batch (0 for a power of two).  A smaller
         workspace of at least 2 M runs the batch in chunks."""
-        return int(getattr(_lib.lib(), f"phast_planner_any{self._sfx}_workspace_len")(self._h, C.c_size_t(batch)))
+        return self._workspace_len(batch)
 
     def time_stages(self, reals, imags, batch: int = 1, dist: int | None = None, workspace=None, reps: int = 10):
         """Average HIP-event milliseconds of the five stages of a forward call on device tensors -- chirp-pad sweep, forward
         M-point transform, spectrum sweep, inverse M-point transform, chirp-post sweep (measurement hook)."""
         re, im = _Slice(reals, self._dtype, "reals"), _Slice(imags, self._dtype, "imags")
-        ws = _any_workspace(self, batch, workspace)
-        ms = (C.c_float * 5)()
-        _check(getattr(_lib.lib(), f"phast_planner_any{self._sfx}_time_stages")(
-            self._h, re.ptr, im.ptr, C.c_size_t(batch), C.c_size_t(self.n if dist is None else dist), ws.ptr,
-            C.c_size_t(ws.len), C.c_int(reps), ms, _stream()))
-        return [float(x) for x in ms]
+        return self._time("time_stages", (re, im), (batch, self.n if dist is None else dist), batch, workspace, reps)
 
 
 class PlannerAny64(_PlannerAny):
@@ -683,58 +699,31 @@ def fft_any_batched(reals, imags, n: int, direction: Direction, planner, dist: i
 # ---------------------------------------------------------------------------------------------
 # real transforms of any length N >= 1 (no reference counterpart: r2c.rs takes powers of two >= 4)
 # ---------------------------------------------------------------------------------------------
-class _PlannerR2cAny:
-    _sfx = "64"
-    _dtype = np.float64
+class _PlannerR2cAny(_AnyHandle):
+    _prefix = "r2c_any"
 
     def __init__(self, n: int):
-        self._h = C.c_void_p()
-        _check(getattr(_lib.lib(), f"phast_planner_r2c_any{self._sfx}_new")(C.c_size_t(n), C.byref(self._h)))
-        self.n = n
+        super().__init__(n)
         self.half = n // 2
         self.m = self.workspace_len(1) // 2  # the inner convolution length (0: a power of two >= 4, N = 1, 2)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value and _lib is not None and _lib._lib is not None:
-                getattr(_lib._lib, f"phast_planner_r2c_any{self._sfx}_free")(self._h)
-                self._h.value = None
-        except Exception:  # interpreter shutdown: modules may already be gone
-            pass
-
-    def describe(self) -> str:
-        buf = C.create_string_buffer(16384)
-        _check(getattr(_lib.lib(), f"phast_planner_r2c_any{self._sfx}_describe")(self._h, buf, C.c_size_t(16384)))
-        return buf.value.decode()
-
-    def device_bytes(self) -> int:
-        return int(getattr(_lib.lib(), f"phast_planner_r2c_any{self._sfx}_device_bytes")(self._h))
 
     def workspace_len(self, batch: int = 1) -> int:
         """Elements of T a device call of ``batch`` transforms works in: 2 M batch (0 for a power of two, N = 1 or 2).  A
         smaller workspace of at least 2 M runs the batch in chunks."""
-        return int(getattr(_lib.lib(), f"phast_planner_r2c_any{self._sfx}_workspace_len")(self._h, C.c_size_t(batch)))
+        return self._workspace_len(batch)
 
     def time_stages(self, input_re, output_re, output_im, batch: int = 1, workspace=None, reps: int = 10):
         """Average HIP-event milliseconds of the five stages of an R2C call on device tensors -- pad sweep, forward M-point
         transform, spectrum sweep, inverse M-point transform, post sweep (measurement hook)"""
         i, ore, oim = (_Slice(x, self._dtype, w) for x, w in ((input_re, "input_re"), (output_re, "output_re"),
                                                                (output_im, "output_im")))
-        ws = _any_workspace(self, batch, workspace)
-        ms = (C.c_float * 5)()
-        _check(getattr(_lib.lib(), f"phast_planner_r2c_any{self._sfx}_time_stages")(
-            self._h, i.ptr, ore.ptr, oim.ptr, C.c_size_t(batch), ws.ptr, C.c_size_t(ws.len), C.c_int(reps), ms, _stream()))
-        return [float(x) for x in ms]
+        return self._time("time_stages", (i, ore, oim), (batch,), batch, workspace, reps)
 
     def time_c2r_stages(self, input_re, input_im, output, batch: int = 1, workspace=None, reps: int = 10):
         """:meth:`time_stages` of a C2R call"""
         ire, iim, out = (_Slice(x, self._dtype, w) for x, w in ((input_re, "input_re"), (input_im, "input_im"),
                                                                  (output, "output")))
-        ws = _any_workspace(self, batch, workspace)
-        ms = (C.c_float * 5)()
-        _check(getattr(_lib.lib(), f"phast_planner_r2c_any{self._sfx}_time_c2r_stages")(
-            self._h, ire.ptr, iim.ptr, out.ptr, C.c_size_t(batch), ws.ptr, C.c_size_t(ws.len), C.c_int(reps), ms, _stream()))
-        return [float(x) for x in ms]
+        return self._time("time_c2r_stages", (ire, iim, out), (batch,), batch, workspace, reps)
 
 
 class PlannerR2cAny64(_PlannerR2cAny):

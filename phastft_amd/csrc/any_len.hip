@@ -10,21 +10,12 @@
 
 namespace phast {
 
-template <typename T> struct AnyVec;  // 16 bytes of T
-template <> struct AnyVec<double> { typedef double type __attribute__((ext_vector_type(2))); static constexpr int N = 2; };
-template <> struct AnyVec<float> { typedef float type __attribute__((ext_vector_type(4))); static constexpr int N = 4; };
-
-// w[k] = exp(-i pi k^2 / N) (cos, sin) in double
-__device__ inline void chirp(unsigned long long k, unsigned long long n, double *c, double *s) {
-    sincospi(chirp_turns(k, n), s, c);
-}
-
 // a[b * M + k] = x[b * in_dist + k] w[k] for k < N, 0 up to M
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) any_pre_kernel(AnySweepArgs a) {
     using V = typename AnyVec<T>::type;
     constexpr int L = AnyVec<T>::N;
-    const unsigned long long g = a.g0 + (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long g = global_group(a);
     if (g >= a.groups) return;
     const unsigned log_gpt = a.log_m - (L == 2 ? 1 : 2);
     const unsigned long long b = g >> log_gpt, k0 = (g & ((1ull << log_gpt) - 1)) * L;
@@ -70,7 +61,7 @@ template <typename T>
 __global__ void __launch_bounds__(256) any_spectrum_kernel(AnySweepArgs a) {
     using V = typename AnyVec<T>::type;
     constexpr int L = AnyVec<T>::N;
-    const unsigned long long g = a.g0 + (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long g = global_group(a);
     if (g >= a.groups) return;
     const unsigned long long o = g * L, k0 = o & ((1ull << a.log_m) - 1);
     V *pr = (V *)((T *)a.out_re + o), *pi = (V *)((T *)a.out_im + o);
@@ -85,10 +76,10 @@ template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) any_post_kernel(AnySweepArgs a) {
     using V = typename AnyVec<T>::type;
     constexpr int L = AnyVec<T>::N;
-    const unsigned long long g = a.g0 + (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long g = global_group(a);
     if (g >= a.groups) return;
-    const unsigned long long b = g < 0xffffffffull ? (unsigned)g / a.gpt : g / a.gpt;
-    const unsigned long long k0 = (g - b * a.gpt) * L;
+    unsigned long long b;
+    const unsigned long long k0 = split_group(g, a.gpt, &b) * L;
     const unsigned long long o = (b << a.log_m) + k0;
     const V cr = *(const V *)((const T *)a.in_re + o), ci = *(const V *)((const T *)a.in_im + o);
     T *xr = (T *)a.out_re + b * a.out_dist, *xi = (T *)a.out_im + b * a.out_dist;
@@ -129,14 +120,10 @@ __global__ void __launch_bounds__(256) any_round_kernel(const double *in, float 
     if (i < count) out[i] = (float)in[i];
 }
 
-static constexpr unsigned long long kMaxBlocks = 0x7fffffffull;
-
 template <typename T> hipError_t launch_any_sweep(int kind, bool vec, const AnySweepArgs &a0, hipStream_t stream) {
     AnySweepArgs a = a0;
-    for (unsigned long long g0 = 0; g0 < a.groups; g0 += kMaxBlocks * 256) {
+    return launch_in_slices(a.groups, [&](dim3 grid, unsigned long long g0) {
         a.g0 = g0;
-        const unsigned long long left = a.groups - g0, blocks = (left + 255) / 256;
-        const dim3 grid((unsigned)(blocks < kMaxBlocks ? blocks : kMaxBlocks));
         if (kind == 0 && vec)
             hipLaunchKernelGGL((any_pre_kernel<T, true>), grid, dim3(256), 0, stream, a);
         else if (kind == 0)
@@ -147,8 +134,7 @@ template <typename T> hipError_t launch_any_sweep(int kind, bool vec, const AnyS
             hipLaunchKernelGGL((any_post_kernel<T, true>), grid, dim3(256), 0, stream, a);
         else
             hipLaunchKernelGGL((any_post_kernel<T, false>), grid, dim3(256), 0, stream, a);
-    }
-    return hipGetLastError();
+    });
 }
 
 hipError_t launch_any_chirp_b(double *re, double *im, unsigned long long n, unsigned log_m, hipStream_t stream) {

@@ -8,15 +8,17 @@
 //     engine      c = M IFFT_M(A) (swap trick)            workspace, in place                  Planner<T>::exec_in
 //     chirp-post  X = w c * scale  (k < N)                workspace -> caller's planes         any_post_kernel
 //
-// The top of this header (the exact phase) has no HIP dependency: tests/test_any_len_cpu.py compiles it for the host.
+// The top of this header (the exact phase) has no HIP dependency: tests/test_any_len_cpu.py compiles it for the host.  The HIP
+// section below it holds the launch interface of the three sweeps and the device helpers they share with the real sweeps
+// (any_real.hip): the 16-byte group type, the chirp, the split of a group index and the launch split at 2^31 - 1 workgroups.
 #pragma once
 
 #include <cstdint>
 
 #if defined(__HIPCC__)
-#define PHAST_HD __host__ __device__
+#include "common.hpp"  // PHAST_HD
 #else
-#define PHAST_HD
+#define PHAST_HD inline  // the host-only top, for g++
 #endif
 
 namespace phast {
@@ -27,7 +29,7 @@ constexpr unsigned long long kAnyMaxN = 1ull << 29;  // M <= 2^30: the f64 engin
 // is no good in floating point (n^2 ~ 2^40 at N ~ 10^6 leaves ~13 bits below the point of the angle: a phase error of
 // ~3e-10).  The quotient is estimated in double and corrected in integers: n mod 2N < 2^30, so its square is < 2^60 and the
 // estimate is off by at most one.
-PHAST_HD inline unsigned long long chirp_r(unsigned long long n, unsigned long long N) {
+PHAST_HD unsigned long long chirp_r(unsigned long long n, unsigned long long N) {
     const unsigned long long two_n = 2 * N;
     if (n >= two_n) n = (unsigned)n % (unsigned)two_n;  // (n + 2N k)^2 = n^2 (mod 2N); both operands < 2^31
     const unsigned long long sq = n * n;
@@ -39,7 +41,7 @@ PHAST_HD inline unsigned long long chirp_r(unsigned long long n, unsigned long l
 }
 
 // the chirp's angle in units of pi: w[n] = exp(i pi t), t = -r / N in (-2, 0] (one rounding: r and N are exact in double)
-PHAST_HD inline double chirp_turns(unsigned long long n, unsigned long long N) { return -(double)chirp_r(n, N) / (double)N; }
+PHAST_HD double chirp_turns(unsigned long long n, unsigned long long N) { return -(double)chirp_r(n, N) / (double)N; }
 
 // the convolution length: the smallest power of two >= 2N - 1 (N itself for a power of two, which never convolves)
 inline unsigned long long any_conv_len(unsigned long long N) {
@@ -79,6 +81,36 @@ template <typename T> hipError_t launch_any_sweep(int kind, bool vec, const AnyS
 hipError_t launch_any_chirp_b(double *re, double *im, unsigned long long n, unsigned log_m, hipStream_t stream);
 // out[i] = (float)in[i], i < count (the f32 planner's Bh, built in f64)
 hipError_t launch_any_round(const double *in, float *out, unsigned long long count, hipStream_t stream);
+
+// ---- shared by the sweeps of any_len.hip and any_real.hip ----
+template <typename T> struct AnyVec;  // 16 bytes of T: the group of one thread
+template <> struct AnyVec<double> { typedef double type __attribute__((ext_vector_type(2))); static constexpr int N = 2; };
+template <> struct AnyVec<float> { typedef float type __attribute__((ext_vector_type(4))); static constexpr int N = 4; };
+
+// w[k] = exp(-i pi k^2 / n) (cos, sin) in double
+__device__ inline void chirp(unsigned long long k, unsigned long long n, double *c, double *s) {
+    sincospi(chirp_turns(k, n), s, c);
+}
+
+// the group of this thread in a launch of AnySweepArgs / AnyRealArgs (a.g0: the launch's first group)
+template <typename A> __device__ inline unsigned long long global_group(const A &a) {
+    return a.g0 + (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+}
+// (transform, group within it) of group g of a sweep with gpt groups per transform
+__device__ inline unsigned long long split_group(unsigned long long g, unsigned gpt, unsigned long long *b) {
+    *b = g < 0xffffffffull ? (unsigned)g / gpt : g / gpt;
+    return g - *b * gpt;
+}
+
+// `groups` groups in 256-thread workgroups: launch(grid, g0) once per slice of at most 2^31 - 1 workgroups from group g0 on
+template <typename F> hipError_t launch_in_slices(unsigned long long groups, F &&launch) {
+    constexpr unsigned long long kMaxBlocks = 0x7fffffffull;
+    for (unsigned long long g0 = 0; g0 < groups; g0 += kMaxBlocks * 256) {
+        const unsigned long long blocks = (groups - g0 + 255) / 256;
+        launch(dim3((unsigned)(blocks < kMaxBlocks ? blocks : kMaxBlocks)), g0);
+    }
+    return hipGetLastError();
+}
 
 }  // namespace phast
 #endif

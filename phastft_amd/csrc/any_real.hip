@@ -1,8 +1,9 @@
 // any_real.hip -- the streaming sweeps of the arbitrary-length real transforms (any_real.hpp has the algorithm).
 //
-// Built as any_len.hip is: one group of 16 bytes per plane per thread, 256-thread workgroups in address order, launches split
-// at 2^31 - 1 workgroups, non-temporal accesses on the caller's data, 16-byte accesses on the caller's side where bases and
-// dist allow it and element accesses otherwise.  The workspace side is always 16-byte aligned (M is a power of two >= 8).
+// Built as any_len.hip is, on the device helpers of any_len.hpp: one group of 16 bytes per plane per thread, 256-thread
+// workgroups in address order, launches split at 2^31 - 1 workgroups, non-temporal accesses on the caller's data, 16-byte
+// accesses on the caller's side where bases and dist allow it and element accesses otherwise.  The workspace side is always
+// 16-byte aligned (M is a power of two >= 8).
 // The pairwise sweeps (untangle, preprocess) own a mirror pair (k, H - k) per point: the k side moves in groups, the H - k
 // side (descending, usually unaligned) in elements.  Chirps (exact phase, any_len.hpp: chirp_r) and the twiddles
 // W^k = exp(-2 pi i k / N) = sincospi(-2k / N) are evaluated on the fly in double, for f32 too: no N-point table.
@@ -10,26 +11,9 @@
 
 namespace phast {
 
-template <typename T> struct RealVec;  // 16 bytes of T
-template <> struct RealVec<double> { typedef double type __attribute__((ext_vector_type(2))); static constexpr int N = 2; };
-template <> struct RealVec<float> { typedef float type __attribute__((ext_vector_type(4))); static constexpr int N = 4; };
-
-// w[k] = exp(-i pi k^2 / l) (cos, sin) in double
-__device__ inline void real_chirp(unsigned long long k, unsigned long long l, double *c, double *s) {
-    sincospi(chirp_turns(k, l), s, c);
-}
 // W^k = exp(-2 pi i k / n), k < n (the quotient is one rounding from exact)
 __device__ inline void real_twiddle(unsigned long long k, unsigned long long n, double *c, double *s) {
     sincospi(-(double)(2 * k) / (double)n, s, c);
-}
-
-__device__ inline unsigned long long global_group(const AnyRealArgs &a) {
-    return a.g0 + (unsigned long long)blockIdx.x * 256 + threadIdx.x;
-}
-// (transform, first point) of group g of a sweep with gpt groups per transform
-__device__ inline unsigned long long split_group(unsigned long long g, unsigned gpt, unsigned long long *b) {
-    *b = g < 0xffffffffull ? (unsigned)g / gpt : g / gpt;
-    return g - *b * gpt;
 }
 
 // (re, im) * (c, s) in double, rounded to T into the two lanes
@@ -51,8 +35,8 @@ __device__ inline void c2r_pre_point(double ar, double ai, double br, double bi,
 // ---- R2C, even N: a[b M + k] = (x[2k] + i x[2k+1]) w_H[k] for k < H, 0 up to M ----
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) any_r2c_pack_kernel(AnyRealArgs a) {
-    using V = typename RealVec<T>::type;
-    constexpr int L = RealVec<T>::N;
+    using V = typename AnyVec<T>::type;
+    constexpr int L = AnyVec<T>::N;
     const unsigned long long g = global_group(a);
     if (g >= a.groups) return;
     const unsigned log_gpt = a.log_m - (L == 2 ? 1 : 2);
@@ -82,7 +66,7 @@ __global__ void __launch_bounds__(256) any_r2c_pack_kernel(AnyRealArgs a) {
         T orr = 0, oi = 0;
         if (k0 + j < a.l) {
             double c, s;
-            real_chirp(k0 + j, a.l, &c, &s);
+            chirp(k0 + j, a.l, &c, &s);
             cmul<T>((double)e[j], (double)o[j], c, s, &orr, &oi);
         }
         vr[j] = orr;
@@ -98,8 +82,8 @@ __global__ void __launch_bounds__(256) any_r2c_pack_kernel(AnyRealArgs a) {
 // X[0] = (Re Z[0] + Im Z[0], 0), X[H] = (Re Z[0] - Im Z[0], 0) exactly ----
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) any_r2c_untangle_kernel(AnyRealArgs a) {
-    using V = typename RealVec<T>::type;
-    constexpr int L = RealVec<T>::N;
+    using V = typename AnyVec<T>::type;
+    constexpr int L = AnyVec<T>::N;
     const unsigned long long g = global_group(a);
     if (g >= a.groups) return;
     unsigned long long b;
@@ -114,7 +98,7 @@ __global__ void __launch_bounds__(256) any_r2c_untangle_kernel(AnyRealArgs a) {
         vr[j] = vi[j] = 0;
         if (k > q) continue;
         double c, s;
-        real_chirp(k, h, &c, &s);
+        chirp(k, h, &c, &s);
         const double zr = fr[j] * c - fi[j] * s, zi = fr[j] * s + fi[j] * c;
         if (k == 0) {
             vr[j] = (T)(zr + zi);
@@ -124,7 +108,7 @@ __global__ void __launch_bounds__(256) any_r2c_untangle_kernel(AnyRealArgs a) {
         }
         const unsigned long long mk = h - k;
         const double mr = cr[mk], mi = ci[mk];
-        real_chirp(mk, h, &c, &s);
+        chirp(mk, h, &c, &s);
         const double yr = mr * c - mi * s, yi = mr * s + mi * c;
         const double sr = 0.5 * (zr + yr), si = 0.5 * (zi - yi);
         const double dr = zr - yr, di = zi + yi;
@@ -155,8 +139,8 @@ __global__ void __launch_bounds__(256) any_r2c_untangle_kernel(AnyRealArgs a) {
 // H / 2 < k < H are written by their mirror's thread ----
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) any_c2r_pre_kernel(AnyRealArgs a) {
-    using V = typename RealVec<T>::type;
-    constexpr int L = RealVec<T>::N;
+    using V = typename AnyVec<T>::type;
+    constexpr int L = AnyVec<T>::N;
     const unsigned long long g = global_group(a);
     if (g >= a.groups) return;
     const unsigned log_gpt = a.log_m - (L == 2 ? 1 : 2);
@@ -191,14 +175,14 @@ __global__ void __launch_bounds__(256) any_c2r_pre_kernel(AnyRealArgs a) {
         double c, s, zr, zi, wc, ws;
         real_twiddle(k, a.n, &c, &s);
         c2r_pre_point(ar, ai, br, bi, c, s, &zr, &zi);
-        real_chirp(k, h, &wc, &ws);
+        chirp(k, h, &wc, &ws);
         T orr, oi;
         cmul<T>(zi, zr, wc, ws, &orr, &oi);
         vr[j] = orr;
         vi[j] = oi;
         if (k != 0 && mk != k) {  // W^(H-k) = -conj(W^k)
             c2r_pre_point(br, bi, ar, ai, -c, s, &zr, &zi);
-            real_chirp(mk, h, &wc, &ws);
+            chirp(mk, h, &wc, &ws);
             cmul<T>(zi, zr, wc, ws, &orr, &oi);
             wr[mk] = orr;
             wi[mk] = oi;
@@ -220,8 +204,8 @@ __global__ void __launch_bounds__(256) any_c2r_pre_kernel(AnyRealArgs a) {
 // ---- C2R, even N: Y = w_H c * scale (the swap trick: z = Im Y + i Re Y), x[2k] = Im Y[k], x[2k+1] = Re Y[k], k < H ----
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) any_c2r_interleave_kernel(AnyRealArgs a) {
-    using V = typename RealVec<T>::type;
-    constexpr int L = RealVec<T>::N;
+    using V = typename AnyVec<T>::type;
+    constexpr int L = AnyVec<T>::N;
     const unsigned long long g = global_group(a);
     if (g >= a.groups) return;
     unsigned long long b;
@@ -232,7 +216,7 @@ __global__ void __launch_bounds__(256) any_c2r_interleave_kernel(AnyRealArgs a) 
 #pragma unroll
     for (int j = 0; j < L; ++j) {
         double c = 0, s = 0;
-        if (k0 + j < a.l) real_chirp(k0 + j, a.l, &c, &s);
+        if (k0 + j < a.l) chirp(k0 + j, a.l, &c, &s);
         cmul<T>((double)cr[j] * a.scale, (double)ci[j] * a.scale, c, s, &o[j], &e[j]);
     }
     T *x = (T *)a.out_re + b * a.out_dist + 2 * k0;
@@ -260,8 +244,8 @@ __global__ void __launch_bounds__(256) any_c2r_interleave_kernel(AnyRealArgs a) 
 // ---- R2C, odd N: a[b M + k] = x[k] w_N[k] (k < N), 0 up to M ----
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) any_r2c_odd_pad_kernel(AnyRealArgs a) {
-    using V = typename RealVec<T>::type;
-    constexpr int L = RealVec<T>::N;
+    using V = typename AnyVec<T>::type;
+    constexpr int L = AnyVec<T>::N;
     const unsigned long long g = global_group(a);
     if (g >= a.groups) return;
     const unsigned log_gpt = a.log_m - (L == 2 ? 1 : 2);
@@ -280,7 +264,7 @@ __global__ void __launch_bounds__(256) any_r2c_odd_pad_kernel(AnyRealArgs a) {
 #pragma unroll
     for (int j = 0; j < L; ++j) {
         double c = 0, s = 0;
-        if (k0 + j < a.l) real_chirp(k0 + j, a.l, &c, &s);
+        if (k0 + j < a.l) chirp(k0 + j, a.l, &c, &s);
         vr[j] = (T)(lx[j] * c);
         vi[j] = (T)(lx[j] * s);
     }
@@ -292,8 +276,8 @@ __global__ void __launch_bounds__(256) any_r2c_odd_pad_kernel(AnyRealArgs a) {
 // ---- R2C, odd N: X[k] = w_N[k] c[k] for k <= (N - 1) / 2; Im X[0] = 0 exactly ----
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) any_r2c_odd_post_kernel(AnyRealArgs a) {
-    using V = typename RealVec<T>::type;
-    constexpr int L = RealVec<T>::N;
+    using V = typename AnyVec<T>::type;
+    constexpr int L = AnyVec<T>::N;
     const unsigned long long g = global_group(a);
     if (g >= a.groups) return;
     unsigned long long b;
@@ -305,7 +289,7 @@ __global__ void __launch_bounds__(256) any_r2c_odd_post_kernel(AnyRealArgs a) {
 #pragma unroll
     for (int j = 0; j < L; ++j) {
         double c = 0, s = 0;
-        if (k0 + j <= q) real_chirp(k0 + j, a.l, &c, &s);
+        if (k0 + j <= q) chirp(k0 + j, a.l, &c, &s);
         T orr, oi;
         cmul<T>((double)cr[j], (double)ci[j], c, s, &orr, &oi);
         vr[j] = orr;
@@ -328,8 +312,8 @@ __global__ void __launch_bounds__(256) any_r2c_odd_post_kernel(AnyRealArgs a) {
 // the swap trick: a[b M + k] = (Im Xh[k] + i Re Xh[k]) w_N[k] (k < N), 0 up to M ----
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) any_c2r_odd_pad_kernel(AnyRealArgs a) {
-    using V = typename RealVec<T>::type;
-    constexpr int L = RealVec<T>::N;
+    using V = typename AnyVec<T>::type;
+    constexpr int L = AnyVec<T>::N;
     const unsigned long long g = global_group(a);
     if (g >= a.groups) return;
     const unsigned log_gpt = a.log_m - (L == 2 ? 1 : 2);
@@ -362,7 +346,7 @@ __global__ void __launch_bounds__(256) any_c2r_odd_pad_kernel(AnyRealArgs a) {
 #pragma unroll
     for (int j = 0; j < L; ++j) {
         double c = 0, s = 0;
-        if (k0 + j < n) real_chirp(k0 + j, n, &c, &s);
+        if (k0 + j < n) chirp(k0 + j, n, &c, &s);
         T orr, oi;
         cmul<T>((double)hi[j], (double)hr[j], c, s, &orr, &oi);
         vr[j] = orr;
@@ -376,8 +360,8 @@ __global__ void __launch_bounds__(256) any_c2r_odd_pad_kernel(AnyRealArgs a) {
 // ---- C2R, odd N: x[k] = Im(w_N[k] c[k]) * scale for k < N (the swap trick's real part) ----
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) any_c2r_odd_post_kernel(AnyRealArgs a) {
-    using V = typename RealVec<T>::type;
-    constexpr int L = RealVec<T>::N;
+    using V = typename AnyVec<T>::type;
+    constexpr int L = AnyVec<T>::N;
     const unsigned long long g = global_group(a);
     if (g >= a.groups) return;
     unsigned long long b;
@@ -389,7 +373,7 @@ __global__ void __launch_bounds__(256) any_c2r_odd_post_kernel(AnyRealArgs a) {
 #pragma unroll
     for (int j = 0; j < L; ++j) {
         double c = 0, s = 0;
-        if (k0 + j < a.l) real_chirp(k0 + j, a.l, &c, &s);
+        if (k0 + j < a.l) chirp(k0 + j, a.l, &c, &s);
         v[j] = (T)(((double)cr[j] * s + (double)ci[j] * c) * a.scale);
     }
     if (VEC && k0 + L <= a.l) {
@@ -432,14 +416,12 @@ __global__ void __launch_bounds__(256) any_real_tiny_kernel(AnyRealArgs a, int c
     }
 }
 
-static constexpr unsigned long long kRealMaxBlocks = 0x7fffffffull;
-
 template <typename T> hipError_t launch_any_real(int kind, bool vec, const AnyRealArgs &a0, hipStream_t stream) {
+    if (kind < kR2cPack || kind > kC2rTiny) return hipErrorInvalidValue;
     AnyRealArgs a = a0;
-    for (unsigned long long g0 = 0; g0 < a.groups; g0 += kRealMaxBlocks * 256) {
+    return launch_in_slices(a.groups, [&](dim3 grid, unsigned long long g0) {
         a.g0 = g0;
-        const unsigned long long left = a.groups - g0, blocks = (left + 255) / 256;
-        const dim3 grid((unsigned)(blocks < kRealMaxBlocks ? blocks : kRealMaxBlocks)), block(256);
+        const dim3 block(256);
 #define PHAST_REAL_LAUNCH(KERNEL)                                                                                       \
     if (vec)                                                                                                            \
         hipLaunchKernelGGL((KERNEL<T, true>), grid, block, 0, stream, a);                                               \
@@ -455,15 +437,12 @@ template <typename T> hipError_t launch_any_real(int kind, bool vec, const AnyRe
         case kR2cOddPost: PHAST_REAL_LAUNCH(any_r2c_odd_post_kernel)
         case kC2rOddPad: PHAST_REAL_LAUNCH(any_c2r_odd_pad_kernel)
         case kC2rOddPost: PHAST_REAL_LAUNCH(any_c2r_odd_post_kernel)
-        case kR2cTiny:
-        case kC2rTiny:
+        default:  // kR2cTiny, kC2rTiny
             hipLaunchKernelGGL(any_real_tiny_kernel<T>, grid, block, 0, stream, a, kind == kC2rTiny ? 1 : 0);
             break;
-        default: return hipErrorInvalidValue;
         }
 #undef PHAST_REAL_LAUNCH
-    }
-    return hipGetLastError();
+    });
 }
 
 template hipError_t launch_any_real<double>(int, bool, const AnyRealArgs &, hipStream_t);

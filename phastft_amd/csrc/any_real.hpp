@@ -7,7 +7,7 @@
 // (C2R); the post sweeps write the half spectrum / the real part.  N = 1, 2: one direct kernel.
 //
 //     R2C even   pack + chirp-pad     x -> a = z w_H (n < H), 0 up to M               caller -> workspace    kind kR2cPack
-//                engine, spectrum, engine (planner_any.hpp, unchanged)
+//                engine, spectrum, engine (AnyPlanner::convolve, planner_any.hpp)
 //                chirp-post+untangle  Z = w_H c; X[k], X[H-k] from (Z[k], Z[H-k])     workspace -> caller    kind kR2cUntangle
 //     C2R even   preprocess + pad     z~[k], z~[H-k] from (X[k], X[H-k]); planes swapped    caller -> workspace   kC2rPre
 //                chirp-post+interleave  x[2n] = Im(w_H c) / H, x[2n+1] = Re(w_H c) / H     workspace -> caller   kC2rInterleave

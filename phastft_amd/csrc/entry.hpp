@@ -67,14 +67,10 @@ static int fft_dev_many(T *const *d_re, T *const *d_im, size_t count, size_t n, 
     pl = pl->route_small();  // 4096 / 8192 points: the plan of a single-transform call (Planner::twin)
     PHAST_ON_DEVICE(pl->device);
     typename Planner<T>::Lease L;  // one workspace for the whole list: the transforms follow each other on the stream
-    if (!pl->passes.empty()) {
-        int rc = pl->check_out(L, s);
-        if (rc) return rc;
-    } else {
-        L.stream = s;
-    }
+    int rc = pl->lease(L, s);
+    if (rc) return rc;
     for (size_t i = 0; i < count; ++i) {
-        int rc = direction == PHAST_REVERSE
+        rc = direction == PHAST_REVERSE
                      ? pl->exec_in(L, d_im[i], d_re[i], n, 0, d_im[i], d_re[i], n, 0, 1, 1.0 / (double)n)
                      : pl->exec_in(L, d_re[i], d_im[i], n, 0, d_re[i], d_im[i], n, 0, 1, 1.0);
         if (rc) return rc;
@@ -104,83 +100,62 @@ static int fft_strided_dev(T *d_re, T *d_im, size_t n, size_t batch, size_t dist
     return pl->exec_strided(d_re, d_im, sb, bb, 1.0, s, gl, (unsigned)tw_col0);
 }
 
-// average kernel duration of every pass over `reps` forward transforms of the same buffers
+// average kernel duration of every pass over `reps` calls of run(&timer) on `s`: pass_ms[0 .. np - 1], *n_passes = np, the
+// slots the launches really used (a batch above the scratch runs in chunks, each with its own plan; the plan and the fuse
+// decision of a real transform are exec_in's)
+template <typename F> static int time_passes_of(int reps, float *pass_ms, int *n_passes, hipStream_t s, F &&run) {
+    int np = 1;
+    double acc[4] = {0, 0, 0, 0};
+    for (int r = 0; r < reps; ++r) {
+        PassTimer tm;
+        int rc = run(&tm);
+        if (rc) return rc;
+        PHAST_HIP(hipStreamSynchronize(s));
+        for (size_t i = 0; i < tm.pass_of.size(); ++i) {
+            float ms = 0;
+            PHAST_HIP(hipEventElapsedTime(&ms, tm.ev[2 * i], tm.ev[2 * i + 1]));
+            acc[tm.pass_of[i] & 3] += ms;
+            np = std::max(np, (tm.pass_of[i] & 3) + 1);
+        }
+    }
+    for (int i = 0; i < np; ++i) pass_ms[i] = (float)(acc[i] / reps);
+    *n_passes = np;
+    return PHAST_OK;
+}
+
+// ... of forward transforms of the same buffers
 template <typename T>
 static int time_passes(const Planner<T> *pl, T *d_re, T *d_im, size_t batch, size_t dist, int reps, float *pass_ms,
                        int *n_passes, hipStream_t s) {
     if (!pl || !d_re || !d_im || !pass_ms || !n_passes || reps < 1) return PHAST_ERR_INVALID_ARG;
-    int np = 1;  // the slots the launches really used (a batch above the scratch runs in chunks, each with its own plan)
     PHAST_ON_DEVICE(pl->device);
-    double acc[4] = {0, 0, 0, 0};
-    for (int r = 0; r < reps; ++r) {
-        PassTimer tm;
-        int rc = pl->exec(d_re, d_im, dist, 0, d_re, d_im, dist, 0, batch, 1.0, s, &tm);
-        if (rc) return rc;
-        PHAST_HIP(hipStreamSynchronize(s));
-        for (size_t i = 0; i < tm.pass_of.size(); ++i) {
-            float ms = 0;
-            PHAST_HIP(hipEventElapsedTime(&ms, tm.ev[2 * i], tm.ev[2 * i + 1]));
-            acc[tm.pass_of[i] & 3] += ms;
-            np = std::max(np, (tm.pass_of[i] & 3) + 1);
-        }
-    }
-    for (int i = 0; i < np; ++i) pass_ms[i] = (float)(acc[i] / reps);
-    *n_passes = np;
-    return PHAST_OK;
+    return time_passes_of(reps, pass_ms, n_passes, s, [&](PassTimer *tm) {
+        return pl->exec(d_re, d_im, dist, 0, d_re, d_im, dist, 0, batch, 1.0, s, tm);
+    });
 }
 
-// the same for a real transform: slots 0..np-1 = passes of the inner N/2-point transform, slot np = the untangle sweep
-// (a transform small enough for the one-pass kernel has the untangle fused: one slot)
+// ... of a real transform: slots 0..np-1 = passes of the inner N/2-point transform, slot np = the untangle sweep (a transform
+// small enough for the one-pass kernel has the untangle fused: one slot)
 template <typename T>
 static int time_passes_r2c(const PlannerR2c<T> *pl, const T *d_in, T *d_ore, T *d_oim, size_t batch, size_t in_dist,
                            size_t out_dist, int reps, float *pass_ms, int *n_passes, hipStream_t s) {
     if (!pl || !d_in || !d_ore || !d_oim || !pass_ms || !n_passes || reps < 1) return PHAST_ERR_INVALID_ARG;
-    int np = 1;  // slots the launches really used: the plan and the fuse decision are exec_in's
     PHAST_ON_DEVICE(pl->dit.device);
-    double acc[4] = {0, 0, 0, 0};
-    for (int r = 0; r < reps; ++r) {
-        PassTimer tm;
-        int rc = pl->dit.passes.empty() ? pl->r2c(d_in, d_ore, d_oim, batch, in_dist, out_dist, s)
-                                        : pl->r2c(d_in, d_ore, d_oim, batch, in_dist, out_dist, s, &tm);
-        if (rc) return rc;
-        PHAST_HIP(hipStreamSynchronize(s));
-        for (size_t i = 0; i < tm.pass_of.size(); ++i) {
-            float ms = 0;
-            PHAST_HIP(hipEventElapsedTime(&ms, tm.ev[2 * i], tm.ev[2 * i + 1]));
-            acc[tm.pass_of[i] & 3] += ms;
-            np = std::max(np, (tm.pass_of[i] & 3) + 1);
-        }
-    }
-    for (int i = 0; i < np; ++i) pass_ms[i] = (float)(acc[i] / reps);
-    *n_passes = np;
-    return PHAST_OK;
+    return time_passes_of(reps, pass_ms, n_passes, s, [&](PassTimer *tm) {
+        return pl->r2c(d_in, d_ore, d_oim, batch, in_dist, out_dist, s, pl->dit.passes.empty() ? nullptr : tm);
+    });
 }
 
-// ... and for the inverse real transform: slots 0..np-1 = passes of the inner transform (the first one forms z on load
-// when its fused form exists, c2r_fused.hpp), slot np = the preprocess sweep otherwise
+// ... and of the inverse real transform: slots 0..np-1 = passes of the inner transform (the first one forms z on load when
+// its fused form exists, c2r_fused.hpp), slot np = the preprocess sweep otherwise
 template <typename T>
 static int time_passes_c2r(const PlannerR2c<T> *pl, const T *d_ire, const T *d_iim, T *d_out, size_t batch, size_t in_dist,
                            size_t out_dist, int reps, float *pass_ms, int *n_passes, hipStream_t s) {
     if (!pl || !d_ire || !d_iim || !d_out || !pass_ms || !n_passes || reps < 1) return PHAST_ERR_INVALID_ARG;
-    int np = 1;
     PHAST_ON_DEVICE(pl->dit.device);
-    double acc[4] = {0, 0, 0, 0};
-    for (int r = 0; r < reps; ++r) {
-        PassTimer tm;
-        int rc = pl->dit.passes.empty() ? pl->c2r(d_ire, d_iim, d_out, batch, in_dist, out_dist, s)
-                                        : pl->c2r(d_ire, d_iim, d_out, batch, in_dist, out_dist, s, &tm);
-        if (rc) return rc;
-        PHAST_HIP(hipStreamSynchronize(s));
-        for (size_t i = 0; i < tm.pass_of.size(); ++i) {
-            float ms = 0;
-            PHAST_HIP(hipEventElapsedTime(&ms, tm.ev[2 * i], tm.ev[2 * i + 1]));
-            acc[tm.pass_of[i] & 3] += ms;
-            np = std::max(np, (tm.pass_of[i] & 3) + 1);
-        }
-    }
-    for (int i = 0; i < np; ++i) pass_ms[i] = (float)(acc[i] / reps);
-    *n_passes = np;
-    return PHAST_OK;
+    return time_passes_of(reps, pass_ms, n_passes, s, [&](PassTimer *tm) {
+        return pl->c2r(d_ire, d_iim, d_out, batch, in_dist, out_dist, s, pl->dit.passes.empty() ? nullptr : tm);
+    });
 }
 
 // lib.rs:41-140 (feature complex-nums): interleaved Complex<T> signal, in place.  The reference copies into two

@@ -127,13 +127,8 @@ int Planner<T>::exec(const void *in_re, const void *in_im, size_t in_dist, unsig
         return twin->exec(in_re, in_im, in_dist, in_mode, out_re, out_im, out_dist, out_mode, batch, scale, stream, timer);
     PHAST_ON_DEVICE(device);
     Lease L;
-    if (!passes.empty()) {  // (the one-pass kernel keeps whole transforms on chip: nothing to check out)
-        int rc = check_out(L, stream);
-        if (rc) return rc;
-    } else {
-        L.stream = stream;
-    }
-    return exec_in(L, in_re, in_im, in_dist, in_mode, out_re, out_im, out_dist, out_mode, batch, scale, timer);
+    int rc = lease(L, stream);
+    return rc ? rc : exec_in(L, in_re, in_im, in_dist, in_mode, out_re, out_im, out_dist, out_mode, batch, scale, timer);
 }
 
 // The launches of one batched transform in the leased workspace, on L.stream.

@@ -225,6 +225,13 @@ template <typename T> struct Planner {
     };
     // workspaces (planner_pool.hpp)
     int check_out(Lease &L, hipStream_t stream, int which = 0) const;
+    // the lease of a _dev call on `stream`: a workspace checked out -- or, for the one-pass kernel, which keeps whole
+    // transforms on chip, nothing to check out: just the stream
+    int lease(Lease &L, hipStream_t stream) const {
+        if (!passes.empty()) return check_out(L, stream);
+        L.stream = stream;
+        return PHAST_OK;
+    }
     void check_in(Workspace *ws, hipStream_t stream, bool host_synchronised) const;
     int ensure_scratch(const Lease &L, size_t batch, size_t *cap_out, bool exact = false) const;
     int check_guards(size_t *bad_out) const;

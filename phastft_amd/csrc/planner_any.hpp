@@ -1,7 +1,9 @@
 // planner_any.hpp -- AnyPlanner<T>: complex transforms of any length N (Bluestein, any_len.hpp) on the power-of-two engine.
 // Immutable after init: the inner Planner<T>(M) and the device table Bh = FFT_M(b) / M.  What a call mutates is the caller's
 // workspace (_dev calls) or a workspace of the inner planner's pool (its staging buffer: host-slice calls), so graph capture
-// and concurrent streams and threads need nothing beyond what the engine already does.
+// and concurrent streams and threads need nothing beyond what the engine already does.  The convolution core (convolve),
+// the chunk loop (for_each_chunk) and the stage timer (time_stages_of) serve the real planner too (planner_any_real.hpp),
+// which runs its own pad and post sweeps around the core.
 #pragma once
 
 #include "any_len.hpp"
@@ -9,6 +11,36 @@
 #include "host_api.hpp"
 
 namespace phast {
+
+// measurement hook of the any-length planners: average milliseconds of the five stages (pad, forward engine, spectrum, inverse
+// engine, post) over `reps` calls of run(lease, ev) on a lease of pl on `s`, which record the six events ev[0..5]; blocks
+template <typename T, typename F> static int time_stages_of(const Planner<T> *pl, int reps, float *ms, hipStream_t s, F &&run) {
+    struct Events {
+        hipEvent_t e[6] = {};
+        ~Events() {
+            for (hipEvent_t x : e)
+                if (x) hipEventDestroy(x);
+        }
+    } ev;
+    for (hipEvent_t &x : ev.e) PHAST_HIP(hipEventCreate(&x));
+    double acc[5] = {0, 0, 0, 0, 0};
+    for (int r = 0; r < reps; ++r) {
+        {
+            typename Planner<T>::Lease L;  // checked in before the wait
+            int rc = pl->lease(L, s);
+            if (!rc) rc = run(L, ev.e);
+            if (rc) return rc;
+        }
+        PHAST_HIP(hipStreamSynchronize(s));
+        for (int i = 0; i < 5; ++i) {
+            float t = 0;
+            PHAST_HIP(hipEventElapsedTime(&t, ev.e[i], ev.e[i + 1]));
+            acc[i] += t;
+        }
+    }
+    for (int i = 0; i < 5; ++i) ms[i] = (float)(acc[i] / reps);
+    return PHAST_OK;
+}
 
 template <typename T> struct AnyPlanner {
     size_t n = 0, m = 0;  // N and the convolution length (m == n: a power of two, the pow2 path)
@@ -84,6 +116,44 @@ template <typename T> struct AnyPlanner {
         return pl;
     }
 
+    // The convolution core of `c` transforms on the chirp-padded workspace w (2 c M elements: c re planes, then c im planes),
+    // in place: forward engine, spectrum sweep, inverse engine.  ev: the events ev[1..4] around the three steps (time_stages)
+    int convolve(const Planner<T> *pl, const typename Planner<T>::Lease &L, const typename Planner<T>::Choice &ch, T *w,
+                 size_t c, hipEvent_t *ev) const {
+        hipStream_t s = L.stream;
+        T *w_re = w, *w_im = w + c * m;
+        if (ev) PHAST_HIP(hipEventRecord(ev[1], s));
+        int rc = pl->exec_in(L, w_re, w_im, m, 0, w_re, w_im, m, 0, c, 1.0, nullptr, nullptr, nullptr, nullptr, &ch);
+        if (rc) return rc;
+        if (ev) PHAST_HIP(hipEventRecord(ev[2], s));
+        AnySweepArgs a{};
+        a.out_re = w_re;
+        a.out_im = w_im;
+        a.bh_re = d_bh;
+        a.bh_im = d_bh + m;
+        a.log_m = log_m;
+        a.groups = c * (m / (16 / sizeof(T)));
+        PHAST_HIP(launch_any_sweep<T>(1, true, a, s));
+        if (ev) PHAST_HIP(hipEventRecord(ev[3], s));
+        // the inverse by the swap trick: FFT of (im, re) = (im, re) of M IFFT -- its 1/M is in Bh
+        rc = pl->exec_in(L, w_im, w_re, m, 0, w_im, w_re, m, 0, c, 1.0, nullptr, nullptr, nullptr, nullptr, &ch);
+        if (rc) return rc;
+        if (ev) PHAST_HIP(hipEventRecord(ev[4], s));
+        return PHAST_OK;
+    }
+
+    // f(b0, c) for the batch in chunks of c <= floor(work_len / 2M) transforms from transform b0 on
+    template <typename F> int for_each_chunk(size_t batch, size_t work_len, F &&f) const {
+        size_t chunk = work_len / (2 * m);
+        const size_t cap = ((size_t)1 << 39) / m;  // a launch's groups stay below 2^38
+        if (chunk > cap) chunk = cap;
+        for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+            int rc = f(b0, batch - b0 < chunk ? batch - b0 : chunk);
+            if (rc) return rc;
+        }
+        return PHAST_OK;
+    }
+
     // `c` transforms: x planes (re, im) at b * dist -> X planes at b * dist, through the workspace w (2 c M elements).
     // ev: optional 6 events recorded around the five stages (time_stages)
     int run_chunk(const Planner<T> *pl, const typename Planner<T>::Lease &L, const typename Planner<T>::Choice &ch,
@@ -104,18 +174,8 @@ template <typename T> struct AnyPlanner {
         a.out_im = w_im;
         a.groups = c * (m / V);
         PHAST_HIP(launch_any_sweep<T>(0, al(x_re) && al(x_im) && dist % V == 0, a, s));
-        if (ev) PHAST_HIP(hipEventRecord(ev[1], s));
-        int rc = pl->exec_in(L, w_re, w_im, m, 0, w_re, w_im, m, 0, c, 1.0, nullptr, nullptr, nullptr, nullptr, &ch);
+        int rc = convolve(pl, L, ch, w, c, ev);
         if (rc) return rc;
-        if (ev) PHAST_HIP(hipEventRecord(ev[2], s));
-        a.bh_re = d_bh;
-        a.bh_im = d_bh + m;
-        PHAST_HIP(launch_any_sweep<T>(1, true, a, s));
-        if (ev) PHAST_HIP(hipEventRecord(ev[3], s));
-        // the inverse by the swap trick: FFT of (im, re) = (im, re) of M IFFT -- its 1/M is in Bh
-        rc = pl->exec_in(L, w_im, w_re, m, 0, w_im, w_re, m, 0, c, 1.0, nullptr, nullptr, nullptr, nullptr, &ch);
-        if (rc) return rc;
-        if (ev) PHAST_HIP(hipEventRecord(ev[4], s));
         a.in_re = w_re;
         a.in_im = w_im;
         a.out_re = o_re;
@@ -128,22 +188,16 @@ template <typename T> struct AnyPlanner {
         return PHAST_OK;
     }
 
-    // the batch in chunks of floor(work_len / 2M) transforms, in place in (re, im); the inverse: the forward of (im, re) * 1/N
+    // the batch in chunks, in place in (re, im); the inverse: the forward of (im, re) * 1/N
     int run(const Planner<T> *pl, const typename Planner<T>::Lease &L, T *re, T *im, size_t batch, size_t dist, int direction,
             T *work, size_t work_len, hipEvent_t *ev = nullptr) const {
         const typename Planner<T>::Choice ch = pl->choose(kC2C, 1, 1);
-        size_t chunk = work_len / (2 * m);
-        const size_t cap = ((size_t)1 << 39) / m;  // a launch's groups stay below 2^38
-        if (chunk > cap) chunk = cap;
         const double scale = direction == PHAST_REVERSE ? 1.0 / (double)n : 1.0;
         if (direction == PHAST_REVERSE) std::swap(re, im);
-        for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-            const size_t c = batch - b0 < chunk ? batch - b0 : chunk;
+        return for_each_chunk(batch, work_len, [&](size_t b0, size_t c) {
             T *r = re + b0 * dist, *i = im + b0 * dist;
-            int rc = run_chunk(pl, L, ch, r, i, r, i, c, dist, work, scale, ev);
-            if (rc) return rc;
-        }
-        return PHAST_OK;
+            return run_chunk(pl, L, ch, r, i, r, i, c, dist, work, scale, ev);
+        });
     }
 
     int check_dev(const T *d_re, const T *d_im, size_t num, size_t batch, size_t dist, int direction, const T *d_work,
@@ -167,13 +221,8 @@ template <typename T> struct AnyPlanner {
         const Planner<T> *pl = engine(s);
         PHAST_ON_DEVICE(device);
         typename Planner<T>::Lease L;
-        if (!pl->passes.empty()) {
-            rc = pl->check_out(L, s);
-            if (rc) return rc;
-        } else {
-            L.stream = s;
-        }
-        return run(pl, L, d_re, d_im, batch, dist, direction, d_work, work_len);
+        rc = pl->lease(L, s);
+        return rc ? rc : run(pl, L, d_re, d_im, batch, dist, direction, d_work, work_len);
     }
 
     // host slices: staged through the staging buffer of a workspace checked out of the inner planner's pool (x planes, then
@@ -216,37 +265,9 @@ template <typename T> struct AnyPlanner {
         if (batch == 1) dist = n;
         const Planner<T> *pl = engine(s);
         PHAST_ON_DEVICE(device);
-        hipEvent_t ev[6] = {};
-        struct EventsGone {
-            hipEvent_t *e;
-            ~EventsGone() {
-                for (int i = 0; i < 6; ++i)
-                    if (e[i]) hipEventDestroy(e[i]);
-            }
-        } gone{ev};
-        for (int i = 0; i < 6; ++i) PHAST_HIP(hipEventCreate(&ev[i]));
-        double acc[5] = {0, 0, 0, 0, 0};
-        for (int r = 0; r < reps; ++r) {
-            {
-                typename Planner<T>::Lease L;
-                if (!pl->passes.empty()) {
-                    rc = pl->check_out(L, s);
-                    if (rc) return rc;
-                } else {
-                    L.stream = s;
-                }
-                rc = run(pl, L, d_re, d_im, batch, dist, PHAST_FORWARD, d_work, work_len, ev);
-                if (rc) return rc;
-            }
-            PHAST_HIP(hipStreamSynchronize(s));
-            for (int i = 0; i < 5; ++i) {
-                float t = 0;
-                PHAST_HIP(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-                acc[i] += t;
-            }
-        }
-        for (int i = 0; i < 5; ++i) ms[i] = (float)(acc[i] / reps);
-        return PHAST_OK;
+        return time_stages_of(pl, reps, ms, s, [&](const auto &L, hipEvent_t *ev) {
+            return run(pl, L, d_re, d_im, batch, dist, PHAST_FORWARD, d_work, work_len, ev);
+        });
     }
 };
 

@@ -2,7 +2,9 @@
 // It holds exactly one of: a PlannerR2c<T>(N) (a power of two >= 4: the existing real path, same bits, no workspace), an
 // AnyPlanner<T> of H = N / 2 (even N) or of N (odd N) whose table, spectrum sweep and engine plan it runs between its own
 // sweeps, or, for N = 1 and 2, a Planner<T>(1) whose workspace pool stages host-slice calls.  Immutable after init, no
-// per-call state: what a call mutates is the caller's workspace (_dev) or a workspace of the inner pool (host slices).
+// per-call state: what a call mutates is the caller's workspace (_dev) or a workspace of the inner pool (host slices).  The
+// convolution core, the chunk loop and the stage timer are AnyPlanner's (planner_any.hpp); this file has the real pad and
+// post sweeps around the core, the direct N = 1, 2 kernel and the argument checks.
 #pragma once
 
 #include "any_real.hpp"
@@ -84,23 +86,8 @@ template <typename T> struct AnyRealPlanner {
         const bool vec_in = al(in_a) && (!c2r || al(in_b)) && (c == 1 || in_dist % V == 0);  // one transform: dist unused
         if (ev) PHAST_HIP(hipEventRecord(ev[0], s));
         PHAST_HIP(launch_any_real<T>(c2r ? (odd ? kC2rOddPad : kC2rPre) : (odd ? kR2cOddPad : kR2cPack), vec_in, a, s));
-        if (ev) PHAST_HIP(hipEventRecord(ev[1], s));
-        int rc = pl->exec_in(L, w_re, w_im, m, 0, w_re, w_im, m, 0, c, 1.0, nullptr, nullptr, nullptr, nullptr, &ch);
+        int rc = any->convolve(pl, L, ch, w, c, ev);
         if (rc) return rc;
-        if (ev) PHAST_HIP(hipEventRecord(ev[2], s));
-        AnySweepArgs sp{};  // the complex path's spectrum sweep, unchanged
-        sp.out_re = w_re;
-        sp.out_im = w_im;
-        sp.bh_re = any->d_bh;
-        sp.bh_im = any->d_bh + m;
-        sp.log_m = any->log_m;
-        sp.groups = c * (m / V);
-        PHAST_HIP(launch_any_sweep<T>(1, true, sp, s));
-        if (ev) PHAST_HIP(hipEventRecord(ev[3], s));
-        // the inverse by the swap trick: FFT of (im, re) = (im, re) of M IFFT -- its 1/M is in Bh
-        rc = pl->exec_in(L, w_im, w_re, m, 0, w_im, w_re, m, 0, c, 1.0, nullptr, nullptr, nullptr, nullptr, &ch);
-        if (rc) return rc;
-        if (ev) PHAST_HIP(hipEventRecord(ev[4], s));
         a.in_re = w_re;
         a.in_im = w_im;
         a.out_re = out_a;
@@ -123,20 +110,14 @@ template <typename T> struct AnyRealPlanner {
         return PHAST_OK;
     }
 
-    // the batch in chunks of floor(work_len / 2M) transforms
+    // the batch in chunks (AnyPlanner::for_each_chunk)
     int run(bool c2r, const Planner<T> *pl, const typename Planner<T>::Lease &L, const T *in_a, const T *in_b, T *out_a,
             T *out_b, size_t batch, size_t in_dist, size_t out_dist, T *work, size_t work_len, hipEvent_t *ev = nullptr) const {
         const typename Planner<T>::Choice ch = pl->choose(kC2C, 1, 1);
-        size_t chunk = work_len / (2 * m);
-        const size_t cap = ((size_t)1 << 39) / m;  // a launch's groups stay below 2^38
-        if (chunk > cap) chunk = cap;
-        for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-            const size_t c = batch - b0 < chunk ? batch - b0 : chunk;
-            int rc = run_chunk(c2r, pl, L, ch, in_a + b0 * in_dist, in_b ? in_b + b0 * in_dist : nullptr, out_a + b0 * out_dist,
-                               out_b ? out_b + b0 * out_dist : nullptr, c, in_dist, out_dist, work, ev);
-            if (rc) return rc;
-        }
-        return PHAST_OK;
+        return any->for_each_chunk(batch, work_len, [&](size_t b0, size_t c) {
+            return run_chunk(c2r, pl, L, ch, in_a + b0 * in_dist, in_b ? in_b + b0 * in_dist : nullptr, out_a + b0 * out_dist,
+                             out_b ? out_b + b0 * out_dist : nullptr, c, in_dist, out_dist, work, ev);
+        });
     }
 
     int run_tiny(bool c2r, const T *in_a, T *out_a, T *out_b, size_t batch, size_t in_dist, size_t out_dist, hipStream_t s) const {
@@ -180,13 +161,8 @@ template <typename T> struct AnyRealPlanner {
         if (tiny) return run_tiny(c2r, in_a, out_a, out_b, batch, in_dist, out_dist, s);
         const Planner<T> *pl = any->engine(s);
         typename Planner<T>::Lease L;
-        if (!pl->passes.empty()) {
-            rc = pl->check_out(L, s);
-            if (rc) return rc;
-        } else {
-            L.stream = s;
-        }
-        return run(c2r, pl, L, in_a, in_b, out_a, out_b, batch, in_dist, out_dist, d_work, work_len);
+        rc = pl->lease(L, s);
+        return rc ? rc : run(c2r, pl, L, in_a, in_b, out_a, out_b, batch, in_dist, out_dist, d_work, work_len);
     }
 
     // host slices, staged through the staging buffer of a workspace of the inner pool (input, output, convolution
@@ -250,37 +226,9 @@ template <typename T> struct AnyRealPlanner {
         if (!any || work_len < 2 * m * batch) return PHAST_ERR_INVALID_ARG;
         const Planner<T> *pl = any->engine(s);
         PHAST_ON_DEVICE(device);
-        hipEvent_t ev[6] = {};
-        struct EventsGone {
-            hipEvent_t *e;
-            ~EventsGone() {
-                for (int i = 0; i < 6; ++i)
-                    if (e[i]) hipEventDestroy(e[i]);
-            }
-        } gone{ev};
-        for (int i = 0; i < 6; ++i) PHAST_HIP(hipEventCreate(&ev[i]));
-        double acc[5] = {0, 0, 0, 0, 0};
-        for (int r = 0; r < reps; ++r) {
-            {
-                typename Planner<T>::Lease L;
-                if (!pl->passes.empty()) {
-                    rc = pl->check_out(L, s);
-                    if (rc) return rc;
-                } else {
-                    L.stream = s;
-                }
-                rc = run(c2r, pl, L, in_a, in_b, out_a, out_b, batch, in_dist, out_dist, d_work, work_len, ev);
-                if (rc) return rc;
-            }
-            PHAST_HIP(hipStreamSynchronize(s));
-            for (int i = 0; i < 5; ++i) {
-                float t = 0;
-                PHAST_HIP(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-                acc[i] += t;
-            }
-        }
-        for (int i = 0; i < 5; ++i) ms[i] = (float)(acc[i] / reps);
-        return PHAST_OK;
+        return time_stages_of(pl, reps, ms, s, [&](const auto &L, hipEvent_t *ev) {
+            return run(c2r, pl, L, in_a, in_b, out_a, out_b, batch, in_dist, out_dist, d_work, work_len, ev);
+        });
     }
 };
 

@@ -94,12 +94,8 @@ template <typename T> struct PlannerR2c {
             return twin->r2c(d_in, d_ore, d_oim, batch, in_dist, out_dist, s, timer);
         PHAST_ON_DEVICE(dit.device);
         Lease L;
-        if (!dit.passes.empty()) {
-            int rc = dit.check_out(L, s);
-            if (rc) return rc;
-        } else {
-            L.stream = s;
-        }
+        int rc = dit.lease(L, s);
+        if (rc) return rc;
         return r2c_in(L, d_in, d_ore, d_oim, batch, in_dist, out_dist, timer);
     }
     int r2c_in(const Lease &L, const T *d_in, T *d_ore, T *d_oim, size_t batch, size_t in_dist, size_t out_dist,
@@ -139,12 +135,8 @@ template <typename T> struct PlannerR2c {
             return twin->c2r(d_ire, d_iim, d_out, batch, in_dist, out_dist, s, timer);
         PHAST_ON_DEVICE(dit.device);
         Lease L;
-        if (!dit.passes.empty()) {
-            int rc = dit.check_out(L, s);
-            if (rc) return rc;
-        } else {
-            L.stream = s;
-        }
+        int rc = dit.lease(L, s);
+        if (rc) return rc;
         return c2r_in(L, d_ire, d_iim, d_out, batch, in_dist, out_dist, timer);
     }
     int c2r_in(const Lease &L, const T *d_ire, const T *d_iim, T *d_out, size_t batch, size_t in_dist, size_t out_dist,
