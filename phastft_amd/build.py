@@ -24,10 +24,6 @@ LIB = os.path.join(LIB_DIR, "libphastft_hip.so")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 
 UNITS = ["c_abi", "tile_f64_a", "tile_f64_bc", "tile_f64_bc_wide", "tile_f32_a", "tile_f32_bc", "tile_f32_bc_wide", "tile_f64_r2c", "tile_f32_r2c", "tile_f64_c2r", "tile_f32_c2r", "wave_f64", "wave_f32", "quad_f64", "quad_f32", "small_fft", "bitrev", "complex_nums", "any_len", "any_real", "r2c", "fill", "probe", "twiddle"]
-# built only with --experimental (lib/libphastft_hip_exp.so): nothing at present (round 6: the f32 wave tiles were rebuilt on
-# float2 column pairs and moved into the product)
-EXPERIMENTAL_UNITS = []
-EXPERIMENTAL_FLAGS = ()
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-ffp-contract=fast", "-Rpass-analysis=kernel-resource-usage"]
 # per-unit compiler options (the scheduling strategy is a translation-unit option: tile_dispatch.hpp says why)
@@ -112,16 +108,12 @@ def _resource_usage(remarks: str) -> dict:
 
 
 def build(force: bool = False, jobs: int | None = None, verbose: bool = False, trace: bool = False,
-          extra: tuple = (), tag: str = "", experimental: bool = False) -> str:
+          extra: tuple = (), tag: str = "") -> str:
     """trace=True builds lib/libphastft_hip_trace.so with per-phase s_memtime stamps (tools/trace_tile.py;
     load it with PHASTFT_HIP_LIB=...); the product library never carries them."""
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(LIB_DIR, exist_ok=True)
     units = list(UNITS)
-    if experimental:
-        units += EXPERIMENTAL_UNITS
-        extra = tuple(extra) + EXPERIMENTAL_FLAGS
-        tag = tag + "_exp"
     jobs = jobs or min(len(units), os.cpu_count() or 4)
     lib = LIB.replace(".so", ("_trace" if trace else "") + tag + ".so")  # tag/extra: experimental variants (tools/)
     with cf.ThreadPoolExecutor(jobs) as ex:
@@ -148,7 +140,6 @@ if __name__ == "__main__":
     ap.add_argument("--force", action="store_true")
     ap.add_argument("--jobs", type=int, default=None)
     ap.add_argument("--trace", action="store_true")
-    ap.add_argument("--experimental", action="store_true", help="lib/libphastft_hip_exp.so: + the f32 wave tiles")
     a = ap.parse_args()
-    build(a.force, a.jobs, verbose=True, trace=a.trace, experimental=a.experimental)
+    build(a.force, a.jobs, verbose=True, trace=a.trace)
     sys.exit(0)

@@ -386,31 +386,19 @@ static hipError_t launch_bitrev_u(U *data, unsigned log_n, size_t batch, size_t 
 //                        (2^26: 3.9 vs 3.6 TB/s)
 //   f64, N >= 2^27       128 x 128 tiles held in registers (1 KiB rows): 2^27 3.4 -> 4.1 TB/s, 2^28 3.9 -> 4.0, 2^30 3.8 -> 4.0;
 //                        below that there are too few tiles per CU for its one workgroup per CU (2^26: 3.7 vs 3.9)
-#ifndef PHAST_BITREV_P3_MIN_LOG   // tuning (tools/ab.sh with build(extra=...)): thresholds of the generations
-#define PHAST_BITREV_P3_MIN_LOG 27
-#endif
-#ifndef PHAST_BITREV_P2_MIN_LOG
-#define PHAST_BITREV_P2_MIN_LOG 25
-#endif
-#ifndef PHAST_BITREV_F32_P2_MIN_LOG
-#define PHAST_BITREV_F32_P2_MIN_LOG 99
-#endif
+constexpr unsigned kBitrevP3MinLog = 27, kBitrevP2MinLog = 25;
 template <> hipError_t launch_bitrev<double>(double *data, unsigned log_n, size_t batch, size_t dist, hipStream_t s) {
     auto *p = reinterpret_cast<unsigned long long *>(data);
     if (log_n < 12) return launch_bitrev_u<unsigned long long, 5, 256>(p, log_n, batch, dist, s);
     const bool even = (dist & 1) == 0 && (reinterpret_cast<size_t>(data) & 15) == 0;  // 16-byte accesses need it
-    if (even && log_n >= PHAST_BITREV_P3_MIN_LOG) return launch_bitrev_persistent3<unsigned long long, 7, 1024>(p, log_n, batch, dist, s);
-    if (even && (((size_t)batch << log_n) >= ((size_t)1 << PHAST_BITREV_P2_MIN_LOG)))
+    if (even && log_n >= kBitrevP3MinLog) return launch_bitrev_persistent3<unsigned long long, 7, 1024>(p, log_n, batch, dist, s);
+    if (even && (((size_t)batch << log_n) >= ((size_t)1 << kBitrevP2MinLog)))
         return launch_bitrev_persistent2<unsigned long long, 6, 256, true>(p, log_n, batch, dist, s, 4);
     return launch_bitrev_persistent<unsigned long long, 6, 512>(p, log_n, batch, dist, s, 4);
 }
 template <> hipError_t launch_bitrev<float>(float *data, unsigned log_n, size_t batch, size_t dist, hipStream_t s) {
     auto *p = reinterpret_cast<unsigned *>(data);
     if (log_n < 12) return launch_bitrev_u<unsigned, 6, 512>(p, log_n, batch, dist, s);
-    const bool even = (dist & 3) == 0 && (reinterpret_cast<size_t>(data) & 15) == 0;
-    // (the default of 99 means "never": the comparison is guarded -- a 64-bit shift by 99 is undefined)
-    if (even && PHAST_BITREV_F32_P2_MIN_LOG < 64 && (((size_t)batch << log_n) >= ((size_t)1 << (PHAST_BITREV_F32_P2_MIN_LOG & 63))))
-        return launch_bitrev_persistent2<unsigned, 6, 256, true>(p, log_n, batch, dist, s, 4);
     return launch_bitrev_persistent<unsigned, 6, 512>(p, log_n, batch, dist, s, 4);
 }
 

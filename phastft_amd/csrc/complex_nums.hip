@@ -10,11 +10,9 @@
 // slices); rows of a wave are contiguous in all three streams, non-temporal on both sides (nothing is read twice).
 #include "kernels.hpp"
 
-#ifndef PHAST_CN_UNROLL  // 16-byte groups per thread
-#define PHAST_CN_UNROLL 1
-#endif
-
 namespace phast {
+
+constexpr int kCnUnroll = 1;  // 16-byte groups per thread
 
 template <typename T> struct Vec16;  // 16 bytes of T
 template <> struct Vec16<double> { typedef double type __attribute__((ext_vector_type(2))); static constexpr int N = 2; };
@@ -27,12 +25,12 @@ __global__ void __launch_bounds__(256) deinterleave_vec_kernel(const T *__restri
     constexpr int N = Vec16<T>::N;
     const V *vin = reinterpret_cast<const V *>(in);
     V *va = reinterpret_cast<V *>(a), *vb = reinterpret_cast<V *>(b);
-    // ONE step per thread, one workgroup per 256 * U groups, workgroups dispatched in address order: measured against the
+    // ONE step per thread, one workgroup per 256 * kCnUnroll groups, workgroups dispatched in address order: measured against the
     // persistent grid-stride form of the same loop (tools/complex_nums_rate.py, profiles/r06_complex_nums.log): 6.3 against
     // 5.1-5.7 TB/s for 4 GiB of f64 pairs -- more than the grid-stride copy probe reaches on the same box
-    const size_t g0 = (size_t)blockIdx.x * (256 * PHAST_CN_UNROLL) + threadIdx.x;
+    const size_t g0 = (size_t)blockIdx.x * (256 * kCnUnroll) + threadIdx.x;
 #pragma unroll
-    for (int u = 0; u < PHAST_CN_UNROLL; ++u) {
+    for (int u = 0; u < kCnUnroll; ++u) {
         const size_t g = g0 + (size_t)u * 256;
         if (g >= groups) break;
         const V lo = __builtin_nontemporal_load(vin + 2 * g), hi = __builtin_nontemporal_load(vin + 2 * g + 1);
@@ -63,9 +61,9 @@ __global__ void __launch_bounds__(256) combine_vec_kernel(const T *__restrict__ 
     constexpr int N = Vec16<T>::N;
     const V *vr = reinterpret_cast<const V *>(re), *vi = reinterpret_cast<const V *>(im);
     V *vo = reinterpret_cast<V *>(out);
-    const size_t g0 = (size_t)blockIdx.x * (256 * PHAST_CN_UNROLL) + threadIdx.x;
+    const size_t g0 = (size_t)blockIdx.x * (256 * kCnUnroll) + threadIdx.x;
 #pragma unroll
-    for (int u = 0; u < PHAST_CN_UNROLL; ++u) {
+    for (int u = 0; u < kCnUnroll; ++u) {
         const size_t g = g0 + (size_t)u * 256;
         if (g >= groups) break;
         const V x = __builtin_nontemporal_load(vr + g), y = __builtin_nontemporal_load(vi + g);
@@ -94,8 +92,8 @@ static inline unsigned sweep_grid(size_t items) {  // the element-wise tail kern
     const size_t want = (items + 255) / 256;
     return (unsigned)(want < 1 ? 1 : want > 8192 ? 8192 : want);
 }
-// the 16-byte kernels: one workgroup per 256 * PHAST_CN_UNROLL groups; beyond 2^31 - 1 workgroups (2^43 scalars) the call is split
-static constexpr size_t kVecBlockGroups = (size_t)256 * PHAST_CN_UNROLL;
+// the 16-byte kernels: one workgroup per 256 * kCnUnroll groups; beyond 2^31 - 1 workgroups (2^43 scalars) the call is split
+static constexpr size_t kVecBlockGroups = (size_t)256 * kCnUnroll;
 static constexpr size_t kVecMaxGroups = kVecBlockGroups * 0x7fffffffull;
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 

@@ -139,11 +139,7 @@ constexpr unsigned kFuseBelow = 0x20;  // real_plan only: ranked WITH the fused 
 // 2^21 x 8 59 -> 66; 2^14 / 2^16 batches +2-7 %; the three-pass plans +0-3 % in f64 and +3-5 % in f32; one transform of
 // 2^20 (wave / quad tiles) unchanged.  128 ... 640 bytes of pad are equivalent within the noise except two points:
 // 256 bytes is the best f32 pad (157 against 150 on the batch), 384 bytes the best f64 pad on the small batches.
-#ifdef PHAST_SCRATCH_PAD_BYTES  // tools: one pad for both types (0 = round 2's power-of-two layout)
-constexpr unsigned scratch_pad_bytes(size_t) { return PHAST_SCRATCH_PAD_BYTES; }
-#else
 constexpr unsigned scratch_pad_bytes(size_t elem_bytes) { return elem_bytes == 8 ? 384u : 256u; }
-#endif
 
 // ---- geometry of one pass (see TileArgs in common.hpp) ----
 struct PassGeom {
@@ -332,7 +328,7 @@ inline bool real_plan(unsigned L, bool c2r, std::vector<unsigned> &lrs, std::vec
 // end (and begin) in 32-point-per-thread passes on 16384- / 32768-point tiles, most of which have no fused untangle /
 // preprocess form: batched R2C then ran three sweeps where two would do, and batched C2R kept a first pass cut for planar
 // input.  Ranked with 2^27 real samples in flight (tools/sweep_real_batch.py, profiles/r04_sweep_real_batch.log):
-// and kept where an alternating A/B of the table (PHAST_REAL_PLANS=0|1, profiles/r04_real_batch_ab.log) confirmed it:
+// and kept where an alternating A/B of the table against the C2C plans (profiles/r04_real_batch_ab.log) confirmed it:
 //   r2c_fft_f32  2^15 749 -> 567 us, 2^17 613 -> 535, 2^18 711 -> 547, 2^19 736 -> 509, 2^20 924 -> 597 (145 -> 225
 //                GSamples/s), 2^21 790 -> 686;   r2c_fft_f64  2^15 1401 -> 1088, 2^16 1168 -> 1001, 2^17 .. 2^20 + 8 .. 17 %
 //   c2r_fft_f32  2^17 566 -> 477, 2^18 .. 2^20 + 3 .. 7 %;   c2r_fft_f64  2^15 .. 2^20 + 2 .. 11 %

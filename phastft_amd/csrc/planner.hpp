@@ -32,21 +32,6 @@ struct R2cFuse {
     const void *tw3n;  // W_N three-level table, N = 2 * (inner transform length)
     unsigned twn_bits;
 };
-static bool c2r_fuse_enabled() {  // PHAST_C2R_FUSE=0: keep the C2R preprocess as a sweep of its own (tools, A/B)
-    static const bool v = [] {
-        const char *e = std::getenv("PHAST_C2R_FUSE");
-        return !(e && *e == '0');
-    }();
-    return v;
-}
-static bool r2c_fuse_enabled() {  // PHAST_R2C_FUSE=0: keep the untangle as a sweep of its own (tools, A/B)
-    static const bool v = [] {
-        const char *e = std::getenv("PHAST_R2C_FUSE");
-        return !(e && *e == '0');
-    }();
-    return v;
-}
-
 static const char *test_perturb_hook() {  // PHAST_TEST_PERTURB_TW3: tests only (Planner::table)
     static const char *v = [] {
         const char *e = std::getenv("PHAST_TEST_PERTURB_TW3");
@@ -300,20 +285,6 @@ template <typename T> struct Planner {
     const std::vector<PassDesc> &plan_for(size_t batch) const;
     const std::vector<PassDesc> &plan_for_r2c(size_t batch, bool fusing = true) const;
     const std::vector<PassDesc> &plan_for_c2r(size_t batch) const;
-    static bool c2r_lat_ok() {  // PHAST_C2R_LAT=0: tools (A/B)
-        static const bool v = [] {
-            const char *e = std::getenv("PHAST_C2R_LAT");
-            return !(e && *e == '0');
-        }();
-        return v;
-    }
-    static bool r2c_lat_ok() {  // PHAST_R2C_LAT=0: tools (A/B)
-        static const bool v = [] {
-            const char *e = std::getenv("PHAST_R2C_LAT");
-            return !(e && *e == '0');
-        }();
-        return v;
-    }
 
     int set_plan(const std::vector<unsigned> &lrs, const std::vector<unsigned> &tls, int which = 0, unsigned lp = 4);
 
@@ -330,31 +301,17 @@ template <typename T> struct Planner {
         return v;
     }
     // ... and a batch of them is one workgroup EACH: below half the chip's CUs the twin still wins (2^13 x 128 f64: 17.8 us
-    // against 21.8, x 32: 11.3 against 17.3; profiles/r04_small_twin_batch.log).  PHAST_SMALL_TWIN_MAX_BATCH: tools.
+    // against 21.8, x 32: 11.3 against 17.3; profiles/r04_small_twin_batch.log): the twin serves up to kTwinMaxBatch.
     // Round 5: 4096 points as well.  Measured per call kind (profiles/r05_small_twin_4096.log, one transform, graph over a cold
     // ring): C2R of 8192 real points 12.5 -> 8.7 us in f64, 11.1 -> 6.7 in f32 (two passes with the preprocess fused into the
     // first against one workgroup's chain) -- adopted; R2C 9.8 -> 10.4 / 8.1 -> 8.8 (the untangle becomes a third kernel) -- not;
     // C2C: 8.48 -> 7.67 us (f64), 6.72 -> 6.50 (f32) once the capture fix let the twin run (call 4's A/B) -- adopted; 2^11 stays
-    // in one workgroup (7.5 us).  PHAST_SMALL_TWIN_MIN_LOG=13 restores round 4's threshold for C2C (tools: A/B).
-    static unsigned twin_min_log_c2c() {
-        static const unsigned v = [] {
-            const char *e = std::getenv("PHAST_SMALL_TWIN_MIN_LOG");
-            const unsigned m = (e && *e) ? (unsigned)std::atoi(e) : kTwinMinLog;
-            return m < kTwinMinLog ? kTwinMinLog : m;
-        }();
-        return v;
-    }
+    // in one workgroup (7.5 us).  C2C uses the twin from kTwinMinLog on, as init creates it.
+    static constexpr size_t kTwinMaxBatch = 128;
     static constexpr unsigned kTwinMinLogR2c = kSmallMaxLog, kTwinMinLogC2r = kTwinMinLog;  // log2 of the INNER length
     // the planner a call of ONE (or a few) C2C transforms runs on: the multi-pass twin where this length has one in use
     const Planner<T> *route_small(size_t batch = 1) const {
-        return (twin && log_n >= twin_min_log_c2c() && batch <= twin_max_batch()) ? twin.get() : this;
-    }
-    static size_t twin_max_batch() {
-        static const size_t v = [] {
-            const char *e = std::getenv("PHAST_SMALL_TWIN_MAX_BATCH");
-            return (e && *e) ? (size_t)std::atoll(e) : (size_t)128;
-        }();
-        return v;
+        return (twin && batch <= kTwinMaxBatch) ? twin.get() : this;
     }
 
     int init(size_t num_points, bool force_multi = false, bool with_twin = true);
@@ -402,18 +359,9 @@ template <typename T> struct Planner {
     // The fused R2C last pass runs HALF as many tiles, each twice as long: it pays once the tiles fill the chip -- from
     // 2^23 complex points in flight (profiles/r03_r2c_fused_ab.log: f32 N = 2^24 108.6 -> 89.9 us; below, one transform is
     // latency-bound and loses: N = 2^20 19.5 -> 31.6 us, 2^22 39.4 -> 42.9).
-    static unsigned fuse_min_log() {  // PHAST_R2C_FUSE_MIN_LOG: tools (A/B of the threshold)
-        static const unsigned v = [] {
-            const char *e = std::getenv("PHAST_R2C_FUSE_MIN_LOG");
-            return (e && *e) ? (unsigned)std::atoi(e) : 0u;
-        }();
-        return v;
-    }
     bool fuse_pays(size_t batch) const {
-        const unsigned min_log = fuse_min_log() ? fuse_min_log() : 23u;
-        if (!r2c_fuse_enabled()) return false;
         if (batch <= 2 && r2c_table_fuses && !passes_r2c.empty()) return true;  // a plan cut for it: 2048-point last-pass tiles
-        return batch * n >= ((size_t)1 << min_log);
+        return batch * n >= ((size_t)1 << 23);
     }
     int exec(const void *in_re, const void *in_im, size_t in_dist, unsigned in_mode, void *out_re, void *out_im, size_t out_dist,
                  unsigned out_mode, size_t batch, double scale, hipStream_t stream, PassTimer *timer = nullptr) const;

@@ -31,8 +31,7 @@ template <typename T> const std::vector<PassDesc> &Planner<T>::plan_for_r2c(size
     if (batch <= 2 && !passes_r2c.empty()) return passes_r2c;  // ranked for R2C itself (plan.hpp: real_plan)
     const std::vector<PassDesc> &ps = plan_for(batch);
     if (&ps == &passes && !passes_r2c_tp.empty()) return passes_r2c_tp;  // ... and for batches of them (real_batch_plan)
-    if (fusing && !ps.empty() && ps.back().r2c_blocks == 0 && log_n <= 25 && !passes_lat.empty() && passes_lat.back().r2c_blocks > 0 &&
-        r2c_lat_ok())
+    if (fusing && !ps.empty() && ps.back().r2c_blocks == 0 && log_n <= 25 && !passes_lat.empty() && passes_lat.back().r2c_blocks > 0)
         return passes_lat;
     return ps;
 }
@@ -44,7 +43,7 @@ template <typename T> const std::vector<PassDesc> &Planner<T>::plan_for_c2r(size
     const std::vector<PassDesc> &ps = (batch <= 2 && !passes_c2r_one.empty())                 ? passes_c2r_one
                                       : (&ps0 == &passes_lat && !passes_c2r_lat.empty()) ? passes_c2r_lat
                                                                                          : ps0;
-    if (!ps.empty() && ps.front().c2r_blocks == 0 && !passes_lat.empty() && passes_lat.front().c2r_blocks > 0 && c2r_lat_ok())
+    if (!ps.empty() && ps.front().c2r_blocks == 0 && !passes_lat.empty() && passes_lat.front().c2r_blocks > 0)
         return passes_lat;
     return ps;
 }
@@ -152,7 +151,7 @@ template <typename T> typename Planner<T>::Choice Planner<T>::choose(int kind, s
     Choice c;
     if (const TunedPlan *t = use_tuned ? tuned_for(kind, batch) : nullptr) {  // measured (tune.hpp) or supplied as wisdom
         c.passes = &t->passes;
-        c.r2c_fuse = kind == kR2C && t->fuse && r2c_fuse_enabled();
+        c.r2c_fuse = kind == kR2C && t->fuse;
         c.tuned = t;
         return c;
     }
@@ -284,18 +283,10 @@ template <typename T> int Planner<T>::default_plans() {
 // of what the C2C plans were cut for (and of R2C: pairs in, planes out).  Where a plan gives its first pass rows of less
 // than a 128-byte line of planar elements and its last pass wider ones (f32: [256x16A][256x16][128x32] -- 64-byte rows
 // exactly where C2R has FOUR streams of them per tile: re / im of the element and of its mirror partner), the same passes
-// in reverse order serve C2R better: [128x32A][256x16][256x16].  PHAST_C2R_REV=0: tools (A/B).
+// in reverse order serve C2R better: [128x32A][256x16][256x16].
 template <typename T> int Planner<T>::make_c2r_plans() {
-    static const bool rev = [] {
-        const char *e = std::getenv("PHAST_C2R_REV");
-        return !(e && *e == '0');
-    }();
-    static const bool table = [] {  // PHAST_REAL_PLANS=0: R2C / C2R keep the C2C plans (tools: A/B, tools/sweep_real.py)
-        const char *e = std::getenv("PHAST_REAL_PLANS");
-        return !(e && *e == '0');
-    }();
     // 1. the ranked plans of ONE real transform (plan.hpp: real_plan)
-    for (int c2r = 0; c2r < 2 && table; ++c2r) {
+    for (int c2r = 0; c2r < 2; ++c2r) {
         std::vector<unsigned> lrs, tls;
         unsigned lp = 4;
         if (!real_plan<T>(log_n, c2r != 0, lrs, tls, lp)) continue;
@@ -305,7 +296,7 @@ template <typename T> int Planner<T>::make_c2r_plans() {
         if (!c2r) r2c_table_fuses = rc == PHAST_OK && fuse_below;
     }
     // 1b. ... and of batches of them in the throughput regime (plan.hpp: real_batch_plan)
-    for (int c2r = 0; c2r < 2 && table; ++c2r) {
+    for (int c2r = 0; c2r < 2; ++c2r) {
         std::vector<unsigned> lrs, tls;
         unsigned lp = 4;
         if (!real_batch_plan<T>(log_n, c2r != 0, lrs, tls, lp)) continue;
@@ -313,7 +304,7 @@ template <typename T> int Planner<T>::make_c2r_plans() {
         if (rc != PHAST_OK && rc != PHAST_ERR_INVALID_ARG) return rc;
     }
     // 2. C2R, two-pass plans: the reversed order
-    for (int k = 0; k < 2 && rev; ++k) {
+    for (int k = 0; k < 2; ++k) {
         if (k == 0 && !passes_c2r_one.empty()) continue;
         const std::vector<PassDesc> &src = k == 0 ? passes_one : passes_lat;
         // (three-pass plans: measured and NOT reversed -- f32 2^24 first pass 38 -> 35 us but the middle pass, now behind
@@ -406,7 +397,7 @@ template <typename T> std::string Planner<T>::describe_call(int kind, size_t bat
         s += buf;
     }
     if (kind == kR2C && c.r2c_fuse && !v->empty() && v->back().r2c_blocks > 0) s += " untangle-fused";
-    if (kind == kC2R && !v->empty() && v->front().c2r_blocks > 0 && c2r_fuse_enabled()) s += " preprocess-fused";
+    if (kind == kC2R && !v->empty() && v->front().c2r_blocks > 0) s += " preprocess-fused";
     return s;
 }
 

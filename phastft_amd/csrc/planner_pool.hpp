@@ -268,7 +268,7 @@ template <typename T> bool Planner<T>::capture_ready(hipStream_t stream) const {
 // its multi-pass twin, which is what serves its small batches
 template <typename T> int Planner<T>::reserve_batch(size_t max_batch) {
     if (max_batch == 0) return PHAST_ERR_INVALID_ARG;
-    if (passes.empty()) return twin ? twin->reserve_batch(std::min(max_batch, twin_max_batch())) : PHAST_OK;
+    if (passes.empty()) return twin ? twin->reserve_batch(std::min(max_batch, kTwinMaxBatch)) : PHAST_OK;
     PHAST_ON_DEVICE(device);
     reserve = max_batch;
     Lease L;

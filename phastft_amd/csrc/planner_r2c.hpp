@@ -77,13 +77,13 @@ template <typename T> struct PlannerR2c {
     // the planner a call of ONE (or a few) real transforms runs on (see Planner::kTwinMinLogR2c / kTwinMinLogC2r)
     const PlannerR2c<T> *route_small(bool c2r, size_t batch = 1) const {
         const unsigned min_log = c2r ? Planner<T>::kTwinMinLogC2r : Planner<T>::kTwinMinLogR2c;
-        return (twin && dit.log_n >= min_log && batch <= Planner<T>::twin_max_batch()) ? twin.get() : this;
+        return (twin && dit.log_n >= min_log && batch <= Planner<T>::kTwinMaxBatch) ? twin.get() : this;
     }
     // PlannerMode::Tune for the real transforms (tune.hpp)
     int tune(int kind, size_t batch, typename Planner<T>::TuneReport *rep);
     // C2R: does the first pass of `ch` form z on load (c2r_fused.hpp), or does the preprocess run as a sweep of its own?
     static bool c2r_fuses(const typename Planner<T>::Choice &ch) {
-        return c2r_fuse_enabled() && ch.passes && !ch.passes->empty() && ch.passes->front().c2r_blocks > 0;
+        return ch.passes && !ch.passes->empty() && ch.passes->front().c2r_blocks > 0;
     }
     // r2c.rs:535-593 / 607-662 on device pointers (a _dev call: checks a workspace out for the enqueue)
     int r2c(const T *d_in, T *d_ore, T *d_oim, size_t batch, size_t in_dist, size_t out_dist, hipStream_t s,

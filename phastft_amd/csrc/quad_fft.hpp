@@ -54,13 +54,7 @@ template <typename T> struct QuadBody {
     static constexpr int EXCH = P * NT;  // registers (V) per plane of the exchange buffer [register][wave][lane]
     typedef V VU __attribute__((aligned(sizeof(T))));  // a register's worth in the caller's memory: element alignment only
     static constexpr int TWQ = 128;      // staged entries of the step-twiddle table: W_256^j (j < 64), then W_64^j (j < 64)
-#ifndef PHAST_WQ_NT_LOADS
-#define PHAST_WQ_NT_LOADS 1
-#endif
-#ifndef PHAST_WQ_NT_STORES
-#define PHAST_WQ_NT_STORES 1
-#endif
-    static constexpr bool NT_LOAD = PHAST_WQ_NT_LOADS, NT_STORE = PHAST_WQ_NT_STORES;
+    // global loads and stores are non-temporal, as in the wave tiles (WaveBody)
 
     struct Regs {
         V re[P], im[P];
@@ -95,13 +89,8 @@ template <typename T> struct QuadBody {
             const size_t urow = (size_t)(64 * (Q >> 2) + 16 * (Q & 3)) * a.in_row_stride;
             const VU *qr = reinterpret_cast<const VU *>(reinterpret_cast<const char *>(pr + urow) + vbyte);
             const VU *qi = reinterpret_cast<const VU *>(reinterpret_cast<const char *>(pi + urow) + vbyte);
-            if constexpr (NT_LOAD) {
-                r.re[Q] = __builtin_nontemporal_load(qr);
-                r.im[Q] = __builtin_nontemporal_load(qi);
-            } else {
-                r.re[Q] = *qr;
-                r.im[Q] = *qi;
-            }
+            r.re[Q] = __builtin_nontemporal_load(qr);
+            r.im[Q] = __builtin_nontemporal_load(qi);
         });
     }
 
@@ -203,13 +192,8 @@ template <typename T> struct QuadBody {
             if constexpr (!PAIRS) {
                 VU *qr = reinterpret_cast<VU *>(reinterpret_cast<char *>(reinterpret_cast<T *>(a.out_re) + at) + vbyte);
                 VU *qi = reinterpret_cast<VU *>(reinterpret_cast<char *>(reinterpret_cast<T *>(a.out_im) + at) + vbyte);
-                if constexpr (NT_STORE) {
-                    __builtin_nontemporal_store(re, qr);
-                    __builtin_nontemporal_store(im, qi);
-                } else {
-                    *qr = re;
-                    *qi = im;
-                }
+                __builtin_nontemporal_store(re, qr);
+                __builtin_nontemporal_store(im, qi);
             } else {
                 const V x = a.out_interleaved == 2 ? im : re, y = a.out_interleaved == 2 ? re : im;
                 cx *q = reinterpret_cast<cx *>(reinterpret_cast<char *>(reinterpret_cast<cx *>(a.out_re) + at) + 2u * vbyte);

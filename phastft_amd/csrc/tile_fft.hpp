@@ -26,24 +26,12 @@
 
 #include "common.hpp"
 
-#ifndef PHAST_TW_PROG_MIN_LR  // shapes whose pre-twiddle is a progression instead of P look-ups (tuning: tools/cmp_throughput.py)
-#define PHAST_TW_PROG_MIN_LR 9
-#endif
-#ifndef PHAST_TW_PROG_MIN_LP
-#define PHAST_TW_PROG_MIN_LP 5
-#endif
-
-#ifndef PHAST_RUNNING_ROW_PTR  // measured, not adopted: see TileBody::load_raw
-#define PHAST_RUNNING_ROW_PTR 0
-#endif
-#ifndef PHAST_FRESH_TID
-#define PHAST_FRESH_TID 1
-#endif
-#ifndef PHAST_TW_PROG_G  // running values of the progression form of the pre-twiddle (common.hpp: tw_progression)
-#define PHAST_TW_PROG_G(P) ((P) >= 32 ? 8 : 4)
-#endif
-
 namespace phast {
+
+// f64 shapes whose pre-twiddle is a progression instead of P look-ups (TileBody::PROG)
+constexpr int kTwProgMinLR = 9, kTwProgMinLP = 5;
+// running values of the progression form of the pre-twiddle (common.hpp: tw_progression)
+constexpr int tw_prog_groups(int P) { return P >= 32 ? 8 : 4; }
 
 // ---- literal twiddles: (re, im) *= W_N^J = exp(-2*pi*i*J/N), N in {2,4,8,16,32}, 0 <= J < N/2 ----
 // cos(a*pi/16), a = 0..8, correctly rounded
@@ -151,10 +139,7 @@ template <typename T, int LR, int LC, int LP, bool PRE_TW, bool TRANSPOSE, bool 
     // out as runs of M elements straight from the registers, and one whole LDS round trip (two or four barriers) of the
     // pass is gone.  The last exchange then has a column pitch of COLS + 32/M cells, which keeps the row-fastest
     // readers (and the column-fastest writers) free of bank conflicts (tests/test_emulator.py audits every shape).
-#ifndef PHAST_DIRECT_RUNS
-#define PHAST_DIRECT_RUNS 1
-#endif
-    static constexpr bool DIRECT = PHAST_DIRECT_RUNS && ALLOW_DIRECT && TRANSPOSE && S >= 2 && M * (int)sizeof(T) >= 128 && M <= 32 &&
+    static constexpr bool DIRECT = ALLOW_DIRECT && TRANSPOSE && S >= 2 && M * (int)sizeof(T) >= 128 && M <= 32 &&
                                    COLS * (int)sizeof(T) >= 128;  // (narrower tiles: a write group spans rows, pitch rules differ)
     static constexpr int PITCH_L = DIRECT ? COLS + 32 / M : COLS;  // column pitch of exchange S - 1
     template <int E> static constexpr int pitch() { return (DIRECT && E == S - 1) ? PITCH_L : COLS; }
@@ -164,15 +149,9 @@ template <typename T, int LR, int LC, int LP, bool PRE_TW, bool TRANSPOSE, bool 
     static constexpr int EXCH = EXCH_E1 > EXCH_ET ? (EXCH_E1 > EXCH_EL ? EXCH_E1 : EXCH_EL) : (EXCH_ET > EXCH_EL ? EXCH_ET : EXCH_EL);
     // Non-temporal global accesses when a tile row is a whole 128-byte line or more: every byte is touched once
     // per pass, and the strided-copy microbenchmark gains 5-10 % (profiles/r01_strided_copy_nt.log).  Narrower
-    // rows share their line with the neighbouring tile and NEED the L2 (nt loads cost 25 % there).
+    // rows share their line with the neighbouring tile and NEED the L2 (nt loads cost 25 % there).  Loads and stores
+    // both take the hint (the two halves measured separately: profiles/r03_nt_halves.log).
     static constexpr bool NT_HINT = COLS * sizeof(T) >= 128;
-#ifndef PHAST_TILE_NT_LOADS  // tools only: the two halves of the hint separately (profiles/r03_nt_halves.log)
-#define PHAST_TILE_NT_LOADS 1
-#endif
-#ifndef PHAST_TILE_NT_STORES
-#define PHAST_TILE_NT_STORES 1
-#endif
-    static constexpr bool NT_LD = NT_HINT && PHAST_TILE_NT_LOADS, NT_ST = NT_HINT && PHAST_TILE_NT_STORES;
     static_assert(LR >= 1 && LR <= 13, "tile FFT length 2..8192 (the multi-pass plans use 64..1024)");
     static_assert(LP >= 1 && LP <= 5 && LP <= LR, "2..32 points per thread");
     static_assert(NT <= 1024 && NT >= 64, "64..1024 threads per workgroup");
@@ -186,7 +165,7 @@ template <typename T, int LR, int LC, int LP, bool PRE_TW, bool TRANSPOSE, bool 
     // (round 4: in f32 every shape takes the progression -- profiles/r04_prog_f32_ab.log: one transform of 2^22 / 2^23 points
     // +3.7 %, 2^20 +1.5 %, 8 x 2^20 +2 %, 2^24 unchanged; the same switch in f64 is neutral to -3 %, so f64 keeps the shape
     // condition)
-    static constexpr bool PROG = PRE_TW && (sizeof(T) == 4 || (LR >= PHAST_TW_PROG_MIN_LR && LP >= PHAST_TW_PROG_MIN_LP));
+    static constexpr bool PROG = PRE_TW && (sizeof(T) == 4 || (LR >= kTwProgMinLR && LP >= kTwProgMinLP));
     // ... which may as well come straight from global memory when the three-level tables (48 KiB from N = 2^28 on)
     // no longer fit the LDS next to the tile: the 16384-point tiles stay available for the largest transforms
     // (2^28 f64: 1024 x 8 tiles with 64-byte rows were the fallback, 20 % slower)
@@ -245,28 +224,18 @@ template <typename T, int LR, int LC, int LP, bool PRE_TW, bool TRANSPOSE, bool 
             const T *pi = reinterpret_cast<const T *>(a.in_im) + ubase;
             // With P independent 64-bit row bases per plane the compiler materialises all of them up front -- 128 SGPRs for
             // 32 rows x 2 planes, 50-79 of them parked in VGPR lanes (v_writelane / v_readlane) in the 32-point kernels.
-            // PHAST_RUNNING_ROW_PTR=1 makes them running pointers (two scalar adds per row, no SGPR spills) -- and the
-            // loads then issue one address computation apart instead of back to back: the 256 x 64 pass of 2^24 x 4 ran
-            // 4 % SLOWER, nothing else moved (profiles/r03_ablation_tid_rowptr.log).  Not adopted.
-            const size_t ustep = (size_t)M * a.in_row_stride;
-            (void)ustep;
+            // Running row pointers instead (two scalar adds per row, no SGPR spills) issue the loads one address
+            // computation apart instead of back to back: the 256 x 64 pass of 2^24 x 4 ran 4 % SLOWER, nothing else
+            // moved (profiles/r03_ablation_tid_rowptr.log), and that variant was removed.
             static_for<0, P>([&](auto j) {
-#if PHAST_RUNNING_ROW_PTR
-                const size_t urow = 0;
-#else
                 const size_t urow = (size_t)(decltype(j)::value * M) * a.in_row_stride;
-#endif
-                if constexpr (NT_LD) {
+                if constexpr (NT_HINT) {
                     r.re[j] = __builtin_nontemporal_load(pr + urow + voff);
                     r.im[j] = __builtin_nontemporal_load(pi + urow + voff);
                 } else {
                     r.re[j] = (pr + urow)[voff];
                     r.im[j] = (pi + urow)[voff];
                 }
-#if PHAST_RUNNING_ROW_PTR
-                pr += ustep;
-                pi += ustep;
-#endif
             });
         } else {
             const cx *pz = reinterpret_cast<const cx *>(a.in_re) + ubase;
@@ -297,7 +266,7 @@ template <typename T, int LR, int LC, int LP, bool PRE_TW, bool TRANSPOSE, bool 
         T br, bi, dr, di;
         tw3_combine<T>(tb, br, bi);
         tw3_combine<T>(td, dr, di);
-        tw_progression<T, P, PHAST_TW_PROG_G(P)>(br, bi, dr, di, [&](auto j, T wr, T wi) {
+        tw_progression<T, P, tw_prog_groups(P)>(br, bi, dr, di, [&](auto j, T wr, T wi) {
             cmul(r.re[decltype(j)::value], r.im[decltype(j)::value], wr, wi);
         });
     }
@@ -420,7 +389,7 @@ template <typename T, int LR, int LC, int LP, bool PRE_TW, bool TRANSPOSE, bool 
     PHAST_HD static void put(const TileArgs &a, size_t ubase, unsigned voff, T re, T im) {
         const T scale = (T)a.scale;
         if (TRANSPOSE || !a.out_interleaved) {
-            if constexpr (NT_ST) {
+            if constexpr (NT_HINT) {
                 __builtin_nontemporal_store(re * scale, reinterpret_cast<T *>(a.out_re) + ubase + voff);
                 __builtin_nontemporal_store(im * scale, reinterpret_cast<T *>(a.out_im) + ubase + voff);
             } else {
@@ -474,11 +443,8 @@ template <typename T, int LR, int LC, int LP, bool PRE_TW, bool TRANSPOSE, bool 
 // the re and im planes one after the other (half the LDS); the rest exchange both planes at once.
 template <typename T, int LP> inline constexpr bool plane_seq_v = (sizeof(T) == 8 && LP == 4) || LP == 5;
 
-#ifndef PHAST_MIN_WAVES
-#define PHAST_MIN_WAVES(LR, LC) 1
-#endif
 template <typename T, int LR, int LC, int LP, bool PRE_TW, bool TRANSPOSE, bool SEQ>
-__global__ void __launch_bounds__(1 << (LR + LC - LP), PHAST_MIN_WAVES(LR, LC)) tile_fft_kernel(const TileArgs a) {
+__global__ void __launch_bounds__(1 << (LR + LC - LP), 1) tile_fft_kernel(const TileArgs a) {
     using Body = TileBody<T, LR, LC, LP, PRE_TW, TRANSPOSE, SEQ>;
     using cx = cx_t<T>;
     constexpr int NT = Body::NT;
@@ -498,16 +464,9 @@ __global__ void __launch_bounds__(1 << (LR + LC - LP), PHAST_MIN_WAVES(LR, LC)) 
     // live -- or spilled -- across a phase; each phase recomputes what it needs with a few integer ops.  (Round 2
     // laundered a VGPR copy of the id once per tile: that VGPR and `col` were what the 32-point f32 kernel spilled.)
     unsigned wave_base = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
-    bool first_fresh = true;
     auto fresh_tid = [&]() {
-#if PHAST_FRESH_TID
         asm volatile("" : "+s"(wave_base));
         return (int)(wave_base | __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
-#else  // tools only: round 2's form, one laundered VGPR copy per tile
-        (void)wave_base;
-        if (first_fresh) asm volatile("" : "+v"(tid));
-        return tid;
-#endif
     };
     // Phase stamps exist only in the -DPHAST_TRACE build (tools/trace_tile.py): even behind a uniform branch the
     // drains below wreck register allocation (256 VGPRs + 300 spills), so the product kernels carry none.
@@ -528,9 +487,6 @@ __global__ void __launch_bounds__(1 << (LR + LC - LP), PHAST_MIN_WAVES(LR, LC)) 
     // the first tile's global loads are issued before the table loads so the two latencies overlap
     typename Body::Regs r;
     unsigned t = blockIdx.x;
-#ifdef PHAST_TILE_STAGGER  // tools only: the workgroups' first loads PHAST_TILE_STAGGER x 64 cycles apart, 8 groups
-    for (unsigned k = ((blockIdx.x >> 3) & 7u) * PHAST_TILE_STAGGER; k > 0; --k) __builtin_amdgcn_s_sleep(1);
-#endif
     if (t < a.tiles_total) {
         Body::locate(a, t, r);
         Body::load_raw(a, tid, r);
@@ -575,9 +531,7 @@ __global__ void __launch_bounds__(1 << (LR + LC - LP), PHAST_MIN_WAVES(LR, LC)) 
     };
 
     while (t < a.tiles_total) {
-        first_fresh = true;
         tid = fresh_tid();  // (see fresh_tid above: nothing derived from the thread id survives a phase)
-        first_fresh = false;
         if constexpr (Body::PROG) {  // only the six table reads differ (ds_read / global_load); the arithmetic is shared
             unsigned e0, de;
             Body::pre_twiddle_exps(a, tid, r, e0, de);

@@ -103,7 +103,7 @@ int Planner<T>::tune_core(int kind, size_t batch, unsigned wisdom_log_n, int rin
             if (kind == kR2C) {
                 // the untangle in the last pass, or as a sweep of its own: both where the static rule's threshold says it could
                 // go either way (below 2^23 complex points in flight), else the fused form wherever it exists
-                const bool fusable = c.passes.back().r2c_blocks > 0 && r2c_fuse_enabled();
+                const bool fusable = c.passes.back().r2c_blocks > 0;
                 if (fusable && batch * n < ((size_t)1 << 23)) {
                     cands.push_back(c);  // (the unfused twin)
                 }

@@ -36,13 +36,7 @@ namespace phast {
 
 // tiles (= waves) per workgroup: 4 measured best for the single 2^20 f64 transform (26.5 us; 27.2 / 27.5 / 29.2 at 1 / 2 / 8);
 // the f32 tile is twice the points: 2 per workgroup keeps one workgroup per CU at 2^20
-#ifndef PHAST_WAVE_TILES_PER_BLOCK
-#define PHAST_WAVE_TILES_PER_BLOCK 4
-#endif
-#ifndef PHAST_WAVE_TILES_PER_BLOCK_F32
-#define PHAST_WAVE_TILES_PER_BLOCK_F32 2
-#endif
-template <typename T> constexpr int wave_block_threads() { return 64 * (sizeof(T) == 4 ? PHAST_WAVE_TILES_PER_BLOCK_F32 : PHAST_WAVE_TILES_PER_BLOCK); }
+template <typename T> constexpr int wave_block_threads() { return 64 * (sizeof(T) == 4 ? 2 : 4); }
 
 template <typename T, bool PRE_TW, bool TRANSPOSE> struct WaveBody {
     using cx = cx_t<T>;
@@ -60,28 +54,8 @@ template <typename T, bool PRE_TW, bool TRANSPOSE> struct WaveBody {
     static constexpr int NT = wave_block_threads<T>(), WAVES = NT / 64;  // tiles (= waves) per workgroup
     static constexpr int CS = ROWS + 1;               // column pitch of the transposing buffer: odd => conflict-free
     static constexpr int XP = TRANSPOSE ? COLS * CS : 0;  // scalar elements per plane per wave
-#ifndef PHAST_WQ_NT_LOADS
-#define PHAST_WQ_NT_LOADS 1
-#endif
-#ifndef PHAST_WQ_NT_STORES
-#define PHAST_WQ_NT_STORES 1
-#endif
-    // cache policy per pass position (tools: -DPHAST_WAVE_NT_A_STORES=0 etc.; measured in profiles/r06_cache_policy_ab.log):
-    // the first pass reads the caller's (cold) array and writes the scratch, the later passes read the scratch
-#ifndef PHAST_WAVE_NT_A_LOADS
-#define PHAST_WAVE_NT_A_LOADS PHAST_WQ_NT_LOADS
-#endif
-#ifndef PHAST_WAVE_NT_A_STORES
-#define PHAST_WAVE_NT_A_STORES PHAST_WQ_NT_STORES
-#endif
-#ifndef PHAST_WAVE_NT_C_LOADS
-#define PHAST_WAVE_NT_C_LOADS PHAST_WQ_NT_LOADS
-#endif
-#ifndef PHAST_WAVE_NT_C_STORES
-#define PHAST_WAVE_NT_C_STORES PHAST_WQ_NT_STORES
-#endif
-    static constexpr bool NT_LOAD = TRANSPOSE ? PHAST_WAVE_NT_A_LOADS : PHAST_WAVE_NT_C_LOADS;
-    static constexpr bool NT_STORE = TRANSPOSE ? PHAST_WAVE_NT_A_STORES : PHAST_WAVE_NT_C_STORES;
+    // Every pass position loads and stores non-temporally: the first pass reads the caller's (cold) array and writes the
+    // scratch, the later passes read the scratch (the cache policy per position: profiles/r06_cache_policy_ab.log).
     // a register's worth in the caller's memory: aligned to ONE ELEMENT only (`&mut v[1..]` is a legal slice: no more than
     // element alignment may be assumed of a caller's pointer; the hardware takes unaligned dword-multiple accesses)
     typedef V VU __attribute__((aligned(sizeof(T))));
@@ -129,13 +103,8 @@ template <typename T, bool PRE_TW, bool TRANSPOSE> struct WaveBody {
                 const size_t urow = (size_t)(decltype(j)::value * TAUS) * a.in_row_stride;
                 const VU *qr = reinterpret_cast<const VU *>(reinterpret_cast<const char *>(pr + urow) + vbyte);
                 const VU *qi = reinterpret_cast<const VU *>(reinterpret_cast<const char *>(pi + urow) + vbyte);
-                if constexpr (NT_LOAD) {
-                    r.re[j] = __builtin_nontemporal_load(qr);
-                    r.im[j] = __builtin_nontemporal_load(qi);
-                } else {
-                    r.re[j] = *qr;
-                    r.im[j] = *qi;
-                }
+                r.re[j] = __builtin_nontemporal_load(qr);
+                r.im[j] = __builtin_nontemporal_load(qi);
             });
         } else {  // first pass of an interleaved / real transform: (re, im) or (im, re) pairs, VW of them side by side
             const cx *pz = reinterpret_cast<const cx *>(a.in_re) + ubase;
@@ -250,13 +219,8 @@ template <typename T, bool PRE_TW, bool TRANSPOSE> struct WaveBody {
         if constexpr (!PAIRS) {
             VU *qr = reinterpret_cast<VU *>(reinterpret_cast<char *>(reinterpret_cast<T *>(a.out_re) + ubase) + vbyte);
             VU *qi = reinterpret_cast<VU *>(reinterpret_cast<char *>(reinterpret_cast<T *>(a.out_im) + ubase) + vbyte);
-            if constexpr (NT_STORE) {
-                __builtin_nontemporal_store(re, qr);
-                __builtin_nontemporal_store(im, qi);
-            } else {
-                *qr = re;
-                *qi = im;
-            }
+            __builtin_nontemporal_store(re, qr);
+            __builtin_nontemporal_store(im, qi);
         } else {
             const V x = a.out_interleaved == 2 ? im : re, y = a.out_interleaved == 2 ? re : im;
             cx *q = reinterpret_cast<cx *>(reinterpret_cast<char *>(reinterpret_cast<cx *>(a.out_re) + ubase) + 2u * vbyte);
@@ -340,21 +304,8 @@ template <typename T, bool PRE_TW, bool TRANSPOSE> struct WaveBody {
 };
 
 // ---- the exchange on the GPU: lane bits (5, 4) <-> register bits (1, 0), one VALU swap per dword pair ----
-// -DPHAST_WAVE_XCHG_BPERMUTE builds the same exchange from ds_bpermute_b32 (the LDS crossbar without the memory: two
-// selects + one DS instruction + an lgkmcnt wait per dword pair) for comparison -- tools/ and profiles/r02_wave_xchg.log:
-// the swap instructions are what the product uses.
-#ifdef PHAST_WAVE_XCHG_BPERMUTE
-template <int BIT> __device__ __forceinline__ void swap_via_bpermute(unsigned &a, unsigned &b) {
-    const unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    const bool up = (lane & BIT) != 0;
-    const unsigned send = up ? a : b;  // the upper lane gives its `a`, the lower lane its `b`
-    const unsigned recv = (unsigned)__builtin_amdgcn_ds_bpermute((int)((lane ^ BIT) << 2), (int)send);
-    if (up) a = recv;
-    else b = recv;
-}
-__device__ __forceinline__ void swap_lane_halves(unsigned &a, unsigned &b) { swap_via_bpermute<32>(a, b); }
-__device__ __forceinline__ void swap_lane_rows(unsigned &a, unsigned &b) { swap_via_bpermute<16>(a, b); }
-#else
+// (the same exchange from ds_bpermute_b32 -- the LDS crossbar without the memory: two selects + one DS instruction + an
+// lgkmcnt wait per dword pair -- was measured against the swaps and removed: profiles/r02_wave_xchg.log)
 __device__ __forceinline__ void swap_lane_halves(unsigned &a, unsigned &b) {  // a.lanes[32..63] <-> b.lanes[0..31]
     auto v = __builtin_amdgcn_permlane32_swap(a, b, false, false);
     a = v[0];
@@ -365,7 +316,6 @@ __device__ __forceinline__ void swap_lane_rows(unsigned &a, unsigned &b) {  // a
     a = v[0];
     b = v[1];
 }
-#endif
 template <bool HALVES> __device__ __forceinline__ void swap_pair(double &a, double &b) {
     unsigned alo = (unsigned)__double2loint(a), ahi = (unsigned)__double2hiint(a);
     unsigned blo = (unsigned)__double2loint(b), bhi = (unsigned)__double2hiint(b);
@@ -416,15 +366,13 @@ template <typename T> __device__ __forceinline__ void wave_exchange(T (&re)[16],
 }
 // Stagger of the waves' loads (see the kernel): group g = ((block & 1) << 2 | wave) & mask sleeps g * units * 64 cycles.
 // Packed as units | mask << 8; PHAST_WAVE_STAGGER="units,mask" overrides the default (tuning, tools/sweep_stagger.py).
-#ifndef PHAST_WAVE_STAGGER_DEFAULT
-#define PHAST_WAVE_STAGGER_DEFAULT (8u | (3u << 8))
-#endif
+constexpr unsigned kWaveStaggerDefault = 8u | (3u << 8);
 inline unsigned wave_stagger_setting() {
     static const unsigned v = [] {
         const char *e = getenv("PHAST_WAVE_STAGGER");
         unsigned units = 0, mask = 0;
         if (e && sscanf(e, "%u,%u", &units, &mask) == 2) return (units & 255u) | ((mask & 7u) << 8);
-        return (unsigned)PHAST_WAVE_STAGGER_DEFAULT;
+        return kWaveStaggerDefault;
     }();
     return v;
 }
@@ -483,13 +431,6 @@ __global__ void __launch_bounds__((wave_block_threads<T>())) wave_fft_kernel(con
     Body::load_raw(a, lane, r);
     PHAST_STAMP(false);  // 2: loads issued
     PHAST_STAMP(true);   // 3: loads back
-#ifdef PHAST_WAVE_WAIT_ALL  // tools only: every load back before anything else happens
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#if defined(PHAST_WAVE_DEBUG_SKIP) && PHAST_WAVE_DEBUG_SKIP >= 4  // tools only: no table staging
-    if (a.tiles_total == 0xffffffffu) l_twr[lane] = twr_stage;
-    if constexpr (TRANSPOSE) { } else { Body::store_rows(a, lane, r); return; }
-#endif
     {  // all 64 powers: lanes 32..63 store W^(e + 32) = -W^e, so step1 needs no sign selects (74 v_cndmask per tile)
         cx w = twr_stage;
         if (lane & 32) {
@@ -501,16 +442,10 @@ __global__ void __launch_bounds__((wave_block_threads<T>())) wave_fft_kernel(con
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#if !defined(PHAST_WAVE_DEBUG_SKIP) || PHAST_WAVE_DEBUG_SKIP < 3   // tools only: 1 = no pre-twiddle, 2 = + no exchange, 3 = no arithmetic at all
-#if !defined(PHAST_WAVE_DEBUG_SKIP) || PHAST_WAVE_DEBUG_SKIP < 1
     if constexpr (PRE_TW) Body::pre_twiddle_apply(twraw, r);
-#endif
     Body::step1(l_twr, lane, r);
-#if !defined(PHAST_WAVE_DEBUG_SKIP) || PHAST_WAVE_DEBUG_SKIP < 2
     wave_exchange<V>(r.re, r.im);
-#endif
     Body::step2(r);
-#endif
     PHAST_STAMP(true);   // 4: arithmetic done
     if constexpr (TRANSPOSE) {
         // wave-private transposition: this wave writes and then reads its own buffer; LDS operations of one wave
@@ -531,82 +466,9 @@ __global__ void __launch_bounds__((wave_block_threads<T>())) wave_fft_kernel(con
 #undef PHAST_STAMP
 }
 
-// ---- two tiles per wave, software-pipelined ("build it, do not model it again") ----
-// Half as many waves, each owning the tiles (2 t, 2 t + 1): both tiles' loads go out back to back (64 loads in flight per
-// lane, two register sets), tile 2 t is computed and stored while tile 2 t + 1's loads are still arriving, then tile 2 t + 1.
-// One wave per SIMD leaves registers free (2 x 64 data VGPRs + temporaries), so the second set costs nothing in occupancy.
-// What the copy model promised (profiles/r02_pipelining_floor.log: 7.3 -> 6.8 us per pass at this pass's arithmetic) assumed
-// the arithmetic is what a pass waits for; measured on the real kernels -- PHAST_WAVE_PIPELINE=1, same-box A/B in
-// profiles/r06_pipelined_tiles_ab.log -- half the SIMDs idle costs more than the overlap gives.  Kept behind the switch.
-template <typename T, bool PRE_TW, bool TRANSPOSE>
-__global__ void __launch_bounds__((wave_block_threads<T>())) wave_fft2_kernel(const TileArgs a, unsigned blocks_total, unsigned stagger) {
-    using Body = WaveBody<T, PRE_TW, TRANSPOSE>;
-    using cx = cx_t<T>;
-    using V = typename Body::V;
-    pin_tile_args(a);
-    pin_scalars(blocks_total, stagger);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    cx *l_twr = reinterpret_cast<cx *>(smem + (size_t)wave * (64 * sizeof(cx) + (size_t)2 * Body::XP * sizeof(T)));
-    T *xp = reinterpret_cast<T *>(l_twr + 64);
-    // slot s of the launch = tiles 2 s and 2 s + 1; slots are dealt to the workgroups in the XCD-aware order of Body::locate
-    const unsigned b = ((blocks_total & 7u) == 0u) ? (blockIdx.x & 7u) * (blocks_total >> 3) + (blockIdx.x >> 3) : blockIdx.x;
-    const unsigned slot = b * Body::WAVES + (unsigned)wave;
-    if (2u * slot >= a.tiles_total) return;
-    typename Body::Regs r0, r1;
-    Body::locate_tile(a, 2u * slot, r0);
-    Body::locate_tile(a, 2u * slot + 1u, r1);
-    const cx twr_stage = reinterpret_cast<const cx *>(a.twr)[lane & 31];
-    typename Body::TwRaw tw0, tw1;
-    if constexpr (PRE_TW) {
-        tw0 = Body::pre_twiddle_fetch(a, reinterpret_cast<const cx *>(a.tw3), lane, r0);
-        tw1 = Body::pre_twiddle_fetch(a, reinterpret_cast<const cx *>(a.tw3), lane, r1);
-    }
-    for (unsigned k = ((((blockIdx.x & 1u) << 2) | (unsigned)wave) & (stagger >> 8)) * (stagger & 255u); k > 0; --k)
-        __builtin_amdgcn_s_sleep(1);
-    Body::load_raw(a, lane, r0);
-    Body::load_raw(a, lane, r1);  // in flight while tile 0 is computed and stored (loads return in order: tile 0's first)
-    {
-        cx w = twr_stage;
-        if (lane & 32) {
-            w.x = -w.x;
-            w.y = -w.y;
-        }
-        l_twr[lane] = w;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    auto finish = [&](typename Body::Regs &r, const typename Body::TwRaw &tw) {
-        if constexpr (PRE_TW) Body::pre_twiddle_apply(tw, r);
-        Body::step1(l_twr, lane, r);
-        wave_exchange<V>(r.re, r.im);
-        Body::step2(r);
-        if constexpr (TRANSPOSE) {
-            Body::xp_park(xp, lane, r);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            Body::xp_pick(xp, lane, r);
-            Body::store_runs(a, lane, r);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the buffer is free again before the next tile parks
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        } else {
-            Body::store_rows(a, lane, r);
-        }
-    };
-    finish(r0, tw0);
-    finish(r1, tw1);
-}
-inline bool wave_pipeline_enabled() {  // PHAST_WAVE_PIPELINE=1: two tiles per wave (wave_fft2_kernel); tools, A/B
-    static const bool on = [] {
-        const char *e = getenv("PHAST_WAVE_PIPELINE");
-        return e && *e == '1';
-    }();
-    return on;
-}
+// One tile per wave.  Two tiles per wave, software-pipelined (the second tile's loads in flight while the first is computed
+// and stored, half as many waves), was built and measured slower: half the SIMDs idle costs more than the overlap gives
+// (profiles/r06_pipelined_tiles_ab.log).
 
 // host-side launcher
 template <typename T, bool PRE_TW, bool TRANSPOSE>
@@ -635,18 +497,6 @@ hipError_t launch_wave_inst(hipStream_t stream, const TileArgs &a, bool query_on
                                                       : ((unsigned long long)Body::COLS * a.out_s1 + 16ull * a.out_row_stride) * esz;
         if (in_span >= (1ull << 32) || out_span >= (1ull << 32)) return hipErrorInvalidValue;
         if (Body::VW == 2 && (TRANSPOSE ? a.out_row_stride != 1 : a.out_s1 != 1)) return hipErrorInvalidValue;
-    }
-    if (wave_pipeline_enabled() && (a.tiles_total % (2u * Body::WAVES)) == 0u) {  // two tiles per wave: half the waves
-        auto kern2 = wave_fft2_kernel<T, PRE_TW, TRANSPOSE>;
-        static PerDeviceLimit lds_limit2;
-        if (hipError_t e = raise_lds_limit(lds_limit2, reinterpret_cast<const void *>(kern2), lds); e != hipSuccess) return e;
-        const unsigned blocks2 = a.tiles_total / (2u * Body::WAVES);
-        const unsigned stagger2 = a.tiles_total <= 2048u ? wave_stagger_setting() : 0u;
-        if (ev_start && ev_stop)
-            hipExtLaunchKernelGGL(kern2, dim3(blocks2), dim3(Body::NT), (uint32_t)lds, stream, ev_start, ev_stop, 0, a, blocks2, stagger2);
-        else
-            hipLaunchKernelGGL(kern2, dim3(blocks2), dim3(Body::NT), lds, stream, a, blocks2, stagger2);
-        return hipGetLastError();
     }
     const unsigned blocks = (a.tiles_total + Body::WAVES - 1) / Body::WAVES;
     // the stagger pays when every wave of the launch is resident at once and they would all move in step: at most one

@@ -97,7 +97,8 @@ def test_product_never_imports_the_oracle():
 
 def test_every_environment_variable_the_library_reads_is_documented():
     """INTEGRATION.md lists the environment variables; a getenv("PHAST...") in the sources that is not in that table is a
-    behaviour switch a maintainer cannot find."""
+    behaviour switch a maintainer cannot find, and a name in the table that the library does not read is a switch that
+    is no longer there."""
     import glob
     import re
 
@@ -105,12 +106,20 @@ def test_every_environment_variable_the_library_reads_is_documented():
     names = set()
     for path in glob.glob(os.path.join(root, "phastft_amd", "csrc", "*")) + glob.glob(os.path.join(root, "phastft_amd", "*.py")):
         if os.path.isfile(path) and path.endswith((".hip", ".hpp", ".py")):
-            names |= set(re.findall(r'getenv\("(PHAST[A-Z0-9_]*)"\)', open(path).read()))
-            names |= set(re.findall(r'environ(?:\.get)?[\[(]\s*["\'](PHAST[A-Z0-9_]*)', open(path).read()))
+            text = open(path).read()
+            names |= set(re.findall(r'getenv\("(PHAST[A-Z0-9_]*)"\)', text))
+            names |= set(re.findall(r'env_long\("(PHAST[A-Z0-9_]*)"', text))
+            names |= set(re.findall(r'environ(?:\.get)?[\[(]\s*["\'](PHAST[A-Z0-9_]*)', text))
     doc = open(os.path.join(root, "INTEGRATION.md")).read()
     assert names, "no environment variables found: the pattern no longer matches the sources"
-    missing = sorted(n for n in names if n not in doc)
-    assert not missing, missing
+    section = doc.split("\n## Environment", 1)[1].split("\n## ", 1)[0]
+    table = set()
+    for line in section.splitlines():
+        if line.startswith("| `"):
+            table |= set(re.findall(r"`(PHAST[A-Z0-9_]*)`", line.split("|")[1]))
+    assert table, "no environment table found in INTEGRATION.md"
+    assert sorted(names - table) == [], "read by the library, missing from the table"
+    assert sorted(table - names) == [], "in the table, not read by the library"
 
 
 def test_wisdom_store_without_a_device():

@@ -2,7 +2,7 @@
 """A library VARIANT for an A/B (tools/ab_single.py --libs): only the named translation units are recompiled with the extra
 flags, every other object is the product's -- a variant of one kernel costs one hipcc run, not a rebuild of the library.
 
-    python tools/build_variant.py --tag _x2 --units wave_f64,wave_f32 -- -DPHAST_WAVE_TILES_PER_BLOCK=2
+    python tools/build_variant.py --tag _trace --units wave_f64,wave_f32 -- -DPHAST_TRACE
 
 writes phastft_amd/lib/libphastft_hip<tag>.so (git-ignored, travels to the GPU box with the snapshot)."""
 import argparse, os, subprocess, sys
