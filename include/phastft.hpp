@@ -18,6 +18,8 @@
 //   (none: powers of two only upstream)                      class PlannerAny64/32, fft_64/32_any[_with_planner] -- any N >= 1
 //   (none: r2c.rs takes powers of two >= 4)                  class PlannerR2cAny64/32, r2c_fft_f64/f32_any[_with_planner],
 //                                                            c2r_fft_f64/f32_any[_with_planner] -- any N >= 1
+//   (none: one axis only upstream)                           class PlannerNd64/32, PlannerR2cNd64/32, fft_64/32_nd[_with_planner],
+//                                                            r2c_fft_f64/f32_nd[...], c2r_fft_f64/f32_nd[...] -- every axis
 //
 // A Rust `&mut [T]` is a (pointer, length) pair here -- `Slice<T>` converts from std::vector / std::array /
 // raw pointer + length.  Where the reference panics (`assert!`), these functions throw `phastft::Panic` whose
@@ -396,6 +398,94 @@ inline void c2r_fft_f64_any(Slice<const double> input_re, Slice<const double> in
 }
 inline void c2r_fft_f32_any(Slice<const float> input_re, Slice<const float> input_im, Slice<float> output) {
     check(phast_c2r_fft_f32_any(input_re.ptr, input_re.len, input_im.ptr, input_im.len, output.ptr, output.len));
+}
+
+// ---- transforms over every axis of a row-major array (numpy fftn / rfftn / irfftn; no reference counterpart) ----
+#define PHASTFT_PLANNER_ND(NAME, CT, PFX)                                                                        \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        explicit NAME(const std::vector<std::size_t> &shape) : shape_(shape) {                                   \
+            check(phast_planner_##PFX##_new(shape.data(), shape.size(), &h_));                                   \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_), shape_(std::move(o.shape_)) { o.h_ = nullptr; }                      \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_##PFX##_free(h_);                                                              \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        const std::vector<std::size_t> &shape() const { return shape_; }                                         \
+        std::string describe() const {                                                                           \
+            std::string s(16384, '\0');                                                                          \
+            check(phast_planner_##PFX##_describe(h_, &s[0], s.size()));                                          \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_##PFX##_device_bytes(h_); }                      \
+        /* elements of T a _dev call of `batch` arrays works in at full speed; workspace_len(1) serves any batch */   \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_##PFX##_workspace_len(h_, batch); } \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+        std::vector<std::size_t> shape_;                                                                         \
+    };
+PHASTFT_PLANNER_ND(PlannerNd64, phast_planner_nd64, nd64)
+PHASTFT_PLANNER_ND(PlannerNd32, phast_planner_nd32, nd32)
+PHASTFT_PLANNER_ND(PlannerR2cNd64, phast_planner_r2c_nd64, r2c_nd64)
+PHASTFT_PLANNER_ND(PlannerR2cNd32, phast_planner_r2c_nd32, r2c_nd32)
+#undef PHASTFT_PLANNER_ND
+
+inline void fft_64_nd_with_planner(Slice<double> reals, Slice<double> imags, Direction direction, const PlannerNd64 &planner) {
+    check(phast_fft_64_nd_with_planner(reals.ptr, reals.len, imags.ptr, imags.len, static_cast<int>(direction), planner.get()));
+}
+inline void fft_32_nd_with_planner(Slice<float> reals, Slice<float> imags, Direction direction, const PlannerNd32 &planner) {
+    check(phast_fft_32_nd_with_planner(reals.ptr, reals.len, imags.ptr, imags.len, static_cast<int>(direction), planner.get()));
+}
+inline void fft_64_nd(Slice<double> reals, Slice<double> imags, const std::vector<std::size_t> &shape, Direction direction) {
+    check(phast_fft_64_nd(reals.ptr, reals.len, imags.ptr, imags.len, shape.data(), shape.size(), static_cast<int>(direction)));
+}
+inline void fft_32_nd(Slice<float> reals, Slice<float> imags, const std::vector<std::size_t> &shape, Direction direction) {
+    check(phast_fft_32_nd(reals.ptr, reals.len, imags.ptr, imags.len, shape.data(), shape.size(), static_cast<int>(direction)));
+}
+inline void r2c_fft_f64_nd_with_planner(Slice<const double> input, Slice<double> output_re, Slice<double> output_im,
+                                        const PlannerR2cNd64 &planner) {
+    check(phast_r2c_fft_f64_nd_with_planner(input.ptr, input.len, output_re.ptr, output_re.len, output_im.ptr, output_im.len,
+                                            planner.get()));
+}
+inline void r2c_fft_f32_nd_with_planner(Slice<const float> input, Slice<float> output_re, Slice<float> output_im,
+                                        const PlannerR2cNd32 &planner) {
+    check(phast_r2c_fft_f32_nd_with_planner(input.ptr, input.len, output_re.ptr, output_re.len, output_im.ptr, output_im.len,
+                                            planner.get()));
+}
+inline void r2c_fft_f64_nd(Slice<const double> input, Slice<double> output_re, Slice<double> output_im,
+                           const std::vector<std::size_t> &shape) {
+    check(phast_r2c_fft_f64_nd(input.ptr, input.len, output_re.ptr, output_re.len, output_im.ptr, output_im.len, shape.data(),
+                               shape.size()));
+}
+inline void r2c_fft_f32_nd(Slice<const float> input, Slice<float> output_re, Slice<float> output_im,
+                           const std::vector<std::size_t> &shape) {
+    check(phast_r2c_fft_f32_nd(input.ptr, input.len, output_re.ptr, output_re.len, output_im.ptr, output_im.len, shape.data(),
+                               shape.size()));
+}
+inline void c2r_fft_f64_nd_with_planner(Slice<const double> input_re, Slice<const double> input_im, Slice<double> output,
+                                        const PlannerR2cNd64 &planner) {
+    check(phast_c2r_fft_f64_nd_with_planner(input_re.ptr, input_re.len, input_im.ptr, input_im.len, output.ptr, output.len,
+                                            planner.get()));
+}
+inline void c2r_fft_f32_nd_with_planner(Slice<const float> input_re, Slice<const float> input_im, Slice<float> output,
+                                        const PlannerR2cNd32 &planner) {
+    check(phast_c2r_fft_f32_nd_with_planner(input_re.ptr, input_re.len, input_im.ptr, input_im.len, output.ptr, output.len,
+                                            planner.get()));
+}
+inline void c2r_fft_f64_nd(Slice<const double> input_re, Slice<const double> input_im, Slice<double> output,
+                           const std::vector<std::size_t> &shape) {
+    check(phast_c2r_fft_f64_nd(input_re.ptr, input_re.len, input_im.ptr, input_im.len, output.ptr, output.len, shape.data(),
+                               shape.size()));
+}
+inline void c2r_fft_f32_nd(Slice<const float> input_re, Slice<const float> input_im, Slice<float> output,
+                           const std::vector<std::size_t> &shape) {
+    check(phast_c2r_fft_f32_nd(input_re.ptr, input_re.len, input_im.ptr, input_im.len, output.ptr, output.len, shape.data(),
+                               shape.size()));
 }
 
 }  // namespace phastft

@@ -362,6 +362,107 @@ int phast_planner_r2c_any32_time_c2r_stages(const phast_planner_r2c_any32 *p, co
                                             const float *d_input_im, float *d_output, size_t batch, float *d_work,
                                             size_t work_len, int reps, float *stage_ms, void *stream);
 
+/* ---- multi-dimensional transforms over every axis of a row-major array (no reference counterpart; numpy fftn / ifftn /
+ * rfftn / irfftn with this library's conventions).  dims[0 .. rank-1]: rank 1 .. 8, every axis 1 .. 2^29,
+ * their product <= 2^30 (else PHAST_ERR_INVALID_ARG, before the device is touched).  Every axis is transformed; leading
+ * batch axes are `batch` / `dist` of the _dev calls.  Each axis runs the any-length path of its length (phast_planner_any*:
+ * a power of two on the engine, else Bluestein), rotated to the contiguous end by a batched planar transpose: r transposes
+ * for rank r.  Axes of length 1 are dropped at _new (the real last axis stays); a shape with one axis left runs the one-axis
+ * call itself (phast_fft_*_any_dev / phast_r2c_fft_*_any_dev ...): same bits, same batch rules.
+ *
+ * Complex: two planes of prod n_i points, in place for the caller; forward unnormalised, the inverse scales by 1 / prod n_i.
+ * R2C: the real array [n_0 .. n_{r-1}] -> two planes [n_0 .. n_{r-2}][n_{r-1} / 2 + 1] (floor); C2R the inverse, scaled by
+ * 1 / prod n_i: the leading axes first, the last axis by the any-length C2R (its rules for a non-Hermitian input and for
+ * Im X[0] carry over).  R2C never writes its input, C2R never its input planes.  The length codes of the one-axis calls
+ * apply with these counts (a wrong count of a complex host call: PHAST_ERR_PLANNER_SIZE; n_total of a _dev call that is not
+ * the planner's prod n_i: PHAST_ERR_PLANNER_SIZE).
+ *
+ * _dev calls: asynchronous on `stream`; arrays `dist` (complex), `in_dist` / `out_dist` (real: the real side >= prod n_i,
+ * the complex side >= the half-spectrum points) elements apart; element alignment suffices.  Workspace (elements of T):
+ * *_workspace_len(p, batch) runs the batch at full speed (the transposed copies of the batch -- two for the real planner,
+ * whose C2R ping-pongs between them -- plus the largest Bluestein workspace a step needs); *_workspace_len(p, 1) serves
+ * any batch, in chunks.  The smallest legal work_len is the copies of one array plus 2 M of the largest Bluestein axis
+ * (M: its convolution length); below it (or null) is PHAST_ERR_INVALID_ARG.  The real planner's lengths count C2R's two
+ * copies; R2C uses one and needs 2 x the half-spectrum points per array less.  For a
+ * shape with one axis left the workspace is that axis planner's.  Planners are immutable after _new and hold no per-call
+ * state: graph capture and concurrent streams need one workspace per call in flight.  With two or more axes left, each
+ * axis runs one engine plan fixed at _new, so the bits of a transform do not depend on the batch, the chunking, the
+ * stream, graph replay or the form of the call.  Host-slice calls stage through the device (they block); the calls
+ * without a planner build one per call. */
+typedef struct phast_planner_nd64 phast_planner_nd64;         /* PlannerNd64 */
+typedef struct phast_planner_nd32 phast_planner_nd32;         /* PlannerNd32 */
+typedef struct phast_planner_r2c_nd64 phast_planner_r2c_nd64; /* PlannerR2cNd64 */
+typedef struct phast_planner_r2c_nd32 phast_planner_r2c_nd32; /* PlannerR2cNd32 */
+int phast_planner_nd64_new(const size_t *dims, size_t rank, phast_planner_nd64 **out);
+int phast_planner_nd32_new(const size_t *dims, size_t rank, phast_planner_nd32 **out);
+void phast_planner_nd64_free(phast_planner_nd64 *p);
+void phast_planner_nd32_free(phast_planner_nd32 *p);
+int phast_planner_nd64_describe(const phast_planner_nd64 *p, char *buf, size_t buf_len);
+int phast_planner_nd32_describe(const phast_planner_nd32 *p, char *buf, size_t buf_len);
+size_t phast_planner_nd64_device_bytes(const phast_planner_nd64 *p);
+size_t phast_planner_nd32_device_bytes(const phast_planner_nd32 *p);
+size_t phast_planner_nd64_workspace_len(const phast_planner_nd64 *p, size_t batch);
+size_t phast_planner_nd32_workspace_len(const phast_planner_nd32 *p, size_t batch);
+int phast_fft_64_nd(double *reals, size_t reals_len, double *imags, size_t imags_len, const size_t *dims, size_t rank,
+                    int direction);
+int phast_fft_32_nd(float *reals, size_t reals_len, float *imags, size_t imags_len, const size_t *dims, size_t rank,
+                    int direction);
+int phast_fft_64_nd_with_planner(double *reals, size_t reals_len, double *imags, size_t imags_len, int direction,
+                                 const phast_planner_nd64 *planner);
+int phast_fft_32_nd_with_planner(float *reals, size_t reals_len, float *imags, size_t imags_len, int direction,
+                                 const phast_planner_nd32 *planner);
+int phast_fft_64_nd_dev(double *d_reals, double *d_imags, size_t n_total, size_t batch, size_t dist, int direction,
+                        const phast_planner_nd64 *planner, double *d_work, size_t work_len, void *stream);
+int phast_fft_32_nd_dev(float *d_reals, float *d_imags, size_t n_total, size_t batch, size_t dist, int direction,
+                        const phast_planner_nd32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/nd_rate.py): step_ms[i] = average milliseconds of step i of the schedule (describe() lists them;
+ * at most 17), *n_steps = their count, over `reps` forward calls of the batch in ONE chunk (two or more axes left,
+ * work_len >= phast_planner_nd*_workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_nd64_time_steps(const phast_planner_nd64 *p, double *d_reals, double *d_imags, size_t batch, size_t dist,
+                                  double *d_work, size_t work_len, int reps, float *step_ms, size_t *n_steps, void *stream);
+int phast_planner_nd32_time_steps(const phast_planner_nd32 *p, float *d_reals, float *d_imags, size_t batch, size_t dist,
+                                  float *d_work, size_t work_len, int reps, float *step_ms, size_t *n_steps, void *stream);
+int phast_planner_r2c_nd64_new(const size_t *dims, size_t rank, phast_planner_r2c_nd64 **out);
+int phast_planner_r2c_nd32_new(const size_t *dims, size_t rank, phast_planner_r2c_nd32 **out);
+void phast_planner_r2c_nd64_free(phast_planner_r2c_nd64 *p);
+void phast_planner_r2c_nd32_free(phast_planner_r2c_nd32 *p);
+int phast_planner_r2c_nd64_describe(const phast_planner_r2c_nd64 *p, char *buf, size_t buf_len);
+int phast_planner_r2c_nd32_describe(const phast_planner_r2c_nd32 *p, char *buf, size_t buf_len);
+size_t phast_planner_r2c_nd64_device_bytes(const phast_planner_r2c_nd64 *p);
+size_t phast_planner_r2c_nd32_device_bytes(const phast_planner_r2c_nd32 *p);
+size_t phast_planner_r2c_nd64_workspace_len(const phast_planner_r2c_nd64 *p, size_t batch);
+size_t phast_planner_r2c_nd32_workspace_len(const phast_planner_r2c_nd32 *p, size_t batch);
+int phast_r2c_fft_f64_nd(const double *input, size_t input_len, double *output_re, size_t output_re_len, double *output_im,
+                         size_t output_im_len, const size_t *dims, size_t rank);
+int phast_r2c_fft_f32_nd(const float *input, size_t input_len, float *output_re, size_t output_re_len, float *output_im,
+                         size_t output_im_len, const size_t *dims, size_t rank);
+int phast_r2c_fft_f64_nd_with_planner(const double *input, size_t input_len, double *output_re, size_t output_re_len,
+                                      double *output_im, size_t output_im_len, const phast_planner_r2c_nd64 *planner);
+int phast_r2c_fft_f32_nd_with_planner(const float *input, size_t input_len, float *output_re, size_t output_re_len,
+                                      float *output_im, size_t output_im_len, const phast_planner_r2c_nd32 *planner);
+int phast_r2c_fft_f64_nd_dev(const double *d_input, double *d_output_re, double *d_output_im, size_t n_total, size_t batch,
+                             size_t in_dist, size_t out_dist, const phast_planner_r2c_nd64 *planner, double *d_work,
+                             size_t work_len, void *stream);
+int phast_r2c_fft_f32_nd_dev(const float *d_input, float *d_output_re, float *d_output_im, size_t n_total, size_t batch,
+                             size_t in_dist, size_t out_dist, const phast_planner_r2c_nd32 *planner, float *d_work,
+                             size_t work_len, void *stream);
+int phast_c2r_fft_f64_nd(const double *input_re, size_t input_re_len, const double *input_im, size_t input_im_len,
+                         double *output, size_t output_len, const size_t *dims, size_t rank);
+int phast_c2r_fft_f32_nd(const float *input_re, size_t input_re_len, const float *input_im, size_t input_im_len,
+                         float *output, size_t output_len, const size_t *dims, size_t rank);
+int phast_c2r_fft_f64_nd_with_planner(const double *input_re, size_t input_re_len, const double *input_im,
+                                      size_t input_im_len, double *output, size_t output_len,
+                                      const phast_planner_r2c_nd64 *planner);
+int phast_c2r_fft_f32_nd_with_planner(const float *input_re, size_t input_re_len, const float *input_im,
+                                      size_t input_im_len, float *output, size_t output_len,
+                                      const phast_planner_r2c_nd32 *planner);
+int phast_c2r_fft_f64_nd_dev(const double *d_input_re, const double *d_input_im, double *d_output, size_t n_total,
+                             size_t batch, size_t in_dist, size_t out_dist, const phast_planner_r2c_nd64 *planner,
+                             double *d_work, size_t work_len, void *stream);
+int phast_c2r_fft_f32_nd_dev(const float *d_input_re, const float *d_input_im, float *d_output, size_t n_total,
+                             size_t batch, size_t in_dist, size_t out_dist, const phast_planner_r2c_nd32 *planner,
+                             float *d_work, size_t work_len, void *stream);
+
 /* ---- bit reversal: algorithms/bravo.rs:303,317 (public with feature bench-internals, lib.rs:20-23) ---- */
 int phast_bit_rev_f64(double *data, size_t len, unsigned log_n); /* host slice */
 int phast_bit_rev_f32(float *data, size_t len, unsigned log_n);

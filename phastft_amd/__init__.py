@@ -20,6 +20,9 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
     (none: powers of two only)                      PlannerAny64/32, fft_64/32_any[_with_planner], fft_any_batched
     (none: r2c.rs takes powers of two >= 4)         PlannerR2cAny64/32, r2c_fft_f64/f32_any[_with_planner],
                                                     c2r_fft_f64/f32_any[_with_planner], r2c_any_batched, c2r_any_batched
+    (none: one axis only)                           PlannerNd64/32, fft_64/32_nd[_with_planner], fft_nd_batched,
+                                                    PlannerR2cNd64/32, r2c_fft_f64/f32_nd[_with_planner],
+                                                    c2r_fft_f64/f32_nd[_with_planner], r2c_nd_batched, c2r_nd_batched
     ==============================================  ==========================================
 
 Slices are 1-D contiguous arrays: ``numpy.ndarray`` (host slices -- staged through device memory, the
@@ -58,6 +61,10 @@ __all__ = [
     "PlannerR2cAny64", "PlannerR2cAny32", "r2c_fft_f64_any", "r2c_fft_f32_any", "r2c_fft_f64_any_with_planner",
     "r2c_fft_f32_any_with_planner", "c2r_fft_f64_any", "c2r_fft_f32_any", "c2r_fft_f64_any_with_planner",
     "c2r_fft_f32_any_with_planner", "r2c_any_batched", "c2r_any_batched",
+    "PlannerNd64", "PlannerNd32", "fft_64_nd", "fft_32_nd", "fft_64_nd_with_planner", "fft_32_nd_with_planner", "fft_nd_batched",
+    "PlannerR2cNd64", "PlannerR2cNd32", "r2c_fft_f64_nd", "r2c_fft_f32_nd", "r2c_fft_f64_nd_with_planner",
+    "r2c_fft_f32_nd_with_planner", "c2r_fft_f64_nd", "c2r_fft_f32_nd", "c2r_fft_f64_nd_with_planner",
+    "c2r_fft_f32_nd_with_planner", "r2c_nd_batched", "c2r_nd_batched",
 ]
 
 
@@ -876,6 +883,251 @@ def c2r_any_batched(input_re, input_im, output, planner, batch: int, in_dist: in
     _check(getattr(_lib.lib(), f"phast_c2r_fft_{fs}_any_dev")(ire.ptr, iim.ptr, out.ptr, C.c_size_t(n), C.c_size_t(batch),
                                                               C.c_size_t(in_dist), C.c_size_t(out_dist), planner._h, ws.ptr,
                                                               C.c_size_t(ws.len), _stream()))
+
+
+# ---------------------------------------------------------------------------------------------
+# multi-dimensional transforms over every axis of a row-major array (numpy fftn / ifftn / rfftn / irfftn; no reference
+# counterpart).  Arrays and tensors of any view shape are taken by their contiguous elements.
+# ---------------------------------------------------------------------------------------------
+def _flat(x):
+    """a contiguous array or tensor of any shape as a 1-D view of its elements (anything else goes to _Slice as it is)"""
+    if _is_torch(x):
+        return x.view(-1) if x.dim() != 1 and x.is_contiguous() else x
+    if isinstance(x, np.ndarray) and x.ndim != 1 and x.flags.c_contiguous:
+        return x.reshape(-1)
+    return x
+
+
+class _NdHandle(_AnyHandle):
+    """the handle of a multi-dimensional planner: phast_planner_{_prefix}{_sfx}_*"""
+
+    _prefix = "nd"
+
+    def __init__(self, shape):
+        self.shape = tuple(int(d) for d in shape)
+        dims = (C.c_size_t * max(1, len(self.shape)))(*self.shape)
+        self._h = C.c_void_p()
+        _check(self._fn("new")(dims, C.c_size_t(len(self.shape)), C.byref(self._h)))
+        self.n = int(np.prod(self.shape, dtype=np.int64))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` arrays works in at full speed; ``workspace_len(1)`` serves any batch, in
+        chunks (include/phastft_hip.h gives the smallest legal length)"""
+        return self._workspace_len(batch)
+
+
+class _PlannerNd(_NdHandle):
+    def time_steps(self, reals, imags, batch: int = 1, dist: int | None = None, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of every step of a forward call on device tensors, in the order describe() lists
+        them (row transforms and transposes; measurement hook)"""
+        re, im = _Slice(_flat(reals), self._dtype, "reals"), _Slice(_flat(imags), self._dtype, "imags")
+        ws = _any_workspace(self, batch, workspace)
+        ms, ns = (C.c_float * 17)(), C.c_size_t()
+        _check(self._fn("time_steps")(self._h, re.ptr, im.ptr, C.c_size_t(batch), C.c_size_t(self.n if dist is None else dist),
+                                      ws.ptr, C.c_size_t(ws.len), C.c_int(reps), ms, C.byref(ns), _stream()))
+        return [float(ms[i]) for i in range(ns.value)]
+
+
+class PlannerNd64(_PlannerNd):
+    """f64 complex transforms over every axis of a row-major array of rank 1 .. 8 (each axis 1 .. 2^29, <= 2^30 points)"""
+
+
+class PlannerNd32(_PlannerNd):
+    """f32 twin of :class:`PlannerNd64`"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+class _PlannerR2cNd(_NdHandle):
+    _prefix = "r2c_nd"
+
+    def __init__(self, shape):
+        super().__init__(shape)
+        self.half = self.n // self.shape[-1] * (self.shape[-1] // 2 + 1)  # points of the half spectrum
+
+
+class PlannerR2cNd64(_PlannerR2cNd):
+    """f64 real transforms (numpy rfftn / irfftn) over every axis of a row-major array of rank 1 .. 8"""
+
+
+class PlannerR2cNd32(_PlannerR2cNd):
+    """f32 twin of :class:`PlannerR2cNd64`"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def _dims(shape):
+    shape = tuple(int(d) for d in shape)
+    return (C.c_size_t * max(1, len(shape)))(*shape), C.c_size_t(len(shape))
+
+
+def _fft_nd(sfx, dtype, reals, imags, shape, direction, planner=None):
+    re, im = _Slice(_flat(reals), dtype, "reals"), _Slice(_flat(imags), dtype, "imags")
+    l = _lib.lib()
+    direction = C.c_int(int(direction))
+    if _same_place(re, im):
+        if re.len != im.len:
+            _check(2)
+        own = planner is None
+        if own:
+            planner = (PlannerNd64 if sfx == "64" else PlannerNd32)(shape)
+        ws = _any_workspace(planner, 1)
+        _check(getattr(l, f"phast_fft_{sfx}_nd_dev")(re.ptr, im.ptr, C.c_size_t(re.len), C.c_size_t(1), C.c_size_t(re.len),
+                                                     direction, planner._h, ws.ptr, C.c_size_t(ws.len), _stream()))
+        if own:
+            import torch
+
+            torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+        return
+    args = [re.ptr, C.c_size_t(re.len), im.ptr, C.c_size_t(im.len)]
+    if planner is None:
+        _check(getattr(l, f"phast_fft_{sfx}_nd")(*args, *_dims(shape), direction))
+    else:
+        _check(getattr(l, f"phast_fft_{sfx}_nd_with_planner")(*args, direction, planner._h))
+
+
+def fft_64_nd(reals, imags, shape, direction: Direction) -> None:
+    """In-place f64 DFT over every axis of the row-major array ``shape`` held by (reals, imags) (numpy fftn; Reverse is
+    ifftn: scaled by 1 / prod(shape))"""
+    _fft_nd("64", np.float64, reals, imags, shape, direction)
+
+
+def fft_32_nd(reals, imags, shape, direction: Direction) -> None:
+    """f32 twin of :func:`fft_64_nd`"""
+    _fft_nd("32", np.float32, reals, imags, shape, direction)
+
+
+def fft_64_nd_with_planner(reals, imags, direction: Direction, planner: PlannerNd64) -> None:
+    _fft_nd("64", np.float64, reals, imags, planner.shape, direction, planner)
+
+
+def fft_32_nd_with_planner(reals, imags, direction: Direction, planner: PlannerNd32) -> None:
+    _fft_nd("32", np.float32, reals, imags, planner.shape, direction, planner)
+
+
+def fft_nd_batched(reals, imags, direction: Direction, planner, batch: int = 1, dist: int | None = None,
+                   workspace=None) -> None:
+    """Device-resident batch of multi-dimensional transforms: array b at ``b*dist`` (default prod(shape)).  ``workspace``: a
+    device tensor of the planner's type of at least ``planner.workspace_len(1)`` elements (fewer than
+    ``planner.workspace_len(batch)`` runs the batch in chunks); by default one from torch's allocator."""
+    dtype, sfx, n = planner._dtype, planner._sfx, planner.n
+    re, im = _Slice(_flat(reals), dtype, "reals"), _Slice(_flat(imags), dtype, "imags")
+    if not _same_place(re, im):
+        raise TypeError("fft_nd_batched needs device tensors")
+    dist = n if dist is None else dist
+    _need("reals", re.len, batch, dist, n)
+    _need("imags", im.len, batch, dist, n)
+    ws = _any_workspace(planner, batch, workspace)
+    _check(getattr(_lib.lib(), f"phast_fft_{sfx}_nd_dev")(re.ptr, im.ptr, C.c_size_t(n), C.c_size_t(batch), C.c_size_t(dist),
+                                                          C.c_int(int(direction)), planner._h, ws.ptr, C.c_size_t(ws.len),
+                                                          _stream()))
+
+
+def _real_nd(c2r, fs, dtype, a, b, c, shape, planner=None):
+    """R2C: (a = the real array; b, c = the planes); C2R: (a, b = the planes; c = the real array)"""
+    names = ("input_re", "input_im", "output") if c2r else ("input_re", "output_re", "output_im")
+    sa, sb, sc = (_Slice(_flat(x), dtype, w) for x, w in zip((a, b, c), names))
+    l, sfx, kind = _lib.lib(), fs[1:], "c2r" if c2r else "r2c"
+    if _same_place(sa, sb, sc):
+        own = planner is None
+        if own:
+            planner = (PlannerR2cNd64 if fs == "f64" else PlannerR2cNd32)(shape)
+        n, h = planner.n, planner.half
+        checks = ((8, sc.len, n), (9, sa.len, h), (10, sb.len, h)) if c2r else ((5, sa.len, n), (6, sb.len, h), (7, sc.len, h))
+        for code, got, want in checks:
+            if got != want:
+                _check(code)
+        ws = _any_workspace(planner, 1)
+        dists = (C.c_size_t(h), C.c_size_t(n)) if c2r else (C.c_size_t(n), C.c_size_t(h))
+        _check(getattr(l, f"phast_{kind}_fft_{fs}_nd_dev")(sa.ptr, sb.ptr, sc.ptr, C.c_size_t(n), C.c_size_t(1), *dists,
+                                                          planner._h, ws.ptr, C.c_size_t(ws.len), _stream()))
+        if own:
+            import torch
+
+            torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+        return
+    args = [sa.ptr, C.c_size_t(sa.len), sb.ptr, C.c_size_t(sb.len), sc.ptr, C.c_size_t(sc.len)]
+    if planner is None:
+        _check(getattr(l, f"phast_{kind}_fft_{fs}_nd")(*args, *_dims(shape)))
+    else:
+        _check(getattr(l, f"phast_{kind}_fft_{fs}_nd_with_planner")(*args, planner._h))
+
+
+def r2c_fft_f64_nd(input_re, output_re, output_im, shape) -> None:
+    """f64 numpy rfftn of the real row-major array ``shape``: the half spectrum [n_0 .. n_{r-2}][n_{r-1} // 2 + 1] into two
+    planes (unnormalised)"""
+    _real_nd(False, "f64", np.float64, input_re, output_re, output_im, shape)
+
+
+def r2c_fft_f32_nd(input_re, output_re, output_im, shape) -> None:
+    """f32 twin of :func:`r2c_fft_f64_nd`"""
+    _real_nd(False, "f32", np.float32, input_re, output_re, output_im, shape)
+
+
+def r2c_fft_f64_nd_with_planner(input_re, output_re, output_im, planner: PlannerR2cNd64) -> None:
+    _real_nd(False, "f64", np.float64, input_re, output_re, output_im, planner.shape, planner)
+
+
+def r2c_fft_f32_nd_with_planner(input_re, output_re, output_im, planner: PlannerR2cNd32) -> None:
+    _real_nd(False, "f32", np.float32, input_re, output_re, output_im, planner.shape, planner)
+
+
+def c2r_fft_f64_nd(input_re, input_im, output, shape) -> None:
+    """f64 numpy irfftn(X, shape) of the half spectrum planes, scaled by 1 / prod(shape); the input planes stay unchanged"""
+    _real_nd(True, "f64", np.float64, input_re, input_im, output, shape)
+
+
+def c2r_fft_f32_nd(input_re, input_im, output, shape) -> None:
+    """f32 twin of :func:`c2r_fft_f64_nd`"""
+    _real_nd(True, "f32", np.float32, input_re, input_im, output, shape)
+
+
+def c2r_fft_f64_nd_with_planner(input_re, input_im, output, planner: PlannerR2cNd64) -> None:
+    _real_nd(True, "f64", np.float64, input_re, input_im, output, planner.shape, planner)
+
+
+def c2r_fft_f32_nd_with_planner(input_re, input_im, output, planner: PlannerR2cNd32) -> None:
+    _real_nd(True, "f32", np.float32, input_re, input_im, output, planner.shape, planner)
+
+
+def _real_nd_batched(c2r, a, b, c, planner, batch, in_dist, out_dist, workspace):
+    dtype, fs = planner._dtype, "f64" if planner._dtype == np.float64 else "f32"
+    names = ("input_re", "input_im", "output") if c2r else ("input_re", "output_re", "output_im")
+    sa, sb, sc = (_Slice(_flat(x), dtype, w) for x, w in zip((a, b, c), names))
+    kind = "c2r" if c2r else "r2c"
+    if not _same_place(sa, sb, sc):
+        raise TypeError(f"{kind}_nd_batched needs device tensors")
+    n, h = planner.n, planner.half
+    in_dist = (h if c2r else n) if in_dist is None else in_dist
+    out_dist = (n if c2r else h) if out_dist is None else out_dist
+    if c2r:
+        _need("input_re", sa.len, batch, in_dist, h)
+        _need("input_im", sb.len, batch, in_dist, h)
+        _need("output", sc.len, batch, out_dist, n)
+    else:
+        _need("input_re", sa.len, batch, in_dist, n)
+        _need("output_re", sb.len, batch, out_dist, h)
+        _need("output_im", sc.len, batch, out_dist, h)
+    ws = _any_workspace(planner, batch, workspace)
+    _check(getattr(_lib.lib(), f"phast_{kind}_fft_{fs}_nd_dev")(sa.ptr, sb.ptr, sc.ptr, C.c_size_t(n), C.c_size_t(batch),
+                                                               C.c_size_t(in_dist), C.c_size_t(out_dist), planner._h, ws.ptr,
+                                                               C.c_size_t(ws.len), _stream()))
+
+
+def r2c_nd_batched(input_re, output_re, output_im, planner, batch: int = 1, in_dist: int | None = None,
+                   out_dist: int | None = None, workspace=None) -> None:
+    """Device-resident batch of multi-dimensional R2C transforms: real array b at ``b*in_dist`` (default prod(shape)), its
+    half spectrum at ``b*out_dist`` (default ``planner.half``); ``workspace`` as for :func:`fft_nd_batched`"""
+    _real_nd_batched(False, input_re, output_re, output_im, planner, batch, in_dist, out_dist, workspace)
+
+
+def c2r_nd_batched(input_re, input_im, output, planner, batch: int = 1, in_dist: int | None = None,
+                   out_dist: int | None = None, workspace=None) -> None:
+    """Device-resident batch of multi-dimensional C2R transforms: half spectrum b at ``b*in_dist`` (default
+    ``planner.half``), its real array at ``b*out_dist`` (default prod(shape)); ``workspace`` as for :func:`fft_nd_batched`"""
+    _real_nd_batched(True, input_re, input_im, output, planner, batch, in_dist, out_dist, workspace)
 
 
 class TransformList:

@@ -56,6 +56,15 @@ phast_planner_r2c_any64_workspace_len phast_planner_r2c_any32_workspace_len phas
 phast_planner_r2c_any64_time_c2r_stages phast_planner_r2c_any32_time_c2r_stages
 phast_r2c_fft_f64_any phast_r2c_fft_f32_any phast_r2c_fft_f64_any_with_planner phast_r2c_fft_f32_any_with_planner phast_r2c_fft_f64_any_dev phast_r2c_fft_f32_any_dev
 phast_c2r_fft_f64_any phast_c2r_fft_f32_any phast_c2r_fft_f64_any_with_planner phast_c2r_fft_f32_any_with_planner phast_c2r_fft_f64_any_dev phast_c2r_fft_f32_any_dev
+phast_planner_nd64_new phast_planner_nd32_new phast_planner_nd64_free phast_planner_nd32_free
+phast_planner_nd64_describe phast_planner_nd32_describe phast_planner_nd64_device_bytes phast_planner_nd32_device_bytes
+phast_planner_nd64_workspace_len phast_planner_nd32_workspace_len phast_planner_nd64_time_steps phast_planner_nd32_time_steps
+phast_fft_64_nd phast_fft_32_nd phast_fft_64_nd_with_planner phast_fft_32_nd_with_planner phast_fft_64_nd_dev phast_fft_32_nd_dev
+phast_planner_r2c_nd64_new phast_planner_r2c_nd32_new phast_planner_r2c_nd64_free phast_planner_r2c_nd32_free
+phast_planner_r2c_nd64_describe phast_planner_r2c_nd32_describe phast_planner_r2c_nd64_device_bytes phast_planner_r2c_nd32_device_bytes
+phast_planner_r2c_nd64_workspace_len phast_planner_r2c_nd32_workspace_len
+phast_r2c_fft_f64_nd phast_r2c_fft_f32_nd phast_r2c_fft_f64_nd_with_planner phast_r2c_fft_f32_nd_with_planner phast_r2c_fft_f64_nd_dev phast_r2c_fft_f32_nd_dev
+phast_c2r_fft_f64_nd phast_c2r_fft_f32_nd phast_c2r_fft_f64_nd_with_planner phast_c2r_fft_f32_nd_with_planner phast_c2r_fft_f64_nd_dev phast_c2r_fft_f32_nd_dev
 """.split()
 
 
@@ -121,5 +130,9 @@ def lib() -> C.CDLL:
         getattr(l, f"phast_planner_r2c_any{sfx}_free").restype = None
         getattr(l, f"phast_planner_r2c_any{sfx}_device_bytes").restype = C.c_size_t
         getattr(l, f"phast_planner_r2c_any{sfx}_workspace_len").restype = C.c_size_t
+        for k in ("nd", "r2c_nd"):
+            getattr(l, f"phast_planner_{k}{sfx}_free").restype = None
+            getattr(l, f"phast_planner_{k}{sfx}_device_bytes").restype = C.c_size_t
+            getattr(l, f"phast_planner_{k}{sfx}_workspace_len").restype = C.c_size_t
     _lib = l
     return l

@@ -16,6 +16,7 @@
 #include "tune.hpp"
 #include "planner_any.hpp"
 #include "planner_any_real.hpp"
+#include "planner_nd.hpp"
 
 // ================================================================================================
 // C ABI
@@ -30,6 +31,10 @@ struct phast_planner_any64 : AnyPlanner<double> {};
 struct phast_planner_any32 : AnyPlanner<float> {};
 struct phast_planner_r2c_any64 : AnyRealPlanner<double> {};
 struct phast_planner_r2c_any32 : AnyRealPlanner<float> {};
+struct phast_planner_nd64 : NdPlanner<double> {};
+struct phast_planner_nd32 : NdPlanner<float> {};
+struct phast_planner_r2c_nd64 : RealNdPlanner<double> {};
+struct phast_planner_r2c_nd32 : RealNdPlanner<float> {};
 
 // W_N^(r*c) tables of a four-step split (twiddle.hip)
 template <typename T> struct TwiddleGrid {
@@ -607,5 +612,135 @@ PHAST_ANY_API(32, float)
     } PHAST_CATCH_RC
 PHAST_ANY_REAL_API(64, f64, double)
 PHAST_ANY_REAL_API(32, f32, float)
+
+// Multi-dimensional transforms (planner_nd.hpp): the shape and the lengths are checked before the device is touched
+#define PHAST_ND_PLANNER_API(NAME, KIND)                                                                                \
+    int phast_planner_##NAME##_new(const size_t *dims, size_t rank, phast_planner_##NAME **out) try {                   \
+        return nd_planner_new(dims, rank, KIND, out);                                                                   \
+    } PHAST_CATCH_RC                                                                                                    \
+    void phast_planner_##NAME##_free(phast_planner_##NAME *p) try { delete p; } PHAST_CATCH_VOID                        \
+    int phast_planner_##NAME##_describe(const phast_planner_##NAME *p, char *buf, size_t len) try {                     \
+        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
+        std::snprintf(buf, len, "%s", p->describe().c_str());                                                          \
+        return PHAST_OK;                                                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_##NAME##_device_bytes(const phast_planner_##NAME *p) try {                                     \
+        return p ? p->device_bytes() : 0;                                                                               \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_##NAME##_workspace_len(const phast_planner_##NAME *p, size_t batch) try {                      \
+        return p ? p->workspace_len(batch) : 0;                                                                         \
+    } PHAST_CATCH_ZERO
+#define PHAST_ND_TIME_API(SFX, T)                                                                                       \
+    int phast_planner_nd##SFX##_time_steps(const phast_planner_nd##SFX *p, T *d_re, T *d_im, size_t batch, size_t dist, \
+                                           T *d_work, size_t work_len, int reps, float *step_ms, size_t *n_steps,       \
+                                           void *stream) try {                                                          \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_steps(d_re, d_im, batch, dist, d_work, work_len, reps, step_ms, n_steps,                         \
+                             static_cast<hipStream_t>(stream));                                                         \
+    } PHAST_CATCH_RC
+PHAST_ND_TIME_API(64, double)
+PHAST_ND_TIME_API(32, float)
+PHAST_ND_PLANNER_API(nd64, kNdC2C)
+PHAST_ND_PLANNER_API(nd32, kNdC2C)
+PHAST_ND_PLANNER_API(r2c_nd64, kNdR2C)
+PHAST_ND_PLANNER_API(r2c_nd32, kNdR2C)
+
+// the product of a legal shape and the half-spectrum points of its real form (0: an illegal shape)
+static unsigned long long nd_points(const size_t *dims, size_t rank, unsigned long long *half_points) {
+    size_t sq[kNdMaxRank];
+    unsigned long long total = 0;
+    int bad = 1;
+    (void)nd_squeeze(dims, rank, kNdC2C, sq, &total, &bad);
+    if (bad) return 0;
+    if (half_points) *half_points = total / dims[rank - 1] * (dims[rank - 1] / 2 + 1);
+    return total;
+}
+
+#define PHAST_ND_API(SFX, T)                                                                                            \
+    int phast_fft_##SFX##_nd(T *re, size_t re_len, T *im, size_t im_len, const size_t *dims, size_t rank,                \
+                             int direction) try {                                                                       \
+        if ((!re && re_len) || (!im && im_len)) return PHAST_ERR_INVALID_ARG;                                           \
+        if (direction != PHAST_FORWARD && direction != PHAST_REVERSE) return PHAST_ERR_INVALID_ARG;                     \
+        const unsigned long long total = nd_points(dims, rank, nullptr);                                                \
+        if (!total) return PHAST_ERR_INVALID_ARG;                                                                       \
+        if (re_len != im_len) return PHAST_ERR_LEN_MISMATCH;                                                            \
+        if (re_len != total) return PHAST_ERR_PLANNER_SIZE;                                                             \
+        NdPlanner<T> *p = nullptr; /* a planner of the call's own */                                                   \
+        int rc = nd_planner_new(dims, rank, kNdC2C, &p);                                                                \
+        if (rc) return rc;                                                                                              \
+        std::unique_ptr<NdPlanner<T>> own(p);                                                                           \
+        return p->fft_host_nd(re, re_len, im, im_len, direction);                                                       \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_fft_##SFX##_nd_with_planner(T *re, size_t re_len, T *im, size_t im_len, int direction,                    \
+                                          const phast_planner_nd##SFX *p) try {                                         \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->fft_host_nd(re, re_len, im, im_len, direction);                                                       \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_fft_##SFX##_nd_dev(T *d_re, T *d_im, size_t n_total, size_t batch, size_t dist, int direction,            \
+                                 const phast_planner_nd##SFX *p, T *d_work, size_t work_len, void *stream) try {        \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->fft_dev_nd(d_re, d_im, n_total, batch, dist, direction, d_work, work_len,                             \
+                             static_cast<hipStream_t>(stream));                                                         \
+    } PHAST_CATCH_RC
+PHAST_ND_API(64, double)
+PHAST_ND_API(32, float)
+
+#define PHAST_ND_REAL_API(SFX, FS, T)                                                                                   \
+    int phast_r2c_fft_##FS##_nd(const T *in, size_t in_len, T *ore, size_t ore_len, T *oim, size_t oim_len,             \
+                                const size_t *dims, size_t rank) try {                                                  \
+        if (!in || !ore || !oim) return PHAST_ERR_INVALID_ARG;                                                          \
+        unsigned long long hp = 0;                                                                                      \
+        const unsigned long long total = nd_points(dims, rank, &hp);                                                    \
+        if (!total) return PHAST_ERR_INVALID_ARG;                                                                       \
+        if (in_len != total) return PHAST_ERR_R2C_INPUT_LEN; /* before the device is touched */                        \
+        if (ore_len != hp) return PHAST_ERR_R2C_OUT_RE_LEN;                                                             \
+        if (oim_len != hp) return PHAST_ERR_R2C_OUT_IM_LEN;                                                             \
+        RealNdPlanner<T> *p = nullptr;                                                                                  \
+        int rc = nd_planner_new(dims, rank, kNdR2C, &p);                                                                \
+        if (rc) return rc;                                                                                              \
+        std::unique_ptr<RealNdPlanner<T>> own(p);                                                                       \
+        return p->host(false, in, in_len, nullptr, 0, ore, ore_len, oim, oim_len);                                      \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_r2c_fft_##FS##_nd_with_planner(const T *in, size_t in_len, T *ore, size_t ore_len, T *oim,                \
+                                             size_t oim_len, const phast_planner_r2c_nd##SFX *p) try {                  \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(false, in, in_len, nullptr, 0, ore, ore_len, oim, oim_len);                                      \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_r2c_fft_##FS##_nd_dev(const T *d_in, T *d_ore, T *d_oim, size_t n_total, size_t batch, size_t in_dist,    \
+                                    size_t out_dist, const phast_planner_r2c_nd##SFX *p, T *d_work, size_t work_len,    \
+                                    void *stream) try {                                                                 \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(false, d_in, nullptr, d_ore, d_oim, n_total, batch, in_dist, out_dist, d_work, work_len,          \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_c2r_fft_##FS##_nd(const T *ire, size_t ire_len, const T *iim, size_t iim_len, T *out, size_t out_len,     \
+                                const size_t *dims, size_t rank) try {                                                  \
+        if (!ire || !iim || !out) return PHAST_ERR_INVALID_ARG;                                                         \
+        unsigned long long hp = 0;                                                                                      \
+        const unsigned long long total = nd_points(dims, rank, &hp);                                                    \
+        if (!total) return PHAST_ERR_INVALID_ARG;                                                                       \
+        if (out_len != total) return PHAST_ERR_C2R_OUTPUT_LEN; /* before the device is touched */                      \
+        if (ire_len != hp) return PHAST_ERR_C2R_IN_RE_LEN;                                                              \
+        if (iim_len != hp) return PHAST_ERR_C2R_IN_IM_LEN;                                                              \
+        RealNdPlanner<T> *p = nullptr;                                                                                  \
+        int rc = nd_planner_new(dims, rank, kNdR2C, &p);                                                                \
+        if (rc) return rc;                                                                                              \
+        std::unique_ptr<RealNdPlanner<T>> own(p);                                                                       \
+        return p->host(true, ire, ire_len, iim, iim_len, out, out_len, nullptr, 0);                                     \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_c2r_fft_##FS##_nd_with_planner(const T *ire, size_t ire_len, const T *iim, size_t iim_len, T *out,        \
+                                             size_t out_len, const phast_planner_r2c_nd##SFX *p) try {                  \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(true, ire, ire_len, iim, iim_len, out, out_len, nullptr, 0);                                     \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_c2r_fft_##FS##_nd_dev(const T *d_ire, const T *d_iim, T *d_out, size_t n_total, size_t batch,             \
+                                    size_t in_dist, size_t out_dist, const phast_planner_r2c_nd##SFX *p, T *d_work,     \
+                                    size_t work_len, void *stream) try {                                                \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(true, d_ire, d_iim, d_out, nullptr, n_total, batch, in_dist, out_dist, d_work, work_len,          \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC
+PHAST_ND_REAL_API(64, f64, double)
+PHAST_ND_REAL_API(32, f32, float)
 
 }  // extern "C"

@@ -114,6 +114,43 @@ extern "C" {
         in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
     pub(crate) fn phast_c2r_fft_f32_any_dev(ire: *const f32, iim: *const f32, out: *mut f32, n: usize, batch: usize,
         in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // multi-dimensional transforms (an extension beyond PhastFT 0.3.0: planner.rs / lib.rs / algorithms/r2c.rs)
+    pub(crate) fn phast_planner_nd64_new(dims: *const usize, rank: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nd32_new(dims: *const usize, rank: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nd64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_nd32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_nd64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_nd32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_fft_64_nd_with_planner(re: *mut f64, re_len: usize, im: *mut f64, im_len: usize,
+        direction: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_fft_32_nd_with_planner(re: *mut f32, re_len: usize, im: *mut f32, im_len: usize,
+        direction: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_fft_64_nd_dev(re: *mut f64, im: *mut f64, n_total: usize, batch: usize, dist: usize,
+        direction: c_int, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_fft_32_nd_dev(re: *mut f32, im: *mut f32, n_total: usize, batch: usize, dist: usize,
+        direction: c_int, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_r2c_nd64_new(dims: *const usize, rank: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_r2c_nd32_new(dims: *const usize, rank: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_r2c_nd64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_r2c_nd32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_r2c_nd64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_r2c_nd32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_r2c_fft_f64_nd_with_planner(input: *const f64, n: usize, ore: *mut f64, ore_len: usize,
+        oim: *mut f64, oim_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_r2c_fft_f32_nd_with_planner(input: *const f32, n: usize, ore: *mut f32, ore_len: usize,
+        oim: *mut f32, oim_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_r2c_fft_f64_nd_dev(input: *const f64, ore: *mut f64, oim: *mut f64, n_total: usize, batch: usize,
+        in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_r2c_fft_f32_nd_dev(input: *const f32, ore: *mut f32, oim: *mut f32, n_total: usize, batch: usize,
+        in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_c2r_fft_f64_nd_with_planner(ire: *const f64, ire_len: usize, iim: *const f64, iim_len: usize,
+        out: *mut f64, n: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_c2r_fft_f32_nd_with_planner(ire: *const f32, ire_len: usize, iim: *const f32, iim_len: usize,
+        out: *mut f32, n: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_c2r_fft_f64_nd_dev(ire: *const f64, iim: *const f64, out: *mut f64, n_total: usize, batch: usize,
+        in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_c2r_fft_f32_nd_dev(ire: *const f32, iim: *const f32, out: *mut f32, n_total: usize, batch: usize,
+        in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
 }
 
 /// Re-raises a library status as the reference's panic: `phast_strerror` returns the exact text of the

@@ -43,9 +43,15 @@ pub use algorithms::r2c::{
     c2r_fft_f64_any_with_planner, r2c_fft_f32_any, r2c_fft_f32_any_dev, r2c_fft_f32_any_with_planner, r2c_fft_f64_any,
     r2c_fft_f64_any_dev, r2c_fft_f64_any_with_planner,
 };
+// multi-dimensional real transforms (an extension beyond PhastFT 0.3.0)
+pub use algorithms::r2c::{
+    c2r_fft_f32_nd, c2r_fft_f32_nd_dev, c2r_fft_f32_nd_with_planner, c2r_fft_f64_nd, c2r_fft_f64_nd_dev,
+    c2r_fft_f64_nd_with_planner, r2c_fft_f32_nd, r2c_fft_f32_nd_dev, r2c_fft_f32_nd_with_planner, r2c_fft_f64_nd,
+    r2c_fft_f64_nd_dev, r2c_fft_f64_nd_with_planner,
+};
 
 use crate::options::Options;
-use crate::planner::{Direction, PlannerAny32, PlannerAny64, PlannerDit32, PlannerDit64};
+use crate::planner::{Direction, PlannerAny32, PlannerAny64, PlannerDit32, PlannerDit64, PlannerNd32, PlannerNd64};
 use std::ffi::{c_int, c_void};
 
 macro_rules! impl_fft {
@@ -103,6 +109,33 @@ impl_fft_any!(f64, PlannerAny64, fft_64_any_with_planner, fft_64_any, phast_fft_
               phast_fft_64_any_dev);
 impl_fft_any!(f32, PlannerAny32, fft_32_any_with_planner, fft_32_any, phast_fft_32_any_with_planner, fft_32_any_dev,
               phast_fft_32_any_dev);
+
+/// Complex transforms over every axis of a row-major array (numpy fftn / ifftn) -- an extension beyond PhastFT 0.3.0.  Planar
+/// slices of prod(shape) points, in place; `Reverse` scales by 1 / prod(shape).
+macro_rules! impl_fft_nd {
+    ($t:ty, $planner:ident, $with_planner:ident, $plain:ident, $c_fn:ident, $dev:ident, $c_dev:ident) => {
+        pub fn $with_planner(reals: &mut [$t], imags: &mut [$t], direction: Direction, planner: &$planner) {
+            ffi::check(unsafe {
+                ffi::$c_fn(reals.as_mut_ptr(), reals.len(), imags.as_mut_ptr(), imags.len(), direction as c_int, planner.h)
+            });
+        }
+        pub fn $plain(reals: &mut [$t], imags: &mut [$t], shape: &[usize], direction: Direction) {
+            let planner = <$planner>::new(shape);
+            $with_planner(reals, imags, direction, &planner);
+        }
+        /// Device-resident, batched, asynchronous on `stream`: `d_work` is a device workspace of at least
+        /// `planner.workspace_len(1)` elements (`planner.workspace_len(batch)` runs the batch in one chunk)
+        pub unsafe fn $dev(d_reals: *mut $t, d_imags: *mut $t, n_total: usize, batch: usize, dist: usize, direction: Direction,
+                           planner: &$planner, d_work: *mut $t, work_len: usize, stream: *mut c_void) {
+            ffi::check(ffi::$c_dev(d_reals, d_imags, n_total, batch, dist, direction as c_int, planner.h, d_work, work_len,
+                                   stream));
+        }
+    };
+}
+impl_fft_nd!(f64, PlannerNd64, fft_64_nd_with_planner, fft_64_nd, phast_fft_64_nd_with_planner, fft_64_nd_dev,
+             phast_fft_64_nd_dev);
+impl_fft_nd!(f32, PlannerNd32, fft_32_nd_with_planner, fft_32_nd, phast_fft_32_nd_with_planner, fft_32_nd_dev,
+             phast_fft_32_nd_dev);
 
 /// Interleaved `Complex<T>` signals (reference: feature `complex-nums`, lib.rs:41-140).  The reference copies into
 /// two planar Vecs, runs the planar path and copies back; the library fuses the (de)interleave into the first

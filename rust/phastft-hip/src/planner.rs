@@ -201,3 +201,49 @@ impl_planner_r2c_any!(PlannerR2cAny64, phast_planner_r2c_any64_new, phast_planne
                       phast_planner_r2c_any64_workspace_len);
 impl_planner_r2c_any!(PlannerR2cAny32, phast_planner_r2c_any32_new, phast_planner_r2c_any32_free,
                       phast_planner_r2c_any32_workspace_len);
+
+macro_rules! impl_planner_nd {
+    ($nd:ident, $new:ident, $free:ident, $ws_len:ident, $what:literal) => {
+        #[doc = concat!("An extension beyond PhastFT 0.3.0, whose planners transform one axis: ", $what, " over every axis of a ",
+                        "row-major array of rank 1 ..= 8 (each axis 1 ..= 2^29, at most 2^30 points; each axis runs the ",
+                        "any-length path of its length, rotated to the contiguous end by a batched transpose).  Immutable ",
+                        "after `new`, like the reference's planners.")]
+        pub struct $nd {
+            pub(crate) h: *mut Opaque,
+            pub(crate) shape: Vec<usize>,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in a
+        // device buffer of its own (host-slice calls)
+        unsafe impl Send for $nd {}
+        unsafe impl Sync for $nd {}
+        impl $nd {
+            /// panics with "invalid argument" for rank 0 or > 8, an axis 0 or > 2^29, more than 2^30 points
+            pub fn new(shape: &[usize]) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe { ffi::$new(shape.as_ptr(), shape.len(), &mut h) });
+                Self { h, shape: shape.to_vec() }
+            }
+            pub fn shape(&self) -> &[usize] {
+                &self.shape
+            }
+            /// elements of the workspace a device call of `batch` arrays works in at full speed; `workspace_len(1)` serves
+            /// any batch, in chunks
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+        }
+        impl Drop for $nd {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_nd!(PlannerNd64, phast_planner_nd64_new, phast_planner_nd64_free, phast_planner_nd64_workspace_len,
+                 "f64 complex transforms (numpy fftn / ifftn)");
+impl_planner_nd!(PlannerNd32, phast_planner_nd32_new, phast_planner_nd32_free, phast_planner_nd32_workspace_len,
+                 "f32 complex transforms (numpy fftn / ifftn)");
+impl_planner_nd!(PlannerR2cNd64, phast_planner_r2c_nd64_new, phast_planner_r2c_nd64_free,
+                 phast_planner_r2c_nd64_workspace_len, "f64 real transforms (numpy rfftn / irfftn)");
+impl_planner_nd!(PlannerR2cNd32, phast_planner_r2c_nd32_new, phast_planner_r2c_nd32_free,
+                 phast_planner_r2c_nd32_workspace_len, "f32 real transforms (numpy rfftn / irfftn)");
