@@ -18,6 +18,8 @@
 //   (none: powers of two only upstream)                      class PlannerAny64/32, fft_64/32_any[_with_planner] -- any N >= 1
 //   (none: r2c.rs takes powers of two >= 4)                  class PlannerR2cAny64/32, r2c_fft_f64/f32_any[_with_planner],
 //                                                            c2r_fft_f64/f32_any[_with_planner] -- any N >= 1
+//   (none: no real-to-real transforms upstream)              class PlannerDct64/32, dct_f64/f32[_with_planner],
+//                                                            dst_f64/f32[_with_planner], enum Norm -- types II and III, any N >= 1
 //   (none: one axis only upstream)                           class PlannerNd64/32, PlannerR2cNd64/32, fft_64/32_nd[_with_planner],
 //                                                            r2c_fft_f64/f32_nd[...], c2r_fft_f64/f32_nd[...] -- every axis
 //
@@ -399,6 +401,51 @@ inline void c2r_fft_f64_any(Slice<const double> input_re, Slice<const double> in
 inline void c2r_fft_f32_any(Slice<const float> input_re, Slice<const float> input_im, Slice<float> output) {
     check(phast_c2r_fft_f32_any(input_re.ptr, input_re.len, input_im.ptr, input_im.len, output.ptr, output.len));
 }
+
+// ---- DCT / DST of types II and III, any length N >= 1 (no reference counterpart; scipy.fft.dct / dst) ----
+enum class Norm : int { Backward = PHAST_NORM_BACKWARD, Ortho = PHAST_NORM_ORTHO, Forward = PHAST_NORM_FORWARD };
+#define PHASTFT_PLANNER_DCT(NAME, CT, SFX)                                                                       \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        explicit NAME(std::size_t n) { check(phast_planner_dct##SFX##_new(n, &h_)); }                            \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }                                                   \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_dct##SFX##_free(h_);                                                           \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_dct##SFX##_describe(h_, &s[0], s.size()));                                       \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_dct##SFX##_device_bytes(h_); }                   \
+        /* elements of T a _dev call of `batch` transforms works in (any length >= workspace_len(1) is legal) */ \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_dct##SFX##_workspace_len(h_, batch); } \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+    };
+PHASTFT_PLANNER_DCT(PlannerDct64, phast_planner_dct64, 64)
+PHASTFT_PLANNER_DCT(PlannerDct32, phast_planner_dct32, 32)
+#undef PHASTFT_PLANNER_DCT
+
+#define PHASTFT_R2R(KIND, FS, T, P)                                                                              \
+    inline void KIND##_##FS(Slice<const T> input, Slice<T> output, int type = 2, Norm norm = Norm::Backward) {   \
+        check(phast_##KIND##_##FS(input.ptr, input.len, output.ptr, output.len, type, static_cast<int>(norm)));  \
+    }                                                                                                            \
+    inline void KIND##_##FS##_with_planner(Slice<const T> input, Slice<T> output, const P &planner, int type = 2, \
+                                           Norm norm = Norm::Backward) {                                         \
+        check(phast_##KIND##_##FS##_with_planner(input.ptr, input.len, output.ptr, output.len, type,             \
+                                                 static_cast<int>(norm), planner.get()));                        \
+    }
+PHASTFT_R2R(dct, f64, double, PlannerDct64)
+PHASTFT_R2R(dct, f32, float, PlannerDct32)
+PHASTFT_R2R(dst, f64, double, PlannerDct64)
+PHASTFT_R2R(dst, f32, float, PlannerDct32)
+#undef PHASTFT_R2R
 
 // ---- transforms over every axis of a row-major array (numpy fftn / rfftn / irfftn; no reference counterpart) ----
 #define PHASTFT_PLANNER_ND(NAME, CT, PFX)                                                                        \

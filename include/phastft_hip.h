@@ -362,6 +362,73 @@ int phast_planner_r2c_any32_time_c2r_stages(const phast_planner_r2c_any32 *p, co
                                             const float *d_input_im, float *d_output, size_t batch, float *d_work,
                                             size_t work_len, int reps, float *stage_ms, void *stream);
 
+/* ---- DCT and DST of types II and III, any length 1 <= N <= 2^29 (no reference counterpart; scipy.fft.dct / dst with
+ * orthogonalize=True, FFTW REDFT10 / REDFT01 / RODFT10 / RODFT01).  With norm = PHAST_NORM_BACKWARD (scipy's default):
+ *     DCT-II   y[k] = 2 sum_{n<N} x[n] cos(pi k (2n+1) / (2N))
+ *     DCT-III  y[k] = x[0] + 2 sum_{1<=n<N} x[n] cos(pi n (2k+1) / (2N))
+ *     DST-II   y[k] = 2 sum_{n<N} x[n] sin(pi (k+1) (2n+1) / (2N))
+ *     DST-III  y[k] = (-1)^k x[N-1] + 2 sum_{n<N-1} x[n] sin(pi (n+1) (2k+1) / (2N))
+ * PHAST_NORM_FORWARD scales the result by 1/(2N); PHAST_NORM_ORTHO by 1/sqrt(2N), and in addition DCT-II divides y[0] and
+ * DST-II y[N-1] by sqrt 2, DCT-III multiplies x[0] and DST-III x[N-1] by sqrt 2 first.  The inverse of type t with norm
+ * backward / ortho / forward is type 5 - t with norm forward / ortho / backward (scipy's idct / idst).  `type` is 2 or 3
+ * (types I and IV are reserved); any other type or norm is PHAST_ERR_INVALID_ARG.
+ *
+ * Algorithm: Makhoul's -- one real transform of the same N (the phast_planner_r2c_any* engine, called
+ * unchanged: R2C for type II, C2R for type III) between two O(N) sweeps.  The caller's device workspace holds
+ * phast_planner_dct*_workspace_len(p, batch) elements of T; any work_len >= phast_planner_dct*_workspace_len(p, 1) runs the
+ * batch in chunks, a null or shorter one is PHAST_ERR_INVALID_ARG.  _dev calls: asynchronous on `stream`; `batch` transforms,
+ * in_dist and out_dist >= N (no parity rule); pointers need element alignment only.  In place (d_out == d_in with in_dist ==
+ * out_dist) is allowed; any other overlap of input and output is undefined.  Out of place, the input is never written.  A
+ * null pointer, a bad type or norm or a short dist is PHAST_ERR_INVALID_ARG, an `n` that is not the planner's
+ * PHAST_ERR_PLANNER_SIZE, host slices of unequal lengths PHAST_ERR_LEN_MISMATCH -- all before the device is touched.  The
+ * planner is immutable and holds no per-call state; the bits of a transform do not depend on the batch, the chunking, the
+ * stream, graph replay, the form of the call (host slice or _dev), in place or out of place, or pointer alignment.
+ * Host-slice calls stage through the device (they block). */
+#define PHAST_NORM_BACKWARD 0
+#define PHAST_NORM_ORTHO 1
+#define PHAST_NORM_FORWARD 2
+typedef struct phast_planner_dct64 phast_planner_dct64; /* PlannerDct64 */
+typedef struct phast_planner_dct32 phast_planner_dct32; /* PlannerDct32 */
+int phast_planner_dct64_new(size_t n, phast_planner_dct64 **out);
+int phast_planner_dct32_new(size_t n, phast_planner_dct32 **out);
+void phast_planner_dct64_free(phast_planner_dct64 *p);
+void phast_planner_dct32_free(phast_planner_dct32 *p);
+int phast_planner_dct64_describe(const phast_planner_dct64 *p, char *buf, size_t buf_len);
+int phast_planner_dct32_describe(const phast_planner_dct32 *p, char *buf, size_t buf_len);
+size_t phast_planner_dct64_device_bytes(const phast_planner_dct64 *p);
+size_t phast_planner_dct32_device_bytes(const phast_planner_dct32 *p);
+size_t phast_planner_dct64_workspace_len(const phast_planner_dct64 *p, size_t batch);
+size_t phast_planner_dct32_workspace_len(const phast_planner_dct32 *p, size_t batch);
+int phast_dct_f64(const double *input, size_t input_len, double *output, size_t output_len, int type, int norm);
+int phast_dct_f32(const float *input, size_t input_len, float *output, size_t output_len, int type, int norm);
+int phast_dst_f64(const double *input, size_t input_len, double *output, size_t output_len, int type, int norm);
+int phast_dst_f32(const float *input, size_t input_len, float *output, size_t output_len, int type, int norm);
+int phast_dct_f64_with_planner(const double *input, size_t input_len, double *output, size_t output_len, int type, int norm,
+                               const phast_planner_dct64 *planner);
+int phast_dct_f32_with_planner(const float *input, size_t input_len, float *output, size_t output_len, int type, int norm,
+                               const phast_planner_dct32 *planner);
+int phast_dst_f64_with_planner(const double *input, size_t input_len, double *output, size_t output_len, int type, int norm,
+                               const phast_planner_dct64 *planner);
+int phast_dst_f32_with_planner(const float *input, size_t input_len, float *output, size_t output_len, int type, int norm,
+                               const phast_planner_dct32 *planner);
+int phast_dct_f64_dev(const double *d_input, double *d_output, size_t n, size_t batch, size_t in_dist, size_t out_dist, int type,
+                      int norm, const phast_planner_dct64 *planner, double *d_work, size_t work_len, void *stream);
+int phast_dct_f32_dev(const float *d_input, float *d_output, size_t n, size_t batch, size_t in_dist, size_t out_dist, int type,
+                      int norm, const phast_planner_dct32 *planner, float *d_work, size_t work_len, void *stream);
+int phast_dst_f64_dev(const double *d_input, double *d_output, size_t n, size_t batch, size_t in_dist, size_t out_dist, int type,
+                      int norm, const phast_planner_dct64 *planner, double *d_work, size_t work_len, void *stream);
+int phast_dst_f32_dev(const float *d_input, float *d_output, size_t n, size_t batch, size_t in_dist, size_t out_dist, int type,
+                      int norm, const phast_planner_dct32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/dct_rate.py): stage_ms[3] = average milliseconds of the pre sweep, the real transform and the post
+ * sweep of a DCT (dst = 0) or DST (dst = 1) of `type` over `reps` calls of `batch` transforms at distance N in ONE chunk
+ * (work_len >= phast_planner_dct*_workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_dct64_time_stages(const phast_planner_dct64 *p, int dst, int type, int norm, const double *d_input,
+                                    double *d_output, size_t batch, double *d_work, size_t work_len, int reps, float *stage_ms,
+                                    void *stream);
+int phast_planner_dct32_time_stages(const phast_planner_dct32 *p, int dst, int type, int norm, const float *d_input,
+                                    float *d_output, size_t batch, float *d_work, size_t work_len, int reps, float *stage_ms,
+                                    void *stream);
+
 /* ---- multi-dimensional transforms over every axis of a row-major array (no reference counterpart; numpy fftn / ifftn /
  * rfftn / irfftn with this library's conventions).  dims[0 .. rank-1]: rank 1 .. 8, every axis 1 .. 2^29,
  * their product <= 2^30 (else PHAST_ERR_INVALID_ARG, before the device is touched).  Every axis is transformed; leading

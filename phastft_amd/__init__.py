@@ -20,6 +20,8 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
     (none: powers of two only)                      PlannerAny64/32, fft_64/32_any[_with_planner], fft_any_batched
     (none: r2c.rs takes powers of two >= 4)         PlannerR2cAny64/32, r2c_fft_f64/f32_any[_with_planner],
                                                     c2r_fft_f64/f32_any[_with_planner], r2c_any_batched, c2r_any_batched
+    (none: no real-to-real transforms)              PlannerDct64/32, dct_f64/f32[_with_planner], dst_f64/f32[_with_planner],
+                                                    dct_batched, dst_batched, idct, idst
     (none: one axis only)                           PlannerNd64/32, fft_64/32_nd[_with_planner], fft_nd_batched,
                                                     PlannerR2cNd64/32, r2c_fft_f64/f32_nd[_with_planner],
                                                     c2r_fft_f64/f32_nd[_with_planner], r2c_nd_batched, c2r_nd_batched
@@ -61,6 +63,8 @@ __all__ = [
     "PlannerR2cAny64", "PlannerR2cAny32", "r2c_fft_f64_any", "r2c_fft_f32_any", "r2c_fft_f64_any_with_planner",
     "r2c_fft_f32_any_with_planner", "c2r_fft_f64_any", "c2r_fft_f32_any", "c2r_fft_f64_any_with_planner",
     "c2r_fft_f32_any_with_planner", "r2c_any_batched", "c2r_any_batched",
+    "PlannerDct64", "PlannerDct32", "dct_f64", "dct_f32", "dst_f64", "dst_f32", "dct_f64_with_planner", "dct_f32_with_planner",
+    "dst_f64_with_planner", "dst_f32_with_planner", "dct_batched", "dst_batched", "idct", "idst",
     "PlannerNd64", "PlannerNd32", "fft_64_nd", "fft_32_nd", "fft_64_nd_with_planner", "fft_32_nd_with_planner", "fft_nd_batched",
     "PlannerR2cNd64", "PlannerR2cNd32", "r2c_fft_f64_nd", "r2c_fft_f32_nd", "r2c_fft_f64_nd_with_planner",
     "r2c_fft_f32_nd_with_planner", "c2r_fft_f64_nd", "c2r_fft_f32_nd", "c2r_fft_f64_nd_with_planner",
@@ -883,6 +887,178 @@ def c2r_any_batched(input_re, input_im, output, planner, batch: int, in_dist: in
     _check(getattr(_lib.lib(), f"phast_c2r_fft_{fs}_any_dev")(ire.ptr, iim.ptr, out.ptr, C.c_size_t(n), C.c_size_t(batch),
                                                               C.c_size_t(in_dist), C.c_size_t(out_dist), planner._h, ws.ptr,
                                                               C.c_size_t(ws.len), _stream()))
+
+
+# ---------------------------------------------------------------------------------------------
+# DCT / DST of types II and III, any length N >= 1 (no reference counterpart; scipy.fft.dct / dst / idct / idst)
+# ---------------------------------------------------------------------------------------------
+_NORMS = {None: 0, "backward": 0, "ortho": 1, "forward": 2}
+
+
+def _norm_code(norm) -> int:
+    if norm not in _NORMS:
+        raise ValueError(f"norm must be None, 'backward', 'ortho' or 'forward', not {norm!r}")
+    return _NORMS[norm]
+
+
+class PlannerDct64(_AnyHandle):
+    """f64 DCT / DST of types II and III of any length 1 <= N <= 2^29 (one planner serves all four and every norm)"""
+
+    _prefix = "dct"
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` transforms works in.  Any workspace of at least ``workspace_len(1)``
+        elements is legal: a smaller one than ``workspace_len(batch)`` runs the batch in chunks."""
+        return self._workspace_len(batch)
+
+    def time_stages(self, input, output, kind: str = "dct", type: int = 2, norm=None, batch: int = 1, workspace=None,
+                    reps: int = 10):
+        """Average HIP-event milliseconds of the pre sweep, the real transform and the post sweep of ``batch`` transforms at
+        distance N on device tensors (measurement hook); ``kind`` is ``"dct"`` or ``"dst"``"""
+        i, o = _Slice(input, self._dtype, "input"), _Slice(output, self._dtype, "output")
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 3)()
+        _check(self._fn("time_stages")(self._h, C.c_int(kind == "dst"), C.c_int(type), C.c_int(_norm_code(norm)), i.ptr, o.ptr,
+                                       C.c_size_t(batch), ws.ptr, C.c_size_t(ws.len), C.c_int(reps), ms, _stream()))
+        return [float(x) for x in ms]
+
+
+class PlannerDct32(PlannerDct64):
+    """f32 twin of :class:`PlannerDct64`"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def _r2r(kind, fs, dtype, input, output, type, norm, planner=None):
+    i, o = _Slice(input, dtype, "input"), _Slice(output, dtype, "output")
+    l, code = _lib.lib(), _norm_code(norm)
+    if _same_place(i, o):
+        if i.len != o.len:
+            _check(2)
+        own = planner is None
+        if own:
+            planner = (PlannerDct64 if fs == "f64" else PlannerDct32)(i.len)
+        ws = _any_workspace(planner, 1)
+        _check(getattr(l, f"phast_{kind}_{fs}_dev")(i.ptr, o.ptr, C.c_size_t(i.len), C.c_size_t(1), C.c_size_t(i.len),
+                                                    C.c_size_t(o.len), C.c_int(type), C.c_int(code), planner._h, ws.ptr,
+                                                    C.c_size_t(ws.len), _stream()))
+        if own:
+            import torch
+
+            torch.cuda.current_stream().synchronize()
+        return
+    args = [i.ptr, C.c_size_t(i.len), o.ptr, C.c_size_t(o.len), C.c_int(type), C.c_int(code)]
+    if planner is None:
+        _check(getattr(l, f"phast_{kind}_{fs}")(*args))
+    else:
+        _check(getattr(l, f"phast_{kind}_{fs}_with_planner")(*args, planner._h))
+
+
+def dct_f64(input, output, type: int = 2, norm=None) -> None:
+    """f64 DCT of ``type`` 2 or 3 of any length N = len(input) into ``output`` (scipy.fft.dct(input, type, norm=norm))"""
+    _r2r("dct", "f64", np.float64, input, output, type, norm)
+
+
+def dct_f32(input, output, type: int = 2, norm=None) -> None:
+    """f32 twin of :func:`dct_f64`"""
+    _r2r("dct", "f32", np.float32, input, output, type, norm)
+
+
+def dst_f64(input, output, type: int = 2, norm=None) -> None:
+    """f64 DST of ``type`` 2 or 3 of any length N = len(input) into ``output`` (scipy.fft.dst(input, type, norm=norm))"""
+    _r2r("dst", "f64", np.float64, input, output, type, norm)
+
+
+def dst_f32(input, output, type: int = 2, norm=None) -> None:
+    """f32 twin of :func:`dst_f64`"""
+    _r2r("dst", "f32", np.float32, input, output, type, norm)
+
+
+def dct_f64_with_planner(input, output, planner: PlannerDct64, type: int = 2, norm=None) -> None:
+    _r2r("dct", "f64", np.float64, input, output, type, norm, planner)
+
+
+def dct_f32_with_planner(input, output, planner: PlannerDct32, type: int = 2, norm=None) -> None:
+    _r2r("dct", "f32", np.float32, input, output, type, norm, planner)
+
+
+def dst_f64_with_planner(input, output, planner: PlannerDct64, type: int = 2, norm=None) -> None:
+    _r2r("dst", "f64", np.float64, input, output, type, norm, planner)
+
+
+def dst_f32_with_planner(input, output, planner: PlannerDct32, type: int = 2, norm=None) -> None:
+    _r2r("dst", "f32", np.float32, input, output, type, norm, planner)
+
+
+def _r2r_batched(kind, input, output, planner, batch, type, norm, in_dist, out_dist, workspace):
+    dtype = planner._dtype
+    fs = "f64" if dtype == np.float64 else "f32"
+    i, o = _Slice(input, dtype, "input"), _Slice(output, dtype, "output")
+    if not _same_place(i, o):
+        raise TypeError(f"{kind}_batched needs device tensors")
+    n = planner.n
+    in_dist = n if in_dist is None else in_dist
+    out_dist = n if out_dist is None else out_dist
+    _need("input", i.len, batch, in_dist, n)
+    _need("output", o.len, batch, out_dist, n)
+    ws = _any_workspace(planner, batch, workspace)
+    _check(getattr(_lib.lib(), f"phast_{kind}_{fs}_dev")(i.ptr, o.ptr, C.c_size_t(n), C.c_size_t(batch), C.c_size_t(in_dist),
+                                                         C.c_size_t(out_dist), C.c_int(type), C.c_int(_norm_code(norm)),
+                                                         planner._h, ws.ptr, C.c_size_t(ws.len), _stream()))
+
+
+def dct_batched(input, output, planner, batch: int, type: int = 2, norm=None, in_dist: int | None = None,
+                out_dist: int | None = None, workspace=None) -> None:
+    """Device-resident batch of DCTs: input b at ``b*in_dist``, output b at ``b*out_dist`` (both default N, any distance
+    >= N).  ``output`` may be ``input`` itself with equal distances (in place).  ``workspace``: a device tensor of the
+    planner's type of at least ``planner.workspace_len(1)`` elements (fewer than ``planner.workspace_len(batch)`` runs the
+    batch in chunks); by default one from torch's allocator."""
+    _r2r_batched("dct", input, output, planner, batch, type, norm, in_dist, out_dist, workspace)
+
+
+def dst_batched(input, output, planner, batch: int, type: int = 2, norm=None, in_dist: int | None = None,
+                out_dist: int | None = None, workspace=None) -> None:
+    """:func:`dct_batched` for the DST"""
+    _r2r_batched("dst", input, output, planner, batch, type, norm, in_dist, out_dist, workspace)
+
+
+_INVERSE_NORM = {None: "forward", "backward": "forward", "ortho": "ortho", "forward": "backward"}
+
+
+def _inverse(type: int, norm):
+    """scipy's idct / idst: type t with norm backward / ortho / forward is the transform of type 5 - t with norm forward /
+    ortho / backward"""
+    _norm_code(norm)
+    if type not in (2, 3):
+        raise ValueError(f"type must be 2 or 3, not {type!r}")
+    return 5 - type, _INVERSE_NORM[norm]
+
+
+def idct(input, output, type: int = 2, norm=None, planner=None) -> None:
+    """scipy.fft.idct of ``type`` 2 or 3: :func:`dct_f64` / :func:`dct_f32` (by the dtype of ``input``) of type 5 - type with
+    the norm swapped between backward and forward"""
+    t, nm = _inverse(type, norm)
+    _r2r_by_dtype("dct", input, output, t, nm, planner)
+
+
+def idst(input, output, type: int = 2, norm=None, planner=None) -> None:
+    """scipy.fft.idst: :func:`idct` for the DST"""
+    t, nm = _inverse(type, norm)
+    _r2r_by_dtype("dst", input, output, t, nm, planner)
+
+
+def _r2r_by_dtype(kind, input, output, type, norm, planner):
+    if planner is not None:
+        dtype = planner._dtype
+    elif _is_torch(input):
+        import torch
+
+        dtype = np.float64 if input.dtype == torch.float64 else np.float32
+    else:
+        dtype = np.float64 if np.asarray(input).dtype == np.float64 else np.float32
+    fs = "f64" if dtype == np.float64 else "f32"
+    _r2r(kind, fs, dtype, input, output, type, norm, planner)
 
 
 # ---------------------------------------------------------------------------------------------

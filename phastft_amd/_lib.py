@@ -56,6 +56,11 @@ phast_planner_r2c_any64_workspace_len phast_planner_r2c_any32_workspace_len phas
 phast_planner_r2c_any64_time_c2r_stages phast_planner_r2c_any32_time_c2r_stages
 phast_r2c_fft_f64_any phast_r2c_fft_f32_any phast_r2c_fft_f64_any_with_planner phast_r2c_fft_f32_any_with_planner phast_r2c_fft_f64_any_dev phast_r2c_fft_f32_any_dev
 phast_c2r_fft_f64_any phast_c2r_fft_f32_any phast_c2r_fft_f64_any_with_planner phast_c2r_fft_f32_any_with_planner phast_c2r_fft_f64_any_dev phast_c2r_fft_f32_any_dev
+phast_planner_dct64_new phast_planner_dct32_new phast_planner_dct64_free phast_planner_dct32_free
+phast_planner_dct64_describe phast_planner_dct32_describe phast_planner_dct64_device_bytes phast_planner_dct32_device_bytes
+phast_planner_dct64_workspace_len phast_planner_dct32_workspace_len phast_planner_dct64_time_stages phast_planner_dct32_time_stages
+phast_dct_f64 phast_dct_f32 phast_dct_f64_with_planner phast_dct_f32_with_planner phast_dct_f64_dev phast_dct_f32_dev
+phast_dst_f64 phast_dst_f32 phast_dst_f64_with_planner phast_dst_f32_with_planner phast_dst_f64_dev phast_dst_f32_dev
 phast_planner_nd64_new phast_planner_nd32_new phast_planner_nd64_free phast_planner_nd32_free
 phast_planner_nd64_describe phast_planner_nd32_describe phast_planner_nd64_device_bytes phast_planner_nd32_device_bytes
 phast_planner_nd64_workspace_len phast_planner_nd32_workspace_len phast_planner_nd64_time_steps phast_planner_nd32_time_steps
@@ -130,7 +135,7 @@ def lib() -> C.CDLL:
         getattr(l, f"phast_planner_r2c_any{sfx}_free").restype = None
         getattr(l, f"phast_planner_r2c_any{sfx}_device_bytes").restype = C.c_size_t
         getattr(l, f"phast_planner_r2c_any{sfx}_workspace_len").restype = C.c_size_t
-        for k in ("nd", "r2c_nd"):
+        for k in ("nd", "r2c_nd", "dct"):
             getattr(l, f"phast_planner_{k}{sfx}_free").restype = None
             getattr(l, f"phast_planner_{k}{sfx}_device_bytes").restype = C.c_size_t
             getattr(l, f"phast_planner_{k}{sfx}_workspace_len").restype = C.c_size_t

@@ -16,6 +16,7 @@
 #include "tune.hpp"
 #include "planner_any.hpp"
 #include "planner_any_real.hpp"
+#include "planner_dct.hpp"
 #include "planner_nd.hpp"
 
 // ================================================================================================
@@ -31,6 +32,8 @@ struct phast_planner_any64 : AnyPlanner<double> {};
 struct phast_planner_any32 : AnyPlanner<float> {};
 struct phast_planner_r2c_any64 : AnyRealPlanner<double> {};
 struct phast_planner_r2c_any32 : AnyRealPlanner<float> {};
+struct phast_planner_dct64 : DctPlanner<double> {};
+struct phast_planner_dct32 : DctPlanner<float> {};
 struct phast_planner_nd64 : NdPlanner<double> {};
 struct phast_planner_nd32 : NdPlanner<float> {};
 struct phast_planner_r2c_nd64 : RealNdPlanner<double> {};
@@ -612,6 +615,58 @@ PHAST_ANY_API(32, float)
     } PHAST_CATCH_RC
 PHAST_ANY_REAL_API(64, f64, double)
 PHAST_ANY_REAL_API(32, f32, float)
+
+// DCT / DST of types II and III (planner_dct.hpp): type, norm and every length are checked before the device is touched
+#define PHAST_DCT_API(SFX, FS, T)                                                                                       \
+    int phast_planner_dct##SFX##_new(size_t n, phast_planner_dct##SFX **out) try {                                      \
+        return any_planner_new(n, out);                                                                                 \
+    } PHAST_CATCH_RC                                                                                                    \
+    void phast_planner_dct##SFX##_free(phast_planner_dct##SFX *p) try { delete p; } PHAST_CATCH_VOID                    \
+    int phast_planner_dct##SFX##_describe(const phast_planner_dct##SFX *p, char *buf, size_t len) try {                 \
+        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
+        std::snprintf(buf, len, "%s", p->describe().c_str());                                                          \
+        return PHAST_OK;                                                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_dct##SFX##_device_bytes(const phast_planner_dct##SFX *p) try {                                 \
+        return p ? p->device_bytes() : 0;                                                                               \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_dct##SFX##_workspace_len(const phast_planner_dct##SFX *p, size_t batch) try {                  \
+        return p ? p->workspace_len(batch) : 0;                                                                         \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_dct##SFX##_time_stages(const phast_planner_dct##SFX *p, int dst, int type, int norm,              \
+                                             const T *d_in, T *d_out, size_t batch, T *d_work, size_t work_len,         \
+                                             int reps, float *stage_ms, void *stream) try {                             \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(type, dst != 0, norm, d_in, d_out, batch, d_work, work_len, reps, stage_ms,               \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    PHAST_DCT_CALLS(SFX, FS, T, dct, false)                                                                             \
+    PHAST_DCT_CALLS(SFX, FS, T, dst, true)
+#define PHAST_DCT_CALLS(SFX, FS, T, KIND, DST)                                                                          \
+    int phast_##KIND##_##FS(const T *in, size_t in_len, T *out, size_t out_len, int type, int norm) try {               \
+        if (!in || !out || !DctPlanner<T>::valid(type, norm)) return PHAST_ERR_INVALID_ARG;                             \
+        if (in_len == 0 || in_len > kAnyMaxN) return PHAST_ERR_INVALID_ARG;                                             \
+        if (in_len != out_len) return PHAST_ERR_LEN_MISMATCH; /* before the device is touched */                       \
+        std::shared_ptr<DctPlanner<T>> pl; /* the planner from in_len, as r2c_fft_*_any */                             \
+        int rc = PlannerCache<DctPlanner<T>>::instance().get(                                                           \
+            in_len, sizeof(T), [](size_t m, DctPlanner<T> **o) { return any_planner_new(m, o); }, &pl);                 \
+        if (rc) return rc;                                                                                              \
+        return pl->host(type, DST, in, in_len, out, out_len, norm);                                                     \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_##KIND##_##FS##_with_planner(const T *in, size_t in_len, T *out, size_t out_len, int type, int norm,      \
+                                           const phast_planner_dct##SFX *p) try {                                       \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(type, DST, in, in_len, out, out_len, norm);                                                      \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_##KIND##_##FS##_dev(const T *d_in, T *d_out, size_t n, size_t batch, size_t in_dist, size_t out_dist,     \
+                                  int type, int norm, const phast_planner_dct##SFX *p, T *d_work, size_t work_len,      \
+                                  void *stream) try {                                                                   \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(type, DST, d_in, d_out, n, batch, in_dist, out_dist, norm, d_work, work_len,                      \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC
+PHAST_DCT_API(64, f64, double)
+PHAST_DCT_API(32, f32, float)
 
 // Multi-dimensional transforms (planner_nd.hpp): the shape and the lengths are checked before the device is touched
 #define PHAST_ND_PLANNER_API(NAME, KIND)                                                                                \

@@ -114,6 +114,29 @@ extern "C" {
         in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
     pub(crate) fn phast_c2r_fft_f32_any_dev(ire: *const f32, iim: *const f32, out: *mut f32, n: usize, batch: usize,
         in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // DCT / DST of types II and III (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/r2r.rs)
+    pub(crate) fn phast_planner_dct64_new(n: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_dct32_new(n: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_dct64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_dct32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_dct64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_dct32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_dct_f64_with_planner(input: *const f64, input_len: usize, output: *mut f64, output_len: usize,
+        ty: c_int, norm: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_dct_f64_dev(input: *const f64, output: *mut f64, n: usize, batch: usize, in_dist: usize, out_dist: usize,
+        ty: c_int, norm: c_int, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_dct_f32_with_planner(input: *const f32, input_len: usize, output: *mut f32, output_len: usize,
+        ty: c_int, norm: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_dct_f32_dev(input: *const f32, output: *mut f32, n: usize, batch: usize, in_dist: usize, out_dist: usize,
+        ty: c_int, norm: c_int, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_dst_f64_with_planner(input: *const f64, input_len: usize, output: *mut f64, output_len: usize,
+        ty: c_int, norm: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_dst_f64_dev(input: *const f64, output: *mut f64, n: usize, batch: usize, in_dist: usize, out_dist: usize,
+        ty: c_int, norm: c_int, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_dst_f32_with_planner(input: *const f32, input_len: usize, output: *mut f32, output_len: usize,
+        ty: c_int, norm: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_dst_f32_dev(input: *const f32, output: *mut f32, n: usize, batch: usize, in_dist: usize, out_dist: usize,
+        ty: c_int, norm: c_int, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // multi-dimensional transforms (an extension beyond PhastFT 0.3.0: planner.rs / lib.rs / algorithms/r2c.rs)
     pub(crate) fn phast_planner_nd64_new(dims: *const usize, rank: usize, out: *mut *mut Opaque) -> c_int;
     pub(crate) fn phast_planner_nd32_new(dims: *const usize, rank: usize, out: *mut *mut Opaque) -> c_int;

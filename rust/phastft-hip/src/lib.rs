@@ -43,6 +43,12 @@ pub use algorithms::r2c::{
     c2r_fft_f64_any_with_planner, r2c_fft_f32_any, r2c_fft_f32_any_dev, r2c_fft_f32_any_with_planner, r2c_fft_f64_any,
     r2c_fft_f64_any_dev, r2c_fft_f64_any_with_planner,
 };
+// DCT / DST of types II and III (an extension beyond PhastFT 0.3.0)
+pub use algorithms::r2r::{
+    dct_f32, dct_f32_dev, dct_f32_with_planner, dct_f64, dct_f64_dev, dct_f64_with_planner, dst_f32, dst_f32_dev,
+    dst_f32_with_planner, dst_f64, dst_f64_dev, dst_f64_with_planner, idct_f32, idct_f64, idst_f32, idst_f64, Norm,
+};
+pub use planner::{PlannerDct32, PlannerDct64};
 // multi-dimensional real transforms (an extension beyond PhastFT 0.3.0)
 pub use algorithms::r2c::{
     c2r_fft_f32_nd, c2r_fft_f32_nd_dev, c2r_fft_f32_nd_with_planner, c2r_fft_f64_nd, c2r_fft_f64_nd_dev,

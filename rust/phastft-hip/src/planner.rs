@@ -202,6 +202,45 @@ impl_planner_r2c_any!(PlannerR2cAny64, phast_planner_r2c_any64_new, phast_planne
 impl_planner_r2c_any!(PlannerR2cAny32, phast_planner_r2c_any32_new, phast_planner_r2c_any32_free,
                       phast_planner_r2c_any32_workspace_len);
 
+macro_rules! impl_planner_dct {
+    ($dct:ident, $new:ident, $free:ident, $ws_len:ident) => {
+        /// An extension beyond PhastFT 0.3.0: the DCT and DST of types II and III of any length 1 <= N <= 2^29 (one real
+        /// transform of the same N between two sweeps).  One planner serves all four transforms and every norm.  Immutable
+        /// after `new`, like the reference's planners.
+        pub struct $dct {
+            pub(crate) h: *mut Opaque,
+            pub(crate) n: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in a
+        // workspace of the library's own pool (host-slice calls)
+        unsafe impl Send for $dct {}
+        unsafe impl Sync for $dct {}
+        impl $dct {
+            /// panics with "invalid argument" for N = 0 or N > 2^29
+            pub fn new(n: usize) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe { ffi::$new(n, &mut h) });
+                Self { h, n }
+            }
+            pub fn num_points(&self) -> usize {
+                self.n
+            }
+            /// elements of the workspace a device call of `batch` transforms works in (any length of at least
+            /// `workspace_len(1)` is legal: a shorter one than `workspace_len(batch)` runs the batch in chunks)
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+        }
+        impl Drop for $dct {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_dct!(PlannerDct64, phast_planner_dct64_new, phast_planner_dct64_free, phast_planner_dct64_workspace_len);
+impl_planner_dct!(PlannerDct32, phast_planner_dct32_new, phast_planner_dct32_free, phast_planner_dct32_workspace_len);
+
 macro_rules! impl_planner_nd {
     ($nd:ident, $new:ident, $free:ident, $ws_len:ident, $what:literal) => {
         #[doc = concat!("An extension beyond PhastFT 0.3.0, whose planners transform one axis: ", $what, " over every axis of a ",
