@@ -20,6 +20,8 @@
 //                                                            c2r_fft_f64/f32_any[_with_planner] -- any N >= 1
 //   (none: no real-to-real transforms upstream)              class PlannerDct64/32, dct_f64/f32[_with_planner],
 //                                                            dst_f64/f32[_with_planner], enum Norm -- types II and III, any N >= 1
+//   (none: no short-time transforms upstream)                class PlannerStft64/32, stft_f64/f32_with_planner,
+//                                                            istft_f64/f32_with_planner, enum PadMode -- torch.stft / istft
 //   (none: one axis only upstream)                           class PlannerNd64/32, PlannerR2cNd64/32, fft_64/32_nd[_with_planner],
 //                                                            r2c_fft_f64/f32_nd[...], c2r_fft_f64/f32_nd[...] -- every axis
 //
@@ -446,6 +448,61 @@ PHASTFT_R2R(dct, f32, float, PlannerDct32)
 PHASTFT_R2R(dst, f64, double, PlannerDct64)
 PHASTFT_R2R(dst, f32, float, PlannerDct32)
 #undef PHASTFT_R2R
+
+// ---- the short-time Fourier transform and its inverse (no reference counterpart; torch.stft / torch.istft(length = L)) ----
+enum class PadMode : int { Reflect = PHAST_PAD_REFLECT, Zero = PHAST_PAD_ZERO };
+#define PHASTFT_PLANNER_STFT(NAME, CT, SFX, T)                                                                   \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* `window`: n_fft values, or empty for all ones */                                                      \
+        NAME(std::size_t signal_len, std::size_t n_fft, std::size_t hop, Slice<const T> window = Slice<const T>(nullptr, 0), \
+             bool center = true, PadMode pad_mode = PadMode::Reflect) {                                          \
+            if (window.len && window.len != n_fft) check(PHAST_ERR_INVALID_ARG);                                 \
+            check(phast_planner_stft##SFX##_new(signal_len, n_fft, hop, window.len ? window.ptr : nullptr, center ? 1 : 0, \
+                                                static_cast<int>(pad_mode), &h_));                               \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }                                                   \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_stft##SFX##_free(h_);                                                          \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_stft##SFX##_describe(h_, &s[0], s.size()));                                      \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_stft##SFX##_device_bytes(h_); }                  \
+        std::size_t frames() const { return phast_planner_stft##SFX##_frames(h_); }                              \
+        std::size_t bins() const { return phast_planner_stft##SFX##_bins(h_); }                                  \
+        /* the minimum of sum_f w^2 over the samples some frame holds: the inverse needs more than 1e-11 */      \
+        double envelope_min() const { return phast_planner_stft##SFX##_envelope_min(h_); }                       \
+        /* elements of T a _dev call of `batch` signals works in; workspace_min: the least a call runs in */     \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_stft##SFX##_workspace_len(h_, batch); } \
+        std::size_t workspace_min(bool inverse = false) const { return phast_planner_stft##SFX##_workspace_min(h_, inverse); } \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+    };
+PHASTFT_PLANNER_STFT(PlannerStft64, phast_planner_stft64, 64, double)
+PHASTFT_PLANNER_STFT(PlannerStft32, phast_planner_stft32, 32, float)
+#undef PHASTFT_PLANNER_STFT
+
+// one host signal of L samples <-> dense planes of frames * bins (frame-major); blocking
+#define PHASTFT_STFT(FS, T, P)                                                                                   \
+    inline void stft_##FS##_with_planner(Slice<const T> signal, Slice<T> output_re, Slice<T> output_im, const P &planner) { \
+        check(phast_stft_##FS##_with_planner(signal.ptr, signal.len, output_re.ptr, output_re.len, output_im.ptr, \
+                                             output_im.len, planner.get()));                                     \
+    }                                                                                                            \
+    inline void istft_##FS##_with_planner(Slice<const T> input_re, Slice<const T> input_im, Slice<T> signal, const P &planner) { \
+        check(phast_istft_##FS##_with_planner(input_re.ptr, input_re.len, input_im.ptr, input_im.len, signal.ptr, \
+                                              signal.len, planner.get()));                                       \
+    }
+PHASTFT_STFT(f64, double, PlannerStft64)
+PHASTFT_STFT(f32, float, PlannerStft32)
+#undef PHASTFT_STFT
 
 // ---- transforms over every axis of a row-major array (numpy fftn / rfftn / irfftn; no reference counterpart) ----
 #define PHASTFT_PLANNER_ND(NAME, CT, PFX)                                                                        \

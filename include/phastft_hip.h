@@ -429,6 +429,81 @@ int phast_planner_dct32_time_stages(const phast_planner_dct32 *p, int dst, int t
                                     float *d_output, size_t batch, float *d_work, size_t work_len, int reps, float *stage_ms,
                                     void *stream);
 
+/* ---- the short-time Fourier transform and its inverse (no reference counterpart; torch.stft / torch.istft(length = L) with
+ * win_length = n_fft and normalized = False).  Signal length L, frame length F = n_fft, hop H, window w[0..F),
+ * p = F / 2 (floor) with `center`, else 0; frames = 1 + (L + 2p - F) / H (floor), bins = F / 2 + 1.
+ *     forward  S[f] = rfft_F(w[j] x~[f H - p + j]), x~ = x inside [0, L); outside, PHAST_PAD_REFLECT mirrors (x[-i], x[2(L-1) - i])
+ *              and PHAST_PAD_ZERO gives 0.  Two dense planes (re, im): signal b, frame f, bin k at (b frames + f) bins + k
+ *              (torch's result transposed).
+ *     inverse  y[f] = irfft_F(S[f]); out[t] = sum_f w[u - f H] y[f][u - f H] / sum_f w^2[u - f H], u = t + p, over the frames
+ *              that hold u in ascending f; a sample no frame holds is written as 0.
+ * _new takes 1 <= H <= F <= 2^29, 1 <= L <= 2^29, p < L with center and reflect, L >= F without center (pad_mode is then
+ * ignored), frames F <= 2^30, `window` a host pointer to F values or NULL for all ones: anything else is
+ * PHAST_ERR_INVALID_ARG before the device is touched.  _envelope_min is the minimum of sum_f w^2 over the samples some frame
+ * holds, computed once on the host in double; the inverse through a planner where it is <= 1e-11 is PHAST_ERR_INVALID_ARG
+ * (torch's NOLA rule and threshold).
+ *
+ * One real transform of F (the phast_planner_r2c_any* engine, called unchanged) and one O(frames F) sweep per direction.
+ * The caller's device workspace holds phast_planner_stft*_workspace_len(p, batch) elements of T.  The forward call runs any
+ * work_len >= _workspace_min(p, 0) (one frame) in chunks of whole frames, the inverse any work_len >= _workspace_min(p, 1)
+ * (one signal's frames) in chunks of whole signals; a null or shorter one is PHAST_ERR_INVALID_ARG.  _dev calls: asynchronous
+ * on `stream`; `batch` signals at sig_dist >= L (any parity), pointers need element alignment only; the signal is never
+ * written by the forward call, the planes never by the inverse.  A signal_len that is not the planner's is
+ * PHAST_ERR_PLANNER_SIZE, host planes that are not frames * bins long PHAST_ERR_LEN_MISMATCH.  The planner is immutable and
+ * holds no per-call state.  The overlap-add is a gather without atomics: the bits of a signal do not depend on the batch, the
+ * chunking, the stream or graph replay wherever the real transform's do not (every F that is not a power of two, and powers
+ * of two up to 4096).  Host-slice calls take one signal, stage through the device and block. */
+#define PHAST_PAD_REFLECT 0
+#define PHAST_PAD_ZERO 1
+typedef struct phast_planner_stft64 phast_planner_stft64; /* PlannerStft64 */
+int phast_planner_stft64_new(size_t signal_len, size_t n_fft, size_t hop, const double *window, int center, int pad_mode,
+                             phast_planner_stft64 **out);
+void phast_planner_stft64_free(phast_planner_stft64 *p);
+int phast_planner_stft64_describe(const phast_planner_stft64 *p, char *buf, size_t buf_len);
+size_t phast_planner_stft64_device_bytes(const phast_planner_stft64 *p);
+size_t phast_planner_stft64_frames(const phast_planner_stft64 *p);
+size_t phast_planner_stft64_bins(const phast_planner_stft64 *p);
+size_t phast_planner_stft64_workspace_len(const phast_planner_stft64 *p, size_t batch);
+size_t phast_planner_stft64_workspace_min(const phast_planner_stft64 *p, int inverse);
+double phast_planner_stft64_envelope_min(const phast_planner_stft64 *p);
+int phast_stft_f64_with_planner(const double *signal, size_t signal_len, double *output_re, size_t output_re_len, double *output_im,
+                                size_t output_im_len, const phast_planner_stft64 *planner);
+int phast_istft_f64_with_planner(const double *input_re, size_t input_re_len, const double *input_im, size_t input_im_len, double *signal,
+                                 size_t signal_len, const phast_planner_stft64 *planner);
+int phast_stft_f64_dev(const double *d_signal, double *d_re, double *d_im, size_t signal_len, size_t batch, size_t sig_dist,
+                       const phast_planner_stft64 *planner, double *d_work, size_t work_len, void *stream);
+int phast_istft_f64_dev(const double *d_re, const double *d_im, double *d_signal, size_t signal_len, size_t batch, size_t sig_dist,
+                        const phast_planner_stft64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/stft_rate.py): stage_ms[2] = average milliseconds of the sweep and of the real transform of the
+ * forward (inverse = 0) or inverse call over `reps` calls of `batch` signals at distance L in ONE chunk (work_len >=
+ * phast_planner_stft*_workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_stft64_time_stages(const phast_planner_stft64 *p, int inverse, double *d_signal, double *d_re, double *d_im, size_t batch,
+                                     double *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_stft32 phast_planner_stft32; /* PlannerStft32 */
+int phast_planner_stft32_new(size_t signal_len, size_t n_fft, size_t hop, const float *window, int center, int pad_mode,
+                             phast_planner_stft32 **out);
+void phast_planner_stft32_free(phast_planner_stft32 *p);
+int phast_planner_stft32_describe(const phast_planner_stft32 *p, char *buf, size_t buf_len);
+size_t phast_planner_stft32_device_bytes(const phast_planner_stft32 *p);
+size_t phast_planner_stft32_frames(const phast_planner_stft32 *p);
+size_t phast_planner_stft32_bins(const phast_planner_stft32 *p);
+size_t phast_planner_stft32_workspace_len(const phast_planner_stft32 *p, size_t batch);
+size_t phast_planner_stft32_workspace_min(const phast_planner_stft32 *p, int inverse);
+double phast_planner_stft32_envelope_min(const phast_planner_stft32 *p);
+int phast_stft_f32_with_planner(const float *signal, size_t signal_len, float *output_re, size_t output_re_len, float *output_im,
+                                size_t output_im_len, const phast_planner_stft32 *planner);
+int phast_istft_f32_with_planner(const float *input_re, size_t input_re_len, const float *input_im, size_t input_im_len, float *signal,
+                                 size_t signal_len, const phast_planner_stft32 *planner);
+int phast_stft_f32_dev(const float *d_signal, float *d_re, float *d_im, size_t signal_len, size_t batch, size_t sig_dist,
+                       const phast_planner_stft32 *planner, float *d_work, size_t work_len, void *stream);
+int phast_istft_f32_dev(const float *d_re, const float *d_im, float *d_signal, size_t signal_len, size_t batch, size_t sig_dist,
+                        const phast_planner_stft32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/stft_rate.py): stage_ms[2] = average milliseconds of the sweep and of the real transform of the
+ * forward (inverse = 0) or inverse call over `reps` calls of `batch` signals at distance L in ONE chunk (work_len >=
+ * phast_planner_stft*_workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_stft32_time_stages(const phast_planner_stft32 *p, int inverse, float *d_signal, float *d_re, float *d_im, size_t batch,
+                                     float *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+
 /* ---- multi-dimensional transforms over every axis of a row-major array (no reference counterpart; numpy fftn / ifftn /
  * rfftn / irfftn with this library's conventions).  dims[0 .. rank-1]: rank 1 .. 8, every axis 1 .. 2^29,
  * their product <= 2^30 (else PHAST_ERR_INVALID_ARG, before the device is touched).  Every axis is transformed; leading

@@ -22,6 +22,8 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
                                                     c2r_fft_f64/f32_any[_with_planner], r2c_any_batched, c2r_any_batched
     (none: no real-to-real transforms)              PlannerDct64/32, dct_f64/f32[_with_planner], dst_f64/f32[_with_planner],
                                                     dct_batched, dst_batched, idct, idst
+    (none: no short-time transforms)                PlannerStft64/32, stft_batched, istft_batched,
+                                                    stft_f64/f32_with_planner, istft_f64/f32_with_planner
     (none: one axis only)                           PlannerNd64/32, fft_64/32_nd[_with_planner], fft_nd_batched,
                                                     PlannerR2cNd64/32, r2c_fft_f64/f32_nd[_with_planner],
                                                     c2r_fft_f64/f32_nd[_with_planner], r2c_nd_batched, c2r_nd_batched
@@ -65,6 +67,8 @@ __all__ = [
     "c2r_fft_f32_any_with_planner", "r2c_any_batched", "c2r_any_batched",
     "PlannerDct64", "PlannerDct32", "dct_f64", "dct_f32", "dst_f64", "dst_f32", "dct_f64_with_planner", "dct_f32_with_planner",
     "dst_f64_with_planner", "dst_f32_with_planner", "dct_batched", "dst_batched", "idct", "idst",
+    "PlannerStft64", "PlannerStft32", "stft_batched", "istft_batched", "stft_f64_with_planner", "stft_f32_with_planner",
+    "istft_f64_with_planner", "istft_f32_with_planner",
     "PlannerNd64", "PlannerNd32", "fft_64_nd", "fft_32_nd", "fft_64_nd_with_planner", "fft_32_nd_with_planner", "fft_nd_batched",
     "PlannerR2cNd64", "PlannerR2cNd32", "r2c_fft_f64_nd", "r2c_fft_f32_nd", "r2c_fft_f64_nd_with_planner",
     "r2c_fft_f32_nd_with_planner", "c2r_fft_f64_nd", "c2r_fft_f32_nd", "c2r_fft_f64_nd_with_planner",
@@ -1059,6 +1063,130 @@ def _r2r_by_dtype(kind, input, output, type, norm, planner):
         dtype = np.float64 if np.asarray(input).dtype == np.float64 else np.float32
     fs = "f64" if dtype == np.float64 else "f32"
     _r2r(kind, fs, dtype, input, output, type, norm, planner)
+
+
+# ---------------------------------------------------------------------------------------------
+# the short-time Fourier transform and its inverse (no reference counterpart; torch.stft / torch.istft(length=L))
+# ---------------------------------------------------------------------------------------------
+_PADS = {"reflect": 0, "zero": 1, "constant": 1}
+
+
+class PlannerStft64(_AnyHandle):
+    """f64 STFT / inverse STFT of signals of ``signal_len`` samples: frames of ``n_fft`` samples ``hop`` apart, times
+    ``window`` (``n_fft`` values; a shorter one is zero-padded on both sides as torch does; None: all ones).  ``center``
+    pads the signal by ``n_fft // 2`` on both sides, by reflection (``pad_mode="reflect"``) or with zeros (``"zero"``).
+    ``torch.stft(x, n_fft, hop, window=w, center=..., pad_mode=..., return_complex=True)`` is the transpose of the
+    (frames, bins) planes; the inverse is ``torch.istft(..., length=signal_len)``."""
+
+    _prefix = "stft"
+
+    def __init__(self, signal_len: int, n_fft: int, hop: int, window=None, center: bool = True, pad_mode: str = "reflect"):
+        if pad_mode not in _PADS:
+            raise ValueError(f"pad_mode must be 'reflect' or 'zero', not {pad_mode!r}")
+        wp = None
+        if window is not None:
+            if _is_torch(window):
+                window = window.detach().cpu().numpy()
+            w = np.ascontiguousarray(window, dtype=self._dtype).reshape(-1)
+            if w.size > n_fft:
+                raise ValueError(f"window: {w.size} values for n_fft = {n_fft}")
+            if w.size < n_fft:  # win_length < n_fft: centred in the frame
+                left = (n_fft - w.size) // 2
+                w = np.concatenate([np.zeros(left, self._dtype), w, np.zeros(n_fft - w.size - left, self._dtype)])
+            wp = w.ctypes.data_as(C.c_void_p)
+        self._h = C.c_void_p()
+        _check(self._fn("new")(C.c_size_t(signal_len), C.c_size_t(n_fft), C.c_size_t(hop), wp, C.c_int(bool(center)),
+                               C.c_int(_PADS[pad_mode]), C.byref(self._h)))
+        self.n = self.signal_len = signal_len
+        self.n_fft, self.hop, self.center, self.pad_mode = n_fft, hop, bool(center), pad_mode
+        self.frames = int(self._fn("frames")(self._h))
+        self.bins = int(self._fn("bins")(self._h))
+        self.envelope_min = float(self._fn("envelope_min")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` signals works in.  A smaller workspace runs the batch in chunks: of
+        whole frames forward (at least ``workspace_min()``), of whole signals for the inverse (``workspace_min(True)``)."""
+        return self._workspace_len(batch)
+
+    def workspace_min(self, inverse: bool = False) -> int:
+        return int(self._fn("workspace_min")(self._h, C.c_int(bool(inverse))))
+
+    def time_stages(self, signal, re, im, inverse: bool = False, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (the sweep, the real transform) of a forward or inverse call of ``batch``
+        signals at distance L on device tensors (measurement hook)"""
+        x, r, i = (_Slice(t, self._dtype, w) for t, w in ((signal, "signal"), (re, "re"), (im, "im")))
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 2)()
+        _check(self._fn("time_stages")(self._h, C.c_int(bool(inverse)), x.ptr, r.ptr, i.ptr, C.c_size_t(batch), ws.ptr,
+                                       C.c_size_t(ws.len), C.c_int(reps), ms, _stream()))
+        return [float(v) for v in ms]
+
+
+class PlannerStft32(PlannerStft64):
+    """f32 twin of :class:`PlannerStft64`"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def _stft_batched(inverse, signal, re, im, planner, batch, sig_dist, workspace):
+    dtype, fs = planner._dtype, "f64" if planner._dtype == np.float64 else "f32"
+    x, r, i = (_Slice(t, dtype, w) for t, w in ((signal, "signal"), (re, "re"), (im, "im")))
+    name = "istft" if inverse else "stft"
+    if not _same_place(x, r, i):
+        raise TypeError(f"{name}_batched needs device tensors")
+    n, pts = planner.signal_len, planner.frames * planner.bins
+    sig_dist = n if sig_dist is None else sig_dist
+    _need("signal", x.len, batch, sig_dist, n)
+    _need("re", r.len, batch, pts, pts)
+    _need("im", i.len, batch, pts, pts)
+    ws = _any_workspace(planner, batch, workspace)
+    args = (r.ptr, i.ptr, x.ptr) if inverse else (x.ptr, r.ptr, i.ptr)
+    _check(getattr(_lib.lib(), f"phast_{name}_{fs}_dev")(*args, C.c_size_t(n), C.c_size_t(batch), C.c_size_t(sig_dist),
+                                                         planner._h, ws.ptr, C.c_size_t(ws.len), _stream()))
+
+
+def stft_batched(signal, out_re, out_im, planner, batch: int, sig_dist: int | None = None, workspace=None) -> None:
+    """Device-resident batch of STFTs: signal b at ``b*sig_dist`` (default L, any distance >= L); frame f, bin k of signal b
+    at ``(b*frames + f)*bins + k`` of the dense planes.  ``workspace``: a device tensor of the planner's type of at least
+    ``planner.workspace_min()`` elements (fewer than ``planner.workspace_len(batch)`` runs the frames in chunks); by default
+    one from torch's allocator."""
+    _stft_batched(False, signal, out_re, out_im, planner, batch, sig_dist, workspace)
+
+
+def istft_batched(in_re, in_im, signal, planner, batch: int, sig_dist: int | None = None, workspace=None) -> None:
+    """Device-resident batch of inverse STFTs by weighted overlap-add (``torch.istft(..., length=L)``): the inverse of
+    :func:`stft_batched`.  ``workspace``: at least ``planner.workspace_min(True)`` elements (one signal's frames).  A planner
+    whose ``envelope_min`` is <= 1e-11 refuses (torch's NOLA rule)."""
+    _stft_batched(True, signal, in_re, in_im, planner, batch, sig_dist, workspace)
+
+
+def _stft_host(name, fs, dtype, a, b, c, planner):
+    sl = [_Slice(t, dtype, w) for t, w in zip((a, b, c), ("signal", "re", "im") if name == "stft" else ("re", "im", "signal"))]
+    if _same_place(*sl):
+        raise TypeError(f"{name}_{fs}_with_planner takes host arrays ({name}_batched takes device tensors)")
+    _check(getattr(_lib.lib(), f"phast_{name}_{fs}_with_planner")(
+        *(v for s in sl for v in (s.ptr, C.c_size_t(s.len))), planner._h))
+
+
+def stft_f64_with_planner(signal, out_re, out_im, planner: PlannerStft64) -> None:
+    """f64 STFT of one host signal of L samples into host planes of frames * bins (blocking)"""
+    _stft_host("stft", "f64", np.float64, signal, out_re, out_im, planner)
+
+
+def stft_f32_with_planner(signal, out_re, out_im, planner: PlannerStft32) -> None:
+    """f32 twin of :func:`stft_f64_with_planner`"""
+    _stft_host("stft", "f32", np.float32, signal, out_re, out_im, planner)
+
+
+def istft_f64_with_planner(in_re, in_im, signal, planner: PlannerStft64) -> None:
+    """f64 inverse STFT of host planes of frames * bins into one host signal of L samples (blocking)"""
+    _stft_host("istft", "f64", np.float64, in_re, in_im, signal, planner)
+
+
+def istft_f32_with_planner(in_re, in_im, signal, planner: PlannerStft32) -> None:
+    """f32 twin of :func:`istft_f64_with_planner`"""
+    _stft_host("istft", "f32", np.float32, in_re, in_im, signal, planner)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -61,6 +61,13 @@ phast_planner_dct64_describe phast_planner_dct32_describe phast_planner_dct64_de
 phast_planner_dct64_workspace_len phast_planner_dct32_workspace_len phast_planner_dct64_time_stages phast_planner_dct32_time_stages
 phast_dct_f64 phast_dct_f32 phast_dct_f64_with_planner phast_dct_f32_with_planner phast_dct_f64_dev phast_dct_f32_dev
 phast_dst_f64 phast_dst_f32 phast_dst_f64_with_planner phast_dst_f32_with_planner phast_dst_f64_dev phast_dst_f32_dev
+phast_planner_stft64_new phast_planner_stft32_new phast_planner_stft64_free phast_planner_stft32_free
+phast_planner_stft64_describe phast_planner_stft32_describe phast_planner_stft64_device_bytes phast_planner_stft32_device_bytes
+phast_planner_stft64_frames phast_planner_stft32_frames phast_planner_stft64_bins phast_planner_stft32_bins
+phast_planner_stft64_workspace_len phast_planner_stft32_workspace_len phast_planner_stft64_workspace_min phast_planner_stft32_workspace_min
+phast_planner_stft64_envelope_min phast_planner_stft32_envelope_min phast_planner_stft64_time_stages phast_planner_stft32_time_stages
+phast_stft_f64_with_planner phast_stft_f32_with_planner phast_istft_f64_with_planner phast_istft_f32_with_planner
+phast_stft_f64_dev phast_stft_f32_dev phast_istft_f64_dev phast_istft_f32_dev
 phast_planner_nd64_new phast_planner_nd32_new phast_planner_nd64_free phast_planner_nd32_free
 phast_planner_nd64_describe phast_planner_nd32_describe phast_planner_nd64_device_bytes phast_planner_nd32_device_bytes
 phast_planner_nd64_workspace_len phast_planner_nd32_workspace_len phast_planner_nd64_time_steps phast_planner_nd32_time_steps
@@ -135,7 +142,10 @@ def lib() -> C.CDLL:
         getattr(l, f"phast_planner_r2c_any{sfx}_free").restype = None
         getattr(l, f"phast_planner_r2c_any{sfx}_device_bytes").restype = C.c_size_t
         getattr(l, f"phast_planner_r2c_any{sfx}_workspace_len").restype = C.c_size_t
-        for k in ("nd", "r2c_nd", "dct"):
+        for k in ("frames", "bins", "workspace_min"):
+            getattr(l, f"phast_planner_stft{sfx}_{k}").restype = C.c_size_t
+        getattr(l, f"phast_planner_stft{sfx}_envelope_min").restype = C.c_double
+        for k in ("nd", "r2c_nd", "dct", "stft"):
             getattr(l, f"phast_planner_{k}{sfx}_free").restype = None
             getattr(l, f"phast_planner_{k}{sfx}_device_bytes").restype = C.c_size_t
             getattr(l, f"phast_planner_{k}{sfx}_workspace_len").restype = C.c_size_t

@@ -17,6 +17,7 @@
 #include "planner_any.hpp"
 #include "planner_any_real.hpp"
 #include "planner_dct.hpp"
+#include "planner_stft.hpp"
 #include "planner_nd.hpp"
 
 // ================================================================================================
@@ -34,6 +35,8 @@ struct phast_planner_r2c_any64 : AnyRealPlanner<double> {};
 struct phast_planner_r2c_any32 : AnyRealPlanner<float> {};
 struct phast_planner_dct64 : DctPlanner<double> {};
 struct phast_planner_dct32 : DctPlanner<float> {};
+struct phast_planner_stft64 : StftPlanner<double> {};
+struct phast_planner_stft32 : StftPlanner<float> {};
 struct phast_planner_nd64 : NdPlanner<double> {};
 struct phast_planner_nd32 : NdPlanner<float> {};
 struct phast_planner_r2c_nd64 : RealNdPlanner<double> {};
@@ -667,6 +670,70 @@ PHAST_ANY_REAL_API(32, f32, float)
     } PHAST_CATCH_RC
 PHAST_DCT_API(64, f64, double)
 PHAST_DCT_API(32, f32, float)
+
+// The short-time Fourier transform and its inverse (planner_stft.hpp): every argument rule, a wrong length and a window that
+// does not overlap-add to nonzero (the inverse) come back before the device is touched
+#define PHAST_STFT_API(SFX, FS, T)                                                                                      \
+    int phast_planner_stft##SFX##_new(size_t signal_len, size_t n_fft, size_t hop, const T *window, int center,         \
+                                      int pad_mode, phast_planner_stft##SFX **out) try {                                \
+        return stft_planner_new<T>(signal_len, n_fft, hop, window, center, pad_mode, out);                              \
+    } PHAST_CATCH_RC                                                                                                    \
+    void phast_planner_stft##SFX##_free(phast_planner_stft##SFX *p) try { delete p; } PHAST_CATCH_VOID                  \
+    int phast_planner_stft##SFX##_describe(const phast_planner_stft##SFX *p, char *buf, size_t len) try {               \
+        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
+        std::snprintf(buf, len, "%s", p->describe().c_str());                                                           \
+        return PHAST_OK;                                                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_stft##SFX##_device_bytes(const phast_planner_stft##SFX *p) try {                               \
+        return p ? p->device_bytes() : 0;                                                                               \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_stft##SFX##_frames(const phast_planner_stft##SFX *p) try {                                     \
+        return p ? p->frames : 0;                                                                                       \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_stft##SFX##_bins(const phast_planner_stft##SFX *p) try {                                       \
+        return p ? p->bins : 0;                                                                                         \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_stft##SFX##_workspace_len(const phast_planner_stft##SFX *p, size_t batch) try {                \
+        return p ? p->workspace_len(batch) : 0;                                                                         \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_stft##SFX##_workspace_min(const phast_planner_stft##SFX *p, int inverse) try {                 \
+        return p ? p->workspace_min(inverse != 0) : 0;                                                                  \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    double phast_planner_stft##SFX##_envelope_min(const phast_planner_stft##SFX *p) try {                               \
+        return p ? p->env_min : 0.0;                                                                                    \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_stft##SFX##_time_stages(const phast_planner_stft##SFX *p, int inverse, T *d_signal, T *d_re,      \
+                                              T *d_im, size_t batch, T *d_work, size_t work_len, int reps,              \
+                                              float *stage_ms, void *stream) try {                                      \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(inverse != 0, d_signal, d_re, d_im, batch, d_work, work_len, reps, stage_ms,              \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_stft_##FS##_with_planner(const T *signal, size_t signal_len, T *ore, size_t ore_len, T *oim,              \
+                                       size_t oim_len, const phast_planner_stft##SFX *p) try {                          \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(false, signal, signal_len, nullptr, 0, ore, ore_len, oim, oim_len);                              \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_istft_##FS##_with_planner(const T *ire, size_t ire_len, const T *iim, size_t iim_len, T *signal,          \
+                                        size_t signal_len, const phast_planner_stft##SFX *p) try {                      \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(true, ire, ire_len, iim, iim_len, signal, signal_len, nullptr, 0);                               \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_stft_##FS##_dev(const T *d_signal, T *d_re, T *d_im, size_t signal_len, size_t batch, size_t sig_dist,    \
+                              const phast_planner_stft##SFX *p, T *d_work, size_t work_len, void *stream) try {         \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->stft_dev(d_signal, d_re, d_im, signal_len, batch, sig_dist, d_work, work_len,                         \
+                           static_cast<hipStream_t>(stream));                                                           \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_istft_##FS##_dev(const T *d_re, const T *d_im, T *d_signal, size_t signal_len, size_t batch,              \
+                               size_t sig_dist, const phast_planner_stft##SFX *p, T *d_work, size_t work_len,           \
+                               void *stream) try {                                                                      \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->istft_dev(d_re, d_im, d_signal, signal_len, batch, sig_dist, d_work, work_len,                        \
+                            static_cast<hipStream_t>(stream));                                                          \
+    } PHAST_CATCH_RC
+PHAST_STFT_API(64, f64, double)
+PHAST_STFT_API(32, f32, float)
 
 // Multi-dimensional transforms (planner_nd.hpp): the shape and the lengths are checked before the device is touched
 #define PHAST_ND_PLANNER_API(NAME, KIND)                                                                                \

@@ -5,3 +5,4 @@ pub mod bravo;
 pub mod dit;
 pub mod r2c;
 pub mod r2r;
+pub mod stft;

@@ -114,6 +114,47 @@ extern "C" {
         in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
     pub(crate) fn phast_c2r_fft_f32_any_dev(ire: *const f32, iim: *const f32, out: *mut f32, n: usize, batch: usize,
         in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // the STFT and its inverse (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/stft.rs)
+    pub(crate) fn phast_planner_stft64_new(signal_len: usize, n_fft: usize, hop: usize, window: *const f64, center: c_int,
+        pad_mode: c_int, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_stft64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_stft64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_stft64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_stft64_frames(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_stft64_bins(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_stft64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_stft64_workspace_min(p: *const Opaque, inverse: c_int) -> usize;
+    pub(crate) fn phast_planner_stft64_envelope_min(p: *const Opaque) -> f64;
+    pub(crate) fn phast_planner_stft64_time_stages(p: *const Opaque, inverse: c_int, signal: *mut f64, re: *mut f64, im: *mut f64,
+        batch: usize, work: *mut f64, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_stft_f64_with_planner(signal: *const f64, signal_len: usize, ore: *mut f64, ore_len: usize, oim: *mut f64,
+        oim_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_istft_f64_with_planner(ire: *const f64, ire_len: usize, iim: *const f64, iim_len: usize, signal: *mut f64,
+        signal_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_stft_f64_dev(signal: *const f64, re: *mut f64, im: *mut f64, signal_len: usize, batch: usize, sig_dist: usize,
+        planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_istft_f64_dev(re: *const f64, im: *const f64, signal: *mut f64, signal_len: usize, batch: usize,
+        sig_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_stft32_new(signal_len: usize, n_fft: usize, hop: usize, window: *const f32, center: c_int,
+        pad_mode: c_int, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_stft32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_stft32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_stft32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_stft32_frames(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_stft32_bins(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_stft32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_stft32_workspace_min(p: *const Opaque, inverse: c_int) -> usize;
+    pub(crate) fn phast_planner_stft32_envelope_min(p: *const Opaque) -> f64;
+    pub(crate) fn phast_planner_stft32_time_stages(p: *const Opaque, inverse: c_int, signal: *mut f32, re: *mut f32, im: *mut f32,
+        batch: usize, work: *mut f32, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_stft_f32_with_planner(signal: *const f32, signal_len: usize, ore: *mut f32, ore_len: usize, oim: *mut f32,
+        oim_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_istft_f32_with_planner(ire: *const f32, ire_len: usize, iim: *const f32, iim_len: usize, signal: *mut f32,
+        signal_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_stft_f32_dev(signal: *const f32, re: *mut f32, im: *mut f32, signal_len: usize, batch: usize, sig_dist: usize,
+        planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_istft_f32_dev(re: *const f32, im: *const f32, signal: *mut f32, signal_len: usize, batch: usize,
+        sig_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // DCT / DST of types II and III (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/r2r.rs)
     pub(crate) fn phast_planner_dct64_new(n: usize, out: *mut *mut Opaque) -> c_int;
     pub(crate) fn phast_planner_dct32_new(n: usize, out: *mut *mut Opaque) -> c_int;

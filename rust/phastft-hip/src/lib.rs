@@ -49,6 +49,12 @@ pub use algorithms::r2r::{
     dst_f32_with_planner, dst_f64, dst_f64_dev, dst_f64_with_planner, idct_f32, idct_f64, idst_f32, idst_f64, Norm,
 };
 pub use planner::{PlannerDct32, PlannerDct64};
+// the short-time Fourier transform and its inverse (an extension beyond PhastFT 0.3.0)
+pub use algorithms::stft::{
+    istft_f32_dev, istft_f32_with_planner, istft_f64_dev, istft_f64_with_planner, stft_f32_dev, stft_f32_with_planner,
+    stft_f64_dev, stft_f64_with_planner,
+};
+pub use planner::{PadMode, PlannerStft32, PlannerStft64};
 // multi-dimensional real transforms (an extension beyond PhastFT 0.3.0)
 pub use algorithms::r2c::{
     c2r_fft_f32_nd, c2r_fft_f32_nd_dev, c2r_fft_f32_nd_with_planner, c2r_fft_f64_nd, c2r_fft_f64_nd_dev,

@@ -241,6 +241,75 @@ macro_rules! impl_planner_dct {
 impl_planner_dct!(PlannerDct64, phast_planner_dct64_new, phast_planner_dct64_free, phast_planner_dct64_workspace_len);
 impl_planner_dct!(PlannerDct32, phast_planner_dct32_new, phast_planner_dct32_free, phast_planner_dct32_workspace_len);
 
+/// How `center` pads the signal (PHAST_PAD_* of the C ABI)
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum PadMode {
+    Reflect = 0,
+    Zero = 1,
+}
+
+macro_rules! impl_planner_stft {
+    ($stft:ident, $t:ty, $new:ident, $free:ident, $frames:ident, $bins:ident, $ws_len:ident, $ws_min:ident, $env:ident) => {
+        /// An extension beyond PhastFT 0.3.0: the short-time Fourier transform of signals of `signal_len` samples and its
+        /// inverse by weighted overlap-add (torch.stft / torch.istft(length = signal_len) with win_length = n_fft): one real
+        /// transform of `n_fft` per frame and one sweep per direction.  Immutable after `new`, like the reference's planners.
+        pub struct $stft {
+            pub(crate) h: *mut Opaque,
+            pub(crate) signal_len: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in
+        // device buffers of its own (host-slice calls)
+        unsafe impl Send for $stft {}
+        unsafe impl Sync for $stft {}
+        impl $stft {
+            /// `window`: `n_fft` values, or `None` for all ones.  Panics with "invalid argument" unless 1 <= hop <= n_fft
+            /// <= 2^29, 1 <= signal_len <= 2^29, n_fft / 2 < signal_len with `center` and `PadMode::Reflect`, signal_len >=
+            /// n_fft without `center`, and frames * n_fft <= 2^30
+            pub fn new(signal_len: usize, n_fft: usize, hop: usize, window: Option<&[$t]>, center: bool, pad_mode: PadMode) -> Self {
+                if let Some(w) = window {
+                    assert_eq!(w.len(), n_fft, "invalid argument");
+                }
+                let mut h = std::ptr::null_mut();
+                let w = window.map_or(std::ptr::null(), |w| w.as_ptr());
+                ffi::check(unsafe { ffi::$new(signal_len, n_fft, hop, w, center as c_int, pad_mode as c_int, &mut h) });
+                Self { h, signal_len }
+            }
+            pub fn signal_len(&self) -> usize {
+                self.signal_len
+            }
+            pub fn frames(&self) -> usize {
+                unsafe { ffi::$frames(self.h) }
+            }
+            pub fn bins(&self) -> usize {
+                unsafe { ffi::$bins(self.h) }
+            }
+            /// the minimum of the window envelope over the samples some frame holds; the inverse needs more than 1e-11
+            pub fn envelope_min(&self) -> f64 {
+                unsafe { ffi::$env(self.h) }
+            }
+            /// elements of the workspace a device call of `batch` signals works in
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+            /// the least workspace a call runs in: one frame forward, one signal's frames for the inverse
+            pub fn workspace_min(&self, inverse: bool) -> usize {
+                unsafe { ffi::$ws_min(self.h, inverse as c_int) }
+            }
+        }
+        impl Drop for $stft {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_stft!(PlannerStft64, f64, phast_planner_stft64_new, phast_planner_stft64_free, phast_planner_stft64_frames,
+                   phast_planner_stft64_bins, phast_planner_stft64_workspace_len, phast_planner_stft64_workspace_min,
+                   phast_planner_stft64_envelope_min);
+impl_planner_stft!(PlannerStft32, f32, phast_planner_stft32_new, phast_planner_stft32_free, phast_planner_stft32_frames,
+                   phast_planner_stft32_bins, phast_planner_stft32_workspace_len, phast_planner_stft32_workspace_min,
+                   phast_planner_stft32_envelope_min);
+
 macro_rules! impl_planner_nd {
     ($nd:ident, $new:ident, $free:ident, $ws_len:ident, $what:literal) => {
         #[doc = concat!("An extension beyond PhastFT 0.3.0, whose planners transform one axis: ", $what, " over every axis of a ",
