@@ -22,6 +22,8 @@
 //                                                            dst_f64/f32[_with_planner], enum Norm -- types II and III, any N >= 1
 //   (none: no short-time transforms upstream)                class PlannerStft64/32, stft_f64/f32_with_planner,
 //                                                            istft_f64/f32_with_planner, enum PadMode -- torch.stft / istft
+//   (none: no convolution upstream)                          class PlannerConv64/32, conv_f64/f32_with_planner, enum ConvMode --
+//                                                            scipy.signal.convolve / correlate by overlap-save
 //   (none: one axis only upstream)                           class PlannerNd64/32, PlannerR2cNd64/32, fft_64/32_nd[_with_planner],
 //                                                            r2c_fft_f64/f32_nd[...], c2r_fft_f64/f32_nd[...] -- every axis
 //
@@ -503,6 +505,54 @@ PHASTFT_PLANNER_STFT(PlannerStft32, phast_planner_stft32, 32, float)
 PHASTFT_STFT(f64, double, PlannerStft64)
 PHASTFT_STFT(f32, float, PlannerStft32)
 #undef PHASTFT_STFT
+
+// ---- overlap-save convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve / correlate) ----
+enum class ConvMode : int { Full = PHAST_CONV_FULL, Same = PHAST_CONV_SAME, Valid = PHAST_CONV_VALID };
+#define PHASTFT_PLANNER_CONV(NAME, CT, SFX, T)                                                                   \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* `taps`: the K filter taps (correlate: the template); block = 0 picks the block from K */              \
+        NAME(std::size_t signal_len, Slice<const T> taps, ConvMode mode = ConvMode::Full, bool correlate = false, \
+             std::size_t block = 0) {                                                                            \
+            check(phast_planner_conv##SFX##_new(signal_len, taps.ptr, taps.len, static_cast<int>(mode), correlate ? 1 : 0, \
+                                                block, &h_));                                                    \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }                                                   \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_conv##SFX##_free(h_);                                                          \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_conv##SFX##_describe(h_, &s[0], s.size()));                                      \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_conv##SFX##_device_bytes(h_); }                  \
+        std::size_t out_len() const { return phast_planner_conv##SFX##_out_len(h_); }                            \
+        std::size_t block() const { return phast_planner_conv##SFX##_block(h_); }                                \
+        std::size_t segments() const { return phast_planner_conv##SFX##_segments(h_); }                          \
+        /* elements of T a _dev call of `batch` signals works in; workspace_min: the least a call runs in */     \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_conv##SFX##_workspace_len(h_, batch); } \
+        std::size_t workspace_min() const { return phast_planner_conv##SFX##_workspace_min(h_); }                \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+    };
+PHASTFT_PLANNER_CONV(PlannerConv64, phast_planner_conv64, 64, double)
+PHASTFT_PLANNER_CONV(PlannerConv32, phast_planner_conv32, 32, float)
+#undef PHASTFT_PLANNER_CONV
+
+// one host signal of L samples -> its out_len() output samples; blocking
+#define PHASTFT_CONV(FS, T, P)                                                                                   \
+    inline void conv_##FS##_with_planner(Slice<const T> signal, Slice<T> output, const P &planner) {             \
+        check(phast_conv_##FS##_with_planner(signal.ptr, signal.len, output.ptr, output.len, planner.get()));    \
+    }
+PHASTFT_CONV(f64, double, PlannerConv64)
+PHASTFT_CONV(f32, float, PlannerConv32)
+#undef PHASTFT_CONV
 
 // ---- transforms over every axis of a row-major array (numpy fftn / rfftn / irfftn; no reference counterpart) ----
 #define PHASTFT_PLANNER_ND(NAME, CT, PFX)                                                                        \

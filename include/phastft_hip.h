@@ -504,6 +504,74 @@ int phast_istft_f32_dev(const float *d_re, const float *d_im, float *d_signal, s
 int phast_planner_stft32_time_stages(const phast_planner_stft32 *p, int inverse, float *d_signal, float *d_re, float *d_im, size_t batch,
                                      float *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
 
+/* ---- overlap-save FIR convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve /
+ * correlate(x, h, mode, method="direct")).  Signal x of L samples, K taps h, both real:
+ *     full[t] = sum_j g[j] x[t - j], t in [0, L + K - 1); g = h (flip = 0: convolution) or g[j] = h[K - 1 - j] (flip = 1:
+ *     correlation); out[i] = full[t0 + i], i < out_len, with
+ *         PHAST_CONV_FULL   t0 = 0            out_len = L + K - 1
+ *         PHAST_CONV_SAME   t0 = (K - 1) / 2  out_len = L
+ *         PHAST_CONV_VALID  t0 = K - 1        out_len = L - K + 1   (L >= K)
+ * The signal is cut into segments of `block` = B >= K samples that overlap by K - 1; a segment is one R2C of B, a multiply by
+ * the filter's spectrum (built once in double by _new) and one C2R of B on the phast_planner_r2c_any* engine, called
+ * unchanged, and yields S = B - K + 1 output samples; _segments is ceil(out_len / S).  block = 0 picks B: the smallest power
+ * of two >= 4 (K - 1), at least 1024, or the smallest power of two >= L + K - 1 where that is smaller (_block tells).  Any
+ * other block needs K <= B <= 2^29; one that is not a power of two runs the Bluestein real path.
+ * _new takes 1 <= L, K <= 2^29, out_len <= 2^29, segments x (B rounded up to 16 bytes) <= 2^30, `taps` a host pointer to K
+ * values, flip 0 or 1: anything else is PHAST_ERR_INVALID_ARG before the device is touched.
+ *
+ * The caller's device workspace holds phast_planner_conv*_workspace_len(p, batch) elements of T; any work_len >=
+ * _workspace_min(p) (one segment) runs the call in chunks of whole segments, a null or shorter one is PHAST_ERR_INVALID_ARG.
+ * _dev calls: asynchronous on `stream`; `batch` signals at sig_dist >= L, their outputs at out_dist >= out_len (any parity),
+ * all through the planner's one filter; pointers need element alignment only; the signal is never written and nothing is
+ * written past out_len of an output.  A signal_len that is not the planner's is PHAST_ERR_PLANNER_SIZE, a host output that is
+ * not out_len long PHAST_ERR_LEN_MISMATCH.  The planner is immutable and holds no per-call state.  An output sample comes from
+ * exactly one segment: the bits of a signal do not depend on the batch, the chunking, the stream or graph replay wherever the
+ * real transform's do not (every B that is not a power of two, and powers of two up to 4096).  Host-slice calls take one
+ * signal, stage through the device and block. */
+#define PHAST_CONV_FULL 0
+#define PHAST_CONV_SAME 1
+#define PHAST_CONV_VALID 2
+typedef struct phast_planner_conv64 phast_planner_conv64; /* PlannerConv64 */
+int phast_planner_conv64_new(size_t signal_len, const double *taps, size_t num_taps, int mode, int flip, size_t block,
+                             phast_planner_conv64 **out);
+void phast_planner_conv64_free(phast_planner_conv64 *p);
+int phast_planner_conv64_describe(const phast_planner_conv64 *p, char *buf, size_t buf_len);
+size_t phast_planner_conv64_device_bytes(const phast_planner_conv64 *p);
+size_t phast_planner_conv64_out_len(const phast_planner_conv64 *p);
+size_t phast_planner_conv64_block(const phast_planner_conv64 *p);
+size_t phast_planner_conv64_segments(const phast_planner_conv64 *p);
+size_t phast_planner_conv64_workspace_len(const phast_planner_conv64 *p, size_t batch);
+size_t phast_planner_conv64_workspace_min(const phast_planner_conv64 *p);
+int phast_conv_f64_with_planner(const double *signal, size_t signal_len, double *output, size_t output_len,
+                                const phast_planner_conv64 *planner);
+int phast_conv_f64_dev(const double *d_signal, double *d_out, size_t signal_len, size_t batch, size_t sig_dist, size_t out_dist,
+                       const phast_planner_conv64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/conv_rate.py): stage_ms[5] = average milliseconds of the segment sweep, the R2C, the spectrum sweep,
+ * the C2R and the save sweep over `reps` calls of `batch` signals at distances L and out_len in ONE chunk (work_len >=
+ * phast_planner_conv*_workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_conv64_time_stages(const phast_planner_conv64 *p, const double *d_signal, double *d_out, size_t batch, double *d_work,
+                                     size_t work_len, int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_conv32 phast_planner_conv32; /* PlannerConv32 */
+int phast_planner_conv32_new(size_t signal_len, const float *taps, size_t num_taps, int mode, int flip, size_t block,
+                             phast_planner_conv32 **out);
+void phast_planner_conv32_free(phast_planner_conv32 *p);
+int phast_planner_conv32_describe(const phast_planner_conv32 *p, char *buf, size_t buf_len);
+size_t phast_planner_conv32_device_bytes(const phast_planner_conv32 *p);
+size_t phast_planner_conv32_out_len(const phast_planner_conv32 *p);
+size_t phast_planner_conv32_block(const phast_planner_conv32 *p);
+size_t phast_planner_conv32_segments(const phast_planner_conv32 *p);
+size_t phast_planner_conv32_workspace_len(const phast_planner_conv32 *p, size_t batch);
+size_t phast_planner_conv32_workspace_min(const phast_planner_conv32 *p);
+int phast_conv_f32_with_planner(const float *signal, size_t signal_len, float *output, size_t output_len,
+                                const phast_planner_conv32 *planner);
+int phast_conv_f32_dev(const float *d_signal, float *d_out, size_t signal_len, size_t batch, size_t sig_dist, size_t out_dist,
+                       const phast_planner_conv32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/conv_rate.py): stage_ms[5] = average milliseconds of the segment sweep, the R2C, the spectrum sweep,
+ * the C2R and the save sweep over `reps` calls of `batch` signals at distances L and out_len in ONE chunk (work_len >=
+ * phast_planner_conv*_workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_conv32_time_stages(const phast_planner_conv32 *p, const float *d_signal, float *d_out, size_t batch, float *d_work,
+                                     size_t work_len, int reps, float *stage_ms, void *stream);
+
 /* ---- multi-dimensional transforms over every axis of a row-major array (no reference counterpart; numpy fftn / ifftn /
  * rfftn / irfftn with this library's conventions).  dims[0 .. rank-1]: rank 1 .. 8, every axis 1 .. 2^29,
  * their product <= 2^30 (else PHAST_ERR_INVALID_ARG, before the device is touched).  Every axis is transformed; leading

@@ -24,6 +24,8 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
                                                     dct_batched, dst_batched, idct, idst
     (none: no short-time transforms)                PlannerStft64/32, stft_batched, istft_batched,
                                                     stft_f64/f32_with_planner, istft_f64/f32_with_planner
+    (none: no convolution)                          PlannerConv64/32, conv_batched, conv_f64/f32_with_planner,
+                                                    fftconvolve, correlate
     (none: one axis only)                           PlannerNd64/32, fft_64/32_nd[_with_planner], fft_nd_batched,
                                                     PlannerR2cNd64/32, r2c_fft_f64/f32_nd[_with_planner],
                                                     c2r_fft_f64/f32_nd[_with_planner], r2c_nd_batched, c2r_nd_batched
@@ -69,6 +71,8 @@ __all__ = [
     "dst_f64_with_planner", "dst_f32_with_planner", "dct_batched", "dst_batched", "idct", "idst",
     "PlannerStft64", "PlannerStft32", "stft_batched", "istft_batched", "stft_f64_with_planner", "stft_f32_with_planner",
     "istft_f64_with_planner", "istft_f32_with_planner",
+    "PlannerConv64", "PlannerConv32", "conv_batched", "conv_f64_with_planner", "conv_f32_with_planner", "fftconvolve",
+    "correlate",
     "PlannerNd64", "PlannerNd32", "fft_64_nd", "fft_32_nd", "fft_64_nd_with_planner", "fft_32_nd_with_planner", "fft_nd_batched",
     "PlannerR2cNd64", "PlannerR2cNd32", "r2c_fft_f64_nd", "r2c_fft_f32_nd", "r2c_fft_f64_nd_with_planner",
     "r2c_fft_f32_nd_with_planner", "c2r_fft_f64_nd", "c2r_fft_f32_nd", "c2r_fft_f64_nd_with_planner",
@@ -1187,6 +1191,119 @@ def istft_f64_with_planner(in_re, in_im, signal, planner: PlannerStft64) -> None
 def istft_f32_with_planner(in_re, in_im, signal, planner: PlannerStft32) -> None:
     """f32 twin of :func:`istft_f64_with_planner`"""
     _stft_host("istft", "f32", np.float32, in_re, in_im, signal, planner)
+
+
+# ---------------------------------------------------------------------------------------------
+# overlap-save FIR convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve / correlate)
+# ---------------------------------------------------------------------------------------------
+_CONV_MODES = {"full": 0, "same": 1, "valid": 2}
+
+
+class PlannerConv64(_AnyHandle):
+    """f64 convolution (``correlate=True``: cross-correlation) of signals of ``signal_len`` samples with the real ``taps``:
+    ``scipy.signal.convolve(x, taps, mode, method="direct")`` / ``scipy.signal.correlate(...)``.  ``mode``: ``"full"``
+    (L + K - 1 samples), ``"same"`` (L) or ``"valid"`` (L - K + 1; needs L >= K).  The signal runs in overlapping segments of
+    ``block`` samples, each one R2C, one multiply by the filter's spectrum and one C2R; ``block=0`` picks a power of two
+    from the number of taps, any other value must be at least ``len(taps)``."""
+
+    _prefix = "conv"
+
+    def __init__(self, signal_len: int, taps, mode: str = "full", correlate: bool = False, block: int = 0):
+        if mode not in _CONV_MODES:
+            raise ValueError(f"mode must be 'full', 'same' or 'valid', not {mode!r}")
+        if _is_torch(taps):
+            taps = taps.detach().cpu().numpy()
+        h = np.ascontiguousarray(taps, dtype=self._dtype).reshape(-1)
+        self._h = C.c_void_p()
+        _check(self._fn("new")(C.c_size_t(signal_len), h.ctypes.data_as(C.c_void_p), C.c_size_t(h.size),
+                               C.c_int(_CONV_MODES[mode]), C.c_int(bool(correlate)), C.c_size_t(block), C.byref(self._h)))
+        self.n = self.signal_len = signal_len
+        self.num_taps, self.mode, self.correlate = h.size, mode, bool(correlate)
+        self.out_len = int(self._fn("out_len")(self._h))
+        self.block = int(self._fn("block")(self._h))
+        self.segments = int(self._fn("segments")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` signals works in.  A smaller workspace of at least ``workspace_min()``
+        (one segment) runs the call in chunks of whole segments."""
+        return self._workspace_len(batch)
+
+    def workspace_min(self) -> int:
+        return int(self._fn("workspace_min")(self._h))
+
+    def time_stages(self, signal, out, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (segment sweep, R2C, spectrum sweep, C2R, save sweep) of a call of ``batch``
+        signals at distances L and out_len on device tensors (measurement hook)"""
+        x, y = _Slice(signal, self._dtype, "signal"), _Slice(out, self._dtype, "out")
+        return self._time("time_stages", (x, y), (batch,), batch, workspace, reps)
+
+
+class PlannerConv32(PlannerConv64):
+    """f32 twin of :class:`PlannerConv64` (the filter's spectrum is built in f64 and rounded)"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def conv_batched(signal, out, planner, batch: int, sig_dist: int | None = None, out_dist: int | None = None,
+                 workspace=None) -> None:
+    """Device-resident batch of convolutions through one planner's filter: signal b at ``b*sig_dist`` (default L, any distance
+    >= L), its output at ``b*out_dist`` (default ``planner.out_len``, any distance >= that).  ``workspace``: a device tensor
+    of the planner's type of at least ``planner.workspace_min()`` elements (fewer than ``planner.workspace_len(batch)`` runs
+    the segments in chunks); by default one from torch's allocator."""
+    dtype, fs = planner._dtype, "f64" if planner._dtype == np.float64 else "f32"
+    x, y = _Slice(signal, dtype, "signal"), _Slice(out, dtype, "out")
+    if not _same_place(x, y):
+        raise TypeError("conv_batched needs device tensors")
+    n, m = planner.signal_len, planner.out_len
+    sig_dist = n if sig_dist is None else sig_dist
+    out_dist = m if out_dist is None else out_dist
+    _need("signal", x.len, batch, sig_dist, n)
+    _need("out", y.len, batch, out_dist, m)
+    ws = _any_workspace(planner, batch, workspace)
+    _check(getattr(_lib.lib(), f"phast_conv_{fs}_dev")(x.ptr, y.ptr, C.c_size_t(n), C.c_size_t(batch), C.c_size_t(sig_dist),
+                                                       C.c_size_t(out_dist), planner._h, ws.ptr, C.c_size_t(ws.len), _stream()))
+
+
+def _conv_host(fs, dtype, signal, out, planner):
+    x, y = _Slice(signal, dtype, "signal"), _Slice(out, dtype, "out")
+    if _same_place(x, y):
+        raise TypeError(f"conv_{fs}_with_planner takes host arrays (conv_batched takes device tensors)")
+    _check(getattr(_lib.lib(), f"phast_conv_{fs}_with_planner")(x.ptr, C.c_size_t(x.len), y.ptr, C.c_size_t(y.len), planner._h))
+
+
+def conv_f64_with_planner(signal, out, planner: PlannerConv64) -> None:
+    """f64 convolution of one host signal of L samples into a host array of ``planner.out_len`` (blocking)"""
+    _conv_host("f64", np.float64, signal, out, planner)
+
+
+def conv_f32_with_planner(signal, out, planner: PlannerConv32) -> None:
+    """f32 twin of :func:`conv_f64_with_planner`"""
+    _conv_host("f32", np.float32, signal, out, planner)
+
+
+def _convolve(x, h, mode, correlate):
+    import torch
+
+    if not _is_torch(x) or x.device.type != "cuda" or x.dtype not in (torch.float64, torch.float32):
+        raise TypeError("need a float64 or float32 device tensor")
+    x = x.contiguous().reshape(-1)
+    planner = (PlannerConv64 if x.dtype == torch.float64 else PlannerConv32)(x.numel(), h, mode, correlate)
+    out = torch.empty(planner.out_len, dtype=x.dtype, device=x.device)
+    conv_batched(x, out, planner, 1)
+    torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+    return out
+
+
+def fftconvolve(x, h, mode: str = "full"):
+    """``scipy.signal.fftconvolve(x, h, mode)`` of one real device tensor with the taps ``h`` (an array or a tensor), by
+    overlap-save through a planner of its own: a new device tensor"""
+    return _convolve(x, h, mode, False)
+
+
+def correlate(x, h, mode: str = "full"):
+    """``scipy.signal.correlate(x, h, mode)`` of one real device tensor with the template ``h``: a new device tensor"""
+    return _convolve(x, h, mode, True)
 
 
 # ---------------------------------------------------------------------------------------------

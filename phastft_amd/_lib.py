@@ -68,6 +68,12 @@ phast_planner_stft64_workspace_len phast_planner_stft32_workspace_len phast_plan
 phast_planner_stft64_envelope_min phast_planner_stft32_envelope_min phast_planner_stft64_time_stages phast_planner_stft32_time_stages
 phast_stft_f64_with_planner phast_stft_f32_with_planner phast_istft_f64_with_planner phast_istft_f32_with_planner
 phast_stft_f64_dev phast_stft_f32_dev phast_istft_f64_dev phast_istft_f32_dev
+phast_planner_conv64_new phast_planner_conv32_new phast_planner_conv64_free phast_planner_conv32_free
+phast_planner_conv64_describe phast_planner_conv32_describe phast_planner_conv64_device_bytes phast_planner_conv32_device_bytes
+phast_planner_conv64_out_len phast_planner_conv32_out_len phast_planner_conv64_block phast_planner_conv32_block
+phast_planner_conv64_segments phast_planner_conv32_segments phast_planner_conv64_workspace_len phast_planner_conv32_workspace_len
+phast_planner_conv64_workspace_min phast_planner_conv32_workspace_min phast_planner_conv64_time_stages phast_planner_conv32_time_stages
+phast_conv_f64_with_planner phast_conv_f32_with_planner phast_conv_f64_dev phast_conv_f32_dev
 phast_planner_nd64_new phast_planner_nd32_new phast_planner_nd64_free phast_planner_nd32_free
 phast_planner_nd64_describe phast_planner_nd32_describe phast_planner_nd64_device_bytes phast_planner_nd32_device_bytes
 phast_planner_nd64_workspace_len phast_planner_nd32_workspace_len phast_planner_nd64_time_steps phast_planner_nd32_time_steps
@@ -145,7 +151,9 @@ def lib() -> C.CDLL:
         for k in ("frames", "bins", "workspace_min"):
             getattr(l, f"phast_planner_stft{sfx}_{k}").restype = C.c_size_t
         getattr(l, f"phast_planner_stft{sfx}_envelope_min").restype = C.c_double
-        for k in ("nd", "r2c_nd", "dct", "stft"):
+        for k in ("out_len", "block", "segments", "workspace_min"):
+            getattr(l, f"phast_planner_conv{sfx}_{k}").restype = C.c_size_t
+        for k in ("nd", "r2c_nd", "dct", "stft", "conv"):
             getattr(l, f"phast_planner_{k}{sfx}_free").restype = None
             getattr(l, f"phast_planner_{k}{sfx}_device_bytes").restype = C.c_size_t
             getattr(l, f"phast_planner_{k}{sfx}_workspace_len").restype = C.c_size_t

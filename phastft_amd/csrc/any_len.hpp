@@ -86,6 +86,11 @@ hipError_t launch_any_round(const double *in, float *out, unsigned long long cou
 template <typename T> struct AnyVec;  // 16 bytes of T: the group of one thread
 template <> struct AnyVec<double> { typedef double type __attribute__((ext_vector_type(2))); static constexpr int N = 2; };
 template <> struct AnyVec<float> { typedef float type __attribute__((ext_vector_type(4))); static constexpr int N = 4; };
+// 16 bytes of T at element alignment: the gathered side of a sweep (stft.hip, conv.hip)
+template <typename T> struct Unaligned;
+template <> struct Unaligned<double> { typedef double type __attribute__((ext_vector_type(2), aligned(8))); };
+template <> struct Unaligned<float> { typedef float type __attribute__((ext_vector_type(4), aligned(4))); };
+__device__ inline bool aligned16(const void *p) { return (reinterpret_cast<unsigned long long>(p) & 15ull) == 0; }
 
 // w[k] = exp(-i pi k^2 / n) (cos, sin) in double
 __device__ inline void chirp(unsigned long long k, unsigned long long n, double *c, double *s) {

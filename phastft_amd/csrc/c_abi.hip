@@ -18,6 +18,7 @@
 #include "planner_any_real.hpp"
 #include "planner_dct.hpp"
 #include "planner_stft.hpp"
+#include "planner_conv.hpp"
 #include "planner_nd.hpp"
 
 // ================================================================================================
@@ -37,6 +38,8 @@ struct phast_planner_dct64 : DctPlanner<double> {};
 struct phast_planner_dct32 : DctPlanner<float> {};
 struct phast_planner_stft64 : StftPlanner<double> {};
 struct phast_planner_stft32 : StftPlanner<float> {};
+struct phast_planner_conv64 : ConvPlanner<double> {};
+struct phast_planner_conv32 : ConvPlanner<float> {};
 struct phast_planner_nd64 : NdPlanner<double> {};
 struct phast_planner_nd32 : NdPlanner<float> {};
 struct phast_planner_r2c_nd64 : RealNdPlanner<double> {};
@@ -734,6 +737,59 @@ PHAST_DCT_API(32, f32, float)
     } PHAST_CATCH_RC
 PHAST_STFT_API(64, f64, double)
 PHAST_STFT_API(32, f32, float)
+
+// Overlap-save convolution and correlation of real signals (planner_conv.hpp): every argument rule and a wrong length come
+// back before the device is touched
+#define PHAST_CONV_API(SFX, FS, T)                                                                                      \
+    int phast_planner_conv##SFX##_new(size_t signal_len, const T *taps, size_t num_taps, int mode, int flip,            \
+                                      size_t block, phast_planner_conv##SFX **out) try {                                \
+        return conv_planner_new<T>(signal_len, taps, num_taps, mode, flip, block, out);                                 \
+    } PHAST_CATCH_RC                                                                                                    \
+    void phast_planner_conv##SFX##_free(phast_planner_conv##SFX *p) try { delete p; } PHAST_CATCH_VOID                  \
+    int phast_planner_conv##SFX##_describe(const phast_planner_conv##SFX *p, char *buf, size_t len) try {               \
+        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
+        std::snprintf(buf, len, "%s", p->describe().c_str());                                                           \
+        return PHAST_OK;                                                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_conv##SFX##_device_bytes(const phast_planner_conv##SFX *p) try {                               \
+        return p ? p->device_bytes() : 0;                                                                               \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_conv##SFX##_out_len(const phast_planner_conv##SFX *p) try {                                    \
+        return p ? p->out_len : 0;                                                                                      \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_conv##SFX##_block(const phast_planner_conv##SFX *p) try {                                      \
+        return p ? p->b : 0;                                                                                            \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_conv##SFX##_segments(const phast_planner_conv##SFX *p) try {                                   \
+        return p ? p->segs : 0;                                                                                         \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_conv##SFX##_workspace_len(const phast_planner_conv##SFX *p, size_t batch) try {                \
+        return p ? p->workspace_len(batch) : 0;                                                                         \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_conv##SFX##_workspace_min(const phast_planner_conv##SFX *p) try {                              \
+        return p ? p->workspace_min() : 0;                                                                              \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_conv##SFX##_time_stages(const phast_planner_conv##SFX *p, const T *d_signal, T *d_out,            \
+                                              size_t batch, T *d_work, size_t work_len, int reps, float *stage_ms,      \
+                                              void *stream) try {                                                       \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(d_signal, d_out, batch, d_work, work_len, reps, stage_ms,                                 \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_conv_##FS##_with_planner(const T *signal, size_t signal_len, T *out, size_t out_len,                      \
+                                       const phast_planner_conv##SFX *p) try {                                          \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(signal, signal_len, out, out_len);                                                               \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_conv_##FS##_dev(const T *d_signal, T *d_out, size_t signal_len, size_t batch, size_t sig_dist,            \
+                              size_t out_dist, const phast_planner_conv##SFX *p, T *d_work, size_t work_len,            \
+                              void *stream) try {                                                                       \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(d_signal, d_out, signal_len, batch, sig_dist, out_dist, d_work, work_len,                         \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC
+PHAST_CONV_API(64, f64, double)
+PHAST_CONV_API(32, f32, float)
 
 // Multi-dimensional transforms (planner_nd.hpp): the shape and the lengths are checked before the device is touched
 #define PHAST_ND_PLANNER_API(NAME, KIND)                                                                                \

@@ -13,13 +13,6 @@
 
 namespace phast {
 
-__device__ inline bool aligned16(const void *p) { return (reinterpret_cast<unsigned long long>(p) & 15ull) == 0; }
-
-// 16 bytes of T at element alignment
-template <typename T> struct Unaligned;
-template <> struct Unaligned<double> { typedef double type __attribute__((ext_vector_type(2), aligned(8))); };
-template <> struct Unaligned<float> { typedef float type __attribute__((ext_vector_type(4), aligned(4))); };
-
 // ---- frame: row q0 + r of the workspace = w[j] x~[f H - p + j], j < F; zeros in the row's padding up to fd ----
 template <typename T>
 __global__ void __launch_bounds__(256) stft_frame_kernel(StftArgs a) {

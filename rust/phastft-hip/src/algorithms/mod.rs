@@ -2,6 +2,7 @@
 //! the same visibility here, so `phastft::algorithms::bravo::bit_rev_bravo_f64` resolves exactly when it
 //! does upstream (benches/bit_reversal.rs:3).
 pub mod bravo;
+pub mod conv;
 pub mod dit;
 pub mod r2c;
 pub mod r2r;

@@ -155,6 +155,39 @@ extern "C" {
         planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     pub(crate) fn phast_istft_f32_dev(re: *const f32, im: *const f32, signal: *mut f32, signal_len: usize, batch: usize,
         sig_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // overlap-save convolution and correlation (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/conv.rs)
+    pub(crate) fn phast_planner_conv64_new(signal_len: usize, taps: *const f64, num_taps: usize, mode: c_int, flip: c_int,
+        block: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_conv64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_conv64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_conv64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_conv64_out_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_conv64_block(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_conv64_segments(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_conv64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_conv64_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_conv64_time_stages(p: *const Opaque, signal: *const f64, out: *mut f64, batch: usize,
+        work: *mut f64, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_conv_f64_with_planner(signal: *const f64, signal_len: usize, out: *mut f64, out_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_conv_f64_dev(signal: *const f64, out: *mut f64, signal_len: usize, batch: usize, sig_dist: usize,
+        out_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_conv32_new(signal_len: usize, taps: *const f32, num_taps: usize, mode: c_int, flip: c_int,
+        block: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_conv32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_conv32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_conv32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_conv32_out_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_conv32_block(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_conv32_segments(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_conv32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_conv32_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_conv32_time_stages(p: *const Opaque, signal: *const f32, out: *mut f32, batch: usize,
+        work: *mut f32, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_conv_f32_with_planner(signal: *const f32, signal_len: usize, out: *mut f32, out_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_conv_f32_dev(signal: *const f32, out: *mut f32, signal_len: usize, batch: usize, sig_dist: usize,
+        out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // DCT / DST of types II and III (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/r2r.rs)
     pub(crate) fn phast_planner_dct64_new(n: usize, out: *mut *mut Opaque) -> c_int;
     pub(crate) fn phast_planner_dct32_new(n: usize, out: *mut *mut Opaque) -> c_int;

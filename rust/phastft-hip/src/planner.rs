@@ -310,6 +310,72 @@ impl_planner_stft!(PlannerStft32, f32, phast_planner_stft32_new, phast_planner_s
                    phast_planner_stft32_bins, phast_planner_stft32_workspace_len, phast_planner_stft32_workspace_min,
                    phast_planner_stft32_envelope_min);
 
+/// Which part of the full convolution a planner yields (PHAST_CONV_* of the C ABI)
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum ConvMode {
+    Full = 0,
+    Same = 1,
+    Valid = 2,
+}
+
+macro_rules! impl_planner_conv {
+    ($conv:ident, $t:ty, $new:ident, $free:ident, $out_len:ident, $block:ident, $segments:ident, $ws_len:ident, $ws_min:ident) => {
+        /// An extension beyond PhastFT 0.3.0: convolution (`correlate`: cross-correlation) of real signals of `signal_len`
+        /// samples with the planner's taps by overlap-save (scipy.signal.convolve / correlate with method = "direct"): one
+        /// R2C, one spectrum multiply and one C2R of `block` points per segment.  Immutable after `new`, like the
+        /// reference's planners.
+        pub struct $conv {
+            pub(crate) h: *mut Opaque,
+            pub(crate) signal_len: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in
+        // device buffers of its own (host-slice calls)
+        unsafe impl Send for $conv {}
+        unsafe impl Sync for $conv {}
+        impl $conv {
+            /// `block` = 0 picks the block from the number of taps.  Panics with "invalid argument" unless 1 <= signal_len,
+            /// taps.len() <= 2^29, signal_len >= taps.len() with `ConvMode::Valid`, taps.len() <= block <= 2^29, at most
+            /// 2^29 output samples and at most 2^30 points in the segments
+            pub fn new(signal_len: usize, taps: &[$t], mode: ConvMode, correlate: bool, block: usize) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe { ffi::$new(signal_len, taps.as_ptr(), taps.len(), mode as c_int, correlate as c_int, block, &mut h) });
+                Self { h, signal_len }
+            }
+            pub fn signal_len(&self) -> usize {
+                self.signal_len
+            }
+            pub fn out_len(&self) -> usize {
+                unsafe { ffi::$out_len(self.h) }
+            }
+            pub fn block(&self) -> usize {
+                unsafe { ffi::$block(self.h) }
+            }
+            pub fn segments(&self) -> usize {
+                unsafe { ffi::$segments(self.h) }
+            }
+            /// elements of the workspace a device call of `batch` signals works in
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+            /// the least workspace a call runs in: one segment
+            pub fn workspace_min(&self) -> usize {
+                unsafe { ffi::$ws_min(self.h) }
+            }
+        }
+        impl Drop for $conv {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_conv!(PlannerConv64, f64, phast_planner_conv64_new, phast_planner_conv64_free, phast_planner_conv64_out_len,
+                   phast_planner_conv64_block, phast_planner_conv64_segments, phast_planner_conv64_workspace_len,
+                   phast_planner_conv64_workspace_min);
+impl_planner_conv!(PlannerConv32, f32, phast_planner_conv32_new, phast_planner_conv32_free, phast_planner_conv32_out_len,
+                   phast_planner_conv32_block, phast_planner_conv32_segments, phast_planner_conv32_workspace_len,
+                   phast_planner_conv32_workspace_min);
+
 macro_rules! impl_planner_nd {
     ($nd:ident, $new:ident, $free:ident, $ws_len:ident, $what:literal) => {
         #[doc = concat!("An extension beyond PhastFT 0.3.0, whose planners transform one axis: ", $what, " over every axis of a ",
