@@ -24,6 +24,8 @@
 //                                                            istft_f64/f32_with_planner, enum PadMode -- torch.stft / istft
 //   (none: no convolution upstream)                          class PlannerConv64/32, conv_f64/f32_with_planner, enum ConvMode --
 //                                                            scipy.signal.convolve / correlate by overlap-save
+//   (none: whole spectra only upstream)                      class PlannerCzt64/32, czt_64/32[_with_planner] -- the chirp-Z transform
+//                                                            on the unit circle (scipy.signal.czt / zoom_fft)
 //   (none: one axis only upstream)                           class PlannerNd64/32, PlannerR2cNd64/32, fft_64/32_nd[_with_planner],
 //                                                            r2c_fft_f64/f32_nd[...], c2r_fft_f64/f32_nd[...] -- every axis
 //
@@ -553,6 +555,60 @@ PHASTFT_PLANNER_CONV(PlannerConv32, phast_planner_conv32, 32, float)
 PHASTFT_CONV(f64, double, PlannerConv64)
 PHASTFT_CONV(f32, float, PlannerConv32)
 #undef PHASTFT_CONV
+
+// ---- the chirp-Z transform on the unit circle and the zoom FFT (no reference counterpart; scipy.signal.czt / zoom_fft) ----
+#define PHASTFT_PLANNER_CZT(NAME, CT, SFX)                                                                       \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* m bins of n points at start + k step turns: X[k] = sum x[n] exp(-2 pi i n (start + k step)) */       \
+        NAME(std::size_t n, std::size_t m, double step, double start = 0.0) : n_(n), m_(m) {                     \
+            check(phast_planner_czt##SFX##_new(n, m, step, start, &h_));                                         \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_), n_(o.n_), m_(o.m_) { o.h_ = nullptr; }                               \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_czt##SFX##_free(h_);                                                           \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_czt##SFX##_describe(h_, &s[0], s.size()));                                       \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t input_len() const { return n_; }                                                             \
+        std::size_t output_len() const { return m_; }                                                            \
+        std::size_t device_bytes() const { return phast_planner_czt##SFX##_device_bytes(h_); }                   \
+        std::size_t conv_len() const { return phast_planner_czt##SFX##_conv_len(h_); }                           \
+        /* elements of T a _dev call of `batch` transforms works in: 2 L batch */                                \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_czt##SFX##_workspace_len(h_, batch); } \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+        std::size_t n_, m_;                                                                                      \
+    };
+PHASTFT_PLANNER_CZT(PlannerCzt64, phast_planner_czt64, 64)
+PHASTFT_PLANNER_CZT(PlannerCzt32, phast_planner_czt32, 32)
+#undef PHASTFT_PLANNER_CZT
+
+// one host signal (in_im.ptr may be null: a real signal) -> its output_len() bins; blocking.  Without a planner the call builds
+// its own from the lengths of the slices.
+#define PHASTFT_CZT(SFX, T, P)                                                                                   \
+    inline void czt_##SFX(Slice<const T> in_re, Slice<const T> in_im, Slice<T> out_re, Slice<T> out_im, double step, \
+                          double start = 0.0) {                                                                  \
+        if ((in_im.ptr && in_im.len != in_re.len) || out_re.len != out_im.len) check(PHAST_ERR_LEN_MISMATCH);    \
+        check(phast_czt_##SFX(in_re.ptr, in_im.ptr, in_re.len, out_re.ptr, out_im.ptr, out_re.len, step, start)); \
+    }                                                                                                            \
+    inline void czt_##SFX##_with_planner(Slice<const T> in_re, Slice<const T> in_im, Slice<T> out_re, Slice<T> out_im, \
+                                         const P &planner) {                                                     \
+        if ((in_im.ptr && in_im.len != in_re.len) || out_re.len != out_im.len) check(PHAST_ERR_LEN_MISMATCH);    \
+        check(phast_czt_##SFX##_with_planner(in_re.ptr, in_im.ptr, in_re.len, out_re.ptr, out_im.ptr, out_re.len, \
+                                             planner.get()));                                                    \
+    }
+PHASTFT_CZT(64, double, PlannerCzt64)
+PHASTFT_CZT(32, float, PlannerCzt32)
+#undef PHASTFT_CZT
 
 // ---- transforms over every axis of a row-major array (numpy fftn / rfftn / irfftn; no reference counterpart) ----
 #define PHASTFT_PLANNER_ND(NAME, CT, PFX)                                                                        \

@@ -572,6 +572,60 @@ int phast_conv_f32_dev(const float *d_signal, float *d_out, size_t signal_len, s
 int phast_planner_conv32_time_stages(const phast_planner_conv32 *p, const float *d_signal, float *d_out, size_t batch, float *d_work,
                                      size_t work_len, int reps, float *stage_ms, void *stream);
 
+/* ---- the chirp-Z transform on the unit circle and the zoom FFT (no reference counterpart; scipy.signal.czt / zoom_fft;
+ * DESIGN.md §17).  N input points x, M output points, `start` and `step` finite doubles in turns (cycles per sample):
+ *     X[k] = sum_{n < N} x[n] exp(-2 pi i n (start + k step)),  k < M
+ * = scipy.signal.czt(x, M, w, a) with w = exp(-2 pi i step), a = exp(2 pi i start), and scipy.signal.zoom_fft(x, [f1, f2], M,
+ * fs = fs, endpoint = e) with start = f1 / fs, step = (f2 - f1) / (fs (M - 1 if e else M)); start = 0, step = 1 / N, M = N is
+ * the forward DFT.  The parameters are turns, never complex numbers: a complex w has lost the bits that matter at large N.
+ * Every angle is formed exactly mod 1 turn in 128-bit fixed point from the two doubles.  Bluestein's schedule in
+ * L = _conv_len = the smallest power of two >= N + M - 1 (at least 8): two L-point transforms between three sweeps.
+ * _new takes 1 <= N, 1 <= M, N + M - 1 <= 2^30 and finite step and start: anything else is PHAST_ERR_INVALID_ARG before the
+ * device is touched.  Points off the unit circle, an inverse and a real-output form are not offered.
+ *
+ * The caller's device workspace holds phast_planner_czt*_workspace_len(p, batch) = 2 L batch elements of T; any work_len >= 2 L
+ * runs the batch in chunks, a null or shorter one is PHAST_ERR_INVALID_ARG.  _dev calls: asynchronous on `stream`; `batch`
+ * inputs at in_dist >= N, their outputs at out_dist >= M; pointers need element alignment only; d_in_im (in_im) may be NULL:
+ * a real signal, of which one plane is read.  The input is never written, nothing is written past M of an output, and the
+ * output must not overlap the input, the workspace or its other plane (PHAST_ERR_INVALID_ARG).  A host call whose n or m is not the
+ * planner's is PHAST_ERR_PLANNER_SIZE.  The planner is immutable and holds no per-call state; the bits of a transform do not
+ * depend on the batch, the chunking, the alignment, the stream or graph replay.  Host-slice calls take one signal, stage
+ * through the device and block; phast_czt_64 / _32 build a planner for the one call. */
+typedef struct phast_planner_czt64 phast_planner_czt64; /* PlannerCzt64 */
+int phast_planner_czt64_new(size_t n, size_t m, double step, double start, phast_planner_czt64 **out);
+void phast_planner_czt64_free(phast_planner_czt64 *p);
+int phast_planner_czt64_describe(const phast_planner_czt64 *p, char *buf, size_t buf_len);
+size_t phast_planner_czt64_device_bytes(const phast_planner_czt64 *p);
+size_t phast_planner_czt64_conv_len(const phast_planner_czt64 *p);
+size_t phast_planner_czt64_workspace_len(const phast_planner_czt64 *p, size_t batch);
+int phast_czt_64(const double *in_re, const double *in_im, size_t n, double *out_re, double *out_im, size_t m, double step, double start);
+int phast_czt_64_with_planner(const double *in_re, const double *in_im, size_t n, double *out_re, double *out_im, size_t m,
+                               const phast_planner_czt64 *planner);
+int phast_czt_64_dev(const double *d_in_re, const double *d_in_im, size_t in_dist, double *d_out_re, double *d_out_im, size_t out_dist,
+                      size_t batch, const phast_planner_czt64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/czt_rate.py): stage_ms[5] = average milliseconds of the pre sweep, the forward L-point transform, the
+ * spectrum sweep, the inverse L-point transform and the post sweep over `reps` calls of `batch` transforms at distances N and M in
+ * ONE chunk (work_len >= phast_planner_czt*_workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_czt64_time_stages(const phast_planner_czt64 *p, const double *d_in_re, const double *d_in_im, double *d_out_re, double *d_out_im, size_t batch,
+                                    double *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_czt32 phast_planner_czt32; /* PlannerCzt32 */
+int phast_planner_czt32_new(size_t n, size_t m, double step, double start, phast_planner_czt32 **out);
+void phast_planner_czt32_free(phast_planner_czt32 *p);
+int phast_planner_czt32_describe(const phast_planner_czt32 *p, char *buf, size_t buf_len);
+size_t phast_planner_czt32_device_bytes(const phast_planner_czt32 *p);
+size_t phast_planner_czt32_conv_len(const phast_planner_czt32 *p);
+size_t phast_planner_czt32_workspace_len(const phast_planner_czt32 *p, size_t batch);
+int phast_czt_32(const float *in_re, const float *in_im, size_t n, float *out_re, float *out_im, size_t m, double step, double start);
+int phast_czt_32_with_planner(const float *in_re, const float *in_im, size_t n, float *out_re, float *out_im, size_t m,
+                               const phast_planner_czt32 *planner);
+int phast_czt_32_dev(const float *d_in_re, const float *d_in_im, size_t in_dist, float *d_out_re, float *d_out_im, size_t out_dist,
+                      size_t batch, const phast_planner_czt32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/czt_rate.py): stage_ms[5] = average milliseconds of the pre sweep, the forward L-point transform, the
+ * spectrum sweep, the inverse L-point transform and the post sweep over `reps` calls of `batch` transforms at distances N and M in
+ * ONE chunk (work_len >= phast_planner_czt*_workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_czt32_time_stages(const phast_planner_czt32 *p, const float *d_in_re, const float *d_in_im, float *d_out_re, float *d_out_im, size_t batch,
+                                    float *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+
 /* ---- multi-dimensional transforms over every axis of a row-major array (no reference counterpart; numpy fftn / ifftn /
  * rfftn / irfftn with this library's conventions).  dims[0 .. rank-1]: rank 1 .. 8, every axis 1 .. 2^29,
  * their product <= 2^30 (else PHAST_ERR_INVALID_ARG, before the device is touched).  Every axis is transformed; leading

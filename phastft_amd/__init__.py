@@ -26,6 +26,7 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
                                                     stft_f64/f32_with_planner, istft_f64/f32_with_planner
     (none: no convolution)                          PlannerConv64/32, conv_batched, conv_f64/f32_with_planner,
                                                     fftconvolve, correlate
+    (none: whole spectra only)                      PlannerCzt64/32, czt_batched, czt_64/32[_with_planner], czt, zoom_fft
     (none: one axis only)                           PlannerNd64/32, fft_64/32_nd[_with_planner], fft_nd_batched,
                                                     PlannerR2cNd64/32, r2c_fft_f64/f32_nd[_with_planner],
                                                     c2r_fft_f64/f32_nd[_with_planner], r2c_nd_batched, c2r_nd_batched
@@ -42,6 +43,7 @@ raise.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import enum
 from dataclasses import dataclass
@@ -73,6 +75,8 @@ __all__ = [
     "istft_f64_with_planner", "istft_f32_with_planner",
     "PlannerConv64", "PlannerConv32", "conv_batched", "conv_f64_with_planner", "conv_f32_with_planner", "fftconvolve",
     "correlate",
+    "PlannerCzt64", "PlannerCzt32", "czt_batched", "czt_64", "czt_32", "czt_64_with_planner", "czt_32_with_planner", "czt",
+    "zoom_fft",
     "PlannerNd64", "PlannerNd32", "fft_64_nd", "fft_32_nd", "fft_64_nd_with_planner", "fft_32_nd_with_planner", "fft_nd_batched",
     "PlannerR2cNd64", "PlannerR2cNd32", "r2c_fft_f64_nd", "r2c_fft_f32_nd", "r2c_fft_f64_nd_with_planner",
     "r2c_fft_f32_nd_with_planner", "c2r_fft_f64_nd", "c2r_fft_f32_nd", "c2r_fft_f64_nd_with_planner",
@@ -1304,6 +1308,173 @@ def fftconvolve(x, h, mode: str = "full"):
 def correlate(x, h, mode: str = "full"):
     """``scipy.signal.correlate(x, h, mode)`` of one real device tensor with the template ``h``: a new device tensor"""
     return _convolve(x, h, mode, True)
+
+
+# ---------------------------------------------------------------------------------------------
+# the chirp-Z transform on the unit circle and the zoom FFT (no reference counterpart; scipy.signal.czt / zoom_fft)
+# ---------------------------------------------------------------------------------------------
+class PlannerCzt64(_AnyHandle):
+    """f64 chirp-Z transform on the unit circle: ``m`` bins of ``n`` points at the frequencies ``start + k*step``, both in
+    turns (cycles per sample): ``X[k] = sum_n x[n] exp(-2j pi n (start + k step))``, which is ``scipy.signal.czt(x, m,
+    w=exp(-2j pi step), a=exp(2j pi start))``.  1 <= n, 1 <= m, n + m - 1 <= 2^30, finite ``step`` and ``start``."""
+
+    _prefix = "czt"
+
+    def __init__(self, n: int, m: int, step: float, start: float = 0.0):
+        self._h = C.c_void_p()
+        _check(self._fn("new")(C.c_size_t(n), C.c_size_t(m), C.c_double(step), C.c_double(start), C.byref(self._h)))
+        self.n, self.m, self.step, self.start = n, m, float(step), float(start)
+        self.conv_len = int(self._fn("conv_len")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` transforms works in: 2 L batch, L = ``conv_len``.  A smaller workspace of
+        at least 2 L runs the batch in chunks."""
+        return self._workspace_len(batch)
+
+    def time_stages(self, in_re, in_im, out_re, out_im, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (pre sweep, forward L-point transform, spectrum sweep, inverse L-point transform,
+        post sweep) of a call of ``batch`` transforms at distances n and m on device tensors (measurement hook)"""
+        bufs = [_Slice(in_re, self._dtype, "in_re"), _NULL if in_im is None else _Slice(in_im, self._dtype, "in_im"),
+                _Slice(out_re, self._dtype, "out_re"), _Slice(out_im, self._dtype, "out_im")]
+        return self._time("time_stages", bufs, (batch,), batch, workspace, reps)
+
+
+class PlannerCzt32(PlannerCzt64):
+    """f32 twin of :class:`PlannerCzt64` (the phases and the table are built in f64 and rounded)"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+class _Null:
+    ptr = None
+
+
+_NULL = _Null()
+
+
+def czt_batched(x_re, x_im, planner, out=None, work=None, stream=None):
+    """Device-resident batch of chirp-Z transforms through one planner: ``x_re`` (and ``x_im``, or ``None`` for a real
+    signal) are torch device tensors of shape ``(batch, n)`` or ``(n,)`` of the planner's type whose last axis is
+    contiguous; returns ``(out_re, out_im)`` of shape ``(batch, m)`` or ``(m,)``.  ``out``: such a pair to write into (it must
+    not overlap the input or ``work``); ``work``: a device tensor of at least ``planner.workspace_len(1)`` elements (fewer than
+    ``planner.workspace_len(batch)`` runs the batch in chunks), by default one from torch's allocator; ``stream``: a
+    ``torch.cuda.Stream``, by default the current one."""
+    import torch
+
+    want = torch.float64 if planner._dtype == np.float64 else torch.float32
+    n, m = planner.n, planner.m
+
+    def plane(t, what, per):
+        if not _is_torch(t) or t.device.type != "cuda" or t.dtype != want:
+            raise TypeError(f"{what}: need a {want} device tensor")
+        if t.dim() not in (1, 2) or t.shape[-1] != per or t.stride(-1) != 1:
+            raise ValueError(f"{what}: need shape (batch, {per}) or ({per},) with a contiguous last axis, not {tuple(t.shape)}")
+        rows = t.shape[0] if t.dim() == 2 else 1
+        dist = t.stride(0) if t.dim() == 2 and rows > 1 else per
+        if dist < per:
+            raise ValueError(f"{what}: rows overlap")
+        return rows, dist
+
+    batch, in_dist = plane(x_re, "x_re", n)
+    if x_im is not None and (plane(x_im, "x_im", n) != (batch, in_dist) or x_im.shape != x_re.shape):
+        raise ValueError("x_im: need the shape and the strides of x_re")
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        if out is None:
+            shape = (batch, m) if x_re.dim() == 2 else (m,)
+            out = (torch.empty(shape, dtype=want, device=x_re.device), torch.empty(shape, dtype=want, device=x_re.device))
+        out_re, out_im = out
+        rows, out_dist = plane(out_re, "out_re", m)
+        if rows != batch or plane(out_im, "out_im", m) != (batch, out_dist) or out_re.dim() != x_re.dim():
+            raise ValueError("out: need a pair of (batch, m) tensors with equal strides")
+        ws = _any_workspace(planner, batch, work)
+        _check(getattr(_lib.lib(), f"phast_czt_{planner._sfx}_dev")(
+            C.c_void_p(x_re.data_ptr()), None if x_im is None else C.c_void_p(x_im.data_ptr()), C.c_size_t(in_dist),
+            C.c_void_p(out_re.data_ptr()), C.c_void_p(out_im.data_ptr()), C.c_size_t(out_dist), C.c_size_t(batch), planner._h,
+            ws.ptr, C.c_size_t(ws.len), _stream()))
+    return out_re, out_im
+
+
+def _czt_host(sfx, dtype, in_re, in_im, out_re, out_im, step, start, planner=None):
+    x = _Slice(in_re, dtype, "in_re")
+    y = _NULL if in_im is None else _Slice(in_im, dtype, "in_im")
+    o_re, o_im = _Slice(out_re, dtype, "out_re"), _Slice(out_im, dtype, "out_im")
+    if _same_place(*(s for s in (x, y, o_re, o_im) if s is not _NULL)):
+        raise TypeError(f"czt_{sfx} takes host arrays (czt_batched takes device tensors)")
+    if (y is not _NULL and y.len != x.len) or o_re.len != o_im.len:
+        _check(2)
+    args = [x.ptr, y.ptr, C.c_size_t(x.len), o_re.ptr, o_im.ptr, C.c_size_t(o_re.len)]
+    if planner is None:
+        _check(getattr(_lib.lib(), f"phast_czt_{sfx}")(*args, C.c_double(step), C.c_double(start)))
+    else:
+        _check(getattr(_lib.lib(), f"phast_czt_{sfx}_with_planner")(*args, planner._h))
+
+
+def czt_64(in_re, in_im, out_re, out_im, step: float, start: float = 0.0) -> None:
+    """f64 chirp-Z transform of one host signal (``in_im`` may be ``None``: a real signal) into host arrays of m bins, through
+    a planner of its own (blocking)"""
+    _czt_host("64", np.float64, in_re, in_im, out_re, out_im, step, start)
+
+
+def czt_32(in_re, in_im, out_re, out_im, step: float, start: float = 0.0) -> None:
+    """f32 twin of :func:`czt_64`"""
+    _czt_host("32", np.float32, in_re, in_im, out_re, out_im, step, start)
+
+
+def czt_64_with_planner(in_re, in_im, out_re, out_im, planner: PlannerCzt64) -> None:
+    _czt_host("64", np.float64, in_re, in_im, out_re, out_im, 0.0, 0.0, planner)
+
+
+def czt_32_with_planner(in_re, in_im, out_re, out_im, planner: PlannerCzt32) -> None:
+    _czt_host("32", np.float32, in_re, in_im, out_re, out_im, 0.0, 0.0, planner)
+
+
+def czt(x, m: int | None = None, step: float | None = None, start: float = 0.0):
+    """The chirp-Z transform on the unit circle of a real or complex device tensor over its last axis: ``m`` bins (default n)
+    at ``start + k*step`` turns (``step`` defaults to 1/m: with ``start = 0`` and ``m = n`` the forward DFT).  float64 /
+    complex128 run in f64, float32 / complex64 in f32; returns a new complex tensor of shape ``x.shape[:-1] + (m,)``."""
+    import torch
+
+    kinds = {torch.float64: (PlannerCzt64, torch.float64), torch.complex128: (PlannerCzt64, torch.float64),
+             torch.float32: (PlannerCzt32, torch.float32), torch.complex64: (PlannerCzt32, torch.float32)}
+    if not _is_torch(x) or x.device.type != "cuda" or x.dtype not in kinds or x.dim() < 1:
+        raise TypeError("need a float64, float32, complex128 or complex64 device tensor of at least one axis")
+    n = x.shape[-1]
+    m = n if m is None else int(m)
+    if n < 1 or m < 1:
+        raise ValueError("need at least one input point and one output point")
+    step = 1.0 / m if step is None else float(step)
+    cls, real = kinds[x.dtype]
+    planner = cls(n, m, step, start)
+    rows = x.reshape(-1, n)
+    if x.is_complex():
+        x_re, x_im = rows.real.contiguous(), rows.imag.contiguous()
+    else:
+        x_re, x_im = rows.contiguous(), None
+    out = torch.empty((2, rows.shape[0], m), dtype=real, device=x.device)
+    if rows.shape[0]:
+        czt_batched(x_re, x_im, planner, out=(out[0], out[1]))
+        torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+    return torch.complex(out[0], out[1]).reshape(x.shape[:-1] + (m,))
+
+
+def zoom_fft(x, fn, m: int | None = None, fs: float = 2.0, endpoint: bool = False):
+    """``scipy.signal.zoom_fft(x, fn, m, fs=fs, endpoint=endpoint)`` of a real or complex device tensor over its last axis:
+    ``m`` bins (default n) of the band ``fn = [f1, f2]`` (a scalar means ``[0, fn]``) at the sampling rate ``fs``."""
+    if np.ndim(fn) == 0:
+        f1, f2 = 0.0, float(fn)
+    elif np.size(fn) == 2:
+        f1, f2 = (float(v) for v in fn)
+    else:
+        raise ValueError("fn must be a scalar or a pair [f1, f2]")
+    if not _is_torch(x) or x.dim() < 1:
+        raise TypeError("need a device tensor of at least one axis")
+    m = x.shape[-1] if m is None else int(m)
+    if m < 1:
+        raise ValueError("need at least one output point")
+    spans = m - 1 if endpoint else m
+    step = (f2 - f1) / (fs * spans) if spans else 0.0
+    return czt(x, m, step, f1 / fs)
 
 
 # ---------------------------------------------------------------------------------------------

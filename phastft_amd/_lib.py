@@ -74,6 +74,11 @@ phast_planner_conv64_out_len phast_planner_conv32_out_len phast_planner_conv64_b
 phast_planner_conv64_segments phast_planner_conv32_segments phast_planner_conv64_workspace_len phast_planner_conv32_workspace_len
 phast_planner_conv64_workspace_min phast_planner_conv32_workspace_min phast_planner_conv64_time_stages phast_planner_conv32_time_stages
 phast_conv_f64_with_planner phast_conv_f32_with_planner phast_conv_f64_dev phast_conv_f32_dev
+phast_planner_czt64_new phast_planner_czt32_new phast_planner_czt64_free phast_planner_czt32_free
+phast_planner_czt64_describe phast_planner_czt32_describe phast_planner_czt64_device_bytes phast_planner_czt32_device_bytes
+phast_planner_czt64_conv_len phast_planner_czt32_conv_len phast_planner_czt64_workspace_len phast_planner_czt32_workspace_len
+phast_planner_czt64_time_stages phast_planner_czt32_time_stages phast_czt_64 phast_czt_32
+phast_czt_64_with_planner phast_czt_32_with_planner phast_czt_64_dev phast_czt_32_dev
 phast_planner_nd64_new phast_planner_nd32_new phast_planner_nd64_free phast_planner_nd32_free
 phast_planner_nd64_describe phast_planner_nd32_describe phast_planner_nd64_device_bytes phast_planner_nd32_device_bytes
 phast_planner_nd64_workspace_len phast_planner_nd32_workspace_len phast_planner_nd64_time_steps phast_planner_nd32_time_steps
@@ -153,7 +158,8 @@ def lib() -> C.CDLL:
         getattr(l, f"phast_planner_stft{sfx}_envelope_min").restype = C.c_double
         for k in ("out_len", "block", "segments", "workspace_min"):
             getattr(l, f"phast_planner_conv{sfx}_{k}").restype = C.c_size_t
-        for k in ("nd", "r2c_nd", "dct", "stft", "conv"):
+        getattr(l, f"phast_planner_czt{sfx}_conv_len").restype = C.c_size_t
+        for k in ("nd", "r2c_nd", "dct", "stft", "conv", "czt"):
             getattr(l, f"phast_planner_{k}{sfx}_free").restype = None
             getattr(l, f"phast_planner_{k}{sfx}_device_bytes").restype = C.c_size_t
             getattr(l, f"phast_planner_{k}{sfx}_workspace_len").restype = C.c_size_t

@@ -19,6 +19,7 @@
 #include "planner_dct.hpp"
 #include "planner_stft.hpp"
 #include "planner_conv.hpp"
+#include "planner_czt.hpp"
 #include "planner_nd.hpp"
 
 // ================================================================================================
@@ -40,6 +41,8 @@ struct phast_planner_stft64 : StftPlanner<double> {};
 struct phast_planner_stft32 : StftPlanner<float> {};
 struct phast_planner_conv64 : ConvPlanner<double> {};
 struct phast_planner_conv32 : ConvPlanner<float> {};
+struct phast_planner_czt64 : CztPlanner<double> {};
+struct phast_planner_czt32 : CztPlanner<float> {};
 struct phast_planner_nd64 : NdPlanner<double> {};
 struct phast_planner_nd32 : NdPlanner<float> {};
 struct phast_planner_r2c_nd64 : RealNdPlanner<double> {};
@@ -790,6 +793,58 @@ PHAST_STFT_API(32, f32, float)
     } PHAST_CATCH_RC
 PHAST_CONV_API(64, f64, double)
 PHAST_CONV_API(32, f32, float)
+
+// The chirp-Z transform on the unit circle (planner_czt.hpp): the lengths and the two doubles are checked before the device
+// is touched; the one-shot form builds a planner of its own for the call
+#define PHAST_CZT_API(SFX, T)                                                                                           \
+    int phast_planner_czt##SFX##_new(size_t n, size_t m, double step, double start, phast_planner_czt##SFX **out) try { \
+        return czt_planner_new(n, m, step, start, out);                                                                 \
+    } PHAST_CATCH_RC                                                                                                    \
+    void phast_planner_czt##SFX##_free(phast_planner_czt##SFX *p) try { delete p; } PHAST_CATCH_VOID                    \
+    int phast_planner_czt##SFX##_describe(const phast_planner_czt##SFX *p, char *buf, size_t len) try {                 \
+        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
+        std::snprintf(buf, len, "%s", p->describe().c_str());                                                           \
+        return PHAST_OK;                                                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_czt##SFX##_device_bytes(const phast_planner_czt##SFX *p) try {                                 \
+        return p ? p->device_bytes() : 0;                                                                               \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_czt##SFX##_conv_len(const phast_planner_czt##SFX *p) try {                                     \
+        return p ? p->m : 0;                                                                                            \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_czt##SFX##_workspace_len(const phast_planner_czt##SFX *p, size_t batch) try {                  \
+        return p ? p->workspace_len(batch) : 0;                                                                         \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_czt##SFX##_time_stages(const phast_planner_czt##SFX *p, const T *d_in_re, const T *d_in_im,       \
+                                             T *d_out_re, T *d_out_im, size_t batch, T *d_work, size_t work_len,        \
+                                             int reps, float *stage_ms, void *stream) try {                             \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(d_in_re, d_in_im, d_out_re, d_out_im, batch, d_work, work_len, reps, stage_ms,            \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_czt_##SFX(const T *in_re, const T *in_im, size_t n, T *out_re, T *out_im, size_t m, double step,          \
+                        double start) try {                                                                             \
+        if (!in_re || !out_re || !out_im) return PHAST_ERR_INVALID_ARG;                                                 \
+        phast_planner_czt##SFX *p = nullptr;                                                                            \
+        int rc = czt_planner_new(n, m, step, start, &p);                                                                \
+        if (rc) return rc;                                                                                              \
+        std::unique_ptr<phast_planner_czt##SFX> own(p);                                                                 \
+        return p->czt_host(in_re, in_im, n, out_re, out_im, m);                                                         \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_czt_##SFX##_with_planner(const T *in_re, const T *in_im, size_t n, T *out_re, T *out_im, size_t m,        \
+                                       const phast_planner_czt##SFX *p) try {                                           \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->czt_host(in_re, in_im, n, out_re, out_im, m);                                                         \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_czt_##SFX##_dev(const T *d_in_re, const T *d_in_im, size_t in_dist, T *d_out_re, T *d_out_im,             \
+                              size_t out_dist, size_t batch, const phast_planner_czt##SFX *p, T *d_work,                \
+                              size_t work_len, void *stream) try {                                                      \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->czt_dev(d_in_re, d_in_im, p->n, in_dist, d_out_re, d_out_im, p->bins, out_dist, batch, d_work,        \
+                          work_len, static_cast<hipStream_t>(stream));                                                  \
+    } PHAST_CATCH_RC
+PHAST_CZT_API(64, double)
+PHAST_CZT_API(32, float)
 
 // Multi-dimensional transforms (planner_nd.hpp): the shape and the lengths are checked before the device is touched
 #define PHAST_ND_PLANNER_API(NAME, KIND)                                                                                \

@@ -2,8 +2,9 @@
 // Immutable after init: the inner Planner<T>(M) and the device table Bh = FFT_M(b) / M.  What a call mutates is the caller's
 // workspace (_dev calls) or a workspace of the inner planner's pool (its staging buffer: host-slice calls), so graph capture
 // and concurrent streams and threads need nothing beyond what the engine already does.  The convolution core (convolve),
-// the chunk loop (for_each_chunk) and the stage timer (time_stages_of) serve the real planner too (planner_any_real.hpp),
-// which runs its own pad and post sweeps around the core.
+// the chunk loop (for_each_chunk) and the table build live in ConvCore<T>, in terms of (m, log_m, d_bh): with the stage timer
+// (time_stages_of) they serve the real planner too (planner_any_real.hpp), which runs its own pad and post sweeps around the
+// core, and the chirp-Z planner (planner_czt.hpp), which derives from ConvCore with a table and sweeps of its own.
 #pragma once
 
 #include "any_len.hpp"
@@ -42,36 +43,35 @@ template <typename T, typename F> static int time_stages_of(const Planner<T> *pl
     return PHAST_OK;
 }
 
-template <typename T> struct AnyPlanner {
-    size_t n = 0, m = 0;  // N and the convolution length (m == n: a power of two, the pow2 path)
+// What every convolution on the engine shares (AnyPlanner below, CztPlanner in planner_czt.hpp): the inner Planner<T>(M), the
+// device table Bh = FFT_M(b) / M, the engine plan, the convolution core and the chunk loop, all in terms of (m, log_m, d_bh)
+template <typename T> struct ConvCore {
+    size_t m = 0;  // the convolution length, a power of two
     unsigned log_m = 0;
     int device = -1;
-    std::unique_ptr<Planner<T>> inner;  // Planner<T>(M), or Planner<T>(N) for a power of two
-    T *d_bh = nullptr;                  // [2][M]: Bh re plane, im plane (1/M folded in); null for a power of two
+    std::unique_ptr<Planner<T>> inner;  // Planner<T>(M)
+    T *d_bh = nullptr;                  // [2][M]: Bh re plane, im plane (1/M folded in)
 
-    bool pow2() const { return d_bh == nullptr; }
-    ~AnyPlanner() {
+    ~ConvCore() {
         DeviceGuard on(device);
         if (d_bh) hipFree(d_bh);
     }
 
-    int init(size_t num_points) {
-        if (num_points == 0 || num_points > kAnyMaxN) return PHAST_ERR_INVALID_ARG;
-        n = num_points;
-        m = (size_t)any_conv_len(n);
+    // the device and the inner planner of `conv_len` points
+    int init_core(size_t conv_len) {
+        m = conv_len;
         log_m = ilog2(m);
         int rc = ensure_device(&device);
         if (rc) return rc;
         inner.reset(new (std::nothrow) Planner<T>());
         if (!inner) return PHAST_ERR_ALLOC;
-        rc = inner->init(m);
-        if (rc || is_pow2(n)) return rc;
-        return make_table();
+        return inner->init(m);
     }
 
-    // b in f64 on the device, FFT_M in an f64 engine with 1/M on its last store (an exact power of two); the f32 planner rounds
-    // the result, so its table carries no f32 transform error.  Synchronised on a stream of its own before init returns.
-    int make_table() {
+    // fill(re, im, stream) writes b as f64 planes [M] on the device; FFT_M in an f64 engine with 1/M on its last store (an exact
+    // power of two); the f32 planner rounds the result, so its table carries no f32 transform error.  Synchronised on a stream
+    // of its own before it returns.
+    template <typename F> int make_table(F &&fill) {
         PHAST_ON_DEVICE(device);
         hipStream_t s = nullptr;
         PHAST_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -93,19 +93,12 @@ template <typename T> struct AnyPlanner {
             br = reinterpret_cast<double *>(b64.p);
         }
         double *bi = br + m;
-        PHAST_HIP(launch_any_chirp_b(br, bi, n, log_m, s));
+        PHAST_HIP(fill(br, bi, s));
         rc = eng->exec(br, bi, m, 0, br, bi, m, 0, 1, 1.0 / (double)m, s);
         if (rc) return rc;
         if constexpr (sizeof(T) == 4) PHAST_HIP(launch_any_round(br, reinterpret_cast<float *>(d_bh), 2 * m, s));
         PHAST_HIP(hipStreamSynchronize(s));
         return PHAST_OK;
-    }
-
-    size_t workspace_len(size_t batch) const { return pow2() ? 0 : 2 * m * batch; }
-    size_t device_bytes() const { return (pow2() ? 0 : 2 * m * sizeof(T)) + (inner ? inner->device_bytes() : 0); }
-    std::string describe() const {
-        if (pow2()) return "any N=" + std::to_string(n) + " (power of two): " + inner->describe();
-        return "any N=" + std::to_string(n) + " M=" + std::to_string(m) + " (Bluestein): " + inner->describe();
     }
 
     // The engine runs ONE plan for every batch and chunk size -- the one of a single transform -- so the bits of a
@@ -152,6 +145,35 @@ template <typename T> struct AnyPlanner {
             if (rc) return rc;
         }
         return PHAST_OK;
+    }
+};
+
+template <typename T> struct AnyPlanner : ConvCore<T> {
+    using ConvCore<T>::m;
+    using ConvCore<T>::log_m;
+    using ConvCore<T>::device;
+    using ConvCore<T>::inner;
+    using ConvCore<T>::d_bh;
+    using ConvCore<T>::engine;
+    using ConvCore<T>::convolve;
+    using ConvCore<T>::for_each_chunk;
+    size_t n = 0;  // N; m == n: a power of two, the pow2 path (inner is Planner<T>(N), d_bh null)
+
+    bool pow2() const { return d_bh == nullptr; }
+
+    int init(size_t num_points) {
+        if (num_points == 0 || num_points > kAnyMaxN) return PHAST_ERR_INVALID_ARG;
+        n = num_points;
+        int rc = this->init_core((size_t)any_conv_len(n));
+        if (rc || is_pow2(n)) return rc;
+        return this->make_table([&](double *br, double *bi, hipStream_t s) { return launch_any_chirp_b(br, bi, n, log_m, s); });
+    }
+
+    size_t workspace_len(size_t batch) const { return pow2() ? 0 : 2 * m * batch; }
+    size_t device_bytes() const { return (pow2() ? 0 : 2 * m * sizeof(T)) + (inner ? inner->device_bytes() : 0); }
+    std::string describe() const {
+        if (pow2()) return "any N=" + std::to_string(n) + " (power of two): " + inner->describe();
+        return "any N=" + std::to_string(n) + " M=" + std::to_string(m) + " (Bluestein): " + inner->describe();
     }
 
     // `c` transforms: x planes (re, im) at b * dist -> X planes at b * dist, through the workspace w (2 c M elements).

@@ -188,6 +188,35 @@ extern "C" {
         planner: *const Opaque) -> c_int;
     pub(crate) fn phast_conv_f32_dev(signal: *const f32, out: *mut f32, signal_len: usize, batch: usize, sig_dist: usize,
         out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // the chirp-Z transform on the unit circle (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/czt.rs)
+    pub(crate) fn phast_planner_czt64_new(n: usize, m: usize, step: f64, start: f64, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_czt64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_czt64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_czt64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_czt64_conv_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_czt64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_czt64_time_stages(p: *const Opaque, in_re: *const f64, in_im: *const f64, out_re: *mut f64,
+        out_im: *mut f64, batch: usize, work: *mut f64, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_czt_64(in_re: *const f64, in_im: *const f64, n: usize, out_re: *mut f64, out_im: *mut f64, m: usize,
+        step: f64, start: f64) -> c_int;
+    pub(crate) fn phast_czt_64_with_planner(in_re: *const f64, in_im: *const f64, n: usize, out_re: *mut f64, out_im: *mut f64,
+        m: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_czt_64_dev(in_re: *const f64, in_im: *const f64, in_dist: usize, out_re: *mut f64, out_im: *mut f64,
+        out_dist: usize, batch: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_czt32_new(n: usize, m: usize, step: f64, start: f64, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_czt32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_czt32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_czt32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_czt32_conv_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_czt32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_czt32_time_stages(p: *const Opaque, in_re: *const f32, in_im: *const f32, out_re: *mut f32,
+        out_im: *mut f32, batch: usize, work: *mut f32, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_czt_32(in_re: *const f32, in_im: *const f32, n: usize, out_re: *mut f32, out_im: *mut f32, m: usize,
+        step: f64, start: f64) -> c_int;
+    pub(crate) fn phast_czt_32_with_planner(in_re: *const f32, in_im: *const f32, n: usize, out_re: *mut f32, out_im: *mut f32,
+        m: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_czt_32_dev(in_re: *const f32, in_im: *const f32, in_dist: usize, out_re: *mut f32, out_im: *mut f32,
+        out_dist: usize, batch: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // DCT / DST of types II and III (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/r2r.rs)
     pub(crate) fn phast_planner_dct64_new(n: usize, out: *mut *mut Opaque) -> c_int;
     pub(crate) fn phast_planner_dct32_new(n: usize, out: *mut *mut Opaque) -> c_int;

@@ -58,6 +58,9 @@ pub use planner::{PadMode, PlannerStft32, PlannerStft64};
 // overlap-save convolution and correlation of real signals (an extension beyond PhastFT 0.3.0)
 pub use algorithms::conv::{conv_f32_dev, conv_f32_with_planner, conv_f64_dev, conv_f64_with_planner};
 pub use planner::{ConvMode, PlannerConv32, PlannerConv64};
+// the chirp-Z transform on the unit circle and the zoom FFT (an extension beyond PhastFT 0.3.0)
+pub use algorithms::czt::{czt_32, czt_32_dev, czt_32_with_planner, czt_64, czt_64_dev, czt_64_with_planner};
+pub use planner::{PlannerCzt32, PlannerCzt64};
 // multi-dimensional real transforms (an extension beyond PhastFT 0.3.0)
 pub use algorithms::r2c::{
     c2r_fft_f32_nd, c2r_fft_f32_nd_dev, c2r_fft_f32_nd_with_planner, c2r_fft_f64_nd, c2r_fft_f64_nd_dev,

@@ -376,6 +376,54 @@ impl_planner_conv!(PlannerConv32, f32, phast_planner_conv32_new, phast_planner_c
                    phast_planner_conv32_block, phast_planner_conv32_segments, phast_planner_conv32_workspace_len,
                    phast_planner_conv32_workspace_min);
 
+macro_rules! impl_planner_czt {
+    ($czt:ident, $new:ident, $free:ident, $conv_len:ident, $ws_len:ident) => {
+        /// An extension beyond PhastFT 0.3.0, whose planners give whole spectra: the chirp-Z transform on the unit circle
+        /// (scipy.signal.czt / zoom_fft), `m` bins of `n` points at the frequencies `start + k * step` turns,
+        /// X[k] = sum x[n] exp(-2 pi i n (start + k step)).  Immutable after `new`, like the reference's planners.
+        pub struct $czt {
+            pub(crate) h: *mut Opaque,
+            pub(crate) n: usize,
+            pub(crate) m: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in
+        // device buffers of its own (host-slice calls)
+        unsafe impl Send for $czt {}
+        unsafe impl Sync for $czt {}
+        impl $czt {
+            /// Panics with "invalid argument" unless 1 <= n, 1 <= m, n + m - 1 <= 2^30 and `step` and `start` are finite
+            pub fn new(n: usize, m: usize, step: f64, start: f64) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe { ffi::$new(n, m, step, start, &mut h) });
+                Self { h, n, m }
+            }
+            pub fn input_len(&self) -> usize {
+                self.n
+            }
+            pub fn output_len(&self) -> usize {
+                self.m
+            }
+            /// the convolution length L: the smallest power of two >= n + m - 1, at least 8
+            pub fn conv_len(&self) -> usize {
+                unsafe { ffi::$conv_len(self.h) }
+            }
+            /// elements of the workspace a device call of `batch` transforms works in: 2 L batch
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+        }
+        impl Drop for $czt {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_czt!(PlannerCzt64, phast_planner_czt64_new, phast_planner_czt64_free, phast_planner_czt64_conv_len,
+                  phast_planner_czt64_workspace_len);
+impl_planner_czt!(PlannerCzt32, phast_planner_czt32_new, phast_planner_czt32_free, phast_planner_czt32_conv_len,
+                  phast_planner_czt32_workspace_len);
+
 macro_rules! impl_planner_nd {
     ($nd:ident, $new:ident, $free:ident, $ws_len:ident, $what:literal) => {
         #[doc = concat!("An extension beyond PhastFT 0.3.0, whose planners transform one axis: ", $what, " over every axis of a ",
