@@ -46,6 +46,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import enum
+import functools
 from dataclasses import dataclass
 
 import numpy as np
@@ -108,40 +109,40 @@ class TuneKind(enum.IntEnum):
     C2R = 3
 
 
-def _tune(fn, handle, batch: int, kind: "TuneKind") -> dict:
+def _tune(planner, batch: int, kind: "TuneKind") -> dict:
     rep = _lib.PhastTuneReport()
-    _check(fn(handle, C.c_size_t(batch), C.c_int(int(kind)), C.byref(rep)))
+    _check(planner._fn("tune")(planner._h, batch, int(kind), C.byref(rep)))
     return {"adopted": bool(rep.adopted), "candidates": int(rep.candidates), "us_heuristic": float(rep.us_heuristic),
             "us_best": float(rep.us_best), "seconds": float(rep.seconds), "plan": rep.plan.decode()}
 
 
 def wisdom_count(layer: int = -1) -> int:
     """Entries of a wisdom layer: 0 built-in, 1 PHAST_WISDOM file, 2 imported, 3 measured by this process; -1 all."""
-    return int(_lib.lib().phast_wisdom_count(C.c_int(layer)))
+    return int(_call("phast_wisdom_count", layer))
 
 
 def wisdom_export() -> str:
     """What this process measured, imported or read from PHAST_WISDOM, as text (csrc/wisdom.hpp) -- without the built-in layer."""
     need = C.c_size_t(0)
-    _check(_lib.lib().phast_wisdom_export(None, C.c_size_t(0), C.byref(need)))
+    _check(_call("phast_wisdom_export", None, 0, C.byref(need)))
     buf = C.create_string_buffer(need.value)
-    _check(_lib.lib().phast_wisdom_export(buf, C.c_size_t(need.value), None))
+    _check(_call("phast_wisdom_export", buf, need.value, None))
     return buf.value.decode()
 
 
 def wisdom_import(text: str) -> None:
     """Planners created afterwards start with the plans the text names."""
-    _check(_lib.lib().phast_wisdom_import(text.encode()))
+    _check(_call("phast_wisdom_import", text.encode()))
 
 
 def wisdom_forget() -> None:
-    _lib.lib().phast_wisdom_forget()
+    _call("phast_wisdom_forget")
 
 
 def wisdom_builtin(enable: bool) -> bool:
     """The wisdom compiled into the library (csrc/builtin_wisdom.inc) off / on for planners made afterwards.  Returns what it
     was before (PHAST_BUILTIN_WISDOM=0 starts it off): `was = wisdom_builtin(False) ... wisdom_builtin(was)` puts it back."""
-    return bool(_lib.lib().phast_wisdom_builtin(1 if enable else 0))
+    return bool(_call("phast_wisdom_builtin", 1 if enable else 0))
 
 
 ERR_INVALID_ARG = 16  # PHAST_ERR_INVALID_ARG (include/phastft_hip.h): e.g. a shape the strided kernels do not cover
@@ -173,6 +174,15 @@ def _check(rc: int) -> None:
     raise PhastPanic(rc, msg)
 
 
+def _call(name: str, *args):
+    """The library's function ``name`` on ``args``, converted by the signature _lib took from the header.  An argument ctypes
+    cannot convert (a float or ``None`` where a count belongs) is a :class:`TypeError`, as from the scalar types themselves."""
+    try:
+        return getattr(_lib.lib(), name)(*args)
+    except C.ArgumentError as e:
+        raise TypeError(str(e)) from None
+
+
 @dataclass
 class Options:
     """options.rs:8-43.  CPU threading knobs: carried for source compatibility, ignored on the GPU."""
@@ -183,7 +193,7 @@ class Options:
     @staticmethod
     def guess_options(input_size: int) -> "Options":
         o = _lib.PhastOptions()
-        _check(_lib.lib().phast_options_guess(C.c_size_t(input_size), C.byref(o)))
+        _check(_call("phast_options_guess", input_size, C.byref(o)))
         return Options(bool(o.multithreaded_bit_reversal), int(o.smallest_parallel_chunk_size))
 
     def _c(self) -> _lib.PhastOptions:
@@ -241,15 +251,44 @@ def _same_place(*slices: _Slice) -> bool:
 # ---------------------------------------------------------------------------------------------
 # planners
 # ---------------------------------------------------------------------------------------------
-class _PlannerDit:
+class _Handle:
+    """an object of the library behind an opaque pointer: {_stem}{_prefix}{_sfx}_* of include/phastft_hip.h"""
+    _stem = "phast_planner_"
     _sfx = "64"
     _dtype = np.float64
 
-    def __init__(self, num_points: int, mode: PlannerMode = PlannerMode.Heuristic):
+    def _new(self, *args, ctor: str = "new") -> None:
         self._h = C.c_void_p()
-        l = _lib.lib()
-        _check(getattr(l, f"phast_planner_dit{self._sfx}_with_mode")(C.c_size_t(num_points), C.c_int(int(mode)),
-                                                                     C.byref(self._h)))
+        _check(self._fn(ctor)(*args, C.byref(self._h)))
+
+    def _fn(self, name: str):
+        return functools.partial(_call, f"{self._stem}{self._prefix}{self._sfx}_{name}")
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None and self._h.value and _lib is not None and _lib._lib is not None:
+                getattr(_lib._lib, f"{self._stem}{self._prefix}{self._sfx}_free")(self._h)
+                self._h.value = None
+        except Exception:  # interpreter shutdown: modules may already be gone
+            pass
+
+    def describe(self) -> str:
+        buf = C.create_string_buffer(16384)   # (a planner may carry a dozen wisdom plans besides its static ones)
+        _check(self._fn("describe")(self._h, buf, 16384))
+        return buf.value.decode()
+
+    def device_bytes(self) -> int:
+        return int(self._fn("device_bytes")(self._h))
+
+    def _workspace_len(self, batch: int) -> int:
+        return int(self._fn("workspace_len")(self._h, batch))
+
+
+class _PlannerDit(_Handle):
+    _prefix = "dit"
+
+    def __init__(self, num_points: int, mode: PlannerMode = PlannerMode.Heuristic):
+        self._new(num_points, int(mode), ctor="with_mode")
         self.num_points = num_points
 
     @classmethod
@@ -262,46 +301,30 @@ class _PlannerDit:
         """planner.rs:65"""
         return cls(num_points, mode)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value and _lib is not None and _lib._lib is not None:
-                getattr(_lib._lib, f"phast_planner_dit{self._sfx}_free")(self._h)
-                self._h.value = None
-        except Exception:  # interpreter shutdown: modules may already be gone
-            pass
-
     # ---- MI355X-side extras (no reference counterpart) ----
-    def describe(self) -> str:
-        buf = C.create_string_buffer(16384)   # (a planner may carry a dozen wisdom plans besides its static ones)
-        _check(getattr(_lib.lib(), f"phast_planner_dit{self._sfx}_describe")(self._h, buf, C.c_size_t(16384)))
-        return buf.value.decode()
-
-    def device_bytes(self) -> int:
-        return int(getattr(_lib.lib(), f"phast_planner_dit{self._sfx}_device_bytes")(self._h))
-
     def describe_call(self, batch: int = 1, kind: "TuneKind" = 0) -> str:
         """The plan a call with ``batch`` transforms runs: ``"<which> [rows x cols ...]..."`` (the library's own answer)."""
         buf = C.create_string_buffer(512)
-        _check(getattr(_lib.lib(), f"phast_planner_dit{self._sfx}_describe_call")(self._h, C.c_size_t(batch), C.c_int(int(kind)), buf, C.c_size_t(512)))
+        _check(self._fn("describe_call")(self._h, batch, int(kind), buf, 512))
         return buf.value.decode()
 
     def check_guards(self) -> int:
         """debug: bytes of the scratch's guard bands overwritten since allocation (see :func:`debug_set_guard_bytes`)"""
         bad = C.c_size_t(0)
-        _check(getattr(_lib.lib(), f"phast_planner_dit{self._sfx}_debug_check_guards")(self._h, C.byref(bad)))
+        _check(self._fn("debug_check_guards")(self._h, C.byref(bad)))
         return int(bad.value)
 
     def reserve_batch(self, max_batch: int) -> None:
-        _check(getattr(_lib.lib(), f"phast_planner_dit{self._sfx}_reserve_batch")(self._h, C.c_size_t(max_batch)))
+        _check(self._fn("reserve_batch")(self._h, max_batch))
 
     def release_graph_workspaces(self) -> int:
         """Hand back the workspaces captured graphs worked in (every graph captured on this planner must be gone)."""
-        return int(getattr(_lib.lib(), f"phast_planner_dit{self._sfx}_release_graph_workspaces")(self._h))
+        return int(self._fn("release_graph_workspaces")(self._h))
 
     def tune(self, batch: int = 1, kind: TuneKind = TuneKind.C2C) -> dict:
         """PlannerMode::Tune for ``batch`` transforms per call (covers batches in (2^(b-1), 2^b]) and the call kind
         ``TuneKind.C2C`` / ``C2CInterleaved``: measures on the device, installs the winner, returns the report."""
-        return _tune(getattr(_lib.lib(), f"phast_planner_dit{self._sfx}_tune"), self._h, batch, kind)
+        return _tune(self, batch, kind)
 
     def set_plan(self, log_rows=(), tile_log=12, points_log=4) -> None:
         """Force the pass factorisation (tuning hook); ``()`` restores the heuristic.  ``tile_log`` is
@@ -310,7 +333,7 @@ class _PlannerDit:
         tls = [tile_log] * n if isinstance(tile_log, int) else list(tile_log)
         arr = (C.c_uint * max(1, n))(*log_rows)
         tarr = (C.c_uint * max(1, n))(*tls)
-        _check(getattr(_lib.lib(), f"phast_planner_dit{self._sfx}_set_plan")(self._h, arr, tarr, C.c_size_t(n), C.c_uint(points_log)))
+        _check(self._fn("set_plan")(self._h, arr, tarr, n, points_log))
 
 
     def time_passes(self, reals, imags, n: int, reps: int = 10):
@@ -319,9 +342,7 @@ class _PlannerDit:
         re, im = _Slice(reals, self._dtype, "reals"), _Slice(imags, self._dtype, "imags")
         ms = (C.c_float * 3)()
         npass = C.c_int()
-        _check(getattr(_lib.lib(), f"phast_planner_dit{self._sfx}_time_passes")(
-            self._h, re.ptr, im.ptr, C.c_size_t(re.len // n), C.c_size_t(n), C.c_int(reps), ms, C.byref(npass),
-            _stream()))
+        _check(self._fn("time_passes")(self._h, re.ptr, im.ptr, re.len // n, n, reps, ms, C.byref(npass), _stream()))
         return [float(ms[i]) for i in range(npass.value)]
 
 
@@ -336,13 +357,11 @@ class PlannerDit32(_PlannerDit):
     _dtype = np.float32
 
 
-class _PlannerR2c:
-    _sfx = "64"
-    _dtype = np.float64
+class _PlannerR2c(_Handle):
+    _prefix = "r2c"
 
     def __init__(self, n: int, mode: PlannerMode = PlannerMode.Heuristic):
-        self._h = C.c_void_p()
-        _check(getattr(_lib.lib(), f"phast_planner_r2c{self._sfx}_with_mode")(C.c_size_t(n), C.c_int(int(mode)), C.byref(self._h)))
+        self._new(n, int(mode), ctor="with_mode")
         self.n = n
 
     @classmethod
@@ -358,27 +377,16 @@ class _PlannerR2c:
     def describe_call(self, batch: int = 1, kind: "TuneKind" = 2) -> str:
         """The plan of the inner transform an ``r2c_fft`` / ``c2r_fft`` call with ``batch`` transforms runs."""
         buf = C.create_string_buffer(512)
-        _check(getattr(_lib.lib(), f"phast_planner_r2c{self._sfx}_describe_call")(self._h, C.c_size_t(batch), C.c_int(int(kind)), buf, C.c_size_t(512)))
+        _check(self._fn("describe_call")(self._h, batch, int(kind), buf, 512))
         return buf.value.decode()
 
     def tune(self, batch: int = 1, kind: TuneKind = TuneKind.R2C) -> dict:
         """PlannerMode::Tune for ``batch`` real transforms per call, ``TuneKind.R2C`` or ``TuneKind.C2R``."""
-        return _tune(getattr(_lib.lib(), f"phast_planner_r2c{self._sfx}_tune"), self._h, batch, kind)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value and _lib is not None and _lib._lib is not None:
-                getattr(_lib._lib, f"phast_planner_r2c{self._sfx}_free")(self._h)
-                self._h.value = None
-        except Exception:  # interpreter shutdown: modules may already be gone
-            pass
-
+        return _tune(self, batch, kind)
 
     def describe(self) -> str:
         """Plan of the inner N/2-point complex transform."""
-        buf = C.create_string_buffer(16384)
-        _check(getattr(_lib.lib(), f"phast_planner_r2c{self._sfx}_describe")(self._h, buf, C.c_size_t(16384)))
-        return buf.value.decode()
+        return super().describe()
 
     def set_plan(self, log_rows=(), tile_log=12, points_log=4) -> None:
         """Force the pass factorisation of the inner N/2-point transform (tuning hook, as ``PlannerDit*.set_plan``);
@@ -387,7 +395,7 @@ class _PlannerR2c:
         tls = [tile_log] * n if isinstance(tile_log, int) else list(tile_log)
         arr = (C.c_uint * max(1, n))(*log_rows)
         tarr = (C.c_uint * max(1, n))(*tls)
-        _check(getattr(_lib.lib(), f"phast_planner_r2c{self._sfx}_set_inner_plan")(self._h, arr, tarr, C.c_size_t(n), C.c_uint(points_log)))
+        _check(self._fn("set_inner_plan")(self._h, arr, tarr, n, points_log))
 
     def time_passes(self, input_re, output_re, output_im, reps: int = 10):
         """Average HIP-event duration (ms) of every kernel of one R2C transform of the device tensors: the passes of the
@@ -396,9 +404,8 @@ class _PlannerR2c:
                                                               (output_im, "output_im")))
         ms = (C.c_float * 4)()
         npass = C.c_int()
-        _check(getattr(_lib.lib(), f"phast_planner_r2c{self._sfx}_time_passes")(
-            self._h, i.ptr, ore.ptr, oim.ptr, C.c_size_t(1), C.c_size_t(self.n), C.c_size_t(self.n // 2 + 1),
-            C.c_int(reps), ms, C.byref(npass), _stream()))
+        _check(self._fn("time_passes")(self._h, i.ptr, ore.ptr, oim.ptr, 1, self.n, self.n // 2 + 1, reps, ms,
+                                       C.byref(npass), _stream()))
         return [float(ms[k]) for k in range(npass.value)]
 
 
@@ -408,9 +415,8 @@ class _PlannerR2c:
         ire, iim, out = (_Slice(x, self._dtype, w) for x, w in ((input_re, "input_re"), (input_im, "input_im"), (output, "output")))
         ms = (C.c_float * 4)()
         npass = C.c_int()
-        _check(getattr(_lib.lib(), f"phast_planner_r2c{self._sfx}_time_c2r_passes")(
-            self._h, ire.ptr, iim.ptr, out.ptr, C.c_size_t(1), C.c_size_t(self.n // 2 + 1), C.c_size_t(self.n),
-            C.c_int(reps), ms, C.byref(npass), _stream()))
+        _check(self._fn("time_c2r_passes")(self._h, ire.ptr, iim.ptr, out.ptr, 1, self.n // 2 + 1, self.n, reps, ms,
+                                           C.byref(npass), _stream()))
         return [float(ms[k]) for k in range(npass.value)]
 
 
@@ -430,8 +436,7 @@ class PlannerR2c32(_PlannerR2c):
 # ---------------------------------------------------------------------------------------------
 def _fft(sfx, dtype, reals, imags, direction, planner=None, opts=None, need_opts=False):
     re, im = _Slice(reals, dtype, "reals"), _Slice(imags, dtype, "imags")
-    l = _lib.lib()
-    direction = C.c_int(int(direction))
+    direction = int(direction)
     if _same_place(re, im):
         # device-resident: the Rust asserts are re-checked here, then the batched _dev entry point is used
         own = planner is None
@@ -439,20 +444,19 @@ def _fft(sfx, dtype, reals, imags, direction, planner=None, opts=None, need_opts
             planner = (PlannerDit64 if sfx == "64" else PlannerDit32)(re.len)  # lib.rs:181: planner from reals.len()
         if re.len != im.len:
             _check(2)
-        _check(getattr(l, f"phast_fft_{sfx}_dit_dev")(re.ptr, im.ptr, C.c_size_t(re.len), C.c_size_t(1),
-                                                      C.c_size_t(re.len), direction, planner._h, _stream()))
+        _check(_call(f"phast_fft_{sfx}_dit_dev", re.ptr, im.ptr, re.len, 1, re.len, direction, planner._h, _stream()))
         if own:
             import torch
 
             torch.cuda.current_stream().synchronize()  # the temporary planner's scratch dies with it
         return
-    args = [re.ptr, C.c_size_t(re.len), im.ptr, C.c_size_t(im.len), direction]
+    args = [re.ptr, re.len, im.ptr, im.len, direction]
     if planner is None:
-        _check(getattr(l, f"phast_fft_{sfx}_dit")(*args))
+        _check(_call(f"phast_fft_{sfx}_dit", *args))
     elif need_opts:
-        _check(getattr(l, f"phast_fft_{sfx}_dit_with_planner_and_opts")(*args, planner._h, C.byref(opts._c())))
+        _check(_call(f"phast_fft_{sfx}_dit_with_planner_and_opts", *args, planner._h, C.byref(opts._c())))
     else:
-        _check(getattr(l, f"phast_fft_{sfx}_dit_with_planner")(*args, planner._h))
+        _check(_call(f"phast_fft_{sfx}_dit_with_planner", *args, planner._h))
 
 
 def fft_64_dit(reals, imags, direction: Direction) -> None:
@@ -489,7 +493,6 @@ def fft_32_dit_with_planner_and_opts(reals, imags, direction: Direction, planner
 # interleaved Complex<T> signals  (lib.rs:41-140, feature `complex-nums`)
 # ---------------------------------------------------------------------------------------------
 def _fft_interleaved(sfx, cdtype, signal, direction, planner=None, opts=None, need_opts=False):
-    l = _lib.lib()
     fdtype = np.float64 if sfx == "64" else np.float32
     if _is_torch(signal):
         import torch
@@ -501,22 +504,20 @@ def _fft_interleaved(sfx, cdtype, signal, direction, planner=None, opts=None, ne
         own = planner is None
         if own:
             planner = (PlannerDit64 if sfx == "64" else PlannerDit32)(n)
-        _check(getattr(l, f"phast_fft_{sfx}_interleaved_dev")(C.c_void_p(signal.data_ptr()), C.c_size_t(n), C.c_size_t(1),
-                                                              C.c_size_t(n), C.c_int(int(direction)), planner._h,
-                                                              _stream()))
+        _check(_call(f"phast_fft_{sfx}_interleaved_dev", signal.data_ptr(), n, 1, n, int(direction), planner._h, _stream()))
         if own:
             torch.cuda.current_stream().synchronize()
         return
     if not (isinstance(signal, np.ndarray) and signal.dtype == cdtype and signal.ndim == 1 and signal.flags.c_contiguous):
         raise TypeError(f"signal: need a contiguous 1-D {np.dtype(cdtype).name} ndarray or a cuda tensor")
     flat = signal.view(fdtype)
-    args = [flat.ctypes.data_as(C.c_void_p), C.c_size_t(signal.size), C.c_int(int(direction))]
+    args = [flat.ctypes.data_as(C.c_void_p), signal.size, int(direction)]
     if planner is None:
-        _check(getattr(l, f"phast_fft_{sfx}_interleaved")(*args))
+        _check(_call(f"phast_fft_{sfx}_interleaved", *args))
     elif need_opts:
-        _check(getattr(l, f"phast_fft_{sfx}_interleaved_with_planner_and_opts")(*args, planner._h, C.byref(opts._c())))
+        _check(_call(f"phast_fft_{sfx}_interleaved_with_planner_and_opts", *args, planner._h, C.byref(opts._c())))
     else:
-        _check(getattr(l, f"phast_fft_{sfx}_interleaved_with_planner")(*args, planner._h))
+        _check(_call(f"phast_fft_{sfx}_interleaved_with_planner", *args, planner._h))
 
 
 def fft_64_interleaved(signal, direction: Direction) -> None:
@@ -562,54 +563,26 @@ def fft_dit_batched(reals, imags, n: int, direction: Direction, planner, dist: i
     if n == 0 or dist < n or re.len < n or (re.len - n) % dist:
         raise ValueError("length must be (batch-1)*dist + n")
     batch = (re.len - n) // dist + 1
-    _check(getattr(_lib.lib(), f"phast_fft_{sfx}_dit_dev")(re.ptr, im.ptr, C.c_size_t(n), C.c_size_t(batch),
-                                                           C.c_size_t(dist), C.c_int(int(direction)), planner._h,
-                                                           _stream()))
+    _check(_call(f"phast_fft_{sfx}_dit_dev", re.ptr, im.ptr, n, batch, dist, int(direction), planner._h, _stream()))
 
 
 
 # ---------------------------------------------------------------------------------------------
 # any length N >= 1 (Bluestein on the power-of-two engine; no reference counterpart -- the reference takes powers of two only)
 # ---------------------------------------------------------------------------------------------
-class _AnyHandle:
+class _AnyHandle(_Handle):
     """the handle of an any-length planner: phast_planner_{_prefix}{_sfx}_*"""
     _prefix = "any"
-    _sfx = "64"
-    _dtype = np.float64
 
     def __init__(self, n: int):
-        self._h = C.c_void_p()
-        _check(self._fn("new")(C.c_size_t(n), C.byref(self._h)))
+        self._new(n)
         self.n = n
-
-    def _fn(self, name: str):
-        return getattr(_lib.lib(), f"phast_planner_{self._prefix}{self._sfx}_{name}")
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value and _lib is not None and _lib._lib is not None:
-                getattr(_lib._lib, f"phast_planner_{self._prefix}{self._sfx}_free")(self._h)
-                self._h.value = None
-        except Exception:  # interpreter shutdown: modules may already be gone
-            pass
-
-    def describe(self) -> str:
-        buf = C.create_string_buffer(16384)
-        _check(self._fn("describe")(self._h, buf, C.c_size_t(16384)))
-        return buf.value.decode()
-
-    def device_bytes(self) -> int:
-        return int(self._fn("device_bytes")(self._h))
-
-    def _workspace_len(self, batch: int) -> int:
-        return int(self._fn("workspace_len")(self._h, C.c_size_t(batch)))
 
     def _time(self, name: str, bufs, counts, batch: int, workspace, reps: int):
         """the five stage times of a *_time_*stages call: (handle, buffers, counts, workspace, reps, ms, stream)"""
         ws = _any_workspace(self, batch, workspace)
         ms = (C.c_float * 5)()
-        _check(self._fn(name)(self._h, *(b.ptr for b in bufs), *(C.c_size_t(c) for c in counts), ws.ptr, C.c_size_t(ws.len),
-                              C.c_int(reps), ms, _stream()))
+        _check(self._fn(name)(self._h, *(b.ptr for b in bufs), *counts, ws.ptr, ws.len, reps, ms, _stream()))
         return [float(x) for x in ms]
 
 
@@ -658,8 +631,7 @@ def _any_workspace(planner, batch: int, workspace=None) -> _Slice:
 
 def _fft_any(sfx, dtype, reals, imags, direction, planner=None):
     re, im = _Slice(reals, dtype, "reals"), _Slice(imags, dtype, "imags")
-    l = _lib.lib()
-    direction = C.c_int(int(direction))
+    direction = int(direction)
     if _same_place(re, im):
         if re.len != im.len:
             _check(2)
@@ -667,18 +639,18 @@ def _fft_any(sfx, dtype, reals, imags, direction, planner=None):
         if own:
             planner = (PlannerAny64 if sfx == "64" else PlannerAny32)(re.len)
         ws = _any_workspace(planner, 1)
-        _check(getattr(l, f"phast_fft_{sfx}_any_dev")(re.ptr, im.ptr, C.c_size_t(re.len), C.c_size_t(1), C.c_size_t(re.len),
-                                                      direction, planner._h, ws.ptr, C.c_size_t(ws.len), _stream()))
+        _check(_call(f"phast_fft_{sfx}_any_dev", re.ptr, im.ptr, re.len, 1, re.len, direction, planner._h, ws.ptr, ws.len,
+                     _stream()))
         if own:
             import torch
 
             torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
         return
-    args = [re.ptr, C.c_size_t(re.len), im.ptr, C.c_size_t(im.len), direction]
+    args = [re.ptr, re.len, im.ptr, im.len, direction]
     if planner is None:
-        _check(getattr(l, f"phast_fft_{sfx}_any")(*args))
+        _check(_call(f"phast_fft_{sfx}_any", *args))
     else:
-        _check(getattr(l, f"phast_fft_{sfx}_any_with_planner")(*args, planner._h))
+        _check(_call(f"phast_fft_{sfx}_any_with_planner", *args, planner._h))
 
 
 def fft_64_any(reals, imags, direction: Direction) -> None:
@@ -714,9 +686,8 @@ def fft_any_batched(reals, imags, n: int, direction: Direction, planner, dist: i
         raise ValueError("length must be (batch-1)*dist + n")
     batch = (re.len - n) // dist + 1
     ws = _any_workspace(planner, batch, workspace)
-    _check(getattr(_lib.lib(), f"phast_fft_{sfx}_any_dev")(re.ptr, im.ptr, C.c_size_t(n), C.c_size_t(batch), C.c_size_t(dist),
-                                                           C.c_int(int(direction)), planner._h, ws.ptr, C.c_size_t(ws.len),
-                                                           _stream()))
+    _check(_call(f"phast_fft_{sfx}_any_dev", re.ptr, im.ptr, n, batch, dist, int(direction), planner._h, ws.ptr, ws.len,
+                 _stream()))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -763,7 +734,7 @@ class PlannerR2cAny32(_PlannerR2cAny):
 def _r2c_any(fs, dtype, input_re, output_re, output_im, planner=None):
     i, ore, oim = _Slice(input_re, dtype, "input_re"), _Slice(output_re, dtype, "output_re"), _Slice(
         output_im, dtype, "output_im")
-    l, sfx = _lib.lib(), fs[1:]
+    sfx = fs[1:]
     if _same_place(i, ore, oim):
         own = planner is None
         if own:
@@ -773,25 +744,23 @@ def _r2c_any(fs, dtype, input_re, output_re, output_im, planner=None):
             if got != want:
                 _check(code)
         ws = _any_workspace(planner, 1)
-        _check(getattr(l, f"phast_r2c_fft_{fs}_any_dev")(i.ptr, ore.ptr, oim.ptr, C.c_size_t(n), C.c_size_t(1), C.c_size_t(n),
-                                                         C.c_size_t(half + 1), planner._h, ws.ptr, C.c_size_t(ws.len),
-                                                         _stream()))
+        _check(_call(f"phast_r2c_fft_{fs}_any_dev", i.ptr, ore.ptr, oim.ptr, n, 1, n, half + 1, planner._h, ws.ptr, ws.len,
+                     _stream()))
         if own:
             import torch
 
             torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
         return
-    args = [i.ptr, C.c_size_t(i.len), ore.ptr, C.c_size_t(ore.len), oim.ptr, C.c_size_t(oim.len)]
+    args = [i.ptr, i.len, ore.ptr, ore.len, oim.ptr, oim.len]
     if planner is None:
-        _check(getattr(l, f"phast_r2c_fft_{fs}_any")(*args))
+        _check(_call(f"phast_r2c_fft_{fs}_any", *args))
     else:
-        _check(getattr(l, f"phast_r2c_fft_{fs}_any_with_planner")(*args, planner._h))
+        _check(_call(f"phast_r2c_fft_{fs}_any_with_planner", *args, planner._h))
 
 
 def _c2r_any(fs, dtype, input_re, input_im, output, planner=None):
     ire, iim, out = _Slice(input_re, dtype, "input_re"), _Slice(input_im, dtype, "input_im"), _Slice(
         output, dtype, "output")
-    l = _lib.lib()
     if _same_place(ire, iim, out):
         own = planner is None
         if own:
@@ -801,19 +770,18 @@ def _c2r_any(fs, dtype, input_re, input_im, output, planner=None):
             if got != want:
                 _check(code)
         ws = _any_workspace(planner, 1)
-        _check(getattr(l, f"phast_c2r_fft_{fs}_any_dev")(ire.ptr, iim.ptr, out.ptr, C.c_size_t(n), C.c_size_t(1),
-                                                         C.c_size_t(half + 1), C.c_size_t(n), planner._h, ws.ptr,
-                                                         C.c_size_t(ws.len), _stream()))
+        _check(_call(f"phast_c2r_fft_{fs}_any_dev", ire.ptr, iim.ptr, out.ptr, n, 1, half + 1, n, planner._h, ws.ptr,
+                     ws.len, _stream()))
         if own:
             import torch
 
             torch.cuda.current_stream().synchronize()
         return
-    args = [ire.ptr, C.c_size_t(ire.len), iim.ptr, C.c_size_t(iim.len), out.ptr, C.c_size_t(out.len)]
+    args = [ire.ptr, ire.len, iim.ptr, iim.len, out.ptr, out.len]
     if planner is None:
-        _check(getattr(l, f"phast_c2r_fft_{fs}_any")(*args))
+        _check(_call(f"phast_c2r_fft_{fs}_any", *args))
     else:
-        _check(getattr(l, f"phast_c2r_fft_{fs}_any_with_planner")(*args, planner._h))
+        _check(_call(f"phast_c2r_fft_{fs}_any_with_planner", *args, planner._h))
 
 
 def r2c_fft_f64_any(input_re, output_re, output_im) -> None:
@@ -875,9 +843,8 @@ def r2c_any_batched(input_re, output_re, output_im, planner, batch: int, in_dist
     _need("output_re", ore.len, batch, out_dist, h1)
     _need("output_im", oim.len, batch, out_dist, h1)
     ws = _any_workspace(planner, batch, workspace)
-    _check(getattr(_lib.lib(), f"phast_r2c_fft_{fs}_any_dev")(i.ptr, ore.ptr, oim.ptr, C.c_size_t(n), C.c_size_t(batch),
-                                                              C.c_size_t(in_dist), C.c_size_t(out_dist), planner._h, ws.ptr,
-                                                              C.c_size_t(ws.len), _stream()))
+    _check(_call(f"phast_r2c_fft_{fs}_any_dev", i.ptr, ore.ptr, oim.ptr, n, batch, in_dist, out_dist, planner._h, ws.ptr,
+                 ws.len, _stream()))
 
 
 def c2r_any_batched(input_re, input_im, output, planner, batch: int, in_dist: int | None = None,
@@ -896,9 +863,8 @@ def c2r_any_batched(input_re, input_im, output, planner, batch: int, in_dist: in
     _need("input_im", iim.len, batch, in_dist, h1)
     _need("output", out.len, batch, out_dist, n)
     ws = _any_workspace(planner, batch, workspace)
-    _check(getattr(_lib.lib(), f"phast_c2r_fft_{fs}_any_dev")(ire.ptr, iim.ptr, out.ptr, C.c_size_t(n), C.c_size_t(batch),
-                                                              C.c_size_t(in_dist), C.c_size_t(out_dist), planner._h, ws.ptr,
-                                                              C.c_size_t(ws.len), _stream()))
+    _check(_call(f"phast_c2r_fft_{fs}_any_dev", ire.ptr, iim.ptr, out.ptr, n, batch, in_dist, out_dist, planner._h, ws.ptr,
+                 ws.len, _stream()))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -930,8 +896,8 @@ class PlannerDct64(_AnyHandle):
         i, o = _Slice(input, self._dtype, "input"), _Slice(output, self._dtype, "output")
         ws = _any_workspace(self, batch, workspace)
         ms = (C.c_float * 3)()
-        _check(self._fn("time_stages")(self._h, C.c_int(kind == "dst"), C.c_int(type), C.c_int(_norm_code(norm)), i.ptr, o.ptr,
-                                       C.c_size_t(batch), ws.ptr, C.c_size_t(ws.len), C.c_int(reps), ms, _stream()))
+        _check(self._fn("time_stages")(self._h, kind == "dst", type, _norm_code(norm), i.ptr, o.ptr, batch, ws.ptr, ws.len,
+                                       reps, ms, _stream()))
         return [float(x) for x in ms]
 
 
@@ -944,7 +910,7 @@ class PlannerDct32(PlannerDct64):
 
 def _r2r(kind, fs, dtype, input, output, type, norm, planner=None):
     i, o = _Slice(input, dtype, "input"), _Slice(output, dtype, "output")
-    l, code = _lib.lib(), _norm_code(norm)
+    code = _norm_code(norm)
     if _same_place(i, o):
         if i.len != o.len:
             _check(2)
@@ -952,19 +918,18 @@ def _r2r(kind, fs, dtype, input, output, type, norm, planner=None):
         if own:
             planner = (PlannerDct64 if fs == "f64" else PlannerDct32)(i.len)
         ws = _any_workspace(planner, 1)
-        _check(getattr(l, f"phast_{kind}_{fs}_dev")(i.ptr, o.ptr, C.c_size_t(i.len), C.c_size_t(1), C.c_size_t(i.len),
-                                                    C.c_size_t(o.len), C.c_int(type), C.c_int(code), planner._h, ws.ptr,
-                                                    C.c_size_t(ws.len), _stream()))
+        _check(_call(f"phast_{kind}_{fs}_dev", i.ptr, o.ptr, i.len, 1, i.len, o.len, type, code, planner._h, ws.ptr, ws.len,
+                     _stream()))
         if own:
             import torch
 
             torch.cuda.current_stream().synchronize()
         return
-    args = [i.ptr, C.c_size_t(i.len), o.ptr, C.c_size_t(o.len), C.c_int(type), C.c_int(code)]
+    args = [i.ptr, i.len, o.ptr, o.len, type, code]
     if planner is None:
-        _check(getattr(l, f"phast_{kind}_{fs}")(*args))
+        _check(_call(f"phast_{kind}_{fs}", *args))
     else:
-        _check(getattr(l, f"phast_{kind}_{fs}_with_planner")(*args, planner._h))
+        _check(_call(f"phast_{kind}_{fs}_with_planner", *args, planner._h))
 
 
 def dct_f64(input, output, type: int = 2, norm=None) -> None:
@@ -1015,9 +980,8 @@ def _r2r_batched(kind, input, output, planner, batch, type, norm, in_dist, out_d
     _need("input", i.len, batch, in_dist, n)
     _need("output", o.len, batch, out_dist, n)
     ws = _any_workspace(planner, batch, workspace)
-    _check(getattr(_lib.lib(), f"phast_{kind}_{fs}_dev")(i.ptr, o.ptr, C.c_size_t(n), C.c_size_t(batch), C.c_size_t(in_dist),
-                                                         C.c_size_t(out_dist), C.c_int(type), C.c_int(_norm_code(norm)),
-                                                         planner._h, ws.ptr, C.c_size_t(ws.len), _stream()))
+    _check(_call(f"phast_{kind}_{fs}_dev", i.ptr, o.ptr, n, batch, in_dist, out_dist, type, _norm_code(norm), planner._h,
+                 ws.ptr, ws.len, _stream()))
 
 
 def dct_batched(input, output, planner, batch: int, type: int = 2, norm=None, in_dist: int | None = None,
@@ -1102,9 +1066,7 @@ class PlannerStft64(_AnyHandle):
                 left = (n_fft - w.size) // 2
                 w = np.concatenate([np.zeros(left, self._dtype), w, np.zeros(n_fft - w.size - left, self._dtype)])
             wp = w.ctypes.data_as(C.c_void_p)
-        self._h = C.c_void_p()
-        _check(self._fn("new")(C.c_size_t(signal_len), C.c_size_t(n_fft), C.c_size_t(hop), wp, C.c_int(bool(center)),
-                               C.c_int(_PADS[pad_mode]), C.byref(self._h)))
+        self._new(signal_len, n_fft, hop, wp, bool(center), _PADS[pad_mode])
         self.n = self.signal_len = signal_len
         self.n_fft, self.hop, self.center, self.pad_mode = n_fft, hop, bool(center), pad_mode
         self.frames = int(self._fn("frames")(self._h))
@@ -1117,7 +1079,7 @@ class PlannerStft64(_AnyHandle):
         return self._workspace_len(batch)
 
     def workspace_min(self, inverse: bool = False) -> int:
-        return int(self._fn("workspace_min")(self._h, C.c_int(bool(inverse))))
+        return int(self._fn("workspace_min")(self._h, bool(inverse)))
 
     def time_stages(self, signal, re, im, inverse: bool = False, batch: int = 1, workspace=None, reps: int = 10):
         """Average HIP-event milliseconds of (the sweep, the real transform) of a forward or inverse call of ``batch``
@@ -1125,8 +1087,8 @@ class PlannerStft64(_AnyHandle):
         x, r, i = (_Slice(t, self._dtype, w) for t, w in ((signal, "signal"), (re, "re"), (im, "im")))
         ws = _any_workspace(self, batch, workspace)
         ms = (C.c_float * 2)()
-        _check(self._fn("time_stages")(self._h, C.c_int(bool(inverse)), x.ptr, r.ptr, i.ptr, C.c_size_t(batch), ws.ptr,
-                                       C.c_size_t(ws.len), C.c_int(reps), ms, _stream()))
+        _check(self._fn("time_stages")(self._h, bool(inverse), x.ptr, r.ptr, i.ptr, batch, ws.ptr, ws.len, reps, ms,
+                                       _stream()))
         return [float(v) for v in ms]
 
 
@@ -1150,8 +1112,7 @@ def _stft_batched(inverse, signal, re, im, planner, batch, sig_dist, workspace):
     _need("im", i.len, batch, pts, pts)
     ws = _any_workspace(planner, batch, workspace)
     args = (r.ptr, i.ptr, x.ptr) if inverse else (x.ptr, r.ptr, i.ptr)
-    _check(getattr(_lib.lib(), f"phast_{name}_{fs}_dev")(*args, C.c_size_t(n), C.c_size_t(batch), C.c_size_t(sig_dist),
-                                                         planner._h, ws.ptr, C.c_size_t(ws.len), _stream()))
+    _check(_call(f"phast_{name}_{fs}_dev", *args, n, batch, sig_dist, planner._h, ws.ptr, ws.len, _stream()))
 
 
 def stft_batched(signal, out_re, out_im, planner, batch: int, sig_dist: int | None = None, workspace=None) -> None:
@@ -1173,8 +1134,7 @@ def _stft_host(name, fs, dtype, a, b, c, planner):
     sl = [_Slice(t, dtype, w) for t, w in zip((a, b, c), ("signal", "re", "im") if name == "stft" else ("re", "im", "signal"))]
     if _same_place(*sl):
         raise TypeError(f"{name}_{fs}_with_planner takes host arrays ({name}_batched takes device tensors)")
-    _check(getattr(_lib.lib(), f"phast_{name}_{fs}_with_planner")(
-        *(v for s in sl for v in (s.ptr, C.c_size_t(s.len))), planner._h))
+    _check(_call(f"phast_{name}_{fs}_with_planner", *(v for s in sl for v in (s.ptr, s.len)), planner._h))
 
 
 def stft_f64_with_planner(signal, out_re, out_im, planner: PlannerStft64) -> None:
@@ -1218,9 +1178,7 @@ class PlannerConv64(_AnyHandle):
         if _is_torch(taps):
             taps = taps.detach().cpu().numpy()
         h = np.ascontiguousarray(taps, dtype=self._dtype).reshape(-1)
-        self._h = C.c_void_p()
-        _check(self._fn("new")(C.c_size_t(signal_len), h.ctypes.data_as(C.c_void_p), C.c_size_t(h.size),
-                               C.c_int(_CONV_MODES[mode]), C.c_int(bool(correlate)), C.c_size_t(block), C.byref(self._h)))
+        self._new(signal_len, h.ctypes.data_as(C.c_void_p), h.size, _CONV_MODES[mode], bool(correlate), block)
         self.n = self.signal_len = signal_len
         self.num_taps, self.mode, self.correlate = h.size, mode, bool(correlate)
         self.out_len = int(self._fn("out_len")(self._h))
@@ -1265,15 +1223,14 @@ def conv_batched(signal, out, planner, batch: int, sig_dist: int | None = None, 
     _need("signal", x.len, batch, sig_dist, n)
     _need("out", y.len, batch, out_dist, m)
     ws = _any_workspace(planner, batch, workspace)
-    _check(getattr(_lib.lib(), f"phast_conv_{fs}_dev")(x.ptr, y.ptr, C.c_size_t(n), C.c_size_t(batch), C.c_size_t(sig_dist),
-                                                       C.c_size_t(out_dist), planner._h, ws.ptr, C.c_size_t(ws.len), _stream()))
+    _check(_call(f"phast_conv_{fs}_dev", x.ptr, y.ptr, n, batch, sig_dist, out_dist, planner._h, ws.ptr, ws.len, _stream()))
 
 
 def _conv_host(fs, dtype, signal, out, planner):
     x, y = _Slice(signal, dtype, "signal"), _Slice(out, dtype, "out")
     if _same_place(x, y):
         raise TypeError(f"conv_{fs}_with_planner takes host arrays (conv_batched takes device tensors)")
-    _check(getattr(_lib.lib(), f"phast_conv_{fs}_with_planner")(x.ptr, C.c_size_t(x.len), y.ptr, C.c_size_t(y.len), planner._h))
+    _check(_call(f"phast_conv_{fs}_with_planner", x.ptr, x.len, y.ptr, y.len, planner._h))
 
 
 def conv_f64_with_planner(signal, out, planner: PlannerConv64) -> None:
@@ -1321,8 +1278,7 @@ class PlannerCzt64(_AnyHandle):
     _prefix = "czt"
 
     def __init__(self, n: int, m: int, step: float, start: float = 0.0):
-        self._h = C.c_void_p()
-        _check(self._fn("new")(C.c_size_t(n), C.c_size_t(m), C.c_double(step), C.c_double(start), C.byref(self._h)))
+        self._new(n, m, step, start)
         self.n, self.m, self.step, self.start = n, m, float(step), float(start)
         self.conv_len = int(self._fn("conv_len")(self._h))
 
@@ -1388,10 +1344,8 @@ def czt_batched(x_re, x_im, planner, out=None, work=None, stream=None):
         if rows != batch or plane(out_im, "out_im", m) != (batch, out_dist) or out_re.dim() != x_re.dim():
             raise ValueError("out: need a pair of (batch, m) tensors with equal strides")
         ws = _any_workspace(planner, batch, work)
-        _check(getattr(_lib.lib(), f"phast_czt_{planner._sfx}_dev")(
-            C.c_void_p(x_re.data_ptr()), None if x_im is None else C.c_void_p(x_im.data_ptr()), C.c_size_t(in_dist),
-            C.c_void_p(out_re.data_ptr()), C.c_void_p(out_im.data_ptr()), C.c_size_t(out_dist), C.c_size_t(batch), planner._h,
-            ws.ptr, C.c_size_t(ws.len), _stream()))
+        _check(_call(f"phast_czt_{planner._sfx}_dev", x_re.data_ptr(), None if x_im is None else x_im.data_ptr(), in_dist,
+                     out_re.data_ptr(), out_im.data_ptr(), out_dist, batch, planner._h, ws.ptr, ws.len, _stream()))
     return out_re, out_im
 
 
@@ -1403,11 +1357,11 @@ def _czt_host(sfx, dtype, in_re, in_im, out_re, out_im, step, start, planner=Non
         raise TypeError(f"czt_{sfx} takes host arrays (czt_batched takes device tensors)")
     if (y is not _NULL and y.len != x.len) or o_re.len != o_im.len:
         _check(2)
-    args = [x.ptr, y.ptr, C.c_size_t(x.len), o_re.ptr, o_im.ptr, C.c_size_t(o_re.len)]
+    args = [x.ptr, y.ptr, x.len, o_re.ptr, o_im.ptr, o_re.len]
     if planner is None:
-        _check(getattr(_lib.lib(), f"phast_czt_{sfx}")(*args, C.c_double(step), C.c_double(start)))
+        _check(_call(f"phast_czt_{sfx}", *args, step, start))
     else:
-        _check(getattr(_lib.lib(), f"phast_czt_{sfx}_with_planner")(*args, planner._h))
+        _check(_call(f"phast_czt_{sfx}_with_planner", *args, planner._h))
 
 
 def czt_64(in_re, in_im, out_re, out_im, step: float, start: float = 0.0) -> None:
@@ -1498,8 +1452,7 @@ class _NdHandle(_AnyHandle):
     def __init__(self, shape):
         self.shape = tuple(int(d) for d in shape)
         dims = (C.c_size_t * max(1, len(self.shape)))(*self.shape)
-        self._h = C.c_void_p()
-        _check(self._fn("new")(dims, C.c_size_t(len(self.shape)), C.byref(self._h)))
+        self._new(dims, len(self.shape))
         self.n = int(np.prod(self.shape, dtype=np.int64))
 
     def workspace_len(self, batch: int = 1) -> int:
@@ -1515,8 +1468,8 @@ class _PlannerNd(_NdHandle):
         re, im = _Slice(_flat(reals), self._dtype, "reals"), _Slice(_flat(imags), self._dtype, "imags")
         ws = _any_workspace(self, batch, workspace)
         ms, ns = (C.c_float * 17)(), C.c_size_t()
-        _check(self._fn("time_steps")(self._h, re.ptr, im.ptr, C.c_size_t(batch), C.c_size_t(self.n if dist is None else dist),
-                                      ws.ptr, C.c_size_t(ws.len), C.c_int(reps), ms, C.byref(ns), _stream()))
+        _check(self._fn("time_steps")(self._h, re.ptr, im.ptr, batch, self.n if dist is None else dist, ws.ptr, ws.len,
+                                      reps, ms, C.byref(ns), _stream()))
         return [float(ms[i]) for i in range(ns.value)]
 
 
@@ -1552,13 +1505,12 @@ class PlannerR2cNd32(_PlannerR2cNd):
 
 def _dims(shape):
     shape = tuple(int(d) for d in shape)
-    return (C.c_size_t * max(1, len(shape)))(*shape), C.c_size_t(len(shape))
+    return (C.c_size_t * max(1, len(shape)))(*shape), len(shape)
 
 
 def _fft_nd(sfx, dtype, reals, imags, shape, direction, planner=None):
     re, im = _Slice(_flat(reals), dtype, "reals"), _Slice(_flat(imags), dtype, "imags")
-    l = _lib.lib()
-    direction = C.c_int(int(direction))
+    direction = int(direction)
     if _same_place(re, im):
         if re.len != im.len:
             _check(2)
@@ -1566,18 +1518,18 @@ def _fft_nd(sfx, dtype, reals, imags, shape, direction, planner=None):
         if own:
             planner = (PlannerNd64 if sfx == "64" else PlannerNd32)(shape)
         ws = _any_workspace(planner, 1)
-        _check(getattr(l, f"phast_fft_{sfx}_nd_dev")(re.ptr, im.ptr, C.c_size_t(re.len), C.c_size_t(1), C.c_size_t(re.len),
-                                                     direction, planner._h, ws.ptr, C.c_size_t(ws.len), _stream()))
+        _check(_call(f"phast_fft_{sfx}_nd_dev", re.ptr, im.ptr, re.len, 1, re.len, direction, planner._h, ws.ptr, ws.len,
+                     _stream()))
         if own:
             import torch
 
             torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
         return
-    args = [re.ptr, C.c_size_t(re.len), im.ptr, C.c_size_t(im.len)]
+    args = [re.ptr, re.len, im.ptr, im.len]
     if planner is None:
-        _check(getattr(l, f"phast_fft_{sfx}_nd")(*args, *_dims(shape), direction))
+        _check(_call(f"phast_fft_{sfx}_nd", *args, *_dims(shape), direction))
     else:
-        _check(getattr(l, f"phast_fft_{sfx}_nd_with_planner")(*args, direction, planner._h))
+        _check(_call(f"phast_fft_{sfx}_nd_with_planner", *args, direction, planner._h))
 
 
 def fft_64_nd(reals, imags, shape, direction: Direction) -> None:
@@ -1612,16 +1564,15 @@ def fft_nd_batched(reals, imags, direction: Direction, planner, batch: int = 1, 
     _need("reals", re.len, batch, dist, n)
     _need("imags", im.len, batch, dist, n)
     ws = _any_workspace(planner, batch, workspace)
-    _check(getattr(_lib.lib(), f"phast_fft_{sfx}_nd_dev")(re.ptr, im.ptr, C.c_size_t(n), C.c_size_t(batch), C.c_size_t(dist),
-                                                          C.c_int(int(direction)), planner._h, ws.ptr, C.c_size_t(ws.len),
-                                                          _stream()))
+    _check(_call(f"phast_fft_{sfx}_nd_dev", re.ptr, im.ptr, n, batch, dist, int(direction), planner._h, ws.ptr, ws.len,
+                 _stream()))
 
 
 def _real_nd(c2r, fs, dtype, a, b, c, shape, planner=None):
     """R2C: (a = the real array; b, c = the planes); C2R: (a, b = the planes; c = the real array)"""
     names = ("input_re", "input_im", "output") if c2r else ("input_re", "output_re", "output_im")
     sa, sb, sc = (_Slice(_flat(x), dtype, w) for x, w in zip((a, b, c), names))
-    l, sfx, kind = _lib.lib(), fs[1:], "c2r" if c2r else "r2c"
+    sfx, kind = fs[1:], "c2r" if c2r else "r2c"
     if _same_place(sa, sb, sc):
         own = planner is None
         if own:
@@ -1632,19 +1583,19 @@ def _real_nd(c2r, fs, dtype, a, b, c, shape, planner=None):
             if got != want:
                 _check(code)
         ws = _any_workspace(planner, 1)
-        dists = (C.c_size_t(h), C.c_size_t(n)) if c2r else (C.c_size_t(n), C.c_size_t(h))
-        _check(getattr(l, f"phast_{kind}_fft_{fs}_nd_dev")(sa.ptr, sb.ptr, sc.ptr, C.c_size_t(n), C.c_size_t(1), *dists,
-                                                          planner._h, ws.ptr, C.c_size_t(ws.len), _stream()))
+        dists = (h, n) if c2r else (n, h)
+        _check(_call(f"phast_{kind}_fft_{fs}_nd_dev", sa.ptr, sb.ptr, sc.ptr, n, 1, *dists, planner._h, ws.ptr, ws.len,
+                     _stream()))
         if own:
             import torch
 
             torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
         return
-    args = [sa.ptr, C.c_size_t(sa.len), sb.ptr, C.c_size_t(sb.len), sc.ptr, C.c_size_t(sc.len)]
+    args = [sa.ptr, sa.len, sb.ptr, sb.len, sc.ptr, sc.len]
     if planner is None:
-        _check(getattr(l, f"phast_{kind}_fft_{fs}_nd")(*args, *_dims(shape)))
+        _check(_call(f"phast_{kind}_fft_{fs}_nd", *args, *_dims(shape)))
     else:
-        _check(getattr(l, f"phast_{kind}_fft_{fs}_nd_with_planner")(*args, planner._h))
+        _check(_call(f"phast_{kind}_fft_{fs}_nd_with_planner", *args, planner._h))
 
 
 def r2c_fft_f64_nd(input_re, output_re, output_im, shape) -> None:
@@ -1703,9 +1654,8 @@ def _real_nd_batched(c2r, a, b, c, planner, batch, in_dist, out_dist, workspace)
         _need("output_re", sb.len, batch, out_dist, h)
         _need("output_im", sc.len, batch, out_dist, h)
     ws = _any_workspace(planner, batch, workspace)
-    _check(getattr(_lib.lib(), f"phast_{kind}_fft_{fs}_nd_dev")(sa.ptr, sb.ptr, sc.ptr, C.c_size_t(n), C.c_size_t(batch),
-                                                               C.c_size_t(in_dist), C.c_size_t(out_dist), planner._h, ws.ptr,
-                                                               C.c_size_t(ws.len), _stream()))
+    _check(_call(f"phast_{kind}_fft_{fs}_nd_dev", sa.ptr, sb.ptr, sc.ptr, n, batch, in_dist, out_dist, planner._h, ws.ptr,
+                 ws.len, _stream()))
 
 
 def r2c_nd_batched(input_re, output_re, output_im, planner, batch: int = 1, in_dist: int | None = None,
@@ -1742,9 +1692,8 @@ class TransformList:
         if first < 0 or k < 0 or first + k > self.count:
             raise ValueError("range outside the list")
         off = first * C.sizeof(C.c_void_p)
-        _check(getattr(_lib.lib(), f"phast_fft_{self.planner._sfx}_dit_many_dev")(
-            C.c_void_p(C.addressof(self._re) + off), C.c_void_p(C.addressof(self._im) + off), C.c_size_t(k),
-            C.c_size_t(self.n), C.c_int(int(direction)), self.planner._h, _stream()))
+        _check(_call(f"phast_fft_{self.planner._sfx}_dit_many_dev", C.addressof(self._re) + off,
+                     C.addressof(self._im) + off, k, self.n, int(direction), self.planner._h, _stream()))
 
 
 def fft_dit_strided(reals, imags, n: int, direction: Direction, planner, batch: int, stride: int,
@@ -1765,13 +1714,11 @@ def fft_dit_strided(reals, imags, n: int, direction: Direction, planner, batch: 
     if re.len < n * stride:
         raise ValueError("the tensors must hold n*stride elements")
     if twiddle_n:
-        _check(getattr(_lib.lib(), f"phast_fft_{sfx}_dit_strided_tw_dev")(
-            re.ptr, im.ptr, C.c_size_t(n), C.c_size_t(batch), C.c_size_t(1), C.c_size_t(stride), C.c_int(int(direction)),
-            planner._h, C.c_size_t(twiddle_n), C.c_size_t(twiddle_col0), _stream()))
+        _check(_call(f"phast_fft_{sfx}_dit_strided_tw_dev", re.ptr, im.ptr, n, batch, 1, stride, int(direction), planner._h,
+                     twiddle_n, twiddle_col0, _stream()))
         return
-    _check(getattr(_lib.lib(), f"phast_fft_{sfx}_dit_strided_dev")(re.ptr, im.ptr, C.c_size_t(n), C.c_size_t(batch),
-                                                                   C.c_size_t(1), C.c_size_t(stride),
-                                                                   C.c_int(int(direction)), planner._h, _stream()))
+    _check(_call(f"phast_fft_{sfx}_dit_strided_dev", re.ptr, im.ptr, n, batch, 1, stride, int(direction), planner._h,
+                 _stream()))
 
 
 def r2c_fft_batched(input_re, output_re, output_im, planner, batch: int) -> None:
@@ -1782,8 +1729,7 @@ def r2c_fft_batched(input_re, output_re, output_im, planner, batch: int) -> None
     n, out = planner.n, planner.n // 2 + 1
     if not _same_place(i, ore, oim) or i.len != batch * n or ore.len != batch * out or oim.len != batch * out:
         raise ValueError("need device tensors of batch*n, batch*(n/2+1), batch*(n/2+1) elements")
-    _check(getattr(_lib.lib(), f"phast_r2c_fft_{fs}_dev")(i.ptr, ore.ptr, oim.ptr, C.c_size_t(batch), C.c_size_t(n),
-                                                          C.c_size_t(out), planner._h, _stream()))
+    _check(_call(f"phast_r2c_fft_{fs}_dev", i.ptr, ore.ptr, oim.ptr, batch, n, out, planner._h, _stream()))
 
 
 def c2r_fft_batched(input_re, input_im, output, planner, batch: int) -> None:
@@ -1794,31 +1740,20 @@ def c2r_fft_batched(input_re, input_im, output, planner, batch: int) -> None:
     n, half1 = planner.n, planner.n // 2 + 1
     if not _same_place(ire, iim, out) or out.len != batch * n or ire.len != batch * half1 or iim.len != batch * half1:
         raise ValueError("need device tensors of batch*(n/2+1), batch*(n/2+1), batch*n elements")
-    _check(getattr(_lib.lib(), f"phast_c2r_fft_{fs}_dev")(ire.ptr, iim.ptr, out.ptr, C.c_size_t(batch), C.c_size_t(half1),
-                                                          C.c_size_t(n), planner._h, _stream()))
+    _check(_call(f"phast_c2r_fft_{fs}_dev", ire.ptr, iim.ptr, out.ptr, batch, half1, n, planner._h, _stream()))
 
 
-class TwiddleGrid64:
+class TwiddleGrid64(_Handle):
     """Device tables of W_N for the inter-factor twiddle of a four-step split (``include/phastft_hip.h``:
     ``phast_twiddle_grid64_*``): ``apply`` multiplies element (r, c) of a row-major device block by
     ``W_N^((row0 + r)*(col0 + c))`` in place.  Used by :mod:`phastft_amd.distributed`."""
 
-    _sfx = "64"
-    _dtype = np.float64
+    _stem = "phast_twiddle_"
+    _prefix = "grid"
 
     def __init__(self, n: int):
-        self._h = C.c_void_p()
-        _check(getattr(_lib.lib(), f"phast_twiddle_grid{self._sfx}_new")(C.c_size_t(n), C.byref(self._h)))
+        self._new(n)
         self.n = n
-
-    def __del__(self):
-        try:
-            h = getattr(self, "_h", None)
-            if h is not None and h.value:
-                getattr(_lib.lib(), f"phast_twiddle_grid{self._sfx}_free")(h)
-                h.value = None
-        except Exception:  # interpreter shutdown: modules may already be gone
-            pass
 
     def apply(self, reals, imags, rows: int, cols: int, row0: int = 0, col0: int = 0, row_pitch: int | None = None):
         re, im = _Slice(reals, self._dtype, "reals"), _Slice(imags, self._dtype, "imags")
@@ -1827,9 +1762,7 @@ class TwiddleGrid64:
         pitch = cols if row_pitch is None else row_pitch
         if re.len != im.len or (rows and re.len < (rows - 1) * pitch + cols):
             raise ValueError("block does not fit the tensors")
-        _check(getattr(_lib.lib(), f"phast_twiddle_grid{self._sfx}_apply_dev")(
-            self._h, re.ptr, im.ptr, C.c_size_t(rows), C.c_size_t(cols), C.c_size_t(pitch), C.c_size_t(row0),
-            C.c_size_t(col0), _stream()))
+        _check(self._fn("apply_dev")(self._h, re.ptr, im.ptr, rows, cols, pitch, row0, col0, _stream()))
 
 
 class TwiddleGrid32(TwiddleGrid64):
@@ -1842,13 +1775,12 @@ class TwiddleGrid32(TwiddleGrid64):
 # ---------------------------------------------------------------------------------------------
 def _bit_rev(fs, dtype, data, n):
     d = _Slice(data, dtype, "data")
-    l = _lib.lib()
     if d.len != (1 << n):
         raise PhastPanic(16, "Data length must be 2^n")  # bravo.rs:228
     if d.dev:
-        _check(getattr(l, f"phast_bit_rev_{fs}_dev")(d.ptr, C.c_uint(n), C.c_size_t(1), C.c_size_t(d.len), _stream()))
+        _check(_call(f"phast_bit_rev_{fs}_dev", d.ptr, n, 1, d.len, _stream()))
     else:
-        _check(getattr(l, f"phast_bit_rev_{fs}")(d.ptr, C.c_size_t(d.len), C.c_uint(n)))
+        _check(_call(f"phast_bit_rev_{fs}", d.ptr, d.len, n))
 
 
 def bit_rev_bravo_f64(data, n: int) -> None:
@@ -1900,9 +1832,9 @@ def deinterleave(data):
     a, b = _like(data, d.len // 2, dtype), _like(data, d.len // 2, dtype)
     sa, sb = _Slice(a, dtype, "out_a"), _Slice(b, dtype, "out_b")
     if d.dev:
-        _check(getattr(_lib.lib(), f"phast_deinterleave_{fs}_dev")(d.ptr, C.c_size_t(d.len), sa.ptr, sb.ptr, _stream()))
+        _check(_call(f"phast_deinterleave_{fs}_dev", d.ptr, d.len, sa.ptr, sb.ptr, _stream()))
     else:
-        _check(getattr(_lib.lib(), f"phast_deinterleave_{fs}")(d.ptr, C.c_size_t(d.len), sa.ptr, C.c_size_t(sa.len), sb.ptr, C.c_size_t(sb.len)))
+        _check(_call(f"phast_deinterleave_{fs}", d.ptr, d.len, sa.ptr, sa.len, sb.ptr, sb.len))
     return a, b
 
 
@@ -1927,9 +1859,9 @@ def combine_re_im(reals, imags):
     out = _like(reals, 2 * r.len, dtype)
     so = _Slice(out, dtype, "out")
     if dev:
-        _check(getattr(_lib.lib(), f"phast_combine_re_im_{fs}_dev")(r.ptr, m.ptr, C.c_size_t(r.len), so.ptr, _stream()))
+        _check(_call(f"phast_combine_re_im_{fs}_dev", r.ptr, m.ptr, r.len, so.ptr, _stream()))
     else:
-        _check(getattr(_lib.lib(), f"phast_combine_re_im_{fs}")(r.ptr, C.c_size_t(r.len), m.ptr, C.c_size_t(m.len), so.ptr, C.c_size_t(so.len)))
+        _check(_call(f"phast_combine_re_im_{fs}", r.ptr, r.len, m.ptr, m.len, so.ptr, so.len))
     if _is_torch(out):
         import torch
 
@@ -1943,7 +1875,6 @@ def combine_re_im(reals, imags):
 def _r2c(fs, dtype, input_re, output_re, output_im, planner=None):
     i, ore, oim = _Slice(input_re, dtype, "input_re"), _Slice(output_re, dtype, "output_re"), _Slice(
         output_im, dtype, "output_im")
-    l = _lib.lib()
     if _same_place(i, ore, oim):
         own = planner is None
         if own:
@@ -1955,18 +1886,17 @@ def _r2c(fs, dtype, input_re, output_re, output_im, planner=None):
             _check(6)
         if oim.len != half + 1:
             _check(7)
-        _check(getattr(l, f"phast_r2c_fft_{fs}_dev")(i.ptr, ore.ptr, oim.ptr, C.c_size_t(1), C.c_size_t(n),
-                                                     C.c_size_t(half + 1), planner._h, _stream()))
+        _check(_call(f"phast_r2c_fft_{fs}_dev", i.ptr, ore.ptr, oim.ptr, 1, n, half + 1, planner._h, _stream()))
         if own:
             import torch
 
             torch.cuda.current_stream().synchronize()
         return
-    args = [i.ptr, C.c_size_t(i.len), ore.ptr, C.c_size_t(ore.len), oim.ptr, C.c_size_t(oim.len)]
+    args = [i.ptr, i.len, ore.ptr, ore.len, oim.ptr, oim.len]
     if planner is None:
-        _check(getattr(l, f"phast_r2c_fft_{fs}")(*args))
+        _check(_call(f"phast_r2c_fft_{fs}", *args))
     else:
-        _check(getattr(l, f"phast_r2c_fft_{fs}_with_planner")(*args, planner._h))
+        _check(_call(f"phast_r2c_fft_{fs}_with_planner", *args, planner._h))
 
 
 def r2c_fft_f64(input_re, output_re, output_im) -> None:
@@ -1992,7 +1922,6 @@ def r2c_fft_f32_with_planner(input_re, output_re, output_im, planner: PlannerR2c
 def _c2r(fs, dtype, input_re, input_im, output, planner=None, scratch=None):
     ire, iim, out = _Slice(input_re, dtype, "input_re"), _Slice(input_im, dtype, "input_im"), _Slice(
         output, dtype, "output")
-    l = _lib.lib()
     sc = None
     if scratch is not None:
         sc = (_Slice(scratch[0], dtype, "scratch_re"), _Slice(scratch[1], dtype, "scratch_im"))
@@ -2011,21 +1940,20 @@ def _c2r(fs, dtype, input_re, input_im, output, planner=None, scratch=None):
             _check(11)
         if sc is not None and sc[1].len != half:
             _check(12)
-        _check(getattr(l, f"phast_c2r_fft_{fs}_dev")(ire.ptr, iim.ptr, out.ptr, C.c_size_t(1), C.c_size_t(half + 1),
-                                                     C.c_size_t(n), planner._h, _stream()))
+        _check(_call(f"phast_c2r_fft_{fs}_dev", ire.ptr, iim.ptr, out.ptr, 1, half + 1, n, planner._h, _stream()))
         if own:
             import torch
 
             torch.cuda.current_stream().synchronize()
         return
-    args = [ire.ptr, C.c_size_t(ire.len), iim.ptr, C.c_size_t(iim.len), out.ptr, C.c_size_t(out.len)]
+    args = [ire.ptr, ire.len, iim.ptr, iim.len, out.ptr, out.len]
     if planner is None:
-        _check(getattr(l, f"phast_c2r_fft_{fs}")(*args))
+        _check(_call(f"phast_c2r_fft_{fs}", *args))
     elif sc is None:
-        _check(getattr(l, f"phast_c2r_fft_{fs}_with_planner")(*args, planner._h))
+        _check(_call(f"phast_c2r_fft_{fs}_with_planner", *args, planner._h))
     else:
-        _check(getattr(l, f"phast_c2r_fft_{fs}_with_planner_and_scratch")(
-            *args, planner._h, sc[0].ptr, C.c_size_t(sc[0].len), sc[1].ptr, C.c_size_t(sc[1].len)))
+        _check(_call(f"phast_c2r_fft_{fs}_with_planner_and_scratch", *args, planner._h, sc[0].ptr, sc[0].len, sc[1].ptr,
+                     sc[1].len))
 
 
 def c2r_fft_f64(input_re, input_im, output) -> None:
@@ -2069,10 +1997,8 @@ def fill_uniform(reals, imags, n: int, seed: int = 0xCAFE, first_id: int = 0) ->
     dtype = np.float64 if reals.dtype == torch.float64 else np.float32
     fs = "f64" if dtype == np.float64 else "f32"
     re = _Slice(reals, dtype, "reals")
-    im_ptr = _Slice(imags, dtype, "imags").ptr if imags is not None else C.c_void_p(0)
-    _check(getattr(_lib.lib(), f"phast_fill_{fs}_dev")(re.ptr, im_ptr, C.c_size_t(n), C.c_size_t(re.len // n),
-                                                       C.c_size_t(n), C.c_ulonglong(seed), C.c_ulonglong(first_id),
-                                                       _stream()))
+    im_ptr = _Slice(imags, dtype, "imags").ptr if imags is not None else None
+    _check(_call(f"phast_fill_{fs}_dev", re.ptr, im_ptr, n, re.len // n, n, seed, first_id, _stream()))
 
 
 def digest(reals, imags, n: int, probe: int = 1):
@@ -2084,9 +2010,7 @@ def digest(reals, imags, n: int, probe: int = 1):
     re, im = _Slice(reals, dtype, "reals"), _Slice(imags, dtype, "imags")
     batch = re.len // n
     out = torch.empty((batch, 4), dtype=torch.float64, device=reals.device)
-    _check(getattr(_lib.lib(), f"phast_digest_{fs}_dev")(re.ptr, im.ptr, C.c_size_t(n), C.c_size_t(batch),
-                                                         C.c_size_t(n), C.c_size_t(probe), C.c_void_p(out.data_ptr()),
-                                                         _stream()))
+    _check(_call(f"phast_digest_{fs}_dev", re.ptr, im.ptr, n, batch, n, probe, out.data_ptr(), _stream()))
     return out
 
 
@@ -2099,15 +2023,14 @@ def stream_probe(mib: int = 1024, reps: int = 5) -> dict:
     a = torch.empty(mib << 17, dtype=torch.float64, device="cuda").fill_(1.0)
     b = torch.empty_like(a)
     out = (C.c_double * 3)()
-    _check(_lib.lib().phast_stream_probe_dev(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_size_t(mib << 20),
-                                             C.c_int(reps), out, _stream()))
+    _check(_call("phast_stream_probe_dev", a.data_ptr(), b.data_ptr(), mib << 20, reps, out, _stream()))
     del a, b
     return {"read": out[0], "write": out[1], "copy": out[2], "unit": "GB/s", "MiB": mib}
 
 
 def debug_set_guard_bytes(nbytes: int) -> None:
     """debug: scratch buffers allocated from now on carry `nbytes` of 0xA5 guard band on either side"""
-    _lib.lib().phast_debug_set_guard_bytes(C.c_size_t(nbytes))
+    _call("phast_debug_set_guard_bytes", nbytes)
 
 
 def graph_upload(graph, stream=None) -> bool:
@@ -2123,13 +2046,13 @@ def graph_upload(graph, stream=None) -> bool:
     import torch
 
     s = stream if stream is not None else torch.cuda.current_stream()
-    _check(_lib.lib().phast_hip_graph_upload(C.c_void_p(int(handle)), C.c_void_p(s.cuda_stream)))
+    _check(_call("phast_hip_graph_upload", int(handle), s.cuda_stream))
     return True
 
 
 def device_info() -> dict:
     name = C.create_string_buffer(256)
     cus, lds, mem = C.c_int(), C.c_size_t(), C.c_size_t()
-    _check(_lib.lib().phast_device_info(name, C.c_size_t(256), C.byref(cus), C.byref(lds), C.byref(mem)))
+    _check(_call("phast_device_info", name, 256, C.byref(cus), C.byref(lds), C.byref(mem)))
     return {"name": name.value.decode(), "compute_units": cus.value, "lds_per_block": lds.value,
             "global_mem_bytes": mem.value}

@@ -500,23 +500,32 @@ PHAST_FFT_API(32, f32, float)
 PHAST_TWIDDLE_API(64, double)
 PHAST_TWIDDLE_API(32, float)
 
+// What every planner behind an opaque handle has in common, whatever it plans: _free, _describe, _device_bytes and
+// _workspace_len of phast_planner_<NAME>.  (The dit and r2c planners differ -- describe_to, twin plans, no workspace length --
+// and spell theirs out above; every family's _new and calls follow below.)
+#define PHAST_HANDLE_API(NAME)                                                                                          \
+    void phast_planner_##NAME##_free(phast_planner_##NAME *p) try { delete p; } PHAST_CATCH_VOID                        \
+    int phast_planner_##NAME##_describe(const phast_planner_##NAME *p, char *buf, size_t len) try {                     \
+        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
+        std::snprintf(buf, len, "%s", p->describe().c_str());                                                           \
+        return PHAST_OK;                                                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_##NAME##_device_bytes(const phast_planner_##NAME *p) try {                                     \
+        return p ? p->device_bytes() : 0;                                                                               \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_##NAME##_workspace_len(const phast_planner_##NAME *p, size_t batch) try {                      \
+        return p ? p->workspace_len(batch) : 0;                                                                         \
+    } PHAST_CATCH_ZERO
+PHAST_HANDLE_API(any64) PHAST_HANDLE_API(any32) PHAST_HANDLE_API(r2c_any64) PHAST_HANDLE_API(r2c_any32)
+PHAST_HANDLE_API(dct64) PHAST_HANDLE_API(dct32) PHAST_HANDLE_API(stft64) PHAST_HANDLE_API(stft32)
+PHAST_HANDLE_API(conv64) PHAST_HANDLE_API(conv32) PHAST_HANDLE_API(czt64) PHAST_HANDLE_API(czt32)
+PHAST_HANDLE_API(nd64) PHAST_HANDLE_API(nd32) PHAST_HANDLE_API(r2c_nd64) PHAST_HANDLE_API(r2c_nd32)
+
 // Arbitrary lengths (Bluestein, planner_any.hpp): arguments are checked before the device is touched
 #define PHAST_ANY_API(SFX, T)                                                                                           \
     int phast_planner_any##SFX##_new(size_t n, phast_planner_any##SFX **out) try {                                      \
         return any_planner_new(n, out);                                                                                 \
     } PHAST_CATCH_RC                                                                                                    \
-    void phast_planner_any##SFX##_free(phast_planner_any##SFX *p) try { delete p; } PHAST_CATCH_VOID                    \
-    int phast_planner_any##SFX##_describe(const phast_planner_any##SFX *p, char *buf, size_t len) try {                 \
-        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
-        std::snprintf(buf, len, "%s", p->describe().c_str());                                                          \
-        return PHAST_OK;                                                                                                \
-    } PHAST_CATCH_RC                                                                                                    \
-    size_t phast_planner_any##SFX##_device_bytes(const phast_planner_any##SFX *p) try {                                 \
-        return p ? p->device_bytes() : 0;                                                                               \
-    } PHAST_CATCH_ZERO                                                                                                  \
-    size_t phast_planner_any##SFX##_workspace_len(const phast_planner_any##SFX *p, size_t batch) try {                  \
-        return p ? p->workspace_len(batch) : 0;                                                                         \
-    } PHAST_CATCH_ZERO                                                                                                  \
     int phast_planner_any##SFX##_time_stages(const phast_planner_any##SFX *p, T *d_re, T *d_im, size_t batch,           \
                                              size_t dist, T *d_work, size_t work_len, int reps, float *stage_ms,        \
                                              void *stream) try {                                                        \
@@ -552,18 +561,6 @@ PHAST_ANY_API(32, float)
     int phast_planner_r2c_any##SFX##_new(size_t n, phast_planner_r2c_any##SFX **out) try {                              \
         return any_planner_new(n, out);                                                                                 \
     } PHAST_CATCH_RC                                                                                                    \
-    void phast_planner_r2c_any##SFX##_free(phast_planner_r2c_any##SFX *p) try { delete p; } PHAST_CATCH_VOID            \
-    int phast_planner_r2c_any##SFX##_describe(const phast_planner_r2c_any##SFX *p, char *buf, size_t len) try {         \
-        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
-        std::snprintf(buf, len, "%s", p->describe().c_str());                                                          \
-        return PHAST_OK;                                                                                                \
-    } PHAST_CATCH_RC                                                                                                    \
-    size_t phast_planner_r2c_any##SFX##_device_bytes(const phast_planner_r2c_any##SFX *p) try {                         \
-        return p ? p->device_bytes() : 0;                                                                               \
-    } PHAST_CATCH_ZERO                                                                                                  \
-    size_t phast_planner_r2c_any##SFX##_workspace_len(const phast_planner_r2c_any##SFX *p, size_t batch) try {          \
-        return p ? p->workspace_len(batch) : 0;                                                                         \
-    } PHAST_CATCH_ZERO                                                                                                  \
     int phast_planner_r2c_any##SFX##_time_stages(const phast_planner_r2c_any##SFX *p, const T *d_in, T *d_out_re,       \
                                                  T *d_out_im, size_t batch, T *d_work, size_t work_len, int reps,       \
                                                  float *stage_ms, void *stream) try {                                   \
@@ -630,18 +627,6 @@ PHAST_ANY_REAL_API(32, f32, float)
     int phast_planner_dct##SFX##_new(size_t n, phast_planner_dct##SFX **out) try {                                      \
         return any_planner_new(n, out);                                                                                 \
     } PHAST_CATCH_RC                                                                                                    \
-    void phast_planner_dct##SFX##_free(phast_planner_dct##SFX *p) try { delete p; } PHAST_CATCH_VOID                    \
-    int phast_planner_dct##SFX##_describe(const phast_planner_dct##SFX *p, char *buf, size_t len) try {                 \
-        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
-        std::snprintf(buf, len, "%s", p->describe().c_str());                                                          \
-        return PHAST_OK;                                                                                                \
-    } PHAST_CATCH_RC                                                                                                    \
-    size_t phast_planner_dct##SFX##_device_bytes(const phast_planner_dct##SFX *p) try {                                 \
-        return p ? p->device_bytes() : 0;                                                                               \
-    } PHAST_CATCH_ZERO                                                                                                  \
-    size_t phast_planner_dct##SFX##_workspace_len(const phast_planner_dct##SFX *p, size_t batch) try {                  \
-        return p ? p->workspace_len(batch) : 0;                                                                         \
-    } PHAST_CATCH_ZERO                                                                                                  \
     int phast_planner_dct##SFX##_time_stages(const phast_planner_dct##SFX *p, int dst, int type, int norm,              \
                                              const T *d_in, T *d_out, size_t batch, T *d_work, size_t work_len,         \
                                              int reps, float *stage_ms, void *stream) try {                             \
@@ -684,23 +669,11 @@ PHAST_DCT_API(32, f32, float)
                                       int pad_mode, phast_planner_stft##SFX **out) try {                                \
         return stft_planner_new<T>(signal_len, n_fft, hop, window, center, pad_mode, out);                              \
     } PHAST_CATCH_RC                                                                                                    \
-    void phast_planner_stft##SFX##_free(phast_planner_stft##SFX *p) try { delete p; } PHAST_CATCH_VOID                  \
-    int phast_planner_stft##SFX##_describe(const phast_planner_stft##SFX *p, char *buf, size_t len) try {               \
-        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
-        std::snprintf(buf, len, "%s", p->describe().c_str());                                                           \
-        return PHAST_OK;                                                                                                \
-    } PHAST_CATCH_RC                                                                                                    \
-    size_t phast_planner_stft##SFX##_device_bytes(const phast_planner_stft##SFX *p) try {                               \
-        return p ? p->device_bytes() : 0;                                                                               \
-    } PHAST_CATCH_ZERO                                                                                                  \
     size_t phast_planner_stft##SFX##_frames(const phast_planner_stft##SFX *p) try {                                     \
         return p ? p->frames : 0;                                                                                       \
     } PHAST_CATCH_ZERO                                                                                                  \
     size_t phast_planner_stft##SFX##_bins(const phast_planner_stft##SFX *p) try {                                       \
         return p ? p->bins : 0;                                                                                         \
-    } PHAST_CATCH_ZERO                                                                                                  \
-    size_t phast_planner_stft##SFX##_workspace_len(const phast_planner_stft##SFX *p, size_t batch) try {                \
-        return p ? p->workspace_len(batch) : 0;                                                                         \
     } PHAST_CATCH_ZERO                                                                                                  \
     size_t phast_planner_stft##SFX##_workspace_min(const phast_planner_stft##SFX *p, int inverse) try {                 \
         return p ? p->workspace_min(inverse != 0) : 0;                                                                  \
@@ -748,15 +721,6 @@ PHAST_STFT_API(32, f32, float)
                                       size_t block, phast_planner_conv##SFX **out) try {                                \
         return conv_planner_new<T>(signal_len, taps, num_taps, mode, flip, block, out);                                 \
     } PHAST_CATCH_RC                                                                                                    \
-    void phast_planner_conv##SFX##_free(phast_planner_conv##SFX *p) try { delete p; } PHAST_CATCH_VOID                  \
-    int phast_planner_conv##SFX##_describe(const phast_planner_conv##SFX *p, char *buf, size_t len) try {               \
-        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
-        std::snprintf(buf, len, "%s", p->describe().c_str());                                                           \
-        return PHAST_OK;                                                                                                \
-    } PHAST_CATCH_RC                                                                                                    \
-    size_t phast_planner_conv##SFX##_device_bytes(const phast_planner_conv##SFX *p) try {                               \
-        return p ? p->device_bytes() : 0;                                                                               \
-    } PHAST_CATCH_ZERO                                                                                                  \
     size_t phast_planner_conv##SFX##_out_len(const phast_planner_conv##SFX *p) try {                                    \
         return p ? p->out_len : 0;                                                                                      \
     } PHAST_CATCH_ZERO                                                                                                  \
@@ -765,9 +729,6 @@ PHAST_STFT_API(32, f32, float)
     } PHAST_CATCH_ZERO                                                                                                  \
     size_t phast_planner_conv##SFX##_segments(const phast_planner_conv##SFX *p) try {                                   \
         return p ? p->segs : 0;                                                                                         \
-    } PHAST_CATCH_ZERO                                                                                                  \
-    size_t phast_planner_conv##SFX##_workspace_len(const phast_planner_conv##SFX *p, size_t batch) try {                \
-        return p ? p->workspace_len(batch) : 0;                                                                         \
     } PHAST_CATCH_ZERO                                                                                                  \
     size_t phast_planner_conv##SFX##_workspace_min(const phast_planner_conv##SFX *p) try {                              \
         return p ? p->workspace_min() : 0;                                                                              \
@@ -800,20 +761,8 @@ PHAST_CONV_API(32, f32, float)
     int phast_planner_czt##SFX##_new(size_t n, size_t m, double step, double start, phast_planner_czt##SFX **out) try { \
         return czt_planner_new(n, m, step, start, out);                                                                 \
     } PHAST_CATCH_RC                                                                                                    \
-    void phast_planner_czt##SFX##_free(phast_planner_czt##SFX *p) try { delete p; } PHAST_CATCH_VOID                    \
-    int phast_planner_czt##SFX##_describe(const phast_planner_czt##SFX *p, char *buf, size_t len) try {                 \
-        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
-        std::snprintf(buf, len, "%s", p->describe().c_str());                                                           \
-        return PHAST_OK;                                                                                                \
-    } PHAST_CATCH_RC                                                                                                    \
-    size_t phast_planner_czt##SFX##_device_bytes(const phast_planner_czt##SFX *p) try {                                 \
-        return p ? p->device_bytes() : 0;                                                                               \
-    } PHAST_CATCH_ZERO                                                                                                  \
     size_t phast_planner_czt##SFX##_conv_len(const phast_planner_czt##SFX *p) try {                                     \
         return p ? p->m : 0;                                                                                            \
-    } PHAST_CATCH_ZERO                                                                                                  \
-    size_t phast_planner_czt##SFX##_workspace_len(const phast_planner_czt##SFX *p, size_t batch) try {                  \
-        return p ? p->workspace_len(batch) : 0;                                                                         \
     } PHAST_CATCH_ZERO                                                                                                  \
     int phast_planner_czt##SFX##_time_stages(const phast_planner_czt##SFX *p, const T *d_in_re, const T *d_in_im,       \
                                              T *d_out_re, T *d_out_im, size_t batch, T *d_work, size_t work_len,        \
@@ -850,19 +799,7 @@ PHAST_CZT_API(32, float)
 #define PHAST_ND_PLANNER_API(NAME, KIND)                                                                                \
     int phast_planner_##NAME##_new(const size_t *dims, size_t rank, phast_planner_##NAME **out) try {                   \
         return nd_planner_new(dims, rank, KIND, out);                                                                   \
-    } PHAST_CATCH_RC                                                                                                    \
-    void phast_planner_##NAME##_free(phast_planner_##NAME *p) try { delete p; } PHAST_CATCH_VOID                        \
-    int phast_planner_##NAME##_describe(const phast_planner_##NAME *p, char *buf, size_t len) try {                     \
-        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
-        std::snprintf(buf, len, "%s", p->describe().c_str());                                                          \
-        return PHAST_OK;                                                                                                \
-    } PHAST_CATCH_RC                                                                                                    \
-    size_t phast_planner_##NAME##_device_bytes(const phast_planner_##NAME *p) try {                                     \
-        return p ? p->device_bytes() : 0;                                                                               \
-    } PHAST_CATCH_ZERO                                                                                                  \
-    size_t phast_planner_##NAME##_workspace_len(const phast_planner_##NAME *p, size_t batch) try {                      \
-        return p ? p->workspace_len(batch) : 0;                                                                         \
-    } PHAST_CATCH_ZERO
+    } PHAST_CATCH_RC
 #define PHAST_ND_TIME_API(SFX, T)                                                                                       \
     int phast_planner_nd##SFX##_time_steps(const phast_planner_nd##SFX *p, T *d_re, T *d_im, size_t batch, size_t dist, \
                                            T *d_work, size_t work_len, int reps, float *step_ms, size_t *n_steps,       \

@@ -28,6 +28,60 @@ def test_header_symbols_exported_and_listed():
     assert sorted(_lib.SYMBOLS) == syms  # the Python loader's list is the header's list
 
 
+def declared_prototypes():
+    """{name: (return type as written, number of parameters)} by a reading of the header that shares nothing with the loader's:
+    the text in front of each name back to the previous `;` or `}`, and the commas up to the closing parenthesis"""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    out = {}
+    for m in re.finditer(r"([^;{}#]*?)\b(phast_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        ret, name, params = m.groups()
+        out[name] = (" ".join(ret.split("\n")[-1].split()), 0 if params.strip() == "void" else params.count(",") + 1)
+    return out
+
+
+def test_every_function_is_bound_with_the_headers_signature():
+    """the loader sets restype and argtypes on every exported function from its prototype in the header: a prototype its parser
+    skipped or misread shows here as a missing or short argtypes, or as the wrong restype"""
+    from phastft_amd import _lib
+
+    lib = _lib.lib()
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols()
+    restypes = {"int": C.c_int, "size_t": C.c_size_t, "double": C.c_double, "void": None, "const char *": C.c_char_p}
+    for name, (ret, nparams) in protos.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == nparams, name
+        assert fn.restype is restypes[ret], (name, ret, fn.restype)
+
+
+def test_bare_python_ints_are_not_truncated_to_32_bits():
+    """no device needed: lengths and counts pass as size_t whatever the caller wraps them in -- a Python int that ctypes took
+    for a C int would lose its high bits without a word"""
+    import phastft_amd as P
+    from phastft_amd import _lib
+
+    lib = _lib.lib()
+    opts = _lib.PhastOptions()
+    assert lib.phast_options_guess(1 << 40, C.byref(opts)) == 0   # truncated: 0 points, PHAST_ERR_NOT_POW2
+    assert opts.multithreaded_bit_reversal
+    h = C.c_void_p()
+    assert lib.phast_planner_any64_new((1 << 40) + 5, C.byref(h)) == 16   # over kAnyMaxN; truncated: 5, a device error
+    assert not h.value
+    total = lib.phast_wisdom_count(-1)
+    assert type(total) is int and total == P.wisdom_count(-1)   # a size_t comes back whole
+
+
+def test_the_header_parser_refuses_what_it_does_not_know():
+    from phastft_amd import _lib
+
+    ok = _lib.parse_prototypes("int phast_x(size_t n, const double *in, phast_planner_dit64 **out);")
+    assert ok == {"phast_x": (C.c_int, [C.c_size_t, C.c_void_p, C.c_void_p])}
+    for bad in ("int phast_x(long n);", "float phast_x(void);", "int phast_x(struct foo *p);", "int phast_x(size_t n) { return 0; }"):
+        with pytest.raises(ValueError) as e:
+            _lib.parse_prototypes(bad)
+        assert "phast_x" in str(e.value), bad   # the message names the prototype
+
+
 def test_header_cites_the_reference():
     text = open(HEADER).read()
     for cite in ("lib.rs:180", "lib.rs:143", "algorithms/dit.rs:263", "planner.rs:55", "planner.rs:194",

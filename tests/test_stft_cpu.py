@@ -273,10 +273,10 @@ def test_argument_codes(lib):
         assert make(100, 16, 4, 2, 0) == INVALID_ARG           # center is 0 or 1
         assert make(100, 16, 4, 1, 2) == INVALID_ARG           # pad_mode is PHAST_PAD_REFLECT or PHAST_PAD_ZERO
         assert make(100, 16, 4, 1, 0, out=False) == INVALID_ARG
-        for name in ("workspace_len", "workspace_min"):
+        for name, one in (("workspace_len", C.c_size_t(1)), ("workspace_min", C.c_int(1))):  # (p, size_t batch), (p, int inverse)
             fn = getattr(lib, f"phast_planner_stft{sfx}_{name}")
             fn.restype = C.c_size_t
-            assert fn(None, C.c_size_t(1)) == 0
+            assert fn(None, one) == 0
         for name in ("device_bytes", "frames", "bins"):
             assert getattr(lib, f"phast_planner_stft{sfx}_{name}")(None) == 0
         assert getattr(lib, f"phast_planner_stft{sfx}_envelope_min")(None) == 0.0
