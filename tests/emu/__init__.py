@@ -3,6 +3,10 @@
 `emu.hip` includes the product's kernel headers (phastft_amd/csrc/tile_fft.hpp, row_fft.hpp, plan.hpp) and runs
 their `__host__ __device__` phase functions thread by thread on the host, so index arithmetic, LDS layouts,
 twiddle tables and plans are checked against the oracle in the GPU-less build container (tests/test_emulator.py).
+
+`sweep_shim.hpp` does the same for the streaming sweep kernels around the engine, whose bodies are plain `__global__`
+functions: it turns a launch into a serial host loop, and `build_sweep_emulator` builds tests/cpp/sweep_emu_test.cpp on it as
+a stand-alone program under ASan and UBSan, linked without the HIP runtime (tests/test_sweep_emulator.py).
 """
 from __future__ import annotations
 
@@ -14,6 +18,17 @@ from phastft_amd import build as _b
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 EMU_LIB = os.path.join(HERE, "libphastft_emu.so")
+
+# The sweep emulator (tests/test_sweep_emulator.py): sweep_shim.hpp turns a launch of a streaming sweep kernel into a serial
+# loop on the host; tests/cpp/sweep_emu_test.cpp #includes the product's .hip files as they stand, one per translation unit.
+SWEEP_SRC = os.path.join(os.path.dirname(HERE), "cpp", "sweep_emu_test.cpp")
+SWEEP_SHIM = os.path.join(HERE, "sweep_shim.hpp")
+SWEEP_EXE = os.path.join(HERE, "build", "sweep_emu_test")
+SWEEP_PARTS = ["main", "any_len", "any_real", "dct", "stft", "conv", "czt", "complex_nums", "r2c"]  # SWEEP_PART = index
+# host code only, under AddressSanitizer and UndefinedBehaviorSanitizer; an uninitialised local is a NaN pattern, not luck
+SWEEP_FLAGS = ["--cuda-host-only", "-x", "hip", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+               "-fno-sanitize-recover=undefined", "-ftrivial-auto-var-init=pattern", "-Wall", "-Wno-unused-function",
+               "-Wno-duplicate-decl-specifier"]
 
 
 def build_emulator(force: bool = False) -> str:
@@ -38,3 +53,44 @@ def build_emulator(force: bool = False) -> str:
         if r.returncode != 0:
             raise RuntimeError(f"link failed for emu:\n{r.stdout}\n{r.stderr}")
     return EMU_LIB
+
+
+def _host_linker() -> str:
+    """clang++ of the ROCm toolchain: the program is linked WITHOUT the HIP runtime, so a call into it would be a link error"""
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(_b.hipcc())))
+    for cand in (os.path.join(rocm, "llvm", "bin", "clang++"), os.path.join(rocm, "lib", "llvm", "bin", "clang++")):
+        if os.path.exists(cand):
+            return cand
+    raise RuntimeError("clang++ of the ROCm toolchain not found next to hipcc")
+
+
+def build_sweep_emulator(force: bool = False, override_dir: str | None = None, parts: tuple = (), out: str | None = None) -> str:
+    """Builds the sweep emulator program and returns its path.  For the checker's self-test: the translation units named in
+    `parts` are compiled with `override_dir` (a mutated copy of a product file) first on the include path, into the directory
+    of `out`; every other object is the regular build's."""
+    exe = out or SWEEP_EXE
+    objdir = os.path.join(HERE, "build")
+    os.makedirs(objdir, exist_ok=True)
+    cpp = os.path.dirname(SWEEP_SRC)
+    hips = [os.path.join(_b.SRC, f) for f in os.listdir(_b.SRC) if f.endswith(".hip")]
+    deps = [SWEEP_SRC, SWEEP_SHIM, os.path.join(cpp, "sanitizer_exit.hpp"), os.path.abspath(__file__)] + hips + _b._deps()
+    inc = ["-I", _b.SRC, "-I", _b.INCLUDE, "-I", HERE, "-I", cpp]
+
+    def part(name: str) -> str:
+        k = SWEEP_PARTS.index(name)
+        mutated = override_dir is not None and name in parts
+        obj = os.path.join(os.path.dirname(exe) if mutated else objdir, f"sweep_part{k}.o")
+        if force or mutated or _b._stale(obj, deps):
+            cmd = [_b.hipcc(), *SWEEP_FLAGS, f"-DSWEEP_PART={k}", *(["-I", override_dir] if mutated else []), *inc, "-c", SWEEP_SRC, "-o", obj]
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError(f"hipcc failed for sweep part {name}:\n{r.stdout}\n{r.stderr}")
+        return obj
+
+    with cf.ThreadPoolExecutor(len(SWEEP_PARTS)) as ex:
+        objs = list(ex.map(part, SWEEP_PARTS))
+    if force or override_dir or _b._stale(exe, objs):
+        r = subprocess.run([_host_linker(), "-fsanitize=address,undefined", *objs, "-o", exe], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"link failed for the sweep emulator:\n{r.stdout}\n{r.stderr}")
+    return exe
