@@ -26,6 +26,8 @@
 //                                                            scipy.signal.convolve / correlate by overlap-save
 //   (none: whole spectra only upstream)                      class PlannerCzt64/32, czt_64/32[_with_planner] -- the chirp-Z transform
 //                                                            on the unit circle (scipy.signal.czt / zoom_fft)
+//   (none: samples on a grid only upstream)                  class PlannerNufft64/32, nufft1_64/32[_with_planner],
+//                                                            nufft2_64/32[_with_planner] -- non-uniform FFTs of types 1 and 2
 //   (none: one axis only upstream)                           class PlannerNd64/32, PlannerR2cNd64/32, fft_64/32_nd[_with_planner],
 //                                                            r2c_fft_f64/f32_nd[...], c2r_fft_f64/f32_nd[...] -- every axis
 //
@@ -609,6 +611,65 @@ PHASTFT_PLANNER_CZT(PlannerCzt32, phast_planner_czt32, 32)
 PHASTFT_CZT(64, double, PlannerCzt64)
 PHASTFT_CZT(32, float, PlannerCzt32)
 #undef PHASTFT_CZT
+
+// ---- non-uniform FFTs of types 1 and 2 in one dimension (no reference counterpart) ----
+#define PHASTFT_PLANNER_NUFFT(NAME, CT, SFX)                                                                     \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* n_modes modes in fftfreq order and the points x (host doubles in turns, reduced mod 1), to the accuracy eps */\
+        NAME(std::size_t n_modes, Slice<const double> x, double eps) : n_(n_modes), m_(x.len) {                  \
+            check(phast_planner_nufft##SFX##_new(n_modes, x.ptr, x.len, eps, &h_));                              \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_), n_(o.n_), m_(o.m_) { o.h_ = nullptr; }                               \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_nufft##SFX##_free(h_);                                                         \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_nufft##SFX##_describe(h_, &s[0], s.size()));                                     \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t num_modes() const { return n_; }                                                             \
+        std::size_t num_points() const { return m_; }                                                            \
+        std::size_t device_bytes() const { return phast_planner_nufft##SFX##_device_bytes(h_); }                 \
+        std::size_t grid_len() const { return phast_planner_nufft##SFX##_grid_len(h_); }                         \
+        int width() const { return phast_planner_nufft##SFX##_width(h_); }                                       \
+        /* elements of T a _dev call of `batch` transforms works in: 2 n_g batch */                              \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_nufft##SFX##_workspace_len(h_, batch); }\
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+        std::size_t n_, m_;                                                                                      \
+    };
+PHASTFT_PLANNER_NUFFT(PlannerNufft64, phast_planner_nufft64, 64)
+PHASTFT_PLANNER_NUFFT(PlannerNufft32, phast_planner_nufft32, 32)
+#undef PHASTFT_PLANNER_NUFFT
+
+// one host vector (in_im.ptr may be null: real data): type 1 takes the values at the points and gives the modes, type 2 the
+// reverse; blocking.  Without a planner the call builds its own from x, eps and the lengths of the slices.
+#define PHASTFT_NUFFT(TYPE, SFX, T, P)                                                                           \
+    inline void nufft##TYPE##_##SFX(Slice<const double> x, Slice<const T> in_re, Slice<const T> in_im, Slice<T> out_re,\
+                                    Slice<T> out_im, double eps, Direction direction = Direction::Forward) {     \
+        if ((in_im.ptr && in_im.len != in_re.len) || out_re.len != out_im.len) check(PHAST_ERR_LEN_MISMATCH);    \
+        if (x.len != (TYPE == 1 ? in_re.len : out_re.len)) check(PHAST_ERR_LEN_MISMATCH);                        \
+        check(phast_nufft##TYPE##_##SFX(x.ptr, x.len, in_re.ptr, in_im.ptr, out_re.ptr, out_im.ptr,              \
+                                        TYPE == 1 ? out_re.len : in_re.len, eps, static_cast<int>(direction)));  \
+    }                                                                                                            \
+    inline void nufft##TYPE##_##SFX##_with_planner(Slice<const T> in_re, Slice<const T> in_im, Slice<T> out_re, Slice<T> out_im,\
+                                                   const P &planner, Direction direction = Direction::Forward) { \
+        if ((in_im.ptr && in_im.len != in_re.len) || out_re.len != out_im.len) check(PHAST_ERR_LEN_MISMATCH);    \
+        check(phast_nufft##TYPE##_##SFX##_with_planner(in_re.ptr, in_im.ptr, in_re.len, out_re.ptr, out_im.ptr, out_re.len,\
+                                                       static_cast<int>(direction), planner.get()));             \
+    }
+PHASTFT_NUFFT(1, 64, double, PlannerNufft64)
+PHASTFT_NUFFT(1, 32, float, PlannerNufft32)
+PHASTFT_NUFFT(2, 64, double, PlannerNufft64)
+PHASTFT_NUFFT(2, 32, float, PlannerNufft32)
+#undef PHASTFT_NUFFT
 
 // ---- transforms over every axis of a row-major array (numpy fftn / rfftn / irfftn; no reference counterpart) ----
 #define PHASTFT_PLANNER_ND(NAME, CT, PFX)                                                                        \

@@ -626,6 +626,76 @@ int phast_czt_32_dev(const float *d_in_re, const float *d_in_im, size_t in_dist,
 int phast_planner_czt32_time_stages(const phast_planner_czt32 *p, const float *d_in_re, const float *d_in_im, float *d_out_re, float *d_out_im, size_t batch,
                                     float *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
 
+/* ---- non-uniform FFTs of types 1 and 2 in one dimension (no reference counterpart).  The planner holds M points
+ * x_j, finite doubles in turns (reduced mod 1; doubles for the f32 planner too), and N modes in numpy fftfreq order: index m holds
+ * the frequency k(m) = m for m < ceil(N / 2) and m - N otherwise.
+ *     type 1 (points -> modes)   F[m] = sum_j c_j exp(-+2 pi i k(m) x_j)
+ *     type 2 (modes -> points)   c_j  = sum_m F[m] exp(-+2 pi i k(m) x_j)
+ * with - for PHAST_FORWARD and + for PHAST_REVERSE, no scaling in either: type 2 Reverse is the adjoint of type 1 Forward, and
+ * x_j = j / N, M = N makes type 1 Forward the DFT.  `eps` asks for that relative accuracy: the spreading kernel is
+ * w = clamp(ceil(log10(1 / eps)) + 1, 2, 16) cells wide on a fine grid of n_g = the smallest power of two >= max(2N, 2w, 8).
+ * 1 <= N <= 2^28, 1 <= M <= 2^30, eps in [1e-14, 1e-1] (f64) or [1e-6, 1e-1] (f32), every x_j finite: anything else is
+ * PHAST_ERR_INVALID_ARG before the device is touched.  `x_turns` is host memory and is sorted by grid cell once, in _new.
+ *
+ * The caller's device workspace holds phast_planner_nufft*_workspace_len(p, batch) = 2 n_g batch elements of T; any work_len >=
+ * 2 n_g runs the batch in chunks, a null or shorter one is PHAST_ERR_INVALID_ARG.  _dev calls: asynchronous on `stream`; `batch`
+ * inputs at in_dist and outputs at out_dist, each at least the row; pointers need element alignment only; the imaginary input
+ * plane may be NULL: real data.  The outputs must not overlap the inputs, the workspace or each other, nor the workspace the
+ * inputs (PHAST_ERR_INVALID_ARG).  The planner is immutable and holds no per-call state; no floating-point atomics are used: the
+ * bits of a transform do not depend on the batch, the chunking, the alignment, the stream or graph replay.  Host-slice calls take
+ * one vector, stage through the device and block (a length that is not the planner's is PHAST_ERR_PLANNER_SIZE);
+ * phast_nufft1_64 / phast_nufft2_64 / _32 build a planner for the one call. */
+typedef struct phast_planner_nufft64 phast_planner_nufft64; /* PlannerNufft64 */
+int phast_planner_nufft64_new(size_t n_modes, const double *x_turns, size_t m_points, double eps, phast_planner_nufft64 **out);
+void phast_planner_nufft64_free(phast_planner_nufft64 *p);
+int phast_planner_nufft64_describe(const phast_planner_nufft64 *p, char *buf, size_t buf_len);
+size_t phast_planner_nufft64_device_bytes(const phast_planner_nufft64 *p);
+size_t phast_planner_nufft64_grid_len(const phast_planner_nufft64 *p);
+int phast_planner_nufft64_width(const phast_planner_nufft64 *p);
+size_t phast_planner_nufft64_workspace_len(const phast_planner_nufft64 *p, size_t batch);
+int phast_nufft1_64(const double *x_turns, size_t m_points, const double *c_re, const double *c_im, double *out_re, double *out_im, size_t n_modes, double eps,
+                    int direction);
+int phast_nufft1_64_with_planner(const double *c_re, const double *c_im, size_t m_points, double *out_re, double *out_im, size_t n_modes, int direction,
+                                 const phast_planner_nufft64 *planner);
+int phast_nufft1_64_dev(const double *d_c_re, const double *d_c_im, size_t in_dist, double *d_out_re, double *d_out_im, size_t out_dist, size_t batch,
+                        int direction, const phast_planner_nufft64 *planner, double *d_work, size_t work_len, void *stream);
+int phast_nufft2_64(const double *x_turns, size_t m_points, const double *f_re, const double *f_im, double *out_re, double *out_im, size_t n_modes, double eps,
+                    int direction);
+int phast_nufft2_64_with_planner(const double *f_re, const double *f_im, size_t n_modes, double *out_re, double *out_im, size_t m_points, int direction,
+                                 const phast_planner_nufft64 *planner);
+int phast_nufft2_64_dev(const double *d_f_re, const double *d_f_im, size_t in_dist, double *d_out_re, double *d_out_im, size_t out_dist, size_t batch,
+                        int direction, const phast_planner_nufft64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/nufft_rate.py): stage_ms[0..2] = average milliseconds of stage a (spread or pre), the n_g-point transform
+ * and stage c (deconvolve or interpolate) over `reps` Forward calls of type `type` (1 or 2) of `batch` transforms at the natural
+ * distances in ONE chunk (work_len >= phast_planner_nufft*_workspace_len(p, batch)); stage_ms[3] and [4] are 0.  Blocks until done. */
+int phast_planner_nufft64_time_stages(const phast_planner_nufft64 *p, const double *d_in_re, const double *d_in_im, double *d_out_re, double *d_out_im, int type,
+                                      size_t batch, double *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_nufft32 phast_planner_nufft32; /* PlannerNufft32 */
+int phast_planner_nufft32_new(size_t n_modes, const double *x_turns, size_t m_points, double eps, phast_planner_nufft32 **out);
+void phast_planner_nufft32_free(phast_planner_nufft32 *p);
+int phast_planner_nufft32_describe(const phast_planner_nufft32 *p, char *buf, size_t buf_len);
+size_t phast_planner_nufft32_device_bytes(const phast_planner_nufft32 *p);
+size_t phast_planner_nufft32_grid_len(const phast_planner_nufft32 *p);
+int phast_planner_nufft32_width(const phast_planner_nufft32 *p);
+size_t phast_planner_nufft32_workspace_len(const phast_planner_nufft32 *p, size_t batch);
+int phast_nufft1_32(const double *x_turns, size_t m_points, const float *c_re, const float *c_im, float *out_re, float *out_im, size_t n_modes, double eps,
+                    int direction);
+int phast_nufft1_32_with_planner(const float *c_re, const float *c_im, size_t m_points, float *out_re, float *out_im, size_t n_modes, int direction,
+                                 const phast_planner_nufft32 *planner);
+int phast_nufft1_32_dev(const float *d_c_re, const float *d_c_im, size_t in_dist, float *d_out_re, float *d_out_im, size_t out_dist, size_t batch,
+                        int direction, const phast_planner_nufft32 *planner, float *d_work, size_t work_len, void *stream);
+int phast_nufft2_32(const double *x_turns, size_t m_points, const float *f_re, const float *f_im, float *out_re, float *out_im, size_t n_modes, double eps,
+                    int direction);
+int phast_nufft2_32_with_planner(const float *f_re, const float *f_im, size_t n_modes, float *out_re, float *out_im, size_t m_points, int direction,
+                                 const phast_planner_nufft32 *planner);
+int phast_nufft2_32_dev(const float *d_f_re, const float *d_f_im, size_t in_dist, float *d_out_re, float *d_out_im, size_t out_dist, size_t batch,
+                        int direction, const phast_planner_nufft32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/nufft_rate.py): stage_ms[0..2] = average milliseconds of stage a (spread or pre), the n_g-point transform
+ * and stage c (deconvolve or interpolate) over `reps` Forward calls of type `type` (1 or 2) of `batch` transforms at the natural
+ * distances in ONE chunk (work_len >= phast_planner_nufft*_workspace_len(p, batch)); stage_ms[3] and [4] are 0.  Blocks until done. */
+int phast_planner_nufft32_time_stages(const phast_planner_nufft32 *p, const float *d_in_re, const float *d_in_im, float *d_out_re, float *d_out_im, int type,
+                                      size_t batch, float *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+
 /* ---- multi-dimensional transforms over every axis of a row-major array (no reference counterpart; numpy fftn / ifftn /
  * rfftn / irfftn with this library's conventions).  dims[0 .. rank-1]: rank 1 .. 8, every axis 1 .. 2^29,
  * their product <= 2^30 (else PHAST_ERR_INVALID_ARG, before the device is touched).  Every axis is transformed; leading

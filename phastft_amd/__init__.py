@@ -27,6 +27,8 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
     (none: no convolution)                          PlannerConv64/32, conv_batched, conv_f64/f32_with_planner,
                                                     fftconvolve, correlate
     (none: whole spectra only)                      PlannerCzt64/32, czt_batched, czt_64/32[_with_planner], czt, zoom_fft
+    (none: samples on a grid only)                  PlannerNufft64/32, nufft1_batched, nufft2_batched,
+                                                    nufft1_64/32[_with_planner], nufft2_64/32[_with_planner], nufft1, nufft2
     (none: one axis only)                           PlannerNd64/32, fft_64/32_nd[_with_planner], fft_nd_batched,
                                                     PlannerR2cNd64/32, r2c_fft_f64/f32_nd[_with_planner],
                                                     c2r_fft_f64/f32_nd[_with_planner], r2c_nd_batched, c2r_nd_batched
@@ -78,6 +80,8 @@ __all__ = [
     "correlate",
     "PlannerCzt64", "PlannerCzt32", "czt_batched", "czt_64", "czt_32", "czt_64_with_planner", "czt_32_with_planner", "czt",
     "zoom_fft",
+    "PlannerNufft64", "PlannerNufft32", "nufft1_batched", "nufft2_batched", "nufft1_64", "nufft1_32", "nufft2_64", "nufft2_32",
+    "nufft1_64_with_planner", "nufft1_32_with_planner", "nufft2_64_with_planner", "nufft2_32_with_planner", "nufft1", "nufft2",
     "PlannerNd64", "PlannerNd32", "fft_64_nd", "fft_32_nd", "fft_64_nd_with_planner", "fft_32_nd_with_planner", "fft_nd_batched",
     "PlannerR2cNd64", "PlannerR2cNd32", "r2c_fft_f64_nd", "r2c_fft_f32_nd", "r2c_fft_f64_nd_with_planner",
     "r2c_fft_f32_nd_with_planner", "c2r_fft_f64_nd", "c2r_fft_f32_nd", "c2r_fft_f64_nd_with_planner",
@@ -1429,6 +1433,201 @@ def zoom_fft(x, fn, m: int | None = None, fs: float = 2.0, endpoint: bool = Fals
     spans = m - 1 if endpoint else m
     step = (f2 - f1) / (fs * spans) if spans else 0.0
     return czt(x, m, step, f1 / fs)
+
+
+# ---------------------------------------------------------------------------------------------
+# non-uniform FFTs of types 1 and 2 in one dimension (no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class PlannerNufft64(_AnyHandle):
+    """f64 non-uniform FFTs of ``points`` (M doubles in turns, any finite value, reduced mod 1) and ``n_modes`` modes in numpy
+    ``fftfreq`` order, ``k = fftfreq(n_modes) * n_modes``, to the relative accuracy ``eps``:
+
+        type 1 (points -> modes)   ``F[m] = sum_j c[j] exp(-+2j pi k[m] x[j])``
+        type 2 (modes -> points)   ``c[j] = sum_m F[m] exp(-+2j pi k[m] x[j])``
+
+    with ``-`` for ``Direction.Forward`` and ``+`` for ``Direction.Reverse`` and no scaling.  1 <= n_modes <= 2^28,
+    1 <= M <= 2^30, eps in [1e-14, 1e-1].  The points are host memory (an array or a sequence) and are sorted once here."""
+
+    _prefix = "nufft"
+    _eps = 1e-12
+
+    def __init__(self, n_modes: int, points, eps: float | None = None):
+        x = np.ascontiguousarray(points.detach().cpu().numpy() if _is_torch(points) else points, dtype=np.float64).reshape(-1)
+        eps = self._eps if eps is None else float(eps)
+        self._new(n_modes, x.ctypes.data_as(C.c_void_p), x.size, eps)
+        self.n = self.n_modes = n_modes
+        self.m = self.m_points = x.size
+        self.eps = eps
+        self.grid_len = int(self._fn("grid_len")(self._h))
+        self.width = int(self._fn("width")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` transforms works in: 2 n_g batch, n_g = ``grid_len``.  A smaller workspace
+        of at least 2 n_g runs the batch in chunks."""
+        return self._workspace_len(batch)
+
+    def time_stages(self, type: int, in_re, in_im, out_re, out_im, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (spread or pre, the n_g-point transform, deconvolve or interpolate) of a Forward
+        call of ``type`` 1 or 2 of ``batch`` transforms at the natural distances on device tensors (measurement hook)"""
+        bufs = [_Slice(in_re, self._dtype, "in_re"), _NULL if in_im is None else _Slice(in_im, self._dtype, "in_im"),
+                _Slice(out_re, self._dtype, "out_re"), _Slice(out_im, self._dtype, "out_im")]
+        return self._time("time_stages", bufs, (type, batch), batch, workspace, reps)[:3]
+
+
+class PlannerNufft32(PlannerNufft64):
+    """f32 twin of :class:`PlannerNufft64`: eps in [1e-6, 1e-1]; the points stay doubles and the table of 1 / phi^ is built in
+    f64 and rounded"""
+
+    _sfx = "32"
+    _dtype = np.float32
+    _eps = 1e-6
+
+
+def _nufft_batched(t, x_re, x_im, planner, direction, out, work, stream):
+    import torch
+
+    want = torch.float64 if planner._dtype == np.float64 else torch.float32
+    n_in, n_out = (planner.m_points, planner.n_modes) if t == 1 else (planner.n_modes, planner.m_points)
+
+    def plane(v, what, per):
+        if not _is_torch(v) or v.device.type != "cuda" or v.dtype != want:
+            raise TypeError(f"{what}: need a {want} device tensor")
+        if v.dim() not in (1, 2) or v.shape[-1] != per or (per > 1 and v.stride(-1) != 1):  # a single element has no stride
+            raise ValueError(f"{what}: need shape (batch, {per}) or ({per},) with a contiguous last axis, not {tuple(v.shape)}")
+        rows = v.shape[0] if v.dim() == 2 else 1
+        dist = v.stride(0) if v.dim() == 2 and rows > 1 else per
+        if dist < per:
+            raise ValueError(f"{what}: rows overlap")
+        return rows, dist
+
+    batch, in_dist = plane(x_re, "x_re", n_in)
+    if x_im is not None and (plane(x_im, "x_im", n_in) != (batch, in_dist) or x_im.shape != x_re.shape):
+        raise ValueError("x_im: need the shape and the strides of x_re")
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        if out is None:
+            shape = (batch, n_out) if x_re.dim() == 2 else (n_out,)
+            out = (torch.empty(shape, dtype=want, device=x_re.device), torch.empty(shape, dtype=want, device=x_re.device))
+        out_re, out_im = out
+        rows, out_dist = plane(out_re, "out_re", n_out)
+        if rows != batch or plane(out_im, "out_im", n_out) != (batch, out_dist) or out_re.dim() != x_re.dim():
+            raise ValueError("out: need a pair of (batch, n_out) tensors with equal strides")
+        ws = _any_workspace(planner, batch, work)
+        _check(_call(f"phast_nufft{t}_{planner._sfx}_dev", x_re.data_ptr(), None if x_im is None else x_im.data_ptr(), in_dist,
+                     out_re.data_ptr(), out_im.data_ptr(), out_dist, batch, int(direction), planner._h, ws.ptr, ws.len,
+                     _stream()))
+    return out_re, out_im
+
+
+def nufft1_batched(c_re, c_im, planner, direction=Direction.Forward, out=None, work=None, stream=None):
+    """Device-resident batch of type 1 transforms (points -> modes) through one planner: ``c_re`` (and ``c_im``, or ``None``
+    for real data) are torch device tensors of shape ``(batch, M)`` or ``(M,)`` of the planner's type whose last axis is
+    contiguous; returns ``(out_re, out_im)`` of shape ``(batch, n_modes)`` or ``(n_modes,)``.  ``out``: such a pair to write
+    into (it must not overlap the input or ``work``); ``work``: a device tensor of at least ``planner.workspace_len(1)``
+    elements (fewer than ``planner.workspace_len(batch)`` runs the batch in chunks), by default one from torch's allocator;
+    ``stream``: a ``torch.cuda.Stream``, by default the current one."""
+    return _nufft_batched(1, c_re, c_im, planner, direction, out, work, stream)
+
+
+def nufft2_batched(f_re, f_im, planner, direction=Direction.Forward, out=None, work=None, stream=None):
+    """Device-resident batch of type 2 transforms (modes -> points): as :func:`nufft1_batched` with inputs of ``n_modes`` and
+    outputs of M values per transform"""
+    return _nufft_batched(2, f_re, f_im, planner, direction, out, work, stream)
+
+
+def _nufft_host(t, sfx, dtype, in_re, in_im, out_re, out_im, direction, planner=None, points=None, eps=None):
+    x = _Slice(in_re, dtype, "in_re")
+    y = _NULL if in_im is None else _Slice(in_im, dtype, "in_im")
+    o_re, o_im = _Slice(out_re, dtype, "out_re"), _Slice(out_im, dtype, "out_im")
+    if _same_place(*(s for s in (x, y, o_re, o_im) if s is not _NULL)):
+        raise TypeError(f"nufft{t}_{sfx} takes host arrays (nufft{t}_batched takes device tensors)")
+    if (y is not _NULL and y.len != x.len) or o_re.len != o_im.len:
+        _check(2)
+    if planner is not None:
+        _check(_call(f"phast_nufft{t}_{sfx}_with_planner", x.ptr, y.ptr, x.len, o_re.ptr, o_im.ptr, o_re.len, int(direction),
+                     planner._h))
+        return
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1)
+    n_modes, m_points = (o_re.len, x.len) if t == 1 else (x.len, o_re.len)
+    if pts.size != m_points:
+        _check(2)
+    _check(_call(f"phast_nufft{t}_{sfx}", pts.ctypes.data_as(C.c_void_p), pts.size, x.ptr, y.ptr, o_re.ptr, o_im.ptr, n_modes,
+                 float(eps), int(direction)))
+
+
+def nufft1_64(points, c_re, c_im, out_re, out_im, eps: float = 1e-12, direction=Direction.Forward) -> None:
+    """f64 type 1 transform of one host vector of M values at ``points`` (``c_im`` may be ``None``: real data) into host arrays
+    of n_modes values, through a planner of its own (blocking)"""
+    _nufft_host(1, "64", np.float64, c_re, c_im, out_re, out_im, direction, points=points, eps=eps)
+
+
+def nufft1_32(points, c_re, c_im, out_re, out_im, eps: float = 1e-6, direction=Direction.Forward) -> None:
+    """f32 twin of :func:`nufft1_64`"""
+    _nufft_host(1, "32", np.float32, c_re, c_im, out_re, out_im, direction, points=points, eps=eps)
+
+
+def nufft2_64(points, f_re, f_im, out_re, out_im, eps: float = 1e-12, direction=Direction.Forward) -> None:
+    """f64 type 2 transform of one host vector of n_modes values into host arrays of M values at ``points`` (blocking)"""
+    _nufft_host(2, "64", np.float64, f_re, f_im, out_re, out_im, direction, points=points, eps=eps)
+
+
+def nufft2_32(points, f_re, f_im, out_re, out_im, eps: float = 1e-6, direction=Direction.Forward) -> None:
+    """f32 twin of :func:`nufft2_64`"""
+    _nufft_host(2, "32", np.float32, f_re, f_im, out_re, out_im, direction, points=points, eps=eps)
+
+
+def nufft1_64_with_planner(c_re, c_im, out_re, out_im, planner: PlannerNufft64, direction=Direction.Forward) -> None:
+    _nufft_host(1, "64", np.float64, c_re, c_im, out_re, out_im, direction, planner)
+
+
+def nufft1_32_with_planner(c_re, c_im, out_re, out_im, planner: PlannerNufft32, direction=Direction.Forward) -> None:
+    _nufft_host(1, "32", np.float32, c_re, c_im, out_re, out_im, direction, planner)
+
+
+def nufft2_64_with_planner(f_re, f_im, out_re, out_im, planner: PlannerNufft64, direction=Direction.Forward) -> None:
+    _nufft_host(2, "64", np.float64, f_re, f_im, out_re, out_im, direction, planner)
+
+
+def nufft2_32_with_planner(f_re, f_im, out_re, out_im, planner: PlannerNufft32, direction=Direction.Forward) -> None:
+    _nufft_host(2, "32", np.float32, f_re, f_im, out_re, out_im, direction, planner)
+
+
+def _nufft(t, points, v, n_modes, eps, direction):
+    import torch
+
+    kinds = {torch.float64: (PlannerNufft64, torch.float64), torch.complex128: (PlannerNufft64, torch.float64),
+             torch.float32: (PlannerNufft32, torch.float32), torch.complex64: (PlannerNufft32, torch.float32)}
+    if not _is_torch(v) or v.device.type != "cuda" or v.dtype not in kinds or v.dim() < 1:
+        raise TypeError("need a float64, float32, complex128 or complex64 device tensor of at least one axis")
+    cls, real = kinds[v.dtype]
+    planner = cls(n_modes, points, eps)
+    n_in, n_out = (planner.m_points, n_modes) if t == 1 else (n_modes, planner.m_points)
+    if v.shape[-1] != n_in:
+        raise ValueError(f"the last axis holds {v.shape[-1]} values, the transform takes {n_in}")
+    rows = v.reshape(-1, n_in)
+    if v.is_complex():
+        x_re, x_im = rows.real.contiguous(), rows.imag.contiguous()
+    else:
+        x_re, x_im = rows.contiguous(), None
+    out = torch.empty((2, rows.shape[0], n_out), dtype=real, device=v.device)
+    if rows.shape[0]:
+        _nufft_batched(t, x_re, x_im, planner, direction, (out[0], out[1]), None, None)
+        torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+    return torch.complex(out[0], out[1]).reshape(v.shape[:-1] + (n_out,))
+
+
+def nufft1(points, c, n_modes: int, eps: float | None = None, direction=Direction.Forward):
+    """Type 1 non-uniform FFT of a real or complex device tensor ``c`` over its last axis (M values at ``points``, in turns)
+    into ``n_modes`` modes in ``fftfreq`` order: a new complex tensor of shape ``c.shape[:-1] + (n_modes,)``.  float64 /
+    complex128 run in f64 (eps defaults to 1e-12), float32 / complex64 in f32 (1e-6)."""
+    return _nufft(1, points, c, int(n_modes), eps, direction)
+
+
+def nufft2(points, F, eps: float | None = None, direction=Direction.Forward):
+    """Type 2 non-uniform FFT of a real or complex device tensor ``F`` of modes over its last axis, evaluated at ``points``
+    (in turns): a new complex tensor of shape ``F.shape[:-1] + (len(points),)``"""
+    if not _is_torch(F) or F.dim() < 1:
+        raise TypeError("need a device tensor of at least one axis")
+    return _nufft(2, points, F, int(F.shape[-1]), eps, direction)
 
 
 # ---------------------------------------------------------------------------------------------

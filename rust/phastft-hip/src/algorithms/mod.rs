@@ -5,6 +5,7 @@ pub mod bravo;
 pub mod conv;
 pub mod czt;
 pub mod dit;
+pub mod nufft;
 pub mod r2c;
 pub mod r2r;
 pub mod stft;

@@ -61,6 +61,12 @@ pub use planner::{ConvMode, PlannerConv32, PlannerConv64};
 // the chirp-Z transform on the unit circle and the zoom FFT (an extension beyond PhastFT 0.3.0)
 pub use algorithms::czt::{czt_32, czt_32_dev, czt_32_with_planner, czt_64, czt_64_dev, czt_64_with_planner};
 pub use planner::{PlannerCzt32, PlannerCzt64};
+// non-uniform FFTs of types 1 and 2 (an extension beyond PhastFT 0.3.0)
+pub use algorithms::nufft::{
+    nufft1_32, nufft1_32_dev, nufft1_32_with_planner, nufft1_64, nufft1_64_dev, nufft1_64_with_planner, nufft2_32, nufft2_32_dev,
+    nufft2_32_with_planner, nufft2_64, nufft2_64_dev, nufft2_64_with_planner,
+};
+pub use planner::{PlannerNufft32, PlannerNufft64};
 // multi-dimensional real transforms (an extension beyond PhastFT 0.3.0)
 pub use algorithms::r2c::{
     c2r_fft_f32_nd, c2r_fft_f32_nd_dev, c2r_fft_f32_nd_with_planner, c2r_fft_f64_nd, c2r_fft_f64_nd_dev,

@@ -424,6 +424,59 @@ impl_planner_czt!(PlannerCzt64, phast_planner_czt64_new, phast_planner_czt64_fre
 impl_planner_czt!(PlannerCzt32, phast_planner_czt32_new, phast_planner_czt32_free, phast_planner_czt32_conv_len,
                   phast_planner_czt32_workspace_len);
 
+macro_rules! impl_planner_nufft {
+    ($nufft:ident, $new:ident, $free:ident, $grid_len:ident, $width:ident, $ws_len:ident) => {
+        /// An extension beyond PhastFT 0.3.0, whose planners take samples on a grid: non-uniform FFTs of types 1 and 2 of the
+        /// points `x` (turns, reduced mod 1) and `n_modes` modes in numpy fftfreq order, to the relative accuracy `eps`.
+        /// Immutable after `new`, like the reference's planners.
+        pub struct $nufft {
+            pub(crate) h: *mut Opaque,
+            pub(crate) n: usize,
+            pub(crate) m: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in
+        // device buffers of its own (host-slice calls)
+        unsafe impl Send for $nufft {}
+        unsafe impl Sync for $nufft {}
+        impl $nufft {
+            /// Panics with "invalid argument" unless 1 <= n_modes <= 2^28, 1 <= x.len() <= 2^30, every x is finite and eps
+            /// lies in [1e-14, 1e-1] (f64) or [1e-6, 1e-1] (f32)
+            pub fn new(n_modes: usize, x: &[f64], eps: f64) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe { ffi::$new(n_modes, x.as_ptr(), x.len(), eps, &mut h) });
+                Self { h, n: n_modes, m: x.len() }
+            }
+            pub fn num_modes(&self) -> usize {
+                self.n
+            }
+            pub fn num_points(&self) -> usize {
+                self.m
+            }
+            /// the fine grid n_g: the smallest power of two >= max(2 n_modes, 2 width, 8)
+            pub fn grid_len(&self) -> usize {
+                unsafe { ffi::$grid_len(self.h) }
+            }
+            /// the width of the spreading kernel in grid cells
+            pub fn width(&self) -> usize {
+                unsafe { ffi::$width(self.h) as usize }
+            }
+            /// elements of the workspace a device call of `batch` transforms works in: 2 n_g batch
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+        }
+        impl Drop for $nufft {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_nufft!(PlannerNufft64, phast_planner_nufft64_new, phast_planner_nufft64_free, phast_planner_nufft64_grid_len,
+                    phast_planner_nufft64_width, phast_planner_nufft64_workspace_len);
+impl_planner_nufft!(PlannerNufft32, phast_planner_nufft32_new, phast_planner_nufft32_free, phast_planner_nufft32_grid_len,
+                    phast_planner_nufft32_width, phast_planner_nufft32_workspace_len);
+
 macro_rules! impl_planner_nd {
     ($nd:ident, $new:ident, $free:ident, $ws_len:ident, $what:literal) => {
         #[doc = concat!("An extension beyond PhastFT 0.3.0, whose planners transform one axis: ", $what, " over every axis of a ",
