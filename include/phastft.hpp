@@ -28,6 +28,8 @@
 //                                                            on the unit circle (scipy.signal.czt / zoom_fft)
 //   (none: samples on a grid only upstream)                  class PlannerNufft64/32, nufft1_64/32[_with_planner],
 //                                                            nufft2_64/32[_with_planner] -- non-uniform FFTs of types 1 and 2
+//   (none: samples on a grid only upstream)                  class PlannerNufft2d64/32, nufft2d1_64/32[_with_planner],
+//                                                            nufft2d2_64/32[_with_planner] -- the same in two dimensions
 //   (none: one axis only upstream)                           class PlannerNd64/32, PlannerR2cNd64/32, fft_64/32_nd[_with_planner],
 //                                                            r2c_fft_f64/f32_nd[...], c2r_fft_f64/f32_nd[...] -- every axis
 //
@@ -670,6 +672,74 @@ PHASTFT_NUFFT(1, 32, float, PlannerNufft32)
 PHASTFT_NUFFT(2, 64, double, PlannerNufft64)
 PHASTFT_NUFFT(2, 32, float, PlannerNufft32)
 #undef PHASTFT_NUFFT
+
+// ---- non-uniform FFTs of types 1 and 2 in two dimensions (no reference counterpart) ----
+#define PHASTFT_PLANNER_NUFFT2D(NAME, CT, SFX)                                                                   \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* n1 x n2 modes, row-major, each axis in fftfreq order, and the points (x, y) (host doubles in turns, reduced  \
+           mod 1 per coordinate; k1 pairs with x, k2 with y), to the accuracy eps */                             \
+        NAME(std::size_t n1, std::size_t n2, Slice<const double> x, Slice<const double> y, double eps)           \
+            : n1_(n1), n2_(n2), m_(x.len) {                                                                      \
+            if (x.len != y.len) check(PHAST_ERR_LEN_MISMATCH);                                                   \
+            check(phast_planner_nufft2d##SFX##_new(n1, n2, x.ptr, y.ptr, x.len, eps, &h_));                      \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_), n1_(o.n1_), n2_(o.n2_), m_(o.m_) { o.h_ = nullptr; }                 \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_nufft2d##SFX##_free(h_);                                                       \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_nufft2d##SFX##_describe(h_, &s[0], s.size()));                                   \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t num_modes_1() const { return n1_; }                                                          \
+        std::size_t num_modes_2() const { return n2_; }                                                          \
+        std::size_t num_points() const { return m_; }                                                            \
+        std::size_t device_bytes() const { return phast_planner_nufft2d##SFX##_device_bytes(h_); }               \
+        std::size_t grid_len() const { return phast_planner_nufft2d##SFX##_grid_len(h_); }                       \
+        std::size_t grid_rows() const { return phast_planner_nufft2d##SFX##_grid_rows(h_); }                     \
+        std::size_t grid_cols() const { return phast_planner_nufft2d##SFX##_grid_cols(h_); }                     \
+        int width() const { return phast_planner_nufft2d##SFX##_width(h_); }                                     \
+        /* elements of T a _dev call of `batch` transforms works in: 4 G batch, G = grid_len() */                \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_nufft2d##SFX##_workspace_len(h_, batch); }\
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+        std::size_t n1_, n2_, m_;                                                                                \
+    };
+PHASTFT_PLANNER_NUFFT2D(PlannerNufft2d64, phast_planner_nufft2d64, 64)
+PHASTFT_PLANNER_NUFFT2D(PlannerNufft2d32, phast_planner_nufft2d32, 32)
+#undef PHASTFT_PLANNER_NUFFT2D
+
+// one host vector (in_im.ptr may be null: real data): type 1 takes the values at the points and gives the n1 x n2 modes
+// (row-major), type 2 the reverse; blocking.  Without a planner the call builds its own from x, y, (n1, n2) and eps.
+#define PHASTFT_NUFFT2D(TYPE, SFX, T, P)                                                                         \
+    inline void nufft2d##TYPE##_##SFX(Slice<const double> x, Slice<const double> y, Slice<const T> in_re, Slice<const T> in_im,\
+                                      Slice<T> out_re, Slice<T> out_im, std::size_t n1, std::size_t n2, double eps,\
+                                      Direction direction = Direction::Forward) {                                \
+        if ((in_im.ptr && in_im.len != in_re.len) || out_re.len != out_im.len || x.len != y.len) check(PHAST_ERR_LEN_MISMATCH);\
+        if (x.len != (TYPE == 1 ? in_re.len : out_re.len)) check(PHAST_ERR_LEN_MISMATCH);                        \
+        if (n2 == 0 || (TYPE == 1 ? out_re.len : in_re.len) / n2 != n1 || (TYPE == 1 ? out_re.len : in_re.len) % n2)\
+            check(PHAST_ERR_LEN_MISMATCH);                                                                       \
+        check(phast_nufft2d##TYPE##_##SFX(x.ptr, y.ptr, x.len, in_re.ptr, in_im.ptr, out_re.ptr, out_im.ptr, n1, n2, eps,\
+                                          static_cast<int>(direction)));                                         \
+    }                                                                                                            \
+    inline void nufft2d##TYPE##_##SFX##_with_planner(Slice<const T> in_re, Slice<const T> in_im, Slice<T> out_re, Slice<T> out_im,\
+                                                     const P &planner, Direction direction = Direction::Forward) {\
+        if ((in_im.ptr && in_im.len != in_re.len) || out_re.len != out_im.len) check(PHAST_ERR_LEN_MISMATCH);    \
+        check(phast_nufft2d##TYPE##_##SFX##_with_planner(in_re.ptr, in_im.ptr, in_re.len, out_re.ptr, out_im.ptr, out_re.len,\
+                                                         static_cast<int>(direction), planner.get()));           \
+    }
+PHASTFT_NUFFT2D(1, 64, double, PlannerNufft2d64)
+PHASTFT_NUFFT2D(1, 32, float, PlannerNufft2d32)
+PHASTFT_NUFFT2D(2, 64, double, PlannerNufft2d64)
+PHASTFT_NUFFT2D(2, 32, float, PlannerNufft2d32)
+#undef PHASTFT_NUFFT2D
 
 // ---- transforms over every axis of a row-major array (numpy fftn / rfftn / irfftn; no reference counterpart) ----
 #define PHASTFT_PLANNER_ND(NAME, CT, PFX)                                                                        \

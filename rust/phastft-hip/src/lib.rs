@@ -67,6 +67,12 @@ pub use algorithms::nufft::{
     nufft2_32_with_planner, nufft2_64, nufft2_64_dev, nufft2_64_with_planner,
 };
 pub use planner::{PlannerNufft32, PlannerNufft64};
+// the same in two dimensions (an extension beyond PhastFT 0.3.0)
+pub use algorithms::nufft2d::{
+    nufft2d1_32, nufft2d1_32_dev, nufft2d1_32_with_planner, nufft2d1_64, nufft2d1_64_dev, nufft2d1_64_with_planner, nufft2d2_32,
+    nufft2d2_32_dev, nufft2d2_32_with_planner, nufft2d2_64, nufft2d2_64_dev, nufft2d2_64_with_planner,
+};
+pub use planner::{PlannerNufft2d32, PlannerNufft2d64};
 // multi-dimensional real transforms (an extension beyond PhastFT 0.3.0)
 pub use algorithms::r2c::{
     c2r_fft_f32_nd, c2r_fft_f32_nd_dev, c2r_fft_f32_nd_with_planner, c2r_fft_f64_nd, c2r_fft_f64_nd_dev,
