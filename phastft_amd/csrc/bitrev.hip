@@ -244,7 +244,7 @@ __global__ void __launch_bounds__(NTH) bitrev_persistent3_kernel(U *data, unsign
     using V2 = typename Vec2<U>::type;
     constexpr int B = 1 << BETA, PER = B * B / (2 * NTH);  // element PAIRS per thread per tile
     static_assert(PER >= 1, "tile too small for this workgroup");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    PHAST_DYNAMIC_LDS(smem_raw);
     U(*s)[B + 1] = reinterpret_cast<U(*)[B + 1]>(smem_raw);
     const unsigned tile_bits = log_n - 2 * BETA;
     const unsigned ustride_log = log_n - BETA;

@@ -11,6 +11,11 @@
 
 #define PHAST_HD __host__ __device__ __forceinline__
 
+// the dynamic LDS of a kernel, as bytes.  A macro so that the host emulation of the barrier kernels (tests/emu/block_shim.hpp, test
+// infrastructure) can give bitrev.hip and twiddle.hip a bounds-checked heap block instead; in every build of the library it is this
+#ifndef PHAST_DYNAMIC_LDS
+#define PHAST_DYNAMIC_LDS(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
+#endif
 
 namespace phast {
 

@@ -12,7 +12,7 @@ namespace phast {
 
 template <typename T> __global__ void __launch_bounds__(256) twiddle_grid_kernel(const TwiddleGridArgs a) {
     using cx = cx_t<T>;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    PHAST_DYNAMIC_LDS(smem);
     cx *tab = reinterpret_cast<cx *>(smem);
     for (unsigned i = threadIdx.x; i < (3u << a.tw_bits); i += blockDim.x) tab[i] = reinterpret_cast<const cx *>(a.tw3)[i];
     __syncthreads();

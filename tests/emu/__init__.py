@@ -7,6 +7,13 @@ twiddle tables and plans are checked against the oracle in the GPU-less build co
 `sweep_shim.hpp` does the same for the streaming sweep kernels around the engine, whose bodies are plain `__global__`
 functions: it turns a launch into a serial host loop, and `build_sweep_emulator` builds tests/cpp/sweep_emu_test.cpp on it as
 a stand-alone program under ASan and UBSan, linked without the HIP runtime (tests/test_sweep_emulator.py).
+
+`block_shim.hpp` is the third emulator, for the kernels that move data through LDS between barriers (nd.hip's transposes, bitrev.hip,
+twiddle.hip, the digest of fill.hip): a workgroup's threads are fibers that run, in ascending or in descending order, from one
+__syncthreads() to the next; static LDS is a global object and dynamic LDS a heap block, both bounds-checked by ASan.
+`build_block_emulator` builds tests/cpp/block_emu_test.cpp on it (tests/test_block_emulator.py).  It checks LDS and global indices,
+barriers (a missing one gives wrong bits in one of the two orders) and which kernel instantiation a shape reaches; it cannot check
+cross-lane operations, timing, races that both serial orders survive, or the device's own arithmetic.
 """
 from __future__ import annotations
 
@@ -29,6 +36,16 @@ SWEEP_PARTS = ["main", "any_len", "any_real", "dct", "stft", "conv", "czt", "com
 SWEEP_FLAGS = ["--cuda-host-only", "-x", "hip", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
                "-fno-sanitize-recover=undefined", "-ftrivial-auto-var-init=pattern", "-Wall", "-Wno-unused-function",
                "-Wno-duplicate-decl-specifier"]
+
+# The block emulator (tests/test_block_emulator.py): block_shim.hpp runs a workgroup as fibers that meet at __syncthreads();
+# tests/cpp/block_emu_test.cpp #includes nd.hip, bitrev.hip, twiddle.hip and fill.hip as they stand, one per translation unit.
+BLOCK_SRC = os.path.join(os.path.dirname(HERE), "cpp", "block_emu_test.cpp")
+BLOCK_SHIM = os.path.join(HERE, "block_shim.hpp")
+BLOCK_EXE = os.path.join(HERE, "build", "block_emu_test")
+BLOCK_PARTS = ["main", "nd", "bitrev", "twiddle", "digest"]  # BLOCK_PART = index
+# as SWEEP_FLAGS, without AddressSanitizer's fake stacks (use-after-return): one per fiber, mapped and unmapped for each of the
+# millions of GPU threads a run emulates, they multiply its time; the frames stay on the fibers' own stacks
+BLOCK_FLAGS = SWEEP_FLAGS + ["-fsanitize-address-use-after-return=never"]
 
 
 def build_emulator(force: bool = False) -> str:
@@ -93,4 +110,34 @@ def build_sweep_emulator(force: bool = False, override_dir: str | None = None, p
         r = subprocess.run([_host_linker(), "-fsanitize=address,undefined", *objs, "-o", exe], capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed for the sweep emulator:\n{r.stdout}\n{r.stderr}")
+    return exe
+
+
+def build_block_emulator(force: bool = False, override_dir: str | None = None, parts: tuple = (), out: str | None = None) -> str:
+    """Builds the block emulator program and returns its path; `override_dir`, `parts` and `out` as build_sweep_emulator's."""
+    exe = out or BLOCK_EXE
+    objdir = os.path.join(HERE, "build")
+    os.makedirs(objdir, exist_ok=True)
+    cpp = os.path.dirname(BLOCK_SRC)
+    hips = [os.path.join(_b.SRC, f) for f in os.listdir(_b.SRC) if f.endswith(".hip")]
+    deps = [BLOCK_SRC, BLOCK_SHIM, os.path.join(cpp, "sanitizer_exit.hpp"), os.path.abspath(__file__)] + hips + _b._deps()
+    inc = ["-I", _b.SRC, "-I", _b.INCLUDE, "-I", HERE, "-I", cpp]
+
+    def part(name: str) -> str:
+        k = BLOCK_PARTS.index(name)
+        mutated = override_dir is not None and name in parts
+        obj = os.path.join(os.path.dirname(exe) if mutated else objdir, f"block_part{k}.o")
+        if force or mutated or _b._stale(obj, deps):
+            cmd = [_b.hipcc(), *BLOCK_FLAGS, f"-DBLOCK_PART={k}", *(["-I", override_dir] if mutated else []), *inc, "-c", BLOCK_SRC, "-o", obj]
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError(f"hipcc failed for block part {name}:\n{r.stdout}\n{r.stderr}")
+        return obj
+
+    with cf.ThreadPoolExecutor(len(BLOCK_PARTS)) as ex:
+        objs = list(ex.map(part, BLOCK_PARTS))
+    if force or override_dir or _b._stale(exe, objs):
+        r = subprocess.run([_host_linker(), "-fsanitize=address,undefined", *objs, "-o", exe], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"link failed for the block emulator:\n{r.stdout}\n{r.stderr}")
     return exe

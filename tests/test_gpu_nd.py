@@ -96,6 +96,38 @@ def test_shapes_match_numpy(gpu, dt, shape, direction):
 
 
 @pytest.mark.parametrize("dt", ["f64", "f32"])
+def test_every_narrow_side_matches_numpy(gpu, dt):
+    """(512, S) for EVERY narrow side S = 2 .. TS - 1 (TS = 32 f64, 64 f32) through the real narrow transposes: one forward call runs
+    the narrow-C transpose and the narrow-R transpose back, and 512 is no multiple of any span, so the last tile of each is ragged.
+    Once with aligned planes (16-byte accesses on both sides where S allows) and once as a batch of 2 at an odd distance in planes one
+    element off a 16-byte boundary (element accesses).  The host emulation (tests/test_block_emulator.py) checks every index of
+    these kernels but computes the f32 reciprocal quotients of nd.hip's fdiv with the HOST's 1.0f / d: this is the check with the
+    device's own.  The gate is the module's (nd_gates against numpy in long double); a misplaced element is an error of O(1).
+    A shape list of its own: SHAPES feeds the error-budget file."""
+    import torch
+
+    tdt = torch.float64 if dt == "f64" else torch.float32
+    for s in range(2, 32 if dt == "f64" else 64):
+        shape, n = (512, s), 512 * s
+        pl = _planner(gpu, dt, shape)
+        arrays = [_input(shape, dt, seed=20 + b) for b in range(2)]
+        refs = [_ref(re, im, shape, 1) for re, im in arrays]
+        g_re, g_im = _dev_fft(gpu, dt, *arrays[0], 1, pl)
+        _check(f"nd-narrow:{shape}", dt, shape, g_re, g_im, refs[0])
+        dist = (n + 1) | 1
+        b_re = torch.zeros(1 + dist + n, dtype=tdt, device="cuda")
+        b_im = torch.zeros_like(b_re)
+        v_re, v_im = b_re[1:], b_im[1:]
+        for b, (re, im) in enumerate(arrays):
+            v_re[b * dist:b * dist + n] = torch.from_numpy(re)
+            v_im[b * dist:b * dist + n] = torch.from_numpy(im)
+        gpu.fft_nd_batched(v_re, v_im, gpu.Direction.Forward, pl, batch=2, dist=dist)
+        for b in range(2):
+            _check(f"nd-narrow-off:{shape}[{b}]", dt, shape, v_re[b * dist:b * dist + n].cpu().numpy(), v_im[b * dist:b * dist + n].cpu().numpy(), refs[b])
+        assert float(b_re[0]) == 0.0 and float(b_re[1 + dist - 1]) == 0.0  # the lead-in and the gap between the arrays keep their zeros
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
 def test_describe_names_the_schedule(gpu, dt):
     d = _planner(gpu, dt, (1, 1000, 64)).describe()
     assert "squeezed [1000x64]" in d and "bluestein M=2048" in d and "pow2" in d, d

@@ -33,7 +33,10 @@ element lies in the band: check() must report exactly that.  It writes only insi
 
 TRANSPOSE_ROWS are N-d shapes for the batched planar transpose (csrc/nd.hip), kept out of the modules' SHAPES lists (whose
 error-budget files list every entry).  What each is MEANT to reach follows from reading launch_nd_transpose's selection; the
-tests do not depend on it (they gate the result against fftn / rfftn / irfftn in long double through the modules' gates):
+tests do not depend on it (they gate the result against fftn / rfftn / irfftn in long double through the modules' gates).  That the
+selection reaches all 4 square and 8 narrow instantiations per type, and that each moves the right bits for every narrow side,
+is CHECKED on the host: tests/cpp/block_emu_test.cpp records the instantiation of every launch and fails if one of the 24 never
+ran (tests/test_block_emulator.py::test_block_kernels_of[nd]):
 
     (65, 67)    complex, aligned: an odd total puts the imaginary plane of the transposed copy off a 16-byte boundary, so the
                 second transpose is nd_transpose_square<VIN = false, VOUT = false> in f32 too (67 % 4 != 0)
