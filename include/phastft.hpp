@@ -30,6 +30,8 @@
 //                                                            nufft2_64/32[_with_planner] -- non-uniform FFTs of types 1 and 2
 //   (none: samples on a grid only upstream)                  class PlannerNufft2d64/32, nufft2d1_64/32[_with_planner],
 //                                                            nufft2d2_64/32[_with_planner] -- the same in two dimensions
+//   (none: samples on a grid only upstream)                  class PlannerNufft3d64/32, nufft3d1_64/32[_with_planner],
+//                                                            nufft3d2_64/32[_with_planner] -- the same in three dimensions
 //   (none: one axis only upstream)                           class PlannerNd64/32, PlannerR2cNd64/32, fft_64/32_nd[_with_planner],
 //                                                            r2c_fft_f64/f32_nd[...], c2r_fft_f64/f32_nd[...] -- every axis
 //
@@ -740,6 +742,77 @@ PHASTFT_NUFFT2D(1, 32, float, PlannerNufft2d32)
 PHASTFT_NUFFT2D(2, 64, double, PlannerNufft2d64)
 PHASTFT_NUFFT2D(2, 32, float, PlannerNufft2d32)
 #undef PHASTFT_NUFFT2D
+
+// ---- non-uniform FFTs of types 1 and 2 in three dimensions (no reference counterpart) ----
+#define PHASTFT_PLANNER_NUFFT3D(NAME, CT, SFX)                                                                   \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* n1 x n2 x n3 modes, row-major, each axis in fftfreq order, and the points (x, y, z) (host doubles in turns,  \
+           reduced mod 1 per coordinate; k1 pairs with x, k2 with y, k3 with z), to the accuracy eps */          \
+        NAME(std::size_t n1, std::size_t n2, std::size_t n3, Slice<const double> x, Slice<const double> y,       \
+             Slice<const double> z, double eps)                                                                  \
+            : n1_(n1), n2_(n2), n3_(n3), m_(x.len) {                                                             \
+            if (x.len != y.len || x.len != z.len) check(PHAST_ERR_LEN_MISMATCH);                                 \
+            check(phast_planner_nufft3d##SFX##_new(n1, n2, n3, x.ptr, y.ptr, z.ptr, x.len, eps, &h_));           \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_), n1_(o.n1_), n2_(o.n2_), n3_(o.n3_), m_(o.m_) { o.h_ = nullptr; }     \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_nufft3d##SFX##_free(h_);                                                       \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_nufft3d##SFX##_describe(h_, &s[0], s.size()));                                   \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t num_modes_1() const { return n1_; }                                                          \
+        std::size_t num_modes_2() const { return n2_; }                                                          \
+        std::size_t num_modes_3() const { return n3_; }                                                          \
+        std::size_t num_points() const { return m_; }                                                            \
+        std::size_t device_bytes() const { return phast_planner_nufft3d##SFX##_device_bytes(h_); }               \
+        std::size_t grid_len() const { return phast_planner_nufft3d##SFX##_grid_len(h_); }                       \
+        /* g1, g2, g3 for axis 0, 1, 2 */                                                                        \
+        std::size_t grid_dim(int axis) const { return phast_planner_nufft3d##SFX##_grid_dim(h_, axis); }         \
+        int width() const { return phast_planner_nufft3d##SFX##_width(h_); }                                     \
+        /* elements of T a _dev call of `batch` transforms works in: 4 G batch, G = grid_len() */                \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_nufft3d##SFX##_workspace_len(h_, batch); }\
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+        std::size_t n1_, n2_, n3_, m_;                                                                           \
+    };
+PHASTFT_PLANNER_NUFFT3D(PlannerNufft3d64, phast_planner_nufft3d64, 64)
+PHASTFT_PLANNER_NUFFT3D(PlannerNufft3d32, phast_planner_nufft3d32, 32)
+#undef PHASTFT_PLANNER_NUFFT3D
+
+// one host vector (in_im.ptr may be null: real data): type 1 takes the values at the points and gives the n1 x n2 x n3 modes
+// (row-major), type 2 the reverse; blocking.  Without a planner the call builds its own from x, y, z, (n1, n2, n3) and eps.
+#define PHASTFT_NUFFT3D(TYPE, SFX, T, P)                                                                         \
+    inline void nufft3d##TYPE##_##SFX(Slice<const double> x, Slice<const double> y, Slice<const double> z, Slice<const T> in_re,\
+                                      Slice<const T> in_im, Slice<T> out_re, Slice<T> out_im, std::size_t n1, std::size_t n2,\
+                                      std::size_t n3, double eps, Direction direction = Direction::Forward) {    \
+        if ((in_im.ptr && in_im.len != in_re.len) || out_re.len != out_im.len || x.len != y.len || x.len != z.len)\
+            check(PHAST_ERR_LEN_MISMATCH);                                                                       \
+        if (x.len != (TYPE == 1 ? in_re.len : out_re.len)) check(PHAST_ERR_LEN_MISMATCH);                        \
+        const std::size_t modes = TYPE == 1 ? out_re.len : in_re.len;                                            \
+        if (n2 == 0 || n3 == 0 || modes % n3 || modes / n3 % n2 || modes / n3 / n2 != n1) check(PHAST_ERR_LEN_MISMATCH);\
+        check(phast_nufft3d##TYPE##_##SFX(x.ptr, y.ptr, z.ptr, x.len, in_re.ptr, in_im.ptr, out_re.ptr, out_im.ptr, n1, n2, n3,\
+                                          eps, static_cast<int>(direction)));                                    \
+    }                                                                                                            \
+    inline void nufft3d##TYPE##_##SFX##_with_planner(Slice<const T> in_re, Slice<const T> in_im, Slice<T> out_re, Slice<T> out_im,\
+                                                     const P &planner, Direction direction = Direction::Forward) {\
+        if ((in_im.ptr && in_im.len != in_re.len) || out_re.len != out_im.len) check(PHAST_ERR_LEN_MISMATCH);    \
+        check(phast_nufft3d##TYPE##_##SFX##_with_planner(in_re.ptr, in_im.ptr, in_re.len, out_re.ptr, out_im.ptr, out_re.len,\
+                                                         static_cast<int>(direction), planner.get()));           \
+    }
+PHASTFT_NUFFT3D(1, 64, double, PlannerNufft3d64)
+PHASTFT_NUFFT3D(1, 32, float, PlannerNufft3d32)
+PHASTFT_NUFFT3D(2, 64, double, PlannerNufft3d64)
+PHASTFT_NUFFT3D(2, 32, float, PlannerNufft3d32)
+#undef PHASTFT_NUFFT3D
 
 // ---- transforms over every axis of a row-major array (numpy fftn / rfftn / irfftn; no reference counterpart) ----
 #define PHASTFT_PLANNER_ND(NAME, CT, PFX)                                                                        \

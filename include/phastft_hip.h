@@ -770,6 +770,78 @@ int phast_nufft2d2_32_dev(const float *d_f_re, const float *d_f_im, size_t in_di
 int phast_planner_nufft2d32_time_stages(const phast_planner_nufft2d32 *p, const float *d_in_re, const float *d_in_im, float *d_out_re, float *d_out_im, int type,
                     size_t batch, float *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
 
+/* ---- non-uniform FFTs of types 1 and 2 in three dimensions (no reference counterpart).  The planner holds M points
+ * (x_j, y_j, z_j), finite doubles in turns (reduced mod 1 per coordinate; doubles for the f32 planner too), and N1 x N2 x N3 modes,
+ * row-major (index (m1 N2 + m2) N3 + m3), each axis in numpy fftfreq order; k1 pairs with x, k2 with y, k3 with z:
+ *     type 1 (points -> modes)   F[m1, m2, m3] = sum_j c_j exp(-+2 pi i (k1(m1) x_j + k2(m2) y_j + k3(m3) z_j))
+ *     type 2 (modes -> points)   c_j = sum_m F[m1, m2, m3] exp(-+2 pi i (k1(m1) x_j + k2(m2) y_j + k3(m3) z_j))
+ * with - for PHAST_FORWARD and + for PHAST_REVERSE, no scaling in either: type 2 Reverse is the adjoint of type 1 Forward, and the
+ * points (j1 / N1, j2 / N2, j3 / N3), M = N1 N2 N3, make type 1 Forward the 3-D DFT.  `eps`, the width w and the per-axis fine grids
+ * g_i = the smallest power of two >= max(2 N_i, 2w, 8) are those of the one-dimensional planner; G = g1 g2 g3 (_grid_len;
+ * _grid_dim(p, axis) is g1, g2, g3 for axis 0, 1, 2 and 0 for any other).  N_i >= 1, G <= 2^28, 1 <= M <= 2^30, eps in [1e-14, 1e-1]
+ * (f64) or [1e-6, 1e-1] (f32), the three point arrays non-null and every coordinate finite: anything else is PHAST_ERR_INVALID_ARG
+ * before the device is touched.  The point arrays are host memory and are sorted by grid cell once, in _new.
+ *
+ * The caller's device workspace holds phast_planner_nufft3d*_workspace_len(p, batch) = 4 G batch elements of T (two grid planes and
+ * what the 3-D transform of the grid works in); any work_len >= that of one transform runs the batch in chunks, a null or shorter
+ * one is PHAST_ERR_INVALID_ARG.  _dev calls: asynchronous on `stream`, no allocation, no synchronisation; `batch` inputs at in_dist
+ * and outputs at out_dist, each at least the row (M or N1 N2 N3); pointers need element alignment only; the imaginary input plane
+ * may be NULL: real data.  The overlap rules, the return codes and the bit-for-bit guarantees are those of the one-dimensional
+ * calls.  Host-slice calls take one vector, stage through a device buffer of their own and block (a length that is not the
+ * planner's is PHAST_ERR_PLANNER_SIZE); phast_nufft3d1_64 / phast_nufft3d2_64 / _32 build a planner for the one call. */
+typedef struct phast_planner_nufft3d64 phast_planner_nufft3d64; /* PlannerNufft3d64 */
+int phast_planner_nufft3d64_new(size_t n1, size_t n2, size_t n3, const double *x_turns, const double *y_turns, const double *z_turns, size_t m_points, double eps, phast_planner_nufft3d64 **out);
+void phast_planner_nufft3d64_free(phast_planner_nufft3d64 *p);
+int phast_planner_nufft3d64_describe(const phast_planner_nufft3d64 *p, char *buf, size_t buf_len);
+size_t phast_planner_nufft3d64_device_bytes(const phast_planner_nufft3d64 *p);
+size_t phast_planner_nufft3d64_grid_len(const phast_planner_nufft3d64 *p);
+size_t phast_planner_nufft3d64_grid_dim(const phast_planner_nufft3d64 *p, int axis);
+int phast_planner_nufft3d64_width(const phast_planner_nufft3d64 *p);
+size_t phast_planner_nufft3d64_workspace_len(const phast_planner_nufft3d64 *p, size_t batch);
+int phast_nufft3d1_64(const double *x_turns, const double *y_turns, const double *z_turns, size_t m_points, const double *c_re, const double *c_im, double *out_re, double *out_im, size_t n1,
+                      size_t n2, size_t n3, double eps, int direction);
+int phast_nufft3d1_64_with_planner(const double *c_re, const double *c_im, size_t m_points, double *out_re, double *out_im, size_t n_modes, int direction,
+                                   const phast_planner_nufft3d64 *planner);
+int phast_nufft3d1_64_dev(const double *d_c_re, const double *d_c_im, size_t in_dist, double *d_out_re, double *d_out_im, size_t out_dist, size_t batch,
+                          int direction, const phast_planner_nufft3d64 *planner, double *d_work, size_t work_len, void *stream);
+int phast_nufft3d2_64(const double *x_turns, const double *y_turns, const double *z_turns, size_t m_points, const double *f_re, const double *f_im, double *out_re, double *out_im, size_t n1,
+                      size_t n2, size_t n3, double eps, int direction);
+int phast_nufft3d2_64_with_planner(const double *f_re, const double *f_im, size_t n_modes, double *out_re, double *out_im, size_t m_points, int direction,
+                                   const phast_planner_nufft3d64 *planner);
+int phast_nufft3d2_64_dev(const double *d_f_re, const double *d_f_im, size_t in_dist, double *d_out_re, double *d_out_im, size_t out_dist, size_t batch,
+                          int direction, const phast_planner_nufft3d64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/nufft3d_rate.py): stage_ms[0..2] = average milliseconds of stage a (spread or pre), the 3-D transform of
+ * the grid and stage c (deconvolve or interpolate) over `reps` Forward calls of type `type` (1 or 2) of `batch` transforms at the natural
+ * distances in ONE chunk (work_len >= phast_planner_nufft3d*_workspace_len(p, batch)); stage_ms[3] and [4] are 0.  Blocks until done. */
+int phast_planner_nufft3d64_time_stages(const phast_planner_nufft3d64 *p, const double *d_in_re, const double *d_in_im, double *d_out_re, double *d_out_im, int type,
+                    size_t batch, double *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_nufft3d32 phast_planner_nufft3d32; /* PlannerNufft3d32 */
+int phast_planner_nufft3d32_new(size_t n1, size_t n2, size_t n3, const double *x_turns, const double *y_turns, const double *z_turns, size_t m_points, double eps, phast_planner_nufft3d32 **out);
+void phast_planner_nufft3d32_free(phast_planner_nufft3d32 *p);
+int phast_planner_nufft3d32_describe(const phast_planner_nufft3d32 *p, char *buf, size_t buf_len);
+size_t phast_planner_nufft3d32_device_bytes(const phast_planner_nufft3d32 *p);
+size_t phast_planner_nufft3d32_grid_len(const phast_planner_nufft3d32 *p);
+size_t phast_planner_nufft3d32_grid_dim(const phast_planner_nufft3d32 *p, int axis);
+int phast_planner_nufft3d32_width(const phast_planner_nufft3d32 *p);
+size_t phast_planner_nufft3d32_workspace_len(const phast_planner_nufft3d32 *p, size_t batch);
+int phast_nufft3d1_32(const double *x_turns, const double *y_turns, const double *z_turns, size_t m_points, const float *c_re, const float *c_im, float *out_re, float *out_im, size_t n1,
+                      size_t n2, size_t n3, double eps, int direction);
+int phast_nufft3d1_32_with_planner(const float *c_re, const float *c_im, size_t m_points, float *out_re, float *out_im, size_t n_modes, int direction,
+                                   const phast_planner_nufft3d32 *planner);
+int phast_nufft3d1_32_dev(const float *d_c_re, const float *d_c_im, size_t in_dist, float *d_out_re, float *d_out_im, size_t out_dist, size_t batch,
+                          int direction, const phast_planner_nufft3d32 *planner, float *d_work, size_t work_len, void *stream);
+int phast_nufft3d2_32(const double *x_turns, const double *y_turns, const double *z_turns, size_t m_points, const float *f_re, const float *f_im, float *out_re, float *out_im, size_t n1,
+                      size_t n2, size_t n3, double eps, int direction);
+int phast_nufft3d2_32_with_planner(const float *f_re, const float *f_im, size_t n_modes, float *out_re, float *out_im, size_t m_points, int direction,
+                                   const phast_planner_nufft3d32 *planner);
+int phast_nufft3d2_32_dev(const float *d_f_re, const float *d_f_im, size_t in_dist, float *d_out_re, float *d_out_im, size_t out_dist, size_t batch,
+                          int direction, const phast_planner_nufft3d32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/nufft3d_rate.py): stage_ms[0..2] = average milliseconds of stage a (spread or pre), the 3-D transform of
+ * the grid and stage c (deconvolve or interpolate) over `reps` Forward calls of type `type` (1 or 2) of `batch` transforms at the natural
+ * distances in ONE chunk (work_len >= phast_planner_nufft3d*_workspace_len(p, batch)); stage_ms[3] and [4] are 0.  Blocks until done. */
+int phast_planner_nufft3d32_time_stages(const phast_planner_nufft3d32 *p, const float *d_in_re, const float *d_in_im, float *d_out_re, float *d_out_im, int type,
+                    size_t batch, float *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+
 /* ---- multi-dimensional transforms over every axis of a row-major array (no reference counterpart; numpy fftn / ifftn /
  * rfftn / irfftn with this library's conventions).  dims[0 .. rank-1]: rank 1 .. 8, every axis 1 .. 2^29,
  * their product <= 2^30 (else PHAST_ERR_INVALID_ARG, before the device is touched).  Every axis is transformed; leading

@@ -32,6 +32,9 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
     (none: samples on a grid only)                  PlannerNufft2d64/32, nufft2d1_batched, nufft2d2_batched,
                                                     nufft2d1_64/32[_with_planner], nufft2d2_64/32[_with_planner],
                                                     nufft2d1, nufft2d2
+    (none: samples on a grid only)                  PlannerNufft3d64/32, nufft3d1_batched, nufft3d2_batched,
+                                                    nufft3d1_64/32[_with_planner], nufft3d2_64/32[_with_planner],
+                                                    nufft3d1, nufft3d2
     (none: one axis only)                           PlannerNd64/32, fft_64/32_nd[_with_planner], fft_nd_batched,
                                                     PlannerR2cNd64/32, r2c_fft_f64/f32_nd[_with_planner],
                                                     c2r_fft_f64/f32_nd[_with_planner], r2c_nd_batched, c2r_nd_batched
@@ -88,6 +91,9 @@ __all__ = [
     "PlannerNufft2d64", "PlannerNufft2d32", "nufft2d1_batched", "nufft2d2_batched", "nufft2d1_64", "nufft2d1_32", "nufft2d2_64",
     "nufft2d2_32", "nufft2d1_64_with_planner", "nufft2d1_32_with_planner", "nufft2d2_64_with_planner", "nufft2d2_32_with_planner",
     "nufft2d1", "nufft2d2",
+    "PlannerNufft3d64", "PlannerNufft3d32", "nufft3d1_batched", "nufft3d2_batched", "nufft3d1_64", "nufft3d1_32", "nufft3d2_64",
+    "nufft3d2_32", "nufft3d1_64_with_planner", "nufft3d1_32_with_planner", "nufft3d2_64_with_planner", "nufft3d2_32_with_planner",
+    "nufft3d1", "nufft3d2",
     "PlannerNd64", "PlannerNd32", "fft_64_nd", "fft_32_nd", "fft_64_nd_with_planner", "fft_32_nd_with_planner", "fft_nd_batched",
     "PlannerR2cNd64", "PlannerR2cNd32", "r2c_fft_f64_nd", "r2c_fft_f32_nd", "r2c_fft_f64_nd_with_planner",
     "r2c_fft_f32_nd_with_planner", "c2r_fft_f64_nd", "c2r_fft_f32_nd", "c2r_fft_f64_nd_with_planner",
@@ -1853,6 +1859,226 @@ def nufft2d2(x, y, F, eps: float | None = None, direction=Direction.Forward):
     if not _is_torch(F) or F.dim() < 2:
         raise TypeError("need a device tensor of at least two axes")
     return _nufft2d(2, x, y, F, tuple(F.shape[-2:]), eps, direction)
+
+
+# ---------------------------------------------------------------------------------------------
+# non-uniform FFTs of types 1 and 2 in three dimensions (no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class PlannerNufft3d64(_AnyHandle):
+    """f64 non-uniform FFTs of the M points ``(x[j], y[j], z[j])`` (doubles in turns, any finite value, reduced mod 1 per coordinate)
+    and ``n_modes = (n1, n2, n3)`` modes, row-major, each axis in numpy ``fftfreq`` order (``k1`` pairs with x, ``k2`` with y, ``k3`` with z), to
+    the relative accuracy ``eps``:
+
+        type 1 (points -> modes)   ``F[m1, m2, m3] = sum_j c[j] exp(-+2j pi (k1[m1] x[j] + k2[m2] y[j] + k3[m3] z[j]))``
+        type 2 (modes -> points)   ``c[j] = sum_m F[m1, m2, m3] exp(-+2j pi (k1[m1] x[j] + k2[m2] y[j] + k3[m3] z[j]))``
+
+    with ``-`` for ``Direction.Forward`` and ``+`` for ``Direction.Reverse`` and no scaling.  n1, n2, n3 >= 1, the fine grid
+    ``grid_len = prod(grid_shape) <= 2^28``, 1 <= M <= 2^30, eps in [1e-14, 1e-1].  The points are host memory
+    (arrays or sequences) and are sorted once here."""
+
+    _prefix = "nufft3d"
+    _eps = 1e-12
+
+    def __init__(self, n_modes, x, y, z, eps: float | None = None):
+        n1, n2, n3 = (int(v) for v in n_modes)
+        px, py, pz = (np.ascontiguousarray(v.detach().cpu().numpy() if _is_torch(v) else v, dtype=np.float64).reshape(-1) for v in (x, y, z))
+        if px.size != py.size or px.size != pz.size:
+            _check(2)
+        eps = self._eps if eps is None else float(eps)
+        self._new(n1, n2, n3, px.ctypes.data_as(C.c_void_p), py.ctypes.data_as(C.c_void_p), pz.ctypes.data_as(C.c_void_p), px.size, eps)
+        self.n_modes = (n1, n2, n3)
+        self.n = n1 * n2 * n3
+        self.m = self.m_points = px.size
+        self.eps = eps
+        self.grid_len = int(self._fn("grid_len")(self._h))
+        self.grid_shape = tuple(int(self._fn("grid_dim")(self._h, axis)) for axis in range(3))
+        self.width = int(self._fn("width")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` transforms works in: 4 G batch, G = ``grid_len``.  A smaller workspace of
+        at least ``workspace_len(1)`` runs the batch in chunks."""
+        return self._workspace_len(batch)
+
+    def time_stages(self, type: int, in_re, in_im, out_re, out_im, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (spread or pre, the 3-D transform of the grid, deconvolve or interpolate) of a
+        Forward call of ``type`` 1 or 2 of ``batch`` transforms at the natural distances on device tensors (measurement hook)"""
+        bufs = [_Slice(_flat(in_re), self._dtype, "in_re"), _NULL if in_im is None else _Slice(_flat(in_im), self._dtype, "in_im"),
+                _Slice(_flat(out_re), self._dtype, "out_re"), _Slice(_flat(out_im), self._dtype, "out_im")]
+        return self._time("time_stages", bufs, (type, batch), batch, workspace, reps)[:3]
+
+
+class PlannerNufft3d32(PlannerNufft3d64):
+    """f32 twin of :class:`PlannerNufft3d64`: eps in [1e-6, 1e-1]; the points stay doubles and the tables of 1 / phi^ are built
+    in f64 and rounded"""
+
+    _sfx = "32"
+    _dtype = np.float32
+    _eps = 1e-6
+
+
+def _nufft3d_batched(t, x_re, x_im, planner, direction, out, work, stream):
+    import torch
+
+    want = torch.float64 if planner._dtype == np.float64 else torch.float32
+    n1, n2, n3 = planner.n_modes
+
+    def plane(v, what, modes):
+        """(transforms, distance, batched) of a point-side or mode-side plane"""
+        if not _is_torch(v) or v.device.type != "cuda" or v.dtype != want:
+            raise TypeError(f"{what}: need a {want} device tensor")
+        per = n1 * n2 * n3 if modes else planner.m_points
+        if modes and (v.dim() == 4 or (v.dim() == 3 and tuple(v.shape) == (n1, n2, n3))):  # (batch, N1, N2, N3) or (N1, N2, N3)
+            ok = (tuple(v.shape[-3:]) == (n1, n2, n3) and (n3 == 1 or v.stride(-1) == 1) and (n2 == 1 or v.stride(-2) == n3)
+                  and (n1 == 1 or v.stride(-3) == n2 * n3))
+            batched = v.dim() == 4
+        else:  # (batch, per) or (per,)
+            ok = v.dim() in (1, 2) and v.shape[-1] == per and (per == 1 or v.stride(-1) == 1)
+            batched = v.dim() == 2
+        if not ok:
+            shapes = f"(batch, {n1}, {n2}, {n3}), ({n1}, {n2}, {n3}), (batch, {per}) or ({per},)" if modes else f"(batch, {per}) or ({per},)"
+            raise ValueError(f"{what}: need shape {shapes} with a contiguous last axis, not {tuple(v.shape)}")
+        rows = v.shape[0] if batched else 1
+        dist = v.stride(0) if batched and rows > 1 else per
+        if dist < per:
+            raise ValueError(f"{what}: rows overlap")
+        return rows, dist, batched
+
+    batch, in_dist, batched = plane(x_re, "x_re", t == 2)
+    if x_im is not None and (plane(x_im, "x_im", t == 2) != (batch, in_dist, batched) or x_im.shape != x_re.shape):
+        raise ValueError("x_im: need the shape and the strides of x_re")
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        if out is None:
+            shape = ((batch,) if batched else ()) + ((n1, n2, n3) if t == 1 else (planner.m_points,))
+            out = (torch.empty(shape, dtype=want, device=x_re.device), torch.empty(shape, dtype=want, device=x_re.device))
+        out_re, out_im = out
+        rows, out_dist, _ = plane(out_re, "out_re", t == 1)
+        if rows != batch or plane(out_im, "out_im", t == 1)[:2] != (batch, out_dist) or out_im.shape != out_re.shape:
+            raise ValueError("out: need a pair of tensors of one row per transform with equal shapes and strides")
+        ws = _any_workspace(planner, batch, work)
+        _check(_call(f"phast_nufft3d{t}_{planner._sfx}_dev", x_re.data_ptr(), None if x_im is None else x_im.data_ptr(), in_dist,
+                     out_re.data_ptr(), out_im.data_ptr(), out_dist, batch, int(direction), planner._h, ws.ptr, ws.len,
+                     _stream()))
+    return out_re, out_im
+
+
+def nufft3d1_batched(c_re, c_im, planner, direction=Direction.Forward, out=None, work=None, stream=None):
+    """Device-resident batch of three-dimensional type 1 transforms (points -> modes) through one planner: ``c_re`` (and ``c_im``,
+    or ``None`` for real data) are torch device tensors of shape ``(batch, M)`` or ``(M,)`` of the planner's type whose last axis
+    is contiguous; returns ``(out_re, out_im)`` of shape ``(batch, n1, n2, n3)`` or ``(n1, n2, n3)``.  ``out``: such a pair to write
+    into, of shape ``(batch, n1, n2, n3)``, ``(n1, n2, n3)`` or flat, ``(batch, n1 n2 n3)`` or ``(n1 n2 n3,)``, with a contiguous last axis
+    (it must not overlap the input or ``work``); ``work``: a device tensor of at least ``planner.workspace_len(1)`` elements
+    (fewer than ``planner.workspace_len(batch)`` runs the batch in chunks), by default one from torch's allocator; ``stream``: a
+    ``torch.cuda.Stream``, by default the current one."""
+    return _nufft3d_batched(1, c_re, c_im, planner, direction, out, work, stream)
+
+
+def nufft3d2_batched(f_re, f_im, planner, direction=Direction.Forward, out=None, work=None, stream=None):
+    """Device-resident batch of three-dimensional type 2 transforms (modes -> points): as :func:`nufft3d1_batched` with inputs of
+    the mode-side shapes and outputs of M values per transform"""
+    return _nufft3d_batched(2, f_re, f_im, planner, direction, out, work, stream)
+
+
+def _nufft3d_host(t, sfx, dtype, in_re, in_im, out_re, out_im, direction, planner=None, x=None, y=None, z=None, n_modes=None, eps=None):
+    a = _Slice(_flat(in_re), dtype, "in_re")
+    b = _NULL if in_im is None else _Slice(_flat(in_im), dtype, "in_im")
+    o_re, o_im = _Slice(_flat(out_re), dtype, "out_re"), _Slice(_flat(out_im), dtype, "out_im")
+    if _same_place(*(s for s in (a, b, o_re, o_im) if s is not _NULL)):
+        raise TypeError(f"nufft3d{t}_{sfx} takes host arrays (nufft3d{t}_batched takes device tensors)")
+    if (b is not _NULL and b.len != a.len) or o_re.len != o_im.len:
+        _check(2)
+    if planner is not None:
+        _check(_call(f"phast_nufft3d{t}_{sfx}_with_planner", a.ptr, b.ptr, a.len, o_re.ptr, o_im.ptr, o_re.len, int(direction),
+                     planner._h))
+        return
+    px, py, pz = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (x, y, z))
+    if len(n_modes) != 3:
+        raise ValueError(f"nufft3d{t}_{sfx}: the mode-side arrays need shape (n1, n2, n3), not {tuple(n_modes)}")
+    n1, n2, n3 = (int(v) for v in n_modes)
+    n_in, n_out = (px.size, n1 * n2 * n3) if t == 1 else (n1 * n2 * n3, px.size)
+    if px.size != py.size or px.size != pz.size or a.len != n_in or o_re.len != n_out:
+        _check(2)
+    _check(_call(f"phast_nufft3d{t}_{sfx}", px.ctypes.data_as(C.c_void_p), py.ctypes.data_as(C.c_void_p), pz.ctypes.data_as(C.c_void_p), px.size,
+                 a.ptr, b.ptr, o_re.ptr, o_im.ptr, n1, n2, n3, float(eps), int(direction)))
+
+
+def nufft3d1_64(x, y, z, c_re, c_im, out_re, out_im, eps: float = 1e-12, direction=Direction.Forward) -> None:
+    """f64 three-dimensional type 1 transform of one host vector of M values at the points ``(x, y, z)`` (``c_im`` may be ``None``:
+    real data) into host arrays of shape ``(n1, n2, n3)``, through a planner of its own (blocking)"""
+    _nufft3d_host(1, "64", np.float64, c_re, c_im, out_re, out_im, direction, x=x, y=y, z=z, n_modes=np.shape(out_re), eps=eps)
+
+
+def nufft3d1_32(x, y, z, c_re, c_im, out_re, out_im, eps: float = 1e-6, direction=Direction.Forward) -> None:
+    """f32 twin of :func:`nufft3d1_64`"""
+    _nufft3d_host(1, "32", np.float32, c_re, c_im, out_re, out_im, direction, x=x, y=y, z=z, n_modes=np.shape(out_re), eps=eps)
+
+
+def nufft3d2_64(x, y, z, f_re, f_im, out_re, out_im, eps: float = 1e-12, direction=Direction.Forward) -> None:
+    """f64 three-dimensional type 2 transform of one host array of shape ``(n1, n2, n3)`` into host arrays of M values at the points
+    ``(x, y)`` (blocking)"""
+    _nufft3d_host(2, "64", np.float64, f_re, f_im, out_re, out_im, direction, x=x, y=y, z=z, n_modes=np.shape(f_re), eps=eps)
+
+
+def nufft3d2_32(x, y, z, f_re, f_im, out_re, out_im, eps: float = 1e-6, direction=Direction.Forward) -> None:
+    """f32 twin of :func:`nufft3d2_64`"""
+    _nufft3d_host(2, "32", np.float32, f_re, f_im, out_re, out_im, direction, x=x, y=y, z=z, n_modes=np.shape(f_re), eps=eps)
+
+
+def nufft3d1_64_with_planner(c_re, c_im, out_re, out_im, planner: PlannerNufft3d64, direction=Direction.Forward) -> None:
+    _nufft3d_host(1, "64", np.float64, c_re, c_im, out_re, out_im, direction, planner)
+
+
+def nufft3d1_32_with_planner(c_re, c_im, out_re, out_im, planner: PlannerNufft3d32, direction=Direction.Forward) -> None:
+    _nufft3d_host(1, "32", np.float32, c_re, c_im, out_re, out_im, direction, planner)
+
+
+def nufft3d2_64_with_planner(f_re, f_im, out_re, out_im, planner: PlannerNufft3d64, direction=Direction.Forward) -> None:
+    _nufft3d_host(2, "64", np.float64, f_re, f_im, out_re, out_im, direction, planner)
+
+
+def nufft3d2_32_with_planner(f_re, f_im, out_re, out_im, planner: PlannerNufft3d32, direction=Direction.Forward) -> None:
+    _nufft3d_host(2, "32", np.float32, f_re, f_im, out_re, out_im, direction, planner)
+
+
+def _nufft3d(t, x, y, z, v, n_modes, eps, direction):
+    import torch
+
+    kinds = {torch.float64: (PlannerNufft3d64, torch.float64), torch.complex128: (PlannerNufft3d64, torch.float64),
+             torch.float32: (PlannerNufft3d32, torch.float32), torch.complex64: (PlannerNufft3d32, torch.float32)}
+    if not _is_torch(v) or v.device.type != "cuda" or v.dtype not in kinds or v.dim() < (1 if t == 1 else 3):
+        raise TypeError("need a float64, float32, complex128 or complex64 device tensor of at least one axis (points) or three (modes)")
+    cls, real = kinds[v.dtype]
+    planner = cls(n_modes, x, y, z, eps)
+    n1, n2, n3 = planner.n_modes
+    tail_in, tail_out = ((planner.m_points,), (n1, n2, n3)) if t == 1 else ((n1, n2, n3), (planner.m_points,))
+    if tuple(v.shape[-len(tail_in):]) != tail_in:
+        raise ValueError(f"the last axes are {tuple(v.shape[-len(tail_in):])}, the transform takes {tail_in}")
+    lead = tuple(v.shape[:-len(tail_in)])
+    n_in, n_out = int(np.prod(tail_in)), int(np.prod(tail_out))
+    rows = v.reshape(-1, n_in)
+    if v.is_complex():
+        x_re, x_im = rows.real.contiguous(), rows.imag.contiguous()
+    else:
+        x_re, x_im = rows.contiguous(), None
+    out = torch.empty((2, rows.shape[0], n_out), dtype=real, device=v.device)
+    if rows.shape[0]:
+        _nufft3d_batched(t, x_re, x_im, planner, direction, (out[0], out[1]), None, None)
+        torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+    return torch.complex(out[0], out[1]).reshape(lead + tail_out)
+
+
+def nufft3d1(x, y, z, c, n_modes, eps: float | None = None, direction=Direction.Forward):
+    """Three-dimensional type 1 non-uniform FFT of a real or complex device tensor ``c`` over its last axis (M values at the
+    points ``(x, y, z)``, in turns) into ``n_modes = (n1, n2, n3)`` modes in ``fftfreq`` order: a new complex tensor of shape
+    ``c.shape[:-1] + (n1, n2, n3)``.  float64 / complex128 run in f64 (eps defaults to 1e-12), float32 / complex64 in f32 (1e-6)."""
+    return _nufft3d(1, x, y, z, c, n_modes, eps, direction)
+
+
+def nufft3d2(x, y, z, F, eps: float | None = None, direction=Direction.Forward):
+    """Three-dimensional type 2 non-uniform FFT of a real or complex device tensor ``F`` of modes over its last three axes, evaluated
+    at the points ``(x, y, z)`` (in turns): a new complex tensor of shape ``F.shape[:-3] + (len(x),)``"""
+    if not _is_torch(F) or F.dim() < 3:
+        raise TypeError("need a device tensor of at least three axes")
+    return _nufft3d(2, x, y, z, F, tuple(F.shape[-3:]), eps, direction)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -23,7 +23,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libphastft_hip.so")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 
-UNITS = ["c_abi", "tile_f64_a", "tile_f64_bc", "tile_f64_bc_wide", "tile_f32_a", "tile_f32_bc", "tile_f32_bc_wide", "tile_f64_r2c", "tile_f32_r2c", "tile_f64_c2r", "tile_f32_c2r", "wave_f64", "wave_f32", "quad_f64", "quad_f32", "small_fft", "bitrev", "complex_nums", "any_len", "any_real", "dct", "stft", "conv", "czt", "nufft", "nufft2d", "nd", "r2c", "fill", "probe", "twiddle"]
+UNITS = ["c_abi", "tile_f64_a", "tile_f64_bc", "tile_f64_bc_wide", "tile_f32_a", "tile_f32_bc", "tile_f32_bc_wide", "tile_f64_r2c", "tile_f32_r2c", "tile_f64_c2r", "tile_f32_c2r", "wave_f64", "wave_f32", "quad_f64", "quad_f32", "small_fft", "bitrev", "complex_nums", "any_len", "any_real", "dct", "stft", "conv", "czt", "nufft", "nufft2d", "nufft3d", "nd", "r2c", "fill", "probe", "twiddle"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-ffp-contract=fast", "-Rpass-analysis=kernel-resource-usage"]
 # per-unit compiler options (the scheduling strategy is a translation-unit option: tile_dispatch.hpp says why)
@@ -34,7 +34,7 @@ UNIT_FLAGS = {"tile_f64_bc_wide": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
               # 19.45 -> 19.10 us; the f64 twins did not move: profiles/r06_max_ilp_ab.log)
               "wave_f32": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
               "quad_f32": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
-RESOURCES = os.path.join(LIB_DIR, "kernel_resources.json")  # per kernel: VGPRs, scratch bytes per lane, occupancy, spills
+RESOURCES = os.path.join(LIB_DIR, "kernel_resources.json")  # per kernel: VGPRs, scratch bytes per lane, occupancy, spills, static LDS
 
 
 def hipcc() -> str:
@@ -89,11 +89,11 @@ def _compile(unit: str, force: bool, trace: bool = False, extra: tuple = (), tag
 
 
 def _resource_usage(remarks: str) -> dict:
-    """{mangled kernel name: {"vgprs", "agprs", "scratch", "occupancy", "vgpr_spill", "sgpr_spill"}} out of the compiler's
+    """{mangled kernel name: {"vgprs", "agprs", "scratch", "occupancy", "vgpr_spill", "sgpr_spill", "lds"}} out of the compiler's
     kernel-resource-usage remarks: a kernel that starts to use scratch memory (a register array the optimiser could
     not keep in registers, or spills) pays for it in HBM traffic -- tests/test_kernel_resources.py watches this."""
     keys = {"VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
-            "VGPRs Spill": "vgpr_spill", "SGPRs Spill": "sgpr_spill"}
+            "VGPRs Spill": "vgpr_spill", "SGPRs Spill": "sgpr_spill", "LDS Size [bytes/block]": "lds"}
     out, cur = {}, None
     for line in remarks.splitlines():
         m = re.search(r"remark:\s+(.*?):\s+(\S+)\s+\[-Rpass-analysis", line)

@@ -23,6 +23,7 @@
 #include "planner_nufft.hpp"
 #include "planner_nd.hpp"
 #include "planner_nufft2d.hpp"
+#include "planner_nufft3d.hpp"
 
 // ================================================================================================
 // C ABI
@@ -49,6 +50,8 @@ struct phast_planner_nufft64 : NufftPlanner<double> {};
 struct phast_planner_nufft32 : NufftPlanner<float> {};
 struct phast_planner_nufft2d64 : Nufft2dPlanner<double> {};
 struct phast_planner_nufft2d32 : Nufft2dPlanner<float> {};
+struct phast_planner_nufft3d64 : Nufft3dPlanner<double> {};
+struct phast_planner_nufft3d32 : Nufft3dPlanner<float> {};
 struct phast_planner_nd64 : NdPlanner<double> {};
 struct phast_planner_nd32 : NdPlanner<float> {};
 struct phast_planner_r2c_nd64 : RealNdPlanner<double> {};
@@ -526,6 +529,7 @@ PHAST_HANDLE_API(any64) PHAST_HANDLE_API(any32) PHAST_HANDLE_API(r2c_any64) PHAS
 PHAST_HANDLE_API(dct64) PHAST_HANDLE_API(dct32) PHAST_HANDLE_API(stft64) PHAST_HANDLE_API(stft32)
 PHAST_HANDLE_API(conv64) PHAST_HANDLE_API(conv32) PHAST_HANDLE_API(czt64) PHAST_HANDLE_API(czt32)
 PHAST_HANDLE_API(nufft64) PHAST_HANDLE_API(nufft32) PHAST_HANDLE_API(nufft2d64) PHAST_HANDLE_API(nufft2d32)
+PHAST_HANDLE_API(nufft3d64) PHAST_HANDLE_API(nufft3d32)
 PHAST_HANDLE_API(nd64) PHAST_HANDLE_API(nd32) PHAST_HANDLE_API(r2c_nd64) PHAST_HANDLE_API(r2c_nd32)
 
 // Arbitrary lengths (Bluestein, planner_any.hpp): arguments are checked before the device is touched
@@ -905,6 +909,60 @@ PHAST_NUFFT_API(32, float)
     PHAST_NUFFT2D_CALLS(SFX, T, 2)
 PHAST_NUFFT2D_API(64, double)
 PHAST_NUFFT2D_API(32, float)
+
+// Non-uniform FFTs of types 1 and 2 in three dimensions (planner_nufft3d.hpp): the same rules, (n1, n2, n3) and (x, y, z)
+#define PHAST_NUFFT3D_CALLS(SFX, T, TYPE)                                                                               \
+    int phast_nufft3d##TYPE##_##SFX(const double *x_turns, const double *y_turns, const double *z_turns,                \
+                                    size_t m_points, const T *in_re, const T *in_im, T *out_re, T *out_im, size_t n1,   \
+                                    size_t n2, size_t n3, double eps, int direction) try {                              \
+        if (!in_re || !out_re || !out_im) return PHAST_ERR_INVALID_ARG;                                                 \
+        phast_planner_nufft3d##SFX *p = nullptr;                                                                        \
+        int rc = nufft3d_planner_new(n1, n2, n3, x_turns, y_turns, z_turns, m_points, eps, sizeof(T) == 4, &p);         \
+        if (rc) return rc;                                                                                              \
+        std::unique_ptr<phast_planner_nufft3d##SFX> own(p);                                                             \
+        return p->nufft_host(TYPE, direction, in_re, in_im, p->in_len(TYPE), out_re, out_im, p->out_len(TYPE));         \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_nufft3d##TYPE##_##SFX##_with_planner(const T *in_re, const T *in_im, size_t in_len, T *out_re, T *out_im, \
+                                                   size_t out_len, int direction,                                       \
+                                                   const phast_planner_nufft3d##SFX *p) try {                           \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->nufft_host(TYPE, direction, in_re, in_im, in_len, out_re, out_im, out_len);                           \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_nufft3d##TYPE##_##SFX##_dev(const T *d_in_re, const T *d_in_im, size_t in_dist, T *d_out_re, T *d_out_im, \
+                                          size_t out_dist, size_t batch, int direction,                                 \
+                                          const phast_planner_nufft3d##SFX *p, T *d_work, size_t work_len,              \
+                                          void *stream) try {                                                           \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->nufft_dev(TYPE, direction, d_in_re, d_in_im, in_dist, d_out_re, d_out_im, out_dist, batch, d_work,    \
+                            work_len, static_cast<hipStream_t>(stream));                                                \
+    } PHAST_CATCH_RC
+#define PHAST_NUFFT3D_API(SFX, T)                                                                                       \
+    int phast_planner_nufft3d##SFX##_new(size_t n1, size_t n2, size_t n3, const double *x_turns, const double *y_turns, \
+                                         const double *z_turns, size_t m_points, double eps,                            \
+                                         phast_planner_nufft3d##SFX **out) try {                                        \
+        return nufft3d_planner_new(n1, n2, n3, x_turns, y_turns, z_turns, m_points, eps, sizeof(T) == 4, out);          \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_nufft3d##SFX##_grid_len(const phast_planner_nufft3d##SFX *p) try {                             \
+        return p ? p->cells : 0;                                                                                        \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_nufft3d##SFX##_grid_dim(const phast_planner_nufft3d##SFX *p, int axis) try {                   \
+        return !p ? 0 : axis == 0 ? p->g1 : axis == 1 ? p->g2 : axis == 2 ? p->g3 : 0;                                  \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_nufft3d##SFX##_width(const phast_planner_nufft3d##SFX *p) try {                                   \
+        return p ? p->w : 0;                                                                                            \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_nufft3d##SFX##_time_stages(const phast_planner_nufft3d##SFX *p, const T *d_in_re,                 \
+                                                 const T *d_in_im, T *d_out_re, T *d_out_im, int type, size_t batch,    \
+                                                 T *d_work, size_t work_len, int reps, float *stage_ms,                 \
+                                                 void *stream) try {                                                    \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(type, d_in_re, d_in_im, d_out_re, d_out_im, batch, d_work, work_len, reps, stage_ms,      \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    PHAST_NUFFT3D_CALLS(SFX, T, 1)                                                                                      \
+    PHAST_NUFFT3D_CALLS(SFX, T, 2)
+PHAST_NUFFT3D_API(64, double)
+PHAST_NUFFT3D_API(32, float)
 
 // Multi-dimensional transforms (planner_nd.hpp): the shape and the lengths are checked before the device is touched
 #define PHAST_ND_PLANNER_API(NAME, KIND)                                                                                \

@@ -1,0 +1,294 @@
+// planner_nufft3d.hpp -- Nufft3dPlanner<T>: non-uniform FFTs of types 1 and 2 in three dimensions (nufft3d.hpp) of M points and
+// N1 x N2 x N3 modes on an owned NdPlanner<T> of dims (g1, g2, g3).  Immutable after init: the Nd planner, the point set sorted by
+// grid cell (positions, permutation, cell starts) and the N1 + N2 + N3 reciprocals 1 / phi^(k) on the device.  What a call mutates
+// is the caller's workspace (_dev calls) or a device buffer of the call's own (host-slice calls), so graph capture and concurrent
+// streams and threads need nothing beyond what the Nd planner already does.
+//
+// Workspace (elements of T) of a chunk of c transforms: c re grids, c im grids, then what the Nd planner asks for c arrays of
+// (g1, g2, g3) (its transposed copies, 2 c G: every axis is a power of two, so there is no Bluestein part): per() = 4 G per
+// transform, G = g1 g2 g3, read from the Nd planner and not assumed.
+#pragma once
+
+#include "nufft3d.hpp"
+#include "planner_nd.hpp"
+
+namespace phast {
+
+template <typename T> struct Nufft3dPlanner {
+    size_t n1 = 0, n2 = 0, n3 = 0, points = 0;  // N1, N2, N3, M
+    size_t g1 = 0, g2 = 0, g3 = 0, cells = 0;   // the fine grid and G = g1 g2 g3
+    unsigned log_g1 = 0, log_g2 = 0, log_g3 = 0;
+    int w = 0, device = -1;
+    double eps = 0;
+    NdPlanner<T> nd;
+    double *d_xs = nullptr, *d_ys = nullptr, *d_zs = nullptr;
+    uint32_t *d_perm = nullptr, *d_cell = nullptr;
+    T *d_inv1 = nullptr, *d_inv2 = nullptr, *d_inv3 = nullptr;
+
+    ~Nufft3dPlanner() {
+        DeviceGuard on(device);
+        for (void *p : {(void *)d_xs, (void *)d_ys, (void *)d_zs, (void *)d_perm, (void *)d_cell, (void *)d_inv1, (void *)d_inv2, (void *)d_inv3})
+            if (p) hipFree(p);
+    }
+
+    // 1 / phi^(k) of an axis of n modes on g grid points in double, rounded to T; phi^ is even in k
+    std::vector<T> inv_table(size_t n, size_t g) const {
+        std::vector<T> inv(n);
+        const NufftQuad hat(w, g);
+        for (size_t k = 0; k <= n / 2; ++k) {
+            const T r = (T)(1.0 / hat((long long)k));
+            if (k < (n + 1) / 2) inv[k] = r;
+            if (k > 0) inv[n - k] = r;
+        }
+        return inv;
+    }
+
+    template <typename E> int upload(E **dst, const E *src, size_t count) {
+        PHAST_HIP(hipMalloc(reinterpret_cast<void **>(dst), count * sizeof(E)));
+        PHAST_HIP(hipMemcpy(*dst, src, count * sizeof(E), hipMemcpyHostToDevice));
+        return PHAST_OK;
+    }
+
+    // `x`, `y`, `z`: M host doubles in turns; the arguments were checked by nufft3d_bad_args
+    int init(size_t n1_, size_t n2_, size_t n3_, const double *x, const double *y, const double *z, size_t m_points, double eps_) {
+        n1 = n1_;
+        n2 = n2_;
+        n3 = n3_;
+        points = m_points;
+        eps = eps_;
+        w = nufft_width(eps);
+        g1 = (size_t)nufft_grid(n1, w);
+        g2 = (size_t)nufft_grid(n2, w);
+        g3 = (size_t)nufft_grid(n3, w);
+        cells = g1 * g2 * g3;
+        log_g1 = ilog2(g1);
+        log_g2 = ilog2(g2);
+        log_g3 = ilog2(g3);
+        const size_t dims[3] = {g1, g2, g3};
+        int rc = nd.init(dims, 3);
+        if (rc) return rc;
+        device = nd.device;
+        std::vector<double> xs(points), ys(points), zs(points);
+        std::vector<uint32_t> perm(points), cell(cells + 1);
+        nufft3d_bin(x, y, z, points, log_g1, log_g2, log_g3, xs.data(), ys.data(), zs.data(), perm.data(), cell.data());
+        const std::vector<T> inv1 = inv_table(n1, g1), inv2 = inv_table(n2, g2), inv3 = inv_table(n3, g3);
+        PHAST_ON_DEVICE(device);
+        if ((rc = upload(&d_xs, xs.data(), points)) || (rc = upload(&d_ys, ys.data(), points)) || (rc = upload(&d_zs, zs.data(), points)) ||
+            (rc = upload(&d_perm, perm.data(), points)) || (rc = upload(&d_cell, cell.data(), cells + 1)) ||
+            (rc = upload(&d_inv1, inv1.data(), n1)) || (rc = upload(&d_inv2, inv2.data(), n2)) || (rc = upload(&d_inv3, inv3.data(), n3)))
+            return rc;
+        return PHAST_OK;
+    }
+
+    // elements of T per transform: the two grid planes and the Nd planner's own share (4 G)
+    size_t per() const { return 2 * cells + nd.workspace_len(1); }
+    size_t workspace_len(size_t batch) const { return per() * batch; }
+    size_t table_bytes() const {
+        return points * (3 * sizeof(double) + sizeof(uint32_t)) + (cells + 1) * sizeof(uint32_t) + (n1 + n2 + n3) * sizeof(T);
+    }
+    size_t device_bytes() const { return table_bytes() + nd.device_bytes(); }
+    std::string describe() const {
+        char f[48];
+        std::snprintf(f, sizeof f, " eps=%.3g w=%d", eps, w);
+        return "nufft3d N=" + std::to_string(n1) + "x" + std::to_string(n2) + "x" + std::to_string(n3) + " M=" + std::to_string(points) + f +
+               " grid=" + std::to_string(g1) + "x" + std::to_string(g2) + "x" + std::to_string(g3) + ": " + nd.describe();
+    }
+    size_t modes() const { return n1 * n2 * n3; }
+    size_t in_len(int type) const { return type == 1 ? points : modes(); }
+    size_t out_len(int type) const { return type == 1 ? modes() : points; }
+
+    // `c` transforms of type 1 or 2: input planes (re, im or null) at b * in_dist -> output planes at b * out_dist, through
+    // the workspace wk (c per() elements: c re grids, c im grids, the Nd planner's).  ev: optional 4 events around the three stages
+    int run_chunk(int type, int direction, const T *x_re, const T *x_im, size_t in_dist, T *o_re, T *o_im, size_t out_dist,
+                  size_t c, T *wk, hipStream_t s, hipEvent_t *ev = nullptr) const {
+        constexpr unsigned V = 16 / sizeof(T);
+        T *w_re = wk, *w_im = wk + c * cells, *w_nd = wk + 2 * c * cells;
+        auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+        // 16-byte accesses: aligned planes and workspace, and the transforms' planes a multiple of the group apart (one
+        // transform has no distance to meet)
+        auto vec = [&](const T *re, const T *im, size_t dist) { return al(re) && al(im) && al(wk) && (c == 1 || dist % V == 0); };
+        Nufft3dArgs a{};
+        a.xs = d_xs;
+        a.ys = d_ys;
+        a.zs = d_zs;
+        a.perm = d_perm;
+        a.cell_start = d_cell;
+        a.inv1 = d_inv1;
+        a.inv2 = d_inv2;
+        a.inv3 = d_inv3;
+        a.in_dist = in_dist;
+        a.out_dist = out_dist;
+        a.n1 = n1;
+        a.n2 = n2;
+        a.n3 = n3;
+        a.m = points;
+        a.log_g1 = log_g1;
+        a.log_g2 = log_g2;
+        a.log_g3 = log_g3;
+        a.w = w;
+        if (ev) PHAST_HIP(hipEventRecord(ev[0], s));
+        a.in_re = x_re;
+        a.in_im = x_im;
+        a.out_re = w_re;
+        a.out_im = w_im;
+        if (type == 1) {
+            a.groups = c * cells;  // a tile of 256 grid points per workgroup
+            PHAST_HIP(launch_nufft3d<T>(0, false, a, s));
+        } else {
+            a.groups = c * (cells / V);
+            PHAST_HIP(launch_nufft3d<T>(2, vec(x_re, x_im, in_dist), a, s));
+        }
+        if (ev) PHAST_HIP(hipEventRecord(ev[1], s));
+        // always the Forward transform (Reverse of the Nd planner scales by 1 / G).  Reverse by the swap trick: the FFT of
+        // (im, re) is (im, re) of the transform with the + sign
+        T *e_re = direction == PHAST_REVERSE ? w_im : w_re, *e_im = direction == PHAST_REVERSE ? w_re : w_im;
+        int rc = nd.fft_dev_nd(e_re, e_im, cells, c, cells, PHAST_FORWARD, w_nd, nd.workspace_len(c), s);
+        if (rc) return rc;
+        if (ev) PHAST_HIP(hipEventRecord(ev[2], s));
+        a.in_re = w_re;
+        a.in_im = w_im;
+        a.out_re = o_re;
+        a.out_im = o_im;
+        if (type == 1) {
+            a.gpt = (unsigned)(n1 * n2 * ((n3 + V - 1) / V));
+            a.groups = c * a.gpt;
+            PHAST_HIP(launch_nufft3d<T>(3, vec(o_re, o_im, out_dist), a, s));
+        } else {
+            a.groups = c * points;
+            PHAST_HIP(launch_nufft3d<T>(1, false, a, s));
+        }
+        if (ev) PHAST_HIP(hipEventRecord(ev[3], s));
+        return PHAST_OK;
+    }
+
+    // the batch in chunks of floor(work_len / per()) transforms; the Nd planner's plans do not depend on the chunk, so neither
+    // do the bits
+    int run(int type, int direction, const T *x_re, const T *x_im, size_t in_dist, T *o_re, T *o_im, size_t out_dist,
+            size_t batch, T *work, size_t work_len, hipStream_t s, hipEvent_t *ev = nullptr) const {
+        size_t chunk = work_len / per();
+        const size_t cap = ((size_t)1 << 38) / cells;  // a launch's groups stay below 2^38
+        if (chunk > cap) chunk = cap;
+        for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+            const size_t c = batch - b0 < chunk ? batch - b0 : chunk;
+            int rc = run_chunk(type, direction, x_re + b0 * in_dist, x_im ? x_im + b0 * in_dist : nullptr, in_dist,
+                               o_re + b0 * out_dist, o_im + b0 * out_dist, out_dist, c, work, s, ev);
+            if (rc) return rc;
+        }
+        return PHAST_OK;
+    }
+
+    // [p, p + len) and [q, q + qlen) share an element
+    static bool overlap(const T *p, size_t len, const T *q, size_t qlen) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+        return p && q && a < b + qlen * sizeof(T) && b < a + len * sizeof(T);
+    }
+
+    // the rules and return codes of NufftPlanner::check_dev
+    int check_dev(int type, int direction, const T *d_in_re, const T *d_in_im, size_t in_dist, const T *d_out_re,
+                  const T *d_out_im, size_t out_dist, size_t batch, const T *d_work, size_t work_len) const {
+        if (!d_in_re || !d_out_re || !d_out_im) return PHAST_ERR_INVALID_ARG;  // d_in_im may be null: real data
+        if (direction != PHAST_FORWARD && direction != PHAST_REVERSE) return PHAST_ERR_INVALID_ARG;
+        const size_t ni = in_len(type), no = out_len(type);
+        if (batch > 1 && (in_dist < ni || out_dist < no)) return PHAST_ERR_INVALID_ARG;
+        if (batch && (!d_work || work_len < per())) return PHAST_ERR_INVALID_ARG;
+        if (batch) {  // the output is written while later chunks still read the input and the workspace
+            const size_t in_span = (batch - 1) * (batch > 1 ? in_dist : 0) + ni, out_span = (batch - 1) * (batch > 1 ? out_dist : 0) + no;
+            for (const T *o : {d_out_re, d_out_im})
+                if (overlap(o, out_span, d_in_re, in_span) || overlap(o, out_span, d_in_im, in_span) ||
+                    overlap(o, out_span, d_work, work_len))
+                    return PHAST_ERR_INVALID_ARG;
+            if (overlap(d_out_re, out_span, d_out_im, out_span)) return PHAST_ERR_INVALID_ARG;
+            if (overlap(d_work, work_len, d_in_re, in_span) || overlap(d_work, work_len, d_in_im, in_span)) return PHAST_ERR_INVALID_ARG;
+        }
+        return PHAST_OK;
+    }
+
+    // device pointers, asynchronous on `s`: no allocation, no synchronisation
+    int nufft_dev(int type, int direction, const T *d_in_re, const T *d_in_im, size_t in_dist, T *d_out_re, T *d_out_im,
+                  size_t out_dist, size_t batch, T *d_work, size_t work_len, hipStream_t s) const {
+        int rc = check_dev(type, direction, d_in_re, d_in_im, in_dist, d_out_re, d_out_im, out_dist, batch, d_work, work_len);
+        if (rc || batch == 0) return rc;
+        if (batch == 1) {
+            in_dist = in_len(type);
+            out_dist = out_len(type);
+        }
+        PHAST_ON_DEVICE(device);
+        return run(type, direction, d_in_re, d_in_im, in_dist, d_out_re, d_out_im, out_dist, batch, d_work, work_len, s);
+    }
+
+    // host slices: through a device buffer of the call's own (input planes, output planes, then the workspace), on the null
+    // stream; blocking.  in_im may be null: real data
+    int nufft_host(int type, int direction, const T *in_re, const T *in_im, size_t num_in, T *out_re, T *out_im,
+                   size_t num_out) const {
+        if (!in_re || !out_re || !out_im) return PHAST_ERR_INVALID_ARG;
+        if (direction != PHAST_FORWARD && direction != PHAST_REVERSE) return PHAST_ERR_INVALID_ARG;
+        const size_t ni = in_len(type), no = out_len(type);
+        if (num_in != ni || num_out != no) return PHAST_ERR_PLANNER_SIZE;
+        PHAST_ON_DEVICE(device);
+        const size_t x_len = (ni + 3) & ~(size_t)3, o_len = (no + 3) & ~(size_t)3;  // every part 16-byte aligned
+        DevBuf buf;
+        int rc = buf.alloc((2 * x_len + 2 * o_len + per()) * sizeof(T));
+        if (rc) return rc;
+        T *d_re = reinterpret_cast<T *>(buf.p), *d_im = d_re + x_len, *d_or = d_im + x_len, *d_oi = d_or + o_len, *d_w = d_oi + o_len;
+        PHAST_HIP(hipMemcpy(d_re, in_re, ni * sizeof(T), hipMemcpyHostToDevice));
+        if (in_im) PHAST_HIP(hipMemcpy(d_im, in_im, ni * sizeof(T), hipMemcpyHostToDevice));
+        rc = run(type, direction, d_re, in_im ? d_im : nullptr, ni, d_or, d_oi, no, 1, d_w, per(), nullptr);
+        if (rc) return rc;
+        PHAST_HIP(hipMemcpy(out_re, d_or, no * sizeof(T), hipMemcpyDeviceToHost));
+        PHAST_HIP(hipMemcpy(out_im, d_oi, no * sizeof(T), hipMemcpyDeviceToHost));
+        return PHAST_OK;
+    }
+
+    // measurement hook: ms[0..2] = average milliseconds of the three stages (spread or pre, the 3-D transform of the grid,
+    // deconvolve or interpolate) over `reps` Forward calls of one chunk (work_len >= workspace_len(batch)) at the natural
+    // distances; ms[3] and ms[4] are 0 (the timer of the any-length planners has five slots); blocks
+    int time_stages(int type, const T *d_in_re, const T *d_in_im, T *d_out_re, T *d_out_im, size_t batch, T *d_work,
+                    size_t work_len, int reps, float *ms, hipStream_t s) const {
+        if (!ms || reps < 1 || batch == 0 || (type != 1 && type != 2)) return PHAST_ERR_INVALID_ARG;
+        const size_t ni = in_len(type), no = out_len(type);
+        int rc = check_dev(type, PHAST_FORWARD, d_in_re, d_in_im, ni, d_out_re, d_out_im, no, batch, d_work, work_len);
+        if (rc) return rc;
+        if (work_len < workspace_len(batch) || batch > ((size_t)1 << 38) / cells) return PHAST_ERR_INVALID_ARG;
+        PHAST_ON_DEVICE(device);
+        struct Events {
+            hipEvent_t e[4] = {};
+            ~Events() {
+                for (hipEvent_t x : e)
+                    if (x) hipEventDestroy(x);
+            }
+        } ev;
+        for (hipEvent_t &x : ev.e) PHAST_HIP(hipEventCreate(&x));
+        double acc[3] = {0, 0, 0};
+        for (int r = 0; r < reps; ++r) {
+            rc = run(type, PHAST_FORWARD, d_in_re, d_in_im, ni, d_out_re, d_out_im, no, batch, d_work, work_len, s, ev.e);
+            if (rc) return rc;
+            PHAST_HIP(hipStreamSynchronize(s));
+            for (int i = 0; i < 3; ++i) {
+                float t = 0;
+                PHAST_HIP(hipEventElapsedTime(&t, ev.e[i], ev.e[i + 1]));
+                acc[i] += t;
+            }
+        }
+        for (int i = 0; i < 5; ++i) ms[i] = i < 3 ? (float)(acc[i] / reps) : 0.0f;
+        return PHAST_OK;
+    }
+};
+
+template <typename P>
+static int nufft3d_planner_new(size_t n1, size_t n2, size_t n3, const double *x, const double *y, const double *z, size_t m_points,
+                               double eps, bool f32, P **out) {
+    if (!out) return PHAST_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (nufft3d_bad_args(n1, n2, n3, m_points, x, y, z, eps, f32)) return PHAST_ERR_INVALID_ARG;  // before the device is touched
+    auto *p = new (std::nothrow) P();
+    if (!p) return PHAST_ERR_ALLOC;
+    int rc = p->init(n1, n2, n3, x, y, z, m_points, eps);
+    if (rc) {
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return PHAST_OK;
+}
+
+}  // namespace phast

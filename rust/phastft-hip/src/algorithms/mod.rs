@@ -7,6 +7,7 @@ pub mod czt;
 pub mod dit;
 pub mod nufft;
 pub mod nufft2d;
+pub mod nufft3d;
 pub mod r2c;
 pub mod r2r;
 pub mod stft;

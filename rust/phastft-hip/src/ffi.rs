@@ -309,6 +309,55 @@ extern "C" {
         out_len: usize, direction: c_int, planner: *const Opaque) -> c_int;
     pub(crate) fn phast_nufft2d2_32_dev(in_re: *const f32, in_im: *const f32, in_dist: usize, out_re: *mut f32, out_im: *mut f32,
         out_dist: usize, batch: usize, direction: c_int, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // the same in three dimensions (planner.rs / algorithms/nufft3d.rs)
+    pub(crate) fn phast_planner_nufft3d64_new(n1: usize, n2: usize, n3: usize, x_turns: *const f64, y_turns: *const f64, z_turns: *const f64,
+        m_points: usize, eps: f64,
+        out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft3d64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_nufft3d64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_nufft3d64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_nufft3d64_grid_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_nufft3d64_grid_dim(p: *const Opaque, axis: c_int) -> usize;
+    pub(crate) fn phast_planner_nufft3d64_width(p: *const Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft3d64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_nufft3d64_time_stages(p: *const Opaque, in_re: *const f64, in_im: *const f64, out_re: *mut f64,
+        out_im: *mut f64, ty: c_int, batch: usize, work: *mut f64, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_nufft3d1_64(x_turns: *const f64, y_turns: *const f64, z_turns: *const f64, m_points: usize, in_re: *const f64, in_im: *const f64,
+        out_re: *mut f64, out_im: *mut f64, n1: usize, n2: usize, n3: usize, eps: f64, direction: c_int) -> c_int;
+    pub(crate) fn phast_nufft3d1_64_with_planner(in_re: *const f64, in_im: *const f64, in_len: usize, out_re: *mut f64, out_im: *mut f64,
+        out_len: usize, direction: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_nufft3d1_64_dev(in_re: *const f64, in_im: *const f64, in_dist: usize, out_re: *mut f64, out_im: *mut f64,
+        out_dist: usize, batch: usize, direction: c_int, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_nufft3d2_64(x_turns: *const f64, y_turns: *const f64, z_turns: *const f64, m_points: usize, in_re: *const f64, in_im: *const f64,
+        out_re: *mut f64, out_im: *mut f64, n1: usize, n2: usize, n3: usize, eps: f64, direction: c_int) -> c_int;
+    pub(crate) fn phast_nufft3d2_64_with_planner(in_re: *const f64, in_im: *const f64, in_len: usize, out_re: *mut f64, out_im: *mut f64,
+        out_len: usize, direction: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_nufft3d2_64_dev(in_re: *const f64, in_im: *const f64, in_dist: usize, out_re: *mut f64, out_im: *mut f64,
+        out_dist: usize, batch: usize, direction: c_int, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_nufft3d32_new(n1: usize, n2: usize, n3: usize, x_turns: *const f64, y_turns: *const f64, z_turns: *const f64,
+        m_points: usize, eps: f64,
+        out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft3d32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_nufft3d32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_nufft3d32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_nufft3d32_grid_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_nufft3d32_grid_dim(p: *const Opaque, axis: c_int) -> usize;
+    pub(crate) fn phast_planner_nufft3d32_width(p: *const Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft3d32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_nufft3d32_time_stages(p: *const Opaque, in_re: *const f32, in_im: *const f32, out_re: *mut f32,
+        out_im: *mut f32, ty: c_int, batch: usize, work: *mut f32, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_nufft3d1_32(x_turns: *const f64, y_turns: *const f64, z_turns: *const f64, m_points: usize, in_re: *const f32, in_im: *const f32,
+        out_re: *mut f32, out_im: *mut f32, n1: usize, n2: usize, n3: usize, eps: f64, direction: c_int) -> c_int;
+    pub(crate) fn phast_nufft3d1_32_with_planner(in_re: *const f32, in_im: *const f32, in_len: usize, out_re: *mut f32, out_im: *mut f32,
+        out_len: usize, direction: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_nufft3d1_32_dev(in_re: *const f32, in_im: *const f32, in_dist: usize, out_re: *mut f32, out_im: *mut f32,
+        out_dist: usize, batch: usize, direction: c_int, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_nufft3d2_32(x_turns: *const f64, y_turns: *const f64, z_turns: *const f64, m_points: usize, in_re: *const f32, in_im: *const f32,
+        out_re: *mut f32, out_im: *mut f32, n1: usize, n2: usize, n3: usize, eps: f64, direction: c_int) -> c_int;
+    pub(crate) fn phast_nufft3d2_32_with_planner(in_re: *const f32, in_im: *const f32, in_len: usize, out_re: *mut f32, out_im: *mut f32,
+        out_len: usize, direction: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_nufft3d2_32_dev(in_re: *const f32, in_im: *const f32, in_dist: usize, out_re: *mut f32, out_im: *mut f32,
+        out_dist: usize, batch: usize, direction: c_int, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // DCT / DST of types II and III (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/r2r.rs)
     pub(crate) fn phast_planner_dct64_new(n: usize, out: *mut *mut Opaque) -> c_int;
     pub(crate) fn phast_planner_dct32_new(n: usize, out: *mut *mut Opaque) -> c_int;

@@ -73,6 +73,12 @@ pub use algorithms::nufft2d::{
     nufft2d2_32_dev, nufft2d2_32_with_planner, nufft2d2_64, nufft2d2_64_dev, nufft2d2_64_with_planner,
 };
 pub use planner::{PlannerNufft2d32, PlannerNufft2d64};
+// and in three dimensions (an extension beyond PhastFT 0.3.0)
+pub use algorithms::nufft3d::{
+    nufft3d1_32, nufft3d1_32_dev, nufft3d1_32_with_planner, nufft3d1_64, nufft3d1_64_dev, nufft3d1_64_with_planner, nufft3d2_32,
+    nufft3d2_32_dev, nufft3d2_32_with_planner, nufft3d2_64, nufft3d2_64_dev, nufft3d2_64_with_planner,
+};
+pub use planner::{PlannerNufft3d32, PlannerNufft3d64};
 // multi-dimensional real transforms (an extension beyond PhastFT 0.3.0)
 pub use algorithms::r2c::{
     c2r_fft_f32_nd, c2r_fft_f32_nd_dev, c2r_fft_f32_nd_with_planner, c2r_fft_f64_nd, c2r_fft_f64_nd_dev,

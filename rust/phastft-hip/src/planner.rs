@@ -537,6 +537,67 @@ impl_planner_nufft2d!(PlannerNufft2d32, phast_planner_nufft2d32_new, phast_plann
                       phast_planner_nufft2d32_grid_rows, phast_planner_nufft2d32_grid_cols, phast_planner_nufft2d32_width,
                       phast_planner_nufft2d32_workspace_len);
 
+macro_rules! impl_planner_nufft3d {
+    ($nufft:ident, $new:ident, $free:ident, $grid_len:ident, $grid_dim:ident, $width:ident, $ws_len:ident) => {
+        /// An extension beyond PhastFT 0.3.0: three-dimensional non-uniform FFTs of types 1 and 2 of the points `(x, y, z)`
+        /// (turns, reduced mod 1 per coordinate) and `n1 x n2 x n3` modes, row-major, each axis in numpy fftfreq order (k1 pairs
+        /// with x, k2 with y, k3 with z), to the relative accuracy `eps`.  Immutable after `new`, like the reference's planners.
+        pub struct $nufft {
+            pub(crate) h: *mut Opaque,
+            pub(crate) n: (usize, usize, usize),
+            pub(crate) m: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in
+        // a device buffer of its own (host-slice calls)
+        unsafe impl Send for $nufft {}
+        unsafe impl Sync for $nufft {}
+        impl $nufft {
+            /// Panics with "invalid argument" unless n1, n2, n3 >= 1, the fine grid g1 g2 g3 <= 2^28, 1 <= x.len() == y.len() == z.len() <= 2^30,
+            /// every coordinate is finite and eps lies in [1e-14, 1e-1] (f64) or [1e-6, 1e-1] (f32)
+            pub fn new(n_modes: (usize, usize, usize), x: &[f64], y: &[f64], z: &[f64], eps: f64) -> Self {
+                assert_eq!(x.len(), y.len());
+                assert_eq!(x.len(), z.len());
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe { ffi::$new(n_modes.0, n_modes.1, n_modes.2, x.as_ptr(), y.as_ptr(), z.as_ptr(), x.len(), eps, &mut h) });
+                Self { h, n: n_modes, m: x.len() }
+            }
+            pub fn num_modes(&self) -> (usize, usize, usize) {
+                self.n
+            }
+            pub fn num_points(&self) -> usize {
+                self.m
+            }
+            /// the fine grid G = g1 g2 g3
+            pub fn grid_len(&self) -> usize {
+                unsafe { ffi::$grid_len(self.h) }
+            }
+            /// (g1, g2, g3): per axis the smallest power of two >= max(2 n, 2 width, 8)
+            pub fn grid_shape(&self) -> (usize, usize, usize) {
+                unsafe { (ffi::$grid_dim(self.h, 0), ffi::$grid_dim(self.h, 1), ffi::$grid_dim(self.h, 2)) }
+            }
+            /// the width of the spreading kernel in grid cells
+            pub fn width(&self) -> usize {
+                unsafe { ffi::$width(self.h) as usize }
+            }
+            /// elements of the workspace a device call of `batch` transforms works in: 4 G batch
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+        }
+        impl Drop for $nufft {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_nufft3d!(PlannerNufft3d64, phast_planner_nufft3d64_new, phast_planner_nufft3d64_free, phast_planner_nufft3d64_grid_len,
+                      phast_planner_nufft3d64_grid_dim, phast_planner_nufft3d64_width,
+                      phast_planner_nufft3d64_workspace_len);
+impl_planner_nufft3d!(PlannerNufft3d32, phast_planner_nufft3d32_new, phast_planner_nufft3d32_free, phast_planner_nufft3d32_grid_len,
+                      phast_planner_nufft3d32_grid_dim, phast_planner_nufft3d32_width,
+                      phast_planner_nufft3d32_workspace_len);
+
 macro_rules! impl_planner_nd {
     ($nd:ident, $new:ident, $free:ident, $ws_len:ident, $what:literal) => {
         #[doc = concat!("An extension beyond PhastFT 0.3.0, whose planners transform one axis: ", $what, " over every axis of a ",
