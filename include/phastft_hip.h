@@ -1068,11 +1068,21 @@ void phast_debug_set_wg_per_cu(int wg_per_cu);
 void phast_debug_set_guard_bytes(size_t bytes);
 int phast_planner_dit64_debug_check_guards(const phast_planner_dit64 *p, size_t *bad_bytes);
 int phast_planner_dit32_debug_check_guards(const phast_planner_dit32 *p, size_t *bad_bytes);
+/* ... and of a real planner: the scratches of its inner N/2-point planner, which the real transforms run in */
+int phast_planner_r2c64_debug_check_guards(const phast_planner_r2c64 *p, size_t *bad_bytes);
+int phast_planner_r2c32_debug_check_guards(const phast_planner_r2c32 *p, size_t *bad_bytes);
 
 /* No C++ exception leaves the library (every entry point is a function-try-block, csrc/c_abi.hip): host memory exhaustion
  * comes back as PHAST_ERR_ALLOC, any other exception as PHAST_ERR_HIP with its text in phast_last_hip_error().  Test hook:
  * throws std::bad_alloc (1), std::runtime_error (2) or an int (3) INSIDE the library and returns what the caller would see. */
 int phast_debug_throw(int what);
+
+/* debug hook (no device needed): the wisdom entry a planner on a device with `cus` compute units of architecture `arch` (the
+ * gfx number read as hex digits, gfx950 -> 0x950; 0 = unknown, matches anything) applies for (element size in bytes,
+ * PHAST_TUNE_* kind, log2 of the caller's length, batch bucket).  Returns the layer it came from (0 built-in, 1 PHAST_WISDOM
+ * file, 2 imported, 3 measured here) and writes its plan ("heuristic" or the plan text) to buf; -1 when no entry applies. */
+int phast_debug_wisdom_lookup(size_t elem_bytes, int kind, unsigned log_n, unsigned bucket, int cus, int arch, char *buf,
+                              size_t buf_len);
 
 /* debug hook: device buffer of [3 passes][4096 workgroups][16] s_memtime stamps written by the tile kernels while
  * set (NULL = off; adds drains, so never leave it on while measuring).  tools/trace_tile.py decodes it. */

@@ -396,6 +396,13 @@ class _PlannerR2c(_Handle):
         _check(self._fn("describe_call")(self._h, batch, int(kind), buf, 512))
         return buf.value.decode()
 
+    def check_guards(self) -> int:
+        """debug: bytes of the guard bands around the inner planner's scratches overwritten since allocation (see
+        :func:`debug_set_guard_bytes`)"""
+        bad = C.c_size_t(0)
+        _check(self._fn("debug_check_guards")(self._h, C.byref(bad)))
+        return int(bad.value)
+
     def tune(self, batch: int = 1, kind: TuneKind = TuneKind.R2C) -> dict:
         """PlannerMode::Tune for ``batch`` real transforms per call, ``TuneKind.R2C`` or ``TuneKind.C2R``."""
         return _tune(self, batch, kind)
@@ -2681,6 +2688,14 @@ def stream_probe(mib: int = 1024, reps: int = 5) -> dict:
 def debug_set_guard_bytes(nbytes: int) -> None:
     """debug: scratch buffers allocated from now on carry `nbytes` of 0xA5 guard band on either side"""
     _call("phast_debug_set_guard_bytes", nbytes)
+
+
+def debug_wisdom_lookup(dtype: str, kind: "TuneKind", log_n: int, bucket: int = 0, cus: int = 0, arch: int = 0):
+    """debug (no device needed): ``(layer, plan text)`` of the wisdom entry a planner on a device with ``cus`` compute units of
+    architecture ``arch`` (0x950 for gfx950; 0 = any) applies for the key, or ``None`` when no entry applies"""
+    buf = C.create_string_buffer(96)
+    layer = int(_call("phast_debug_wisdom_lookup", 8 if dtype == "f64" else 4, int(kind), log_n, bucket, cus, arch, buf, 96))
+    return None if layer < 0 else (layer, buf.value.decode())
 
 
 def graph_upload(graph, stream=None) -> bool:

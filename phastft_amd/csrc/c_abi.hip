@@ -153,6 +153,16 @@ int phast_wisdom_import(const char *text) try {
 void phast_wisdom_forget(void) try { WisdomStore::instance().forget(); } PHAST_CATCH_VOID
 int phast_wisdom_builtin(int enable) try { return WisdomStore::instance().set_builtin(enable != 0) ? 1 : 0; } PHAST_CATCH_ZERO
 size_t phast_wisdom_count(int layer) try { return WisdomStore::instance().count(layer); } PHAST_CATCH_ZERO
+int phast_debug_wisdom_lookup(size_t elem_bytes, int kind, unsigned log_n, unsigned bucket, int cus, int arch, char *buf,
+                              size_t buf_len) try {
+    if ((elem_bytes != 4 && elem_bytes != 8) || kind < 0 || kind >= kNumKinds) return -1;
+    // through lookup_all, the call a planner makes (Planner::apply_wisdom)
+    const std::map<unsigned, WisdomEntry> all = WisdomStore::instance().lookup_all(elem_bytes, kind, log_n, cus, arch);
+    const auto it = all.find(bucket);
+    if (it == all.end()) return -1;
+    if (buf && buf_len) std::snprintf(buf, buf_len, "%s", it->second.heuristic ? "heuristic" : spec_to_string(it->second.spec).c_str());
+    return it->second.layer;
+} catch (...) { return -1; }
 
 const char *phast_strerror(int code) {
     switch (code) {
@@ -279,6 +289,15 @@ int phast_options_guess(size_t input_size, phast_options *out) try {
         const PlannerR2c<T> *q = p->route_small(kind == kC2R, batch);                                                   \
         std::snprintf(buf, len, "%s", q->dit.passes.empty() ? "one-pass" : q->dit.describe_call(kind, batch).c_str());  \
         return PHAST_OK;                                                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_planner_r2c##SFX##_debug_check_guards(const phast_planner_r2c##SFX *p, size_t *bad_bytes) try {           \
+        if (!p || !bad_bytes) return PHAST_ERR_INVALID_ARG;                                                             \
+        /* the real transforms run on the inner planner's workspace pool -- and on the multi-pass twin's */             \
+        int rc = p->dit.check_guards(bad_bytes);                                                                        \
+        size_t bad_twin = 0;                                                                                            \
+        if (rc == PHAST_OK && p->twin) rc = p->twin->dit.check_guards(&bad_twin);                                       \
+        *bad_bytes += bad_twin;                                                                                         \
+        return rc;                                                                                                      \
     } PHAST_CATCH_RC                                                                                                    \
     int phast_planner_dit##SFX##_reserve_batch(phast_planner_dit##SFX *p, size_t max_batch) try {                       \
         if (!p || max_batch == 0) return PHAST_ERR_INVALID_ARG;                                                         \

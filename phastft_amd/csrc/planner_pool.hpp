@@ -244,6 +244,12 @@ template <typename T> int Planner<T>::check_guards(size_t *bad_out) const {
             for (unsigned char c : h) bad += c != kGuardFill;
         }
     }
+    if (twin) {  // one (or a few) transforms of the one-pass lengths run on the multi-pass twin: its scratches count too
+        size_t bad_twin = 0;
+        int rc = twin->check_guards(&bad_twin);
+        if (rc) return rc;
+        bad += bad_twin;
+    }
     *bad_out = bad;
     return PHAST_OK;
 }

@@ -260,9 +260,12 @@ int Planner<T>::tune_core(int kind, size_t batch, unsigned wisdom_log_n, int rin
         }
         if (rep) rep->candidates = (unsigned)screened;
         // ---- 4b. the winner must compute what the static rule's plan computes.  Every candidate is built from kernels that are
-        // parity-tested on their own, but the tuner composes them in combinations no test enumerates: before a plan is adopted
-        // its output for one set of inputs is compared with the static rule's, transform by transform, through the digests
-        // (energy, sums, a probed bin) -- far coarser than the parity gates, and enough to stop a plan whose geometry is wrong.
+        // parity-tested on their own, and tests/test_gpu_plan_space.py runs the combinations the tuner can compose -- every plan
+        // of enumerate_plans up to 2^19 points, every pass class beyond (tests/golden/plan_space.json) -- against the parity
+        // gates.  That is a test of the build that was tested; this check is the one that runs on the user's device: before a
+        // plan is adopted its output for one set of inputs is compared with the static rule's, transform by transform, through
+        // the digests (energy, sums, a probed bin) -- far coarser than the parity gates, and enough to stop a plan whose geometry
+        // is wrong.
         if (best >= 0 && med_best < (float)(1.0 - TuneKnobs::min_gain()) * med_heur) {
             DevBuf d_dig;  // [static rule | winner] x [two probed bins] x batch x 4
             rc = d_dig.alloc(4 * batch * 4 * sizeof(double));

@@ -11,7 +11,7 @@
 // measured on a device with another CU count or architecture, or by another generation of the kernels, are kept (and exported)
 // but never applied.
 //
-// Layers (kept apart, resolved at look-up), later wins: built-in wisdom (builtin_wisdom.inc: generated on an MI355X by tools/make_builtin_wisdom.py; off with
+// Layers (kept apart, resolved at look-up), the latest one whose entry applies to the device wins: built-in wisdom (builtin_wisdom.inc: generated on an MI355X by tools/make_builtin_wisdom.py; off with
 // PHAST_BUILTIN_WISDOM=0) < the file named by PHAST_WISDOM (read on first use, rewritten after every tuning run) <
 // phast_wisdom_import() < tuning runs of this process.
 //
@@ -88,8 +88,8 @@ class WisdomStore {
     bool lookup(size_t elem_bytes, int kind, unsigned log_n, unsigned bucket, int cus, int arch, WisdomEntry *out) {
         std::lock_guard<std::mutex> lk(mu_);
         load_layers_locked();
-        const WisdomEntry *e = find_locked(key(elem_bytes, kind, log_n, bucket));
-        if (!e || !e->applies(cus, arch)) return false;
+        const WisdomEntry *e = find_locked(key(elem_bytes, kind, log_n, bucket), cus, arch);
+        if (!e) return false;
         if (out) *out = *e;
         return true;
     }
@@ -100,10 +100,12 @@ class WisdomStore {
         load_layers_locked();
         const std::string prefix = key(elem_bytes, kind, log_n, 0);
         const std::string stem = prefix.substr(0, prefix.size() - 1);  // "... <log_n> "
-        for (int layer = builtin_on_ ? 0 : 1; layer < kLayers; ++layer)  // later layers overwrite earlier ones
-            for (auto it = layers_[layer].lower_bound(stem); it != layers_[layer].end() && it->first.compare(0, stem.size(), stem) == 0; ++it)
-                out[(unsigned)std::atoi(it->first.c_str() + stem.size())] = it->second;
-        for (auto it = out.begin(); it != out.end();) it = it->second.applies(cus, arch) ? std::next(it) : out.erase(it);
+        for (int layer = builtin_on_ ? 0 : 1; layer < kLayers; ++layer)
+            for (auto it = layers_[layer].lower_bound(stem); it != layers_[layer].end() && it->first.compare(0, stem.size(), stem) == 0; ++it) {
+                const unsigned bucket = (unsigned)std::atoi(it->first.c_str() + stem.size());
+                if (out.count(bucket)) continue;
+                if (const WisdomEntry *e = find_locked(it->first, cus, arch)) out[bucket] = *e;
+            }
         return out;
     }
     void record(size_t elem_bytes, int kind, unsigned log_n, unsigned bucket, const WisdomEntry &e) {
@@ -130,7 +132,9 @@ class WisdomStore {
         load_layers_locked();
         return export_locked();
     }
-    size_t count(int layer) {  // keys whose winning entry belongs to `layer` (0 built-in .. 3 measured here), -1: all keys
+    // keys whose TOPMOST entry belongs to `layer` (0 built-in .. 3 measured here), -1: all keys.  A census of the store that knows
+    // no device: an entry of a later layer counts as covering its key whether or not it would apply (lookup decides that per device)
+    size_t count(int layer) {
         std::lock_guard<std::mutex> lk(mu_);
         load_layers_locked();
         size_t c = 0;
@@ -169,10 +173,12 @@ class WisdomStore {
             ;
         return text;
     }
-    const WisdomEntry *find_locked(const std::string &k) const {
+    // the entry of the latest layer that APPLIES to the device: an entry measured on another CU count or architecture, or by
+    // another generation of the kernels, is kept and exported but does not hide an applicable entry of an earlier layer
+    const WisdomEntry *find_locked(const std::string &k, int cus, int arch) const {
         for (int l = kLayers - 1; l >= (builtin_on_ ? 0 : 1); --l) {
             auto it = layers_[l].find(k);
-            if (it != layers_[l].end()) return &it->second;
+            if (it != layers_[l].end() && it->second.applies(cus, arch)) return &it->second;
         }
         return nullptr;
     }

@@ -600,5 +600,78 @@ int phast_emu_enumerate_plans(unsigned L, size_t elem_bytes, size_t batch, const
     }
     return (int)specs.size();
 }
+}  // extern "C"
+
+// What Planner::prepare_passes (planner_plans.hpp) decides about a pass list without running anything -- restated on the
+// kernels' own host-side LDS formulas, so that it needs no device: the dynamic LDS each pass asks for (a plan with a pass over
+// 160 KiB is refused: "tile does not fit one CU's LDS"), and whether the last pass has the fused R2C form / the first pass the
+// fused C2R form (r2c_blocks / c2r_blocks > 0).
+namespace phast {
+constexpr size_t kCuLds = (size_t)160 * 1024;
+template <typename T> static size_t emu_pass_lds(const PassGeom &p) {
+    if (p.quad) return QuadBody<T>::lds_bytes(p.tw_bits);
+    if (p.wave) return p.transpose ? WaveBody<T, false, true>::lds_bytes(p.tw_bits) : WaveBody<T, true, false>::lds_bytes(p.tw_bits);
+#define PHAST_LDS(LR_, LC_, LP_)                                                                                \
+    if (p.lr == LR_ && p.lc == LC_ && p.lp == LP_)                                                              \
+        return p.transpose ? TileBody<T, LR_, LC_, LP_, false, true, plane_seq_v<T, LP_>>::lds_bytes(p.tw_bits) \
+                           : TileBody<T, LR_, LC_, LP_, true, false, plane_seq_v<T, LP_>>::lds_bytes(p.tw_bits);
+    PHAST_TILE_SHAPES(PHAST_LDS)
+    if constexpr (sizeof(T) == 4) {
+        PHAST_TILE_SHAPES_F32(PHAST_LDS)
+    }
+#undef PHAST_LDS
+    return ~(size_t)0;
+}
+// launch_r2c_last_inst's request: the exchange, the inter-pass tables (always staged) and the W_rows table
+template <typename T> static size_t emu_r2c_last_lds(const PassGeom &p) {
+#define PHAST_LDS(LR_, LC_, LP_)                                                                                         \
+    if (p.lr == LR_ && p.lc == LC_ && p.lp == LP_) {                                                                     \
+        using Body = TileBody<T, LR_, LC_, LP_, true, false, plane_seq_v<T, LP_>>;                                       \
+        return (size_t)Body::EXCH * sizeof(T) * (Body::PLANE_SEQ ? 1 : 2) + (size_t)(3u << p.tw_bits) * sizeof(cx_t<T>) + \
+               Body::TWR * sizeof(cx_t<T>);                                                                              \
+    }
+    PHAST_TILE_SHAPES(PHAST_LDS)
+#undef PHAST_LDS
+    return ~(size_t)0;
+}
+// 0 = a plan the planner builds, 1 = refused (make_passes, or a pass that does not fit the LDS)
+template <typename T> static int emu_plan_forms(unsigned L, const PlanSpec &s, bool *r2c_fused, bool *c2r_fused) {
+    *r2c_fused = *c2r_fused = false;
+    std::vector<PassGeom> ps;
+    if (!make_passes(L, s.lrs(), s.tls(), ps, s.lp, sizeof(T))) return 1;
+    for (const PassGeom &p : ps)
+        if (emu_pass_lds<T>(p) > kCuLds) return 1;
+    const PassGeom &q = ps.back(), &f = ps.front();
+    *r2c_fused = ps.size() > 1 && !q.wave && !q.quad && q.pre_tw && q.log_s_in >= q.lc + 1 && r2c_shape_ok(q.lr, q.lc, q.lp, sizeof(T)) &&
+                 emu_r2c_last_lds<T>(q) <= kCuLds;
+    *c2r_fused = ps.size() > 1 && !f.wave && !f.quad && f.transpose && !f.pre_tw && f.log_s_in >= f.lc + 1 &&
+                 c2r_shape_ok(f.lr, f.lc, f.lp, sizeof(T)) && ((emu_pass_lds<T>(f) + 15) & ~(size_t)15) <= kCuLds;
+    return 0;
+}
+}  // namespace phast
+
+extern "C" {
+// The plan space as text (tests/golden/make_plan_space.py): every spec of enumerate_plans(L, elem_bytes, 1, tl_lo, tl_hi) in the
+// form of spec_to_string, one per line, followed by a word of flags -- `x` the planner's build step refuses it, `r` its last
+// pass has the fused R2C form, `c` its first pass the fused C2R form, `-` none of these.  Returns the bytes needed (with the
+// NUL); writes only when they fit `len`.
+size_t phast_emu_list_plans(unsigned L, size_t elem_bytes, unsigned tl_lo, unsigned tl_hi, char *buf, size_t len) {
+    using namespace phast;
+    std::vector<PlanSpec> specs;
+    enumerate_plans(L, elem_bytes, 1, tl_lo, tl_hi, specs);
+    std::string out;
+    for (const PlanSpec &s : specs) {
+        bool r = false, c = false;
+        const int refused = elem_bytes == 8 ? emu_plan_forms<double>(L, s, &r, &c) : emu_plan_forms<float>(L, s, &r, &c);
+        std::string flags = std::string(refused ? "x" : "") + (r ? "r" : "") + (c ? "c" : "");
+        out += spec_to_string(s) + " " + (flags.empty() ? "-" : flags) + "\n";
+    }
+    if (buf && len >= out.size() + 1) std::memcpy(buf, out.c_str(), out.size() + 1);
+    return out.size() + 1;
+}
+// plan.hpp: tune_tile_range -- the tile sizes a tuning run with `points` in flight tries
+void phast_emu_tune_tile_range(size_t points, size_t elem_bytes, unsigned *tl_lo, unsigned *tl_hi) {
+    phast::tune_tile_range(points, elem_bytes, *tl_lo, *tl_hi);
+}
 #endif
 }

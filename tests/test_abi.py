@@ -233,6 +233,48 @@ def test_wisdom_store_without_a_device():
     P.wisdom_builtin(was)
 
 
+def test_wisdom_entries_that_do_not_apply_do_not_hide_the_ones_that_do():
+    """csrc/wisdom.hpp: find_locked / lookup_all resolve a key among the entries that APPLY to the device, top layer first.  (ADVICE
+    r06: the top layer's entry used to be picked first and only then asked whether it applies, so that an imported line measured by another
+    generation of the kernels (lib=), on another CU count or another architecture switched the built-in plan of its key off.)"""
+    import phastft_amd as P
+
+    P.wisdom_forget()
+    was = P.wisdom_builtin(True)
+    try:
+        line = next(ln for ln in open(os.path.join(ROOT, "phastft_amd", "csrc", "builtin_wisdom.inc")).read().splitlines()
+                    if ln.startswith('"f64 c2c ') and "heuristic" not in ln)[1:]
+        dt, kind, log_n, bucket, plan = line.split(" ")[:5]
+        log_n, bucket = int(log_n), int(bucket)
+        builtin = (0, plan)
+        other = "6,7@10,10:p8" if plan != "6,7@10,10:p8" else "7,6@10,10:p8"   # (any plan text: look-up does not build it)
+        assert P.debug_wisdom_lookup(dt, 0, log_n, bucket, cus=256, arch=0x950) == builtin
+        key = f"{dt} {kind} {log_n} {bucket}"
+        for header in ("phastft-hip-wisdom 1 cus=256 arch=gfx950 lib=5",    # another generation of the kernels
+                       "phastft-hip-wisdom 1 cus=304 arch=gfx950 lib=6",    # another CU count
+                       "phastft-hip-wisdom 1 cus=256 arch=gfx90a lib=6"):   # another architecture
+            P.wisdom_forget()
+            P.wisdom_import(f"{header}\n{key} {other} fuse=0 us=1.00 heur=2.00\n")
+            assert P.debug_wisdom_lookup(dt, 0, log_n, bucket, cus=256, arch=0x950) == builtin, header
+            assert f"{key} {other}" in P.wisdom_export()     # kept and exported all the same
+        # ... and where the imported line was measured, it is the one that applies (lib=5 never is)
+        assert P.debug_wisdom_lookup(dt, 0, log_n, bucket, cus=256, arch=0x90a) == (2, other)
+        P.wisdom_forget()
+        P.wisdom_import(f"phastft-hip-wisdom 1 cus=304 arch=gfx950 lib=6\n{key} {other} fuse=0 us=1.00 heur=2.00\n")
+        assert P.debug_wisdom_lookup(dt, 0, log_n, bucket, cus=304, arch=0x950) == (2, other)
+        # an applicable line of a later layer still wins over the built-in one, a text without cus= applies anywhere
+        P.wisdom_forget()
+        P.wisdom_import(f"phastft-hip-wisdom 1\n{key} {other} fuse=0 us=1.00 heur=2.00\n")
+        assert P.debug_wisdom_lookup(dt, 0, log_n, bucket, cus=256, arch=0x950) == (2, other)
+        P.wisdom_builtin(False)   # without the built-in layer a foreign line leaves nothing to apply
+        P.wisdom_forget()
+        P.wisdom_import(f"phastft-hip-wisdom 1 cus=256 arch=gfx950 lib=5\n{key} {other} fuse=0 us=1.00 heur=2.00\n")
+        assert P.debug_wisdom_lookup(dt, 0, log_n, bucket, cus=256, arch=0x950) is None
+    finally:
+        P.wisdom_forget()
+        P.wisdom_builtin(was)
+
+
 def test_wisdom_file_is_loaded_at_first_use(tmp_path):
     """PHAST_WISDOM=<path>: read when the store is first used (no device needed); PHAST_BUILTIN_WISDOM=0 leaves the built-in
     layer out.  (The rewrite after a tuning run needs a GPU: tests/test_gpu_parity_r5.py.)"""

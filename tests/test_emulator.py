@@ -643,3 +643,73 @@ def test_every_builtin_wisdom_line_is_a_candidate_of_its_tuning_run(emu):
         assert cnt > 0 and bad.value == 0 and has.value == 1, (m.group(0), cnt, bad.value)
         lines += 1
     assert lines >= 300, lines
+
+
+# ---- the plan space as a fixture (tests/golden/plan_space.json): what tests/test_gpu_plan_space.py runs on the device ----
+@pytest.fixture(scope="module")
+def plan_space():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("make_plan_space", os.path.join(ROOT, "tests", "golden", "make_plan_space.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_plan_space_fixture_is_what_the_generator_writes_now(emu, plan_space):
+    """a tile shape added to or taken from plan.hpp, a changed rule of make_passes or enumerate_plans, a new built-in wisdom
+    line: the list the GPU test runs must follow (python tests/golden/make_plan_space.py)"""
+    assert open(plan_space.PATH).read() == plan_space.generate(emu), "tests/golden/plan_space.json is stale: regenerate it"
+
+
+def test_tuning_candidates_are_in_the_plan_space_fixture(emu, plan_space):
+    """whatever batch a tuning run is for, its candidates (enumerate_plans over tune_tile_range(batch << L)) are plans the
+    fixture lists for that length: the fixture's tile range per type is a superset of every range the tuner uses"""
+    emu.phast_emu_tune_tile_range.argtypes = [C.c_size_t, C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+    emu.phast_emu_tune_tile_range.restype = None
+    space = plan_space.load()
+    ranges = {"f64": set(), "f32": set()}
+    for dt, eb in (("f64", 8), ("f32", 4)):
+        for L, batch in [(13, 1), (13, 300), (14, 64), (15, 1), (15, 4096), (16, 2), (16, 100), (17, 1), (17, 16), (17, 1024),
+                         (18, 1), (18, 8), (18, 128), (19, 1), (19, 4), (19, 33)]:
+            lo, hi = C.c_uint(), C.c_uint()
+            emu.phast_emu_tune_tile_range(batch << L, eb, C.byref(lo), C.byref(hi))
+            ranges[dt].add((lo.value, hi.value))
+            assert plan_space.TILE_RANGE[dt][0] <= lo.value and hi.value <= plan_space.TILE_RANGE[dt][1]
+            cands = {s for s, _ in plan_space.list_plans(emu, L, dt, lo.value, hi.value)}
+            listed = {e.split(" ")[0] for e in space[dt]["exhaustive"][str(L)]}
+            assert cands and cands <= listed, (dt, L, batch, sorted(cands - listed)[:5])
+    # every range tune_tile_range can give was among the samples, for both types
+    assert ranges["f64"] == {(10, 13), (10, 14), (11, 14), (12, 14)}, ranges
+    assert ranges["f32"] == {(10, 13), (10, 14), (11, 15), (12, 15)}, ranges
+
+
+def test_plan_space_cover_reaches_every_pass_class(emu, plan_space):
+    """the classes (role, kind, rows, cols) of every buildable plan the odometer lists for L = 13 .. 25, over the whole tile
+    range: each must occur in a plan of the fixture (the exhaustive lengths or the cover set), so each runs on the device"""
+    space = plan_space.load()
+
+    def covered(doc, dt):
+        have = set()
+        for group in ("exhaustive", "cover"):
+            for entries in doc[dt][group].values():
+                have |= {plan_space.class_name(c) for c in plan_space.classes_of(entries, dt)}
+        return have
+
+    for dt in ("f64", "f32"):
+        lo, hi = plan_space.TILE_RANGE[dt]
+        universe = set()
+        for L in range(13, 26):
+            universe |= {plan_space.class_name(c) for c in plan_space.classes_of(plan_space.list_plans(emu, L, dt, lo, hi), dt)}
+        assert set(space[dt]["classes"]) == universe
+        assert covered(space, dt) == universe, sorted(universe - covered(space, dt))
+        # middle passes of 512 rows and more exist from L = 21 on only, the 32-point ones of 1024 / 2048 rows from L = 24 / 25
+        assert {"middle p16 9 3", "middle p32 10 2", "middle p32 11 3"} <= universe
+        # teeth: without the cover plans that hold one of the cover's own classes the same check fails
+        only_cover = sorted(universe - {plan_space.class_name(c) for v in space[dt]["exhaustive"].values() for c in plan_space.classes_of(v, dt)})
+        assert only_cover, dt
+        gone = only_cover[len(only_cover) // 2]
+        cut = {dt: {"exhaustive": space[dt]["exhaustive"],
+                    "cover": {L: [e for e in v if gone not in {plan_space.class_name(c) for c in plan_space.pass_classes(e.split(" ")[0], dt)}]
+                              for L, v in space[dt]["cover"].items()}}}
+        assert gone not in covered(cut, dt) and covered(cut, dt) != universe, gone
