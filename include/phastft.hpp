@@ -32,6 +32,8 @@
 //                                                            nufft2d2_64/32[_with_planner] -- the same in two dimensions
 //   (none: samples on a grid only upstream)                  class PlannerNufft3d64/32, nufft3d1_64/32[_with_planner],
 //                                                            nufft3d2_64/32[_with_planner] -- the same in three dimensions
+//   (none: samples on a grid only upstream)                  class PlannerNufftT3_64/32, nufft3_64/32[_with_planner] -- the
+//                                                            non-uniform FFT of type 3 (points to arbitrary frequencies)
 //   (none: one axis only upstream)                           class PlannerNd64/32, PlannerR2cNd64/32, fft_64/32_nd[_with_planner],
 //                                                            r2c_fft_f64/f32_nd[...], c2r_fft_f64/f32_nd[...] -- every axis
 //
@@ -674,6 +676,64 @@ PHASTFT_NUFFT(1, 32, float, PlannerNufft32)
 PHASTFT_NUFFT(2, 64, double, PlannerNufft64)
 PHASTFT_NUFFT(2, 32, float, PlannerNufft32)
 #undef PHASTFT_NUFFT
+
+// ---- the non-uniform FFT of type 3 in one dimension (no reference counterpart) ----
+#define PHASTFT_PLANNER_NUFFT_T3(NAME, CT, SFX)                                                                  \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* the sources x and the target frequencies s (host doubles, any finite values, s x in turns), to the accuracy eps */\
+        NAME(Slice<const double> x, Slice<const double> s, double eps) : m_(x.len), k_(s.len) {                  \
+            check(phast_planner_nufft_t3_##SFX##_new(x.ptr, x.len, s.ptr, s.len, eps, &h_));                     \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_), m_(o.m_), k_(o.k_) { o.h_ = nullptr; }                               \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_nufft_t3_##SFX##_free(h_);                                                     \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_nufft_t3_##SFX##_describe(h_, &s[0], s.size()));                                 \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t num_points() const { return m_; }                                                            \
+        std::size_t num_targets() const { return k_; }                                                           \
+        std::size_t device_bytes() const { return phast_planner_nufft_t3_##SFX##_device_bytes(h_); }             \
+        /* the fine grid n_f */                                                                                  \
+        std::size_t grid_len() const { return phast_planner_nufft_t3_##SFX##_grid_len(h_); }                     \
+        int width() const { return phast_planner_nufft_t3_##SFX##_width(h_); }                                   \
+        /* elements of T a _dev call of `batch` transforms works in: 4 n_f batch */                              \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_nufft_t3_##SFX##_workspace_len(h_, batch); }\
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+        std::size_t m_, k_;                                                                                      \
+    };
+PHASTFT_PLANNER_NUFFT_T3(PlannerNufftT3_64, phast_planner_nufft_t3_64, 64)
+PHASTFT_PLANNER_NUFFT_T3(PlannerNufftT3_32, phast_planner_nufft_t3_32, 32)
+#undef PHASTFT_PLANNER_NUFFT_T3
+
+// one host vector of values at the sources (c_im.ptr may be null: real data) to the values at the targets; blocking.  Without a
+// planner the call builds its own from x, s and eps.
+#define PHASTFT_NUFFT_T3(SFX, T, P)                                                                              \
+    inline void nufft3_##SFX(Slice<const double> x, Slice<const double> s, Slice<const T> c_re, Slice<const T> c_im,\
+                             Slice<T> out_re, Slice<T> out_im, double eps, Direction direction = Direction::Forward) {\
+        if ((c_im.ptr && c_im.len != c_re.len) || out_re.len != out_im.len) check(PHAST_ERR_LEN_MISMATCH);       \
+        if (x.len != c_re.len || s.len != out_re.len) check(PHAST_ERR_LEN_MISMATCH);                             \
+        check(phast_nufft3_##SFX(x.ptr, x.len, s.ptr, s.len, c_re.ptr, c_im.ptr, out_re.ptr, out_im.ptr, eps,    \
+                                 static_cast<int>(direction)));                                                  \
+    }                                                                                                            \
+    inline void nufft3_##SFX##_with_planner(Slice<const T> c_re, Slice<const T> c_im, Slice<T> out_re, Slice<T> out_im,\
+                                            const P &planner, Direction direction = Direction::Forward) {        \
+        if ((c_im.ptr && c_im.len != c_re.len) || out_re.len != out_im.len) check(PHAST_ERR_LEN_MISMATCH);       \
+        check(phast_nufft3_##SFX##_with_planner(c_re.ptr, c_im.ptr, c_re.len, out_re.ptr, out_im.ptr, out_re.len,\
+                                                static_cast<int>(direction), planner.get()));                    \
+    }
+PHASTFT_NUFFT_T3(64, double, PlannerNufftT3_64)
+PHASTFT_NUFFT_T3(32, float, PlannerNufftT3_32)
+#undef PHASTFT_NUFFT_T3
 
 // ---- non-uniform FFTs of types 1 and 2 in two dimensions (no reference counterpart) ----
 #define PHASTFT_PLANNER_NUFFT2D(NAME, CT, SFX)                                                                   \

@@ -842,6 +842,60 @@ int phast_nufft3d2_32_dev(const float *d_f_re, const float *d_f_im, size_t in_di
 int phast_planner_nufft3d32_time_stages(const phast_planner_nufft3d32 *p, const float *d_in_re, const float *d_in_im, float *d_out_re, float *d_out_im, int type,
                     size_t batch, float *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
 
+/* ---- the non-uniform FFT of type 3 in one dimension (no reference counterpart; FINUFFT's type 3) ----
+ * M sources x_j (host doubles, any finite values, in a unit U) and K target frequencies s_k (host doubles, any finite values,
+ * in 1 / U); the product s_k x_j is in TURNS:
+ *
+ *     f[k] = sum_j c[j] exp(-+2 pi i s[k] x[j]),   j < M, k < K       (- PHAST_FORWARD, + PHAST_REVERSE; no scaling)
+ *
+ * to the relative accuracy eps in [1e-14, 1e-1] (f64) or [1e-6, 1e-1] (f32).  1 <= M <= 2^30, 1 <= K <= 2^30, and the fine grid
+ * n_f = the smallest power of two >= max(8 S X + w, 2 w, 8) -- X and S the half-widths of the two point sets about their centres,
+ * w the kernel width of eps -- is at most 2^28 (phast_planner_nufft_t3_*_grid_len); anything else is PHAST_ERR_INVALID_ARG before
+ * the device is touched.  Both point sets are fixed at _new.  The error grows with the conditioning of the problem,
+ * 2 pi (|C_s| + S) X 2^-53, and with nothing else that depends on the centres C_x, C_s.
+ *
+ * Data are planar (re, im); a null imaginary INPUT plane means real data.  _dev: `batch` transforms share the planner, transform b
+ * at b * in_dist (>= M) and b * out_dist (>= K); asynchronous on `stream`.  The caller's device workspace holds
+ * phast_planner_nufft_t3_*_workspace_len(p, batch) = 4 n_f batch elements of T; any work_len >= _workspace_len(p, 1) runs the
+ * batch in chunks.  The output may not overlap the input or the workspace, nor the workspace the input.  The host-slice forms
+ * block (a length that is not the planner's is PHAST_ERR_PLANNER_SIZE); phast_nufft3_64 / _32 build a planner for the one call. */
+typedef struct phast_planner_nufft_t3_64 phast_planner_nufft_t3_64; /* PlannerNufftT3_64 */
+int phast_planner_nufft_t3_64_new(const double *x, size_t m_points, const double *s, size_t k_targets, double eps, phast_planner_nufft_t3_64 **out);
+void phast_planner_nufft_t3_64_free(phast_planner_nufft_t3_64 *p);
+int phast_planner_nufft_t3_64_describe(const phast_planner_nufft_t3_64 *p, char *buf, size_t buf_len);
+size_t phast_planner_nufft_t3_64_device_bytes(const phast_planner_nufft_t3_64 *p);
+size_t phast_planner_nufft_t3_64_grid_len(const phast_planner_nufft_t3_64 *p);
+int phast_planner_nufft_t3_64_width(const phast_planner_nufft_t3_64 *p);
+size_t phast_planner_nufft_t3_64_workspace_len(const phast_planner_nufft_t3_64 *p, size_t batch);
+int phast_nufft3_64(const double *x, size_t m_points, const double *s, size_t k_targets, const double *c_re, const double *c_im, double *out_re, double *out_im, double eps,
+                    int direction);
+int phast_nufft3_64_with_planner(const double *c_re, const double *c_im, size_t m_points, double *out_re, double *out_im, size_t k_targets, int direction,
+                                 const phast_planner_nufft_t3_64 *planner);
+int phast_nufft3_64_dev(const double *d_c_re, const double *d_c_im, size_t in_dist, double *d_out_re, double *d_out_im, size_t out_dist, size_t batch,
+                        int direction, const phast_planner_nufft_t3_64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook: stage_ms[0..3] = average HIP-event milliseconds of (spread, the n_g-point transform, interpolate, post) over `reps` Forward calls at the
+ * natural distances in ONE chunk (work_len >= phast_planner_nufft_t3_*_workspace_len(p, batch)); stage_ms[4] is 0.  Blocks until done. */
+int phast_planner_nufft_t3_64_time_stages(const phast_planner_nufft_t3_64 *p, const double *d_in_re, const double *d_in_im, double *d_out_re, double *d_out_im, size_t batch,
+                    double *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_nufft_t3_32 phast_planner_nufft_t3_32; /* PlannerNufftT3_32 */
+int phast_planner_nufft_t3_32_new(const double *x, size_t m_points, const double *s, size_t k_targets, double eps, phast_planner_nufft_t3_32 **out);
+void phast_planner_nufft_t3_32_free(phast_planner_nufft_t3_32 *p);
+int phast_planner_nufft_t3_32_describe(const phast_planner_nufft_t3_32 *p, char *buf, size_t buf_len);
+size_t phast_planner_nufft_t3_32_device_bytes(const phast_planner_nufft_t3_32 *p);
+size_t phast_planner_nufft_t3_32_grid_len(const phast_planner_nufft_t3_32 *p);
+int phast_planner_nufft_t3_32_width(const phast_planner_nufft_t3_32 *p);
+size_t phast_planner_nufft_t3_32_workspace_len(const phast_planner_nufft_t3_32 *p, size_t batch);
+int phast_nufft3_32(const double *x, size_t m_points, const double *s, size_t k_targets, const float *c_re, const float *c_im, float *out_re, float *out_im, double eps,
+                    int direction);
+int phast_nufft3_32_with_planner(const float *c_re, const float *c_im, size_t m_points, float *out_re, float *out_im, size_t k_targets, int direction,
+                                 const phast_planner_nufft_t3_32 *planner);
+int phast_nufft3_32_dev(const float *d_c_re, const float *d_c_im, size_t in_dist, float *d_out_re, float *d_out_im, size_t out_dist, size_t batch,
+                        int direction, const phast_planner_nufft_t3_32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook: stage_ms[0..3] = average HIP-event milliseconds of (spread, the n_g-point transform, interpolate, post) over `reps` Forward calls at the
+ * natural distances in ONE chunk (work_len >= phast_planner_nufft_t3_*_workspace_len(p, batch)); stage_ms[4] is 0.  Blocks until done. */
+int phast_planner_nufft_t3_32_time_stages(const phast_planner_nufft_t3_32 *p, const float *d_in_re, const float *d_in_im, float *d_out_re, float *d_out_im, size_t batch,
+                    float *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+
 /* ---- multi-dimensional transforms over every axis of a row-major array (no reference counterpart; numpy fftn / ifftn /
  * rfftn / irfftn with this library's conventions).  dims[0 .. rank-1]: rank 1 .. 8, every axis 1 .. 2^29,
  * their product <= 2^30 (else PHAST_ERR_INVALID_ARG, before the device is touched).  Every axis is transformed; leading

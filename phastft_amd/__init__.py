@@ -35,6 +35,7 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
     (none: samples on a grid only)                  PlannerNufft3d64/32, nufft3d1_batched, nufft3d2_batched,
                                                     nufft3d1_64/32[_with_planner], nufft3d2_64/32[_with_planner],
                                                     nufft3d1, nufft3d2
+    (none: samples on a grid only)                  PlannerNufftT3_64/32, nufft3_batched, nufft3_64/32[_with_planner], nufft3
     (none: one axis only)                           PlannerNd64/32, fft_64/32_nd[_with_planner], fft_nd_batched,
                                                     PlannerR2cNd64/32, r2c_fft_f64/f32_nd[_with_planner],
                                                     c2r_fft_f64/f32_nd[_with_planner], r2c_nd_batched, c2r_nd_batched
@@ -94,6 +95,8 @@ __all__ = [
     "PlannerNufft3d64", "PlannerNufft3d32", "nufft3d1_batched", "nufft3d2_batched", "nufft3d1_64", "nufft3d1_32", "nufft3d2_64",
     "nufft3d2_32", "nufft3d1_64_with_planner", "nufft3d1_32_with_planner", "nufft3d2_64_with_planner", "nufft3d2_32_with_planner",
     "nufft3d1", "nufft3d2",
+    "PlannerNufftT3_64", "PlannerNufftT3_32", "nufft3_batched", "nufft3_64", "nufft3_32", "nufft3_64_with_planner",
+    "nufft3_32_with_planner", "nufft3",
     "PlannerNd64", "PlannerNd32", "fft_64_nd", "fft_32_nd", "fft_64_nd_with_planner", "fft_32_nd_with_planner", "fft_nd_batched",
     "PlannerR2cNd64", "PlannerR2cNd32", "r2c_fft_f64_nd", "r2c_fft_f32_nd", "r2c_fft_f64_nd_with_planner",
     "r2c_fft_f32_nd_with_planner", "c2r_fft_f64_nd", "c2r_fft_f32_nd", "c2r_fft_f64_nd_with_planner",
@@ -1647,6 +1650,163 @@ def nufft2(points, F, eps: float | None = None, direction=Direction.Forward):
     if not _is_torch(F) or F.dim() < 1:
         raise TypeError("need a device tensor of at least one axis")
     return _nufft(2, points, F, int(F.shape[-1]), eps, direction)
+
+
+# ---------------------------------------------------------------------------------------------
+# the non-uniform FFT of type 3 in one dimension (no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+def _host_doubles(v):
+    return np.ascontiguousarray(v.detach().cpu().numpy() if _is_torch(v) else v, dtype=np.float64).reshape(-1)
+
+
+class PlannerNufftT3_64(_AnyHandle):
+    """f64 non-uniform FFT of type 3: ``sources`` (M doubles x, any finite values, in a unit U) to ``targets`` (K doubles s, any
+    finite values, in 1 / U), the product ``s[k] * x[j]`` in turns, to the relative accuracy ``eps``:
+
+        ``f[k] = sum_j c[j] exp(-+2j pi s[k] x[j])``
+
+    with ``-`` for ``Direction.Forward`` and ``+`` for ``Direction.Reverse`` and no scaling.  1 <= M, K <= 2^30, eps in
+    [1e-14, 1e-1], and the fine grid ``grid_len`` = the smallest power of two >= max(8 S X + w, 2 w, 8) -- X and S the
+    half-widths of the two point sets -- is at most 2^28.  Both point sets are host memory and are fixed here."""
+
+    _prefix = "nufft_t3_"
+    _eps = 1e-12
+
+    def __init__(self, sources, targets, eps: float | None = None):
+        x, s = _host_doubles(sources), _host_doubles(targets)
+        eps = self._eps if eps is None else float(eps)
+        self._new(x.ctypes.data_as(C.c_void_p), x.size, s.ctypes.data_as(C.c_void_p), s.size, eps)
+        self.m = self.m_points = x.size
+        self.k = self.k_targets = s.size
+        self.eps = eps
+        self.grid_len = int(self._fn("grid_len")(self._h))
+        self.width = int(self._fn("width")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` transforms works in: 4 n_f batch, n_f = ``grid_len``.  A smaller workspace
+        of at least 4 n_f runs the batch in chunks."""
+        return self._workspace_len(batch)
+
+    def time_stages(self, in_re, in_im, out_re, out_im, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (spread, the n_g-point transform, interpolate, post) of a Forward call of ``batch``
+        transforms at the natural distances on device tensors (measurement hook)"""
+        bufs = [_Slice(in_re, self._dtype, "in_re"), _NULL if in_im is None else _Slice(in_im, self._dtype, "in_im"),
+                _Slice(out_re, self._dtype, "out_re"), _Slice(out_im, self._dtype, "out_im")]
+        return self._time("time_stages", bufs, (batch,), batch, workspace, reps)[:4]
+
+
+class PlannerNufftT3_32(PlannerNufftT3_64):
+    """f32 twin of :class:`PlannerNufftT3_64`: eps in [1e-6, 1e-1]; the points stay doubles and every table is built in f64
+    and rounded"""
+
+    _sfx = "32"
+    _dtype = np.float32
+    _eps = 1e-6
+
+
+def nufft3_batched(c_re, c_im, planner, direction=Direction.Forward, out=None, work=None, stream=None):
+    """Device-resident batch of type 3 transforms through one planner: ``c_re`` (and ``c_im``, or ``None`` for real data) are
+    torch device tensors of shape ``(batch, M)`` or ``(M,)`` of the planner's type whose last axis is contiguous; returns
+    ``(out_re, out_im)`` of shape ``(batch, K)`` or ``(K,)``.  ``out``: such a pair to write into (it must not overlap the
+    input or ``work``); ``work``: a device tensor of at least ``planner.workspace_len(1)`` elements (fewer than
+    ``planner.workspace_len(batch)`` runs the batch in chunks), by default one from torch's allocator; ``stream``: a
+    ``torch.cuda.Stream``, by default the current one."""
+    import torch
+
+    want = torch.float64 if planner._dtype == np.float64 else torch.float32
+    n_in, n_out = planner.m_points, planner.k_targets
+
+    def plane(v, what, per):
+        if not _is_torch(v) or v.device.type != "cuda" or v.dtype != want:
+            raise TypeError(f"{what}: need a {want} device tensor")
+        if v.dim() not in (1, 2) or v.shape[-1] != per or (per > 1 and v.stride(-1) != 1):  # a single element has no stride
+            raise ValueError(f"{what}: need shape (batch, {per}) or ({per},) with a contiguous last axis, not {tuple(v.shape)}")
+        rows = v.shape[0] if v.dim() == 2 else 1
+        dist = v.stride(0) if v.dim() == 2 and rows > 1 else per
+        if dist < per:
+            raise ValueError(f"{what}: rows overlap")
+        return rows, dist
+
+    batch, in_dist = plane(c_re, "c_re", n_in)
+    if c_im is not None and (plane(c_im, "c_im", n_in) != (batch, in_dist) or c_im.shape != c_re.shape):
+        raise ValueError("c_im: need the shape and the strides of c_re")
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        if out is None:
+            shape = (batch, n_out) if c_re.dim() == 2 else (n_out,)
+            out = (torch.empty(shape, dtype=want, device=c_re.device), torch.empty(shape, dtype=want, device=c_re.device))
+        out_re, out_im = out
+        rows, out_dist = plane(out_re, "out_re", n_out)
+        if rows != batch or plane(out_im, "out_im", n_out) != (batch, out_dist) or out_re.dim() != c_re.dim():
+            raise ValueError("out: need a pair of (batch, K) tensors with equal strides")
+        ws = _any_workspace(planner, batch, work)
+        _check(_call(f"phast_nufft3_{planner._sfx}_dev", c_re.data_ptr(), None if c_im is None else c_im.data_ptr(), in_dist,
+                     out_re.data_ptr(), out_im.data_ptr(), out_dist, batch, int(direction), planner._h, ws.ptr, ws.len,
+                     _stream()))
+    return out_re, out_im
+
+
+def _nufft3_host(sfx, dtype, c_re, c_im, out_re, out_im, direction, planner=None, sources=None, targets=None, eps=None):
+    x = _Slice(c_re, dtype, "c_re")
+    y = _NULL if c_im is None else _Slice(c_im, dtype, "c_im")
+    o_re, o_im = _Slice(out_re, dtype, "out_re"), _Slice(out_im, dtype, "out_im")
+    if _same_place(*(v for v in (x, y, o_re, o_im) if v is not _NULL)):
+        raise TypeError(f"nufft3_{sfx} takes host arrays (nufft3_batched takes device tensors)")
+    if (y is not _NULL and y.len != x.len) or o_re.len != o_im.len:
+        _check(2)
+    if planner is not None:
+        _check(_call(f"phast_nufft3_{sfx}_with_planner", x.ptr, y.ptr, x.len, o_re.ptr, o_im.ptr, o_re.len, int(direction),
+                     planner._h))
+        return
+    xs, ss = _host_doubles(sources), _host_doubles(targets)
+    if xs.size != x.len or ss.size != o_re.len:
+        _check(2)
+    _check(_call(f"phast_nufft3_{sfx}", xs.ctypes.data_as(C.c_void_p), xs.size, ss.ctypes.data_as(C.c_void_p), ss.size, x.ptr,
+                 y.ptr, o_re.ptr, o_im.ptr, float(eps), int(direction)))
+
+
+def nufft3_64(sources, targets, c_re, c_im, out_re, out_im, eps: float = 1e-12, direction=Direction.Forward) -> None:
+    """f64 type 3 transform of one host vector of M values at ``sources`` (``c_im`` may be ``None``: real data) into host arrays
+    of K values at ``targets``, through a planner of its own (blocking)"""
+    _nufft3_host("64", np.float64, c_re, c_im, out_re, out_im, direction, sources=sources, targets=targets, eps=eps)
+
+
+def nufft3_32(sources, targets, c_re, c_im, out_re, out_im, eps: float = 1e-6, direction=Direction.Forward) -> None:
+    """f32 twin of :func:`nufft3_64`"""
+    _nufft3_host("32", np.float32, c_re, c_im, out_re, out_im, direction, sources=sources, targets=targets, eps=eps)
+
+
+def nufft3_64_with_planner(c_re, c_im, out_re, out_im, planner: PlannerNufftT3_64, direction=Direction.Forward) -> None:
+    _nufft3_host("64", np.float64, c_re, c_im, out_re, out_im, direction, planner)
+
+
+def nufft3_32_with_planner(c_re, c_im, out_re, out_im, planner: PlannerNufftT3_32, direction=Direction.Forward) -> None:
+    _nufft3_host("32", np.float32, c_re, c_im, out_re, out_im, direction, planner)
+
+
+def nufft3(x, s, c, eps: float | None = None, direction=Direction.Forward):
+    """Type 3 non-uniform FFT of a real or complex device tensor ``c`` over its last axis (M values at the sources ``x``) at the
+    target frequencies ``s`` (``s[k] * x[j]`` in turns): a new complex tensor of shape ``c.shape[:-1] + (len(s),)``.  float64 /
+    complex128 run in f64 (eps defaults to 1e-12), float32 / complex64 in f32 (1e-6)."""
+    import torch
+
+    kinds = {torch.float64: (PlannerNufftT3_64, torch.float64), torch.complex128: (PlannerNufftT3_64, torch.float64),
+             torch.float32: (PlannerNufftT3_32, torch.float32), torch.complex64: (PlannerNufftT3_32, torch.float32)}
+    if not _is_torch(c) or c.device.type != "cuda" or c.dtype not in kinds or c.dim() < 1:
+        raise TypeError("need a float64, float32, complex128 or complex64 device tensor of at least one axis")
+    cls, real = kinds[c.dtype]
+    planner = cls(x, s, eps)
+    if c.shape[-1] != planner.m_points:
+        raise ValueError(f"the last axis holds {c.shape[-1]} values, the transform takes {planner.m_points}")
+    rows = c.reshape(-1, planner.m_points)
+    if c.is_complex():
+        c_re, c_im = rows.real.contiguous(), rows.imag.contiguous()
+    else:
+        c_re, c_im = rows.contiguous(), None
+    out = torch.empty((2, rows.shape[0], planner.k_targets), dtype=real, device=c.device)
+    if rows.shape[0]:
+        nufft3_batched(c_re, c_im, planner, direction, (out[0], out[1]))
+        torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+    return torch.complex(out[0], out[1]).reshape(c.shape[:-1] + (planner.k_targets,))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -24,6 +24,7 @@
 #include "planner_nd.hpp"
 #include "planner_nufft2d.hpp"
 #include "planner_nufft3d.hpp"
+#include "planner_nufft_t3.hpp"
 
 // ================================================================================================
 // C ABI
@@ -52,6 +53,8 @@ struct phast_planner_nufft2d64 : Nufft2dPlanner<double> {};
 struct phast_planner_nufft2d32 : Nufft2dPlanner<float> {};
 struct phast_planner_nufft3d64 : Nufft3dPlanner<double> {};
 struct phast_planner_nufft3d32 : Nufft3dPlanner<float> {};
+struct phast_planner_nufft_t3_64 : NufftT3Planner<double> {};
+struct phast_planner_nufft_t3_32 : NufftT3Planner<float> {};
 struct phast_planner_nd64 : NdPlanner<double> {};
 struct phast_planner_nd32 : NdPlanner<float> {};
 struct phast_planner_r2c_nd64 : RealNdPlanner<double> {};
@@ -548,7 +551,7 @@ PHAST_HANDLE_API(any64) PHAST_HANDLE_API(any32) PHAST_HANDLE_API(r2c_any64) PHAS
 PHAST_HANDLE_API(dct64) PHAST_HANDLE_API(dct32) PHAST_HANDLE_API(stft64) PHAST_HANDLE_API(stft32)
 PHAST_HANDLE_API(conv64) PHAST_HANDLE_API(conv32) PHAST_HANDLE_API(czt64) PHAST_HANDLE_API(czt32)
 PHAST_HANDLE_API(nufft64) PHAST_HANDLE_API(nufft32) PHAST_HANDLE_API(nufft2d64) PHAST_HANDLE_API(nufft2d32)
-PHAST_HANDLE_API(nufft3d64) PHAST_HANDLE_API(nufft3d32)
+PHAST_HANDLE_API(nufft3d64) PHAST_HANDLE_API(nufft3d32) PHAST_HANDLE_API(nufft_t3_64) PHAST_HANDLE_API(nufft_t3_32)
 PHAST_HANDLE_API(nd64) PHAST_HANDLE_API(nd32) PHAST_HANDLE_API(r2c_nd64) PHAST_HANDLE_API(r2c_nd32)
 
 // Arbitrary lengths (Bluestein, planner_any.hpp): arguments are checked before the device is touched
@@ -982,6 +985,51 @@ PHAST_NUFFT2D_API(32, float)
     PHAST_NUFFT3D_CALLS(SFX, T, 2)
 PHAST_NUFFT3D_API(64, double)
 PHAST_NUFFT3D_API(32, float)
+
+// The non-uniform FFT of type 3 (planner_nufft_t3.hpp): M sources x, K target frequencies s, s x in turns.  The counts, eps,
+// the points and the size of the fine grid are checked before the device is touched; the one-shot form builds a planner of
+// its own for the call.
+#define PHAST_NUFFT_T3_API(SFX, T)                                                                                      \
+    int phast_planner_nufft_t3_##SFX##_new(const double *x, size_t m_points, const double *s, size_t k_targets,         \
+                                           double eps, phast_planner_nufft_t3_##SFX **out) try {                        \
+        return nufft_t3_planner_new(x, m_points, s, k_targets, eps, sizeof(T) == 4, out);                               \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_nufft_t3_##SFX##_grid_len(const phast_planner_nufft_t3_##SFX *p) try {                         \
+        return p ? (size_t)p->grid.nf : 0;                                                                              \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_nufft_t3_##SFX##_width(const phast_planner_nufft_t3_##SFX *p) try {                               \
+        return p ? p->grid.w : 0;                                                                                       \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_nufft_t3_##SFX##_time_stages(const phast_planner_nufft_t3_##SFX *p, const T *d_in_re,             \
+                                                   const T *d_in_im, T *d_out_re, T *d_out_im, size_t batch, T *d_work, \
+                                                   size_t work_len, int reps, float *stage_ms, void *stream) try {      \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(d_in_re, d_in_im, d_out_re, d_out_im, batch, d_work, work_len, reps, stage_ms,            \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_nufft3_##SFX(const double *x, size_t m_points, const double *s, size_t k_targets, const T *c_re,          \
+                           const T *c_im, T *out_re, T *out_im, double eps, int direction) try {                        \
+        if (!c_re || !out_re || !out_im) return PHAST_ERR_INVALID_ARG;                                                  \
+        phast_planner_nufft_t3_##SFX *p = nullptr;                                                                      \
+        int rc = nufft_t3_planner_new(x, m_points, s, k_targets, eps, sizeof(T) == 4, &p);                              \
+        if (rc) return rc;                                                                                              \
+        std::unique_ptr<phast_planner_nufft_t3_##SFX> own(p);                                                           \
+        return p->nufft_host(direction, c_re, c_im, m_points, out_re, out_im, k_targets);                               \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_nufft3_##SFX##_with_planner(const T *c_re, const T *c_im, size_t m_points, T *out_re, T *out_im,          \
+                                          size_t k_targets, int direction, const phast_planner_nufft_t3_##SFX *p) try { \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->nufft_host(direction, c_re, c_im, m_points, out_re, out_im, k_targets);                               \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_nufft3_##SFX##_dev(const T *d_c_re, const T *d_c_im, size_t in_dist, T *d_out_re, T *d_out_im,            \
+                                 size_t out_dist, size_t batch, int direction, const phast_planner_nufft_t3_##SFX *p,   \
+                                 T *d_work, size_t work_len, void *stream) try {                                        \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->nufft_dev(direction, d_c_re, d_c_im, in_dist, d_out_re, d_out_im, out_dist, batch, d_work, work_len,  \
+                            static_cast<hipStream_t>(stream));                                                          \
+    } PHAST_CATCH_RC
+PHAST_NUFFT_T3_API(64, double)
+PHAST_NUFFT_T3_API(32, float)
 
 // Multi-dimensional transforms (planner_nd.hpp): the shape and the lengths are checked before the device is touched
 #define PHAST_ND_PLANNER_API(NAME, KIND)                                                                                \

@@ -156,8 +156,10 @@ struct NufftQuad {
         }
         a1 = 4 * q * (double)w / (double)grid;
     }
-    double operator()(long long k) const {
-        const double a = a1 * (double)k;
+    double operator()(long long k) const { return at((double)k); }
+    // the same rule at a real argument: phi^ at k / n_g turns per cell, |k| <= n_g / 4 (nufft_t3.hpp)
+    double at(double k) const {
+        const double a = a1 * k;
         double acc = 0;
         for (size_t i = 0; i < s.size(); ++i) acc += f[i] * std::cos(a * s[i]);
         return acc;

@@ -74,15 +74,8 @@ template <typename T> struct NufftPlanner : ConvCore<T> {
     size_t in_len(int type) const { return type == 1 ? points : modes; }
     size_t out_len(int type) const { return type == 1 ? modes : points; }
 
-    // `c` transforms of type 1 or 2: input planes (re, im or null) at b * in_dist -> output planes at b * out_dist, through
-    // the workspace wk (2 c n_g elements: c re planes, then c im planes).  ev: optional 6 events; ev[0..3] bound the three stages
-    int run_chunk(const Planner<T> *pl, const typename Planner<T>::Lease &L, const typename Planner<T>::Choice &ch, int type,
-                  int direction, const T *x_re, const T *x_im, size_t in_dist, T *o_re, T *o_im, size_t out_dist, size_t c,
-                  T *wk, hipEvent_t *ev = nullptr) const {
-        hipStream_t s = L.stream;
-        constexpr unsigned V = 16 / sizeof(T);
-        T *w_re = wk, *w_im = wk + c * m;
-        auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    // the arguments every launch of a chunk shares: the tables, the sizes and the caller's distances
+    NufftArgs chunk_args(size_t in_dist, size_t out_dist) const {
         NufftArgs a{};
         a.xs = d_xs;
         a.perm = d_perm;
@@ -94,35 +87,77 @@ template <typename T> struct NufftPlanner : ConvCore<T> {
         a.m = points;
         a.log_g = log_m;
         a.w = w;
-        if (ev) PHAST_HIP(hipEventRecord(ev[0], s));
+        return a;
+    }
+    static bool aligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+    // The three stages of a chunk of `c` transforms on the workspace wk (2 c n_g elements: c re planes, then c im planes), each
+    // callable on its own: the type-3 planner (planner_nufft_t3.hpp) puts a stage of its own in front of `transform` and runs
+    // `interpolate` as it stands.
+    // stage a of type 2: the caller's modes (re, im or null) at b * a.in_dist over phi^ into the slots of the grid
+    int pre(NufftArgs a, const T *x_re, const T *x_im, size_t c, T *wk, hipStream_t s) const {
+        constexpr unsigned V = 16 / sizeof(T);
         a.in_re = x_re;
         a.in_im = x_im;
-        a.out_re = w_re;
-        a.out_im = w_im;
-        if (type == 1) {
-            a.groups = c * m;
-            PHAST_HIP(launch_nufft<T>(0, false, a, s));
-        } else {
-            a.groups = c * (m / V);
-            PHAST_HIP(launch_nufft<T>(2, al(x_re) && al(x_im) && al(wk) && in_dist % V == 0, a, s));
-        }
-        if (ev) PHAST_HIP(hipEventRecord(ev[1], s));
-        // Reverse by the swap trick: FFT of (im, re) = (im, re) of the transform with the + sign
+        a.out_re = wk;
+        a.out_im = wk + c * m;
+        a.groups = c * (m / V);
+        PHAST_HIP(launch_nufft<T>(2, aligned(x_re) && aligned(x_im) && aligned(wk) && a.in_dist % V == 0, a, s));
+        return PHAST_OK;
+    }
+    // stage b: the n_g-point transform of the c grids, in place.  Reverse by the swap trick: FFT of (im, re) = (im, re) of the
+    // transform with the + sign
+    int transform(const Planner<T> *pl, const typename Planner<T>::Lease &L, const typename Planner<T>::Choice &ch, int direction,
+                  size_t c, T *wk) const {
+        T *w_re = wk, *w_im = wk + c * m;
         T *e_re = direction == PHAST_REVERSE ? w_im : w_re, *e_im = direction == PHAST_REVERSE ? w_re : w_im;
-        int rc = pl->exec_in(L, e_re, e_im, m, 0, e_re, e_im, m, 0, c, 1.0, nullptr, nullptr, nullptr, nullptr, &ch);
-        if (rc) return rc;
-        if (ev) PHAST_HIP(hipEventRecord(ev[2], s));
-        a.in_re = w_re;
-        a.in_im = w_im;
+        return pl->exec_in(L, e_re, e_im, m, 0, e_re, e_im, m, 0, c, 1.0, nullptr, nullptr, nullptr, nullptr, &ch);
+    }
+    // stage c of type 2: the grids at the sorted points, onto the caller's planes at b * a.out_dist
+    int interpolate(NufftArgs a, size_t c, const T *wk, T *o_re, T *o_im, hipStream_t s) const {
+        a.in_re = wk;
+        a.in_im = wk + c * m;
         a.out_re = o_re;
         a.out_im = o_im;
+        a.groups = c * points;
+        PHAST_HIP(launch_nufft<T>(1, false, a, s));
+        return PHAST_OK;
+    }
+
+    // `c` transforms of type 1 or 2: input planes (re, im or null) at b * in_dist -> output planes at b * out_dist, through
+    // the workspace wk (2 c n_g elements: c re planes, then c im planes).  ev: optional 6 events; ev[0..3] bound the three stages
+    int run_chunk(const Planner<T> *pl, const typename Planner<T>::Lease &L, const typename Planner<T>::Choice &ch, int type,
+                  int direction, const T *x_re, const T *x_im, size_t in_dist, T *o_re, T *o_im, size_t out_dist, size_t c,
+                  T *wk, hipEvent_t *ev = nullptr) const {
+        hipStream_t s = L.stream;
+        constexpr unsigned V = 16 / sizeof(T);
+        T *w_re = wk, *w_im = wk + c * m;
+        NufftArgs a = chunk_args(in_dist, out_dist);
+        int rc;
+        if (ev) PHAST_HIP(hipEventRecord(ev[0], s));
         if (type == 1) {
+            a.in_re = x_re;
+            a.in_im = x_im;
+            a.out_re = w_re;
+            a.out_im = w_im;
+            a.groups = c * m;
+            PHAST_HIP(launch_nufft<T>(0, false, a, s));
+        } else if ((rc = pre(a, x_re, x_im, c, wk, s))) {
+            return rc;
+        }
+        if (ev) PHAST_HIP(hipEventRecord(ev[1], s));
+        if ((rc = transform(pl, L, ch, direction, c, wk))) return rc;
+        if (ev) PHAST_HIP(hipEventRecord(ev[2], s));
+        if (type == 1) {
+            a.in_re = w_re;
+            a.in_im = w_im;
+            a.out_re = o_re;
+            a.out_im = o_im;
             a.gpt = (unsigned)((modes + V - 1) / V);
             a.groups = c * a.gpt;
-            PHAST_HIP(launch_nufft<T>(3, al(o_re) && al(o_im) && al(wk) && out_dist % V == 0, a, s));
-        } else {
-            a.groups = c * points;
-            PHAST_HIP(launch_nufft<T>(1, false, a, s));
+            PHAST_HIP(launch_nufft<T>(3, aligned(o_re) && aligned(o_im) && aligned(wk) && out_dist % V == 0, a, s));
+        } else if ((rc = interpolate(a, c, wk, o_re, o_im, s))) {
+            return rc;
         }
         if (ev)
             for (int i = 3; i < 6; ++i) PHAST_HIP(hipEventRecord(ev[i], s));

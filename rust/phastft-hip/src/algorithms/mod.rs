@@ -8,6 +8,7 @@ pub mod dit;
 pub mod nufft;
 pub mod nufft2d;
 pub mod nufft3d;
+pub mod nufft_t3;
 pub mod r2c;
 pub mod r2r;
 pub mod stft;

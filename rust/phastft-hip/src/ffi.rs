@@ -358,6 +358,37 @@ extern "C" {
         out_len: usize, direction: c_int, planner: *const Opaque) -> c_int;
     pub(crate) fn phast_nufft3d2_32_dev(in_re: *const f32, in_im: *const f32, in_dist: usize, out_re: *mut f32, out_im: *mut f32,
         out_dist: usize, batch: usize, direction: c_int, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // the non-uniform FFT of type 3
+    pub(crate) fn phast_planner_nufft_t3_64_new(x: *const f64, m_points: usize, s: *const f64, k_targets: usize, eps: f64, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft_t3_64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_nufft_t3_64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_nufft_t3_64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_nufft_t3_64_grid_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_nufft_t3_64_width(p: *const Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft_t3_64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_nufft_t3_64_time_stages(p: *const Opaque, in_re: *const f64, in_im: *const f64, out_re: *mut f64,
+        out_im: *mut f64, batch: usize, work: *mut f64, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_nufft3_64(x: *const f64, m_points: usize, s: *const f64, k_targets: usize, c_re: *const f64, c_im: *const f64,
+        out_re: *mut f64, out_im: *mut f64, eps: f64, direction: c_int) -> c_int;
+    pub(crate) fn phast_nufft3_64_with_planner(c_re: *const f64, c_im: *const f64, m_points: usize, out_re: *mut f64, out_im: *mut f64,
+        k_targets: usize, direction: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_nufft3_64_dev(c_re: *const f64, c_im: *const f64, in_dist: usize, out_re: *mut f64, out_im: *mut f64,
+        out_dist: usize, batch: usize, direction: c_int, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_nufft_t3_32_new(x: *const f64, m_points: usize, s: *const f64, k_targets: usize, eps: f64, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft_t3_32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_nufft_t3_32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_nufft_t3_32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_nufft_t3_32_grid_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_nufft_t3_32_width(p: *const Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft_t3_32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_nufft_t3_32_time_stages(p: *const Opaque, in_re: *const f32, in_im: *const f32, out_re: *mut f32,
+        out_im: *mut f32, batch: usize, work: *mut f32, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_nufft3_32(x: *const f64, m_points: usize, s: *const f64, k_targets: usize, c_re: *const f32, c_im: *const f32,
+        out_re: *mut f32, out_im: *mut f32, eps: f64, direction: c_int) -> c_int;
+    pub(crate) fn phast_nufft3_32_with_planner(c_re: *const f32, c_im: *const f32, m_points: usize, out_re: *mut f32, out_im: *mut f32,
+        k_targets: usize, direction: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_nufft3_32_dev(c_re: *const f32, c_im: *const f32, in_dist: usize, out_re: *mut f32, out_im: *mut f32,
+        out_dist: usize, batch: usize, direction: c_int, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // DCT / DST of types II and III (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/r2r.rs)
     pub(crate) fn phast_planner_dct64_new(n: usize, out: *mut *mut Opaque) -> c_int;
     pub(crate) fn phast_planner_dct32_new(n: usize, out: *mut *mut Opaque) -> c_int;

@@ -79,6 +79,9 @@ pub use algorithms::nufft3d::{
     nufft3d2_32_dev, nufft3d2_32_with_planner, nufft3d2_64, nufft3d2_64_dev, nufft3d2_64_with_planner,
 };
 pub use planner::{PlannerNufft3d32, PlannerNufft3d64};
+// the non-uniform FFT of type 3 (an extension beyond PhastFT 0.3.0)
+pub use algorithms::nufft_t3::{nufft3_32, nufft3_32_dev, nufft3_32_with_planner, nufft3_64, nufft3_64_dev, nufft3_64_with_planner};
+pub use planner::{PlannerNufftT3_32, PlannerNufftT3_64};
 // multi-dimensional real transforms (an extension beyond PhastFT 0.3.0)
 pub use algorithms::r2c::{
     c2r_fft_f32_nd, c2r_fft_f32_nd_dev, c2r_fft_f32_nd_with_planner, c2r_fft_f64_nd, c2r_fft_f64_nd_dev,

@@ -598,6 +598,60 @@ impl_planner_nufft3d!(PlannerNufft3d32, phast_planner_nufft3d32_new, phast_plann
                       phast_planner_nufft3d32_grid_dim, phast_planner_nufft3d32_width,
                       phast_planner_nufft3d32_workspace_len);
 
+macro_rules! impl_planner_nufft_t3 {
+    ($nufft:ident, $new:ident, $free:ident, $grid_len:ident, $width:ident, $ws_len:ident) => {
+        /// An extension beyond PhastFT 0.3.0: the non-uniform FFT of type 3 of the sources `x` (any finite values, in a unit U)
+        /// at the target frequencies `s` (any finite values, in 1 / U; `s[k] * x[j]` in turns), to the relative accuracy `eps`.
+        /// Immutable after `new`, like the reference's planners.
+        #[allow(non_camel_case_types)]
+        pub struct $nufft {
+            pub(crate) h: *mut Opaque,
+            pub(crate) m: usize,
+            pub(crate) k: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in
+        // device buffers of its own (host-slice calls)
+        unsafe impl Send for $nufft {}
+        unsafe impl Sync for $nufft {}
+        impl $nufft {
+            /// Panics with "invalid argument" unless 1 <= x.len(), s.len() <= 2^30, every x and s is finite, eps lies in
+            /// [1e-14, 1e-1] (f64) or [1e-6, 1e-1] (f32) and the fine grid is at most 2^28 points
+            pub fn new(x: &[f64], s: &[f64], eps: f64) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe { ffi::$new(x.as_ptr(), x.len(), s.as_ptr(), s.len(), eps, &mut h) });
+                Self { h, m: x.len(), k: s.len() }
+            }
+            pub fn num_points(&self) -> usize {
+                self.m
+            }
+            pub fn num_targets(&self) -> usize {
+                self.k
+            }
+            /// the fine grid n_f: the smallest power of two >= max(8 S X + width, 2 width, 8), X and S the half-widths
+            pub fn grid_len(&self) -> usize {
+                unsafe { ffi::$grid_len(self.h) }
+            }
+            /// the width of the spreading kernel in grid cells
+            pub fn width(&self) -> usize {
+                unsafe { ffi::$width(self.h) as usize }
+            }
+            /// elements of the workspace a device call of `batch` transforms works in: 4 n_f batch
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+        }
+        impl Drop for $nufft {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_nufft_t3!(PlannerNufftT3_64, phast_planner_nufft_t3_64_new, phast_planner_nufft_t3_64_free,
+                       phast_planner_nufft_t3_64_grid_len, phast_planner_nufft_t3_64_width, phast_planner_nufft_t3_64_workspace_len);
+impl_planner_nufft_t3!(PlannerNufftT3_32, phast_planner_nufft_t3_32_new, phast_planner_nufft_t3_32_free,
+                       phast_planner_nufft_t3_32_grid_len, phast_planner_nufft_t3_32_width, phast_planner_nufft_t3_32_workspace_len);
+
 macro_rules! impl_planner_nd {
     ($nd:ident, $new:ident, $free:ident, $ws_len:ident, $what:literal) => {
         #[doc = concat!("An extension beyond PhastFT 0.3.0, whose planners transform one axis: ", $what, " over every axis of a ",
