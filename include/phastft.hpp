@@ -31,7 +31,8 @@
 //   (none: samples on a grid only upstream)                  class PlannerNufft2d64/32, nufft2d1_64/32[_with_planner],
 //                                                            nufft2d2_64/32[_with_planner] -- the same in two dimensions
 //   (none: samples on a grid only upstream)                  class PlannerNufft3d64/32, nufft3d1_64/32[_with_planner],
-//                                                            nufft3d2_64/32[_with_planner] -- the same in three dimensions
+//                                                            nufft3d2_64/32[_with_planner] -- the same in three dimensions;
+//                                                            all three: from_device / set_points_dev -- points in device memory
 //   (none: samples on a grid only upstream)                  class PlannerNufftT3_64/32, nufft3_64/32[_with_planner] -- the
 //                                                            non-uniform FFT of type 3 (points to arbitrary frequencies)
 //   (none: one axis only upstream)                           class PlannerNd64/32, PlannerR2cNd64/32, fft_64/32_nd[_with_planner],
@@ -632,6 +633,20 @@ PHASTFT_CZT(32, float, PlannerCzt32)
         ~NAME() {                                                                                                \
             if (h_) phast_planner_nufft##SFX##_free(h_);                                                         \
         }                                                                                                        \
+        /* the same from m_points doubles in DEVICE memory, sorted on the device into the tables the constructor builds on the\
+           host; ordered after the earlier work of `stream`, blocks until the planner is built */\
+        static NAME from_device(std::size_t n_modes, const double *d_x, std::size_t m_points, double eps,        \
+                                void *stream = nullptr) {                                                        \
+            CT *h = nullptr;                                                                                     \
+            check(phast_planner_nufft##SFX##_new_dev(n_modes, d_x, m_points, eps, stream, &h));                  \
+            return NAME(h, n_modes, m_points);                                                                   \
+        }                                                                                                        \
+        /* new points, the same number of them, from device memory: the tables are rewritten in place (a captured graph\
+           stays valid).  Ordered after the earlier work of `stream` ONLY: work on other streams that uses the planner must\
+           have finished.  Blocks; a rejected point set leaves the planner as it was */                          \
+        void set_points_dev(const double *d_x, std::size_t m_points, void *stream = nullptr) {                   \
+            check(phast_planner_nufft##SFX##_set_points_dev(h_, d_x, m_points, stream));                         \
+        }                                                                                                        \
         const CT *get() const { return h_; }                                                                     \
         std::string describe() const {                                                                           \
             std::string s(4096, '\0');                                                                           \
@@ -648,6 +663,7 @@ PHASTFT_CZT(32, float, PlannerCzt32)
         std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_nufft##SFX##_workspace_len(h_, batch); }\
                                                                                                                  \
       private:                                                                                                   \
+        NAME(CT *h, std::size_t n, std::size_t m) : h_(h), n_(n), m_(m) {}                                       \
         CT *h_ = nullptr;                                                                                        \
         std::size_t n_, m_;                                                                                      \
     };
@@ -752,6 +768,17 @@ PHASTFT_NUFFT_T3(32, float, PlannerNufftT3_32)
         ~NAME() {                                                                                                \
             if (h_) phast_planner_nufft2d##SFX##_free(h_);                                                       \
         }                                                                                                        \
+        /* the same from m_points doubles per coordinate in DEVICE memory: as PlannerNufft64::from_device */     \
+        static NAME from_device(std::size_t n1, std::size_t n2, const double *d_x, const double *d_y, std::size_t m_points,\
+                                double eps, void *stream = nullptr) {                                            \
+            CT *h = nullptr;                                                                                     \
+            check(phast_planner_nufft2d##SFX##_new_dev(n1, n2, d_x, d_y, m_points, eps, stream, &h));            \
+            return NAME(h, n1, n2, m_points);                                                                    \
+        }                                                                                                        \
+        /* new points, the same number of them, from device memory: as PlannerNufft64::set_points_dev */         \
+        void set_points_dev(const double *d_x, const double *d_y, std::size_t m_points, void *stream = nullptr) {\
+            check(phast_planner_nufft2d##SFX##_set_points_dev(h_, d_x, d_y, m_points, stream));                  \
+        }                                                                                                        \
         const CT *get() const { return h_; }                                                                     \
         std::string describe() const {                                                                           \
             std::string s(4096, '\0');                                                                           \
@@ -771,6 +798,7 @@ PHASTFT_NUFFT_T3(32, float, PlannerNufftT3_32)
         std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_nufft2d##SFX##_workspace_len(h_, batch); }\
                                                                                                                  \
       private:                                                                                                   \
+        NAME(CT *h, std::size_t n1, std::size_t n2, std::size_t m) : h_(h), n1_(n1), n2_(n2), m_(m) {}           \
         CT *h_ = nullptr;                                                                                        \
         std::size_t n1_, n2_, m_;                                                                                \
     };
@@ -821,6 +849,18 @@ PHASTFT_NUFFT2D(2, 32, float, PlannerNufft2d32)
         ~NAME() {                                                                                                \
             if (h_) phast_planner_nufft3d##SFX##_free(h_);                                                       \
         }                                                                                                        \
+        /* the same from m_points doubles per coordinate in DEVICE memory: as PlannerNufft64::from_device */     \
+        static NAME from_device(std::size_t n1, std::size_t n2, std::size_t n3, const double *d_x, const double *d_y,\
+                                const double *d_z, std::size_t m_points, double eps, void *stream = nullptr) {   \
+            CT *h = nullptr;                                                                                     \
+            check(phast_planner_nufft3d##SFX##_new_dev(n1, n2, n3, d_x, d_y, d_z, m_points, eps, stream, &h));   \
+            return NAME(h, n1, n2, n3, m_points);                                                                \
+        }                                                                                                        \
+        /* new points, the same number of them, from device memory: as PlannerNufft64::set_points_dev */         \
+        void set_points_dev(const double *d_x, const double *d_y, const double *d_z, std::size_t m_points,       \
+                            void *stream = nullptr) {                                                            \
+            check(phast_planner_nufft3d##SFX##_set_points_dev(h_, d_x, d_y, d_z, m_points, stream));             \
+        }                                                                                                        \
         const CT *get() const { return h_; }                                                                     \
         std::string describe() const {                                                                           \
             std::string s(4096, '\0');                                                                           \
@@ -841,6 +881,7 @@ PHASTFT_NUFFT2D(2, 32, float, PlannerNufft2d32)
         std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_nufft3d##SFX##_workspace_len(h_, batch); }\
                                                                                                                  \
       private:                                                                                                   \
+        NAME(CT *h, std::size_t n1, std::size_t n2, std::size_t n3, std::size_t m) : h_(h), n1_(n1), n2_(n2), n3_(n3), m_(m) {}\
         CT *h_ = nullptr;                                                                                        \
         std::size_t n1_, n2_, n3_, m_;                                                                           \
     };

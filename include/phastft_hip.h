@@ -644,9 +644,25 @@ int phast_planner_czt32_time_stages(const phast_planner_czt32 *p, const float *d
  * inputs (PHAST_ERR_INVALID_ARG).  The planner is immutable and holds no per-call state; no floating-point atomics are used: the
  * bits of a transform do not depend on the batch, the chunking, the alignment, the stream or graph replay.  Host-slice calls take
  * one vector, stage through the device and block (a length that is not the planner's is PHAST_ERR_PLANNER_SIZE);
- * phast_nufft1_64 / phast_nufft2_64 / _32 build a planner for the one call. */
+ * phast_nufft1_64 / phast_nufft2_64 / _32 build a planner for the one call.
+ *
+ * Points in DEVICE memory: _new_dev is _new with `d_x_turns` a device pointer; the points are sorted on the device
+ * by a deterministic stable radix sort, into the very tables _new builds on the host, so a transform gives the same bits through
+ * either.  _set_points_dev gives an existing planner (built by either) new points, THE SAME M of them (another m_points is
+ * PHAST_ERR_PLANNER_SIZE): the tables are rewritten in place, at the same addresses, so a HIP graph captured through the planner
+ * stays valid and, replayed, transforms at the new points; nothing else of the planner changes.  Both order themselves after the
+ * earlier work of `stream`, allocate their temporary device memory (16 M bytes and a little) inside the call, free it, and BLOCK
+ * until the tables are written.  A point that is not finite, a null pointer or a stream that is capturing is
+ * PHAST_ERR_INVALID_ARG: _new_dev then builds no planner, and _set_points_dev leaves the planner as it was (the new points are
+ * checked and sorted in temporaries first).  _set_points_dev orders itself after the earlier work of `stream` ONLY: as with _free,
+ * the caller must have finished the work on other streams that uses the planner, and no other thread may use the planner during
+ * the call. */
 typedef struct phast_planner_nufft64 phast_planner_nufft64; /* PlannerNufft64 */
 int phast_planner_nufft64_new(size_t n_modes, const double *x_turns, size_t m_points, double eps, phast_planner_nufft64 **out);
+int phast_planner_nufft64_new_dev(size_t n_modes, const double *d_x_turns, size_t m_points, double eps, void *stream, phast_planner_nufft64 **out);
+int phast_planner_nufft64_set_points_dev(phast_planner_nufft64 *p, const double *d_x_turns, size_t m_points, void *stream);
+/* measurement hook (tools/nufft_sort_rate.py): one _set_points_dev; stage_ms[0..2] = the milliseconds of its keys, sort and tables stages */
+int phast_planner_nufft64_time_set_points(phast_planner_nufft64 *p, const double *d_x_turns, size_t m_points, float *stage_ms, void *stream);
 void phast_planner_nufft64_free(phast_planner_nufft64 *p);
 int phast_planner_nufft64_describe(const phast_planner_nufft64 *p, char *buf, size_t buf_len);
 size_t phast_planner_nufft64_device_bytes(const phast_planner_nufft64 *p);
@@ -672,6 +688,10 @@ int phast_planner_nufft64_time_stages(const phast_planner_nufft64 *p, const doub
                                       size_t batch, double *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
 typedef struct phast_planner_nufft32 phast_planner_nufft32; /* PlannerNufft32 */
 int phast_planner_nufft32_new(size_t n_modes, const double *x_turns, size_t m_points, double eps, phast_planner_nufft32 **out);
+int phast_planner_nufft32_new_dev(size_t n_modes, const double *d_x_turns, size_t m_points, double eps, void *stream, phast_planner_nufft32 **out);
+int phast_planner_nufft32_set_points_dev(phast_planner_nufft32 *p, const double *d_x_turns, size_t m_points, void *stream);
+/* measurement hook (tools/nufft_sort_rate.py): one _set_points_dev; stage_ms[0..2] = the milliseconds of its keys, sort and tables stages */
+int phast_planner_nufft32_time_set_points(phast_planner_nufft32 *p, const double *d_x_turns, size_t m_points, float *stage_ms, void *stream);
 void phast_planner_nufft32_free(phast_planner_nufft32 *p);
 int phast_planner_nufft32_describe(const phast_planner_nufft32 *p, char *buf, size_t buf_len);
 size_t phast_planner_nufft32_device_bytes(const phast_planner_nufft32 *p);
@@ -717,6 +737,12 @@ int phast_planner_nufft32_time_stages(const phast_planner_nufft32 *p, const floa
  * planner for the one call. */
 typedef struct phast_planner_nufft2d64 phast_planner_nufft2d64; /* PlannerNufft2d64 */
 int phast_planner_nufft2d64_new(size_t n1, size_t n2, const double *x_turns, const double *y_turns, size_t m_points, double eps, phast_planner_nufft2d64 **out);
+/* points in device memory: _new_dev, _set_points_dev and the hook as the one-dimensional planner's (d_x and d_y: M doubles each) */
+int phast_planner_nufft2d64_new_dev(size_t n1, size_t n2, const double *d_x_turns, const double *d_y_turns, size_t m_points, double eps, void *stream,
+                                    phast_planner_nufft2d64 **out);
+int phast_planner_nufft2d64_set_points_dev(phast_planner_nufft2d64 *p, const double *d_x_turns, const double *d_y_turns, size_t m_points, void *stream);
+int phast_planner_nufft2d64_time_set_points(phast_planner_nufft2d64 *p, const double *d_x_turns, const double *d_y_turns, size_t m_points, float *stage_ms,
+                                            void *stream);
 void phast_planner_nufft2d64_free(phast_planner_nufft2d64 *p);
 int phast_planner_nufft2d64_describe(const phast_planner_nufft2d64 *p, char *buf, size_t buf_len);
 size_t phast_planner_nufft2d64_device_bytes(const phast_planner_nufft2d64 *p);
@@ -744,6 +770,11 @@ int phast_planner_nufft2d64_time_stages(const phast_planner_nufft2d64 *p, const 
                     size_t batch, double *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
 typedef struct phast_planner_nufft2d32 phast_planner_nufft2d32; /* PlannerNufft2d32 */
 int phast_planner_nufft2d32_new(size_t n1, size_t n2, const double *x_turns, const double *y_turns, size_t m_points, double eps, phast_planner_nufft2d32 **out);
+int phast_planner_nufft2d32_new_dev(size_t n1, size_t n2, const double *d_x_turns, const double *d_y_turns, size_t m_points, double eps, void *stream,
+                                    phast_planner_nufft2d32 **out);
+int phast_planner_nufft2d32_set_points_dev(phast_planner_nufft2d32 *p, const double *d_x_turns, const double *d_y_turns, size_t m_points, void *stream);
+int phast_planner_nufft2d32_time_set_points(phast_planner_nufft2d32 *p, const double *d_x_turns, const double *d_y_turns, size_t m_points, float *stage_ms,
+                                            void *stream);
 void phast_planner_nufft2d32_free(phast_planner_nufft2d32 *p);
 int phast_planner_nufft2d32_describe(const phast_planner_nufft2d32 *p, char *buf, size_t buf_len);
 size_t phast_planner_nufft2d32_device_bytes(const phast_planner_nufft2d32 *p);
@@ -791,6 +822,13 @@ int phast_planner_nufft2d32_time_stages(const phast_planner_nufft2d32 *p, const 
  * planner's is PHAST_ERR_PLANNER_SIZE); phast_nufft3d1_64 / phast_nufft3d2_64 / _32 build a planner for the one call. */
 typedef struct phast_planner_nufft3d64 phast_planner_nufft3d64; /* PlannerNufft3d64 */
 int phast_planner_nufft3d64_new(size_t n1, size_t n2, size_t n3, const double *x_turns, const double *y_turns, const double *z_turns, size_t m_points, double eps, phast_planner_nufft3d64 **out);
+/* points in device memory: _new_dev, _set_points_dev and the hook as the one-dimensional planner's (d_x, d_y and d_z: M doubles each) */
+int phast_planner_nufft3d64_new_dev(size_t n1, size_t n2, size_t n3, const double *d_x_turns, const double *d_y_turns, const double *d_z_turns, size_t m_points,
+                                    double eps, void *stream, phast_planner_nufft3d64 **out);
+int phast_planner_nufft3d64_set_points_dev(phast_planner_nufft3d64 *p, const double *d_x_turns, const double *d_y_turns, const double *d_z_turns, size_t m_points,
+                                           void *stream);
+int phast_planner_nufft3d64_time_set_points(phast_planner_nufft3d64 *p, const double *d_x_turns, const double *d_y_turns, const double *d_z_turns,
+                                            size_t m_points, float *stage_ms, void *stream);
 void phast_planner_nufft3d64_free(phast_planner_nufft3d64 *p);
 int phast_planner_nufft3d64_describe(const phast_planner_nufft3d64 *p, char *buf, size_t buf_len);
 size_t phast_planner_nufft3d64_device_bytes(const phast_planner_nufft3d64 *p);
@@ -817,6 +855,12 @@ int phast_planner_nufft3d64_time_stages(const phast_planner_nufft3d64 *p, const 
                     size_t batch, double *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
 typedef struct phast_planner_nufft3d32 phast_planner_nufft3d32; /* PlannerNufft3d32 */
 int phast_planner_nufft3d32_new(size_t n1, size_t n2, size_t n3, const double *x_turns, const double *y_turns, const double *z_turns, size_t m_points, double eps, phast_planner_nufft3d32 **out);
+int phast_planner_nufft3d32_new_dev(size_t n1, size_t n2, size_t n3, const double *d_x_turns, const double *d_y_turns, const double *d_z_turns, size_t m_points,
+                                    double eps, void *stream, phast_planner_nufft3d32 **out);
+int phast_planner_nufft3d32_set_points_dev(phast_planner_nufft3d32 *p, const double *d_x_turns, const double *d_y_turns, const double *d_z_turns, size_t m_points,
+                                           void *stream);
+int phast_planner_nufft3d32_time_set_points(phast_planner_nufft3d32 *p, const double *d_x_turns, const double *d_y_turns, const double *d_z_turns,
+                                            size_t m_points, float *stage_ms, void *stream);
 void phast_planner_nufft3d32_free(phast_planner_nufft3d32 *p);
 int phast_planner_nufft3d32_describe(const phast_planner_nufft3d32 *p, char *buf, size_t buf_len);
 size_t phast_planner_nufft3d32_device_bytes(const phast_planner_nufft3d32 *p);

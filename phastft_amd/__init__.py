@@ -1460,7 +1460,53 @@ def zoom_fft(x, fn, m: int | None = None, fs: float = 2.0, endpoint: bool = Fals
 # ---------------------------------------------------------------------------------------------
 # non-uniform FFTs of types 1 and 2 in one dimension (no reference counterpart)
 # ---------------------------------------------------------------------------------------------
-class PlannerNufft64(_AnyHandle):
+def _device_points(*coords):
+    """``(pointers, M)`` of the coordinate arrays of a point set in device memory: contiguous float64 device tensors of M
+    values each.  Anything else is a :class:`TypeError`: nothing is copied or converted behind the caller's back."""
+    import torch
+
+    for v in coords:
+        if not _is_torch(v) or v.device.type != "cuda" or v.dtype != torch.float64 or not v.is_contiguous():
+            raise TypeError("points in device memory: need contiguous float64 device tensors")
+    m = coords[0].numel()
+    if any(v.numel() != m for v in coords):
+        raise ValueError("points in device memory: the coordinate arrays differ in length")
+    return [C.c_void_p(v.data_ptr()) for v in coords], m
+
+
+class _DevicePoints:
+    """``from_device`` and ``set_points`` of the NUFFT planners of types 1 and 2: the points stay in device memory and are
+    sorted there, into the very tables the host constructor builds, so the transforms give the same bits through either."""
+
+    @classmethod
+    def _from_device(cls, n_modes, coords, eps, stream):
+        import torch
+
+        ptrs, m = _device_points(*coords)
+        self = cls.__new__(cls)
+        eps = cls._eps if eps is None else float(eps)
+        shape = tuple(int(v) for v in n_modes) if isinstance(n_modes, (tuple, list)) else (int(n_modes),)
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            self._new(*shape, *ptrs, m, eps, _stream(), ctor="new_dev")
+        self._describe_points(shape[0] if len(shape) == 1 else shape, m, eps)
+        return self
+
+    def _set_points(self, coords, stream) -> None:
+        import torch
+
+        ptrs, m = _device_points(*coords)
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            _check(self._fn("set_points_dev")(self._h, *ptrs, m, _stream()))
+
+    def time_set_points(self, *coords):
+        """HIP-event milliseconds of the keys, sort and tables stages of one ``set_points`` (measurement hook)"""
+        ptrs, m = _device_points(*coords)
+        ms = (C.c_float * 3)()
+        _check(self._fn("time_set_points")(self._h, *ptrs, m, ms, _stream()))
+        return [float(x) for x in ms]
+
+
+class PlannerNufft64(_DevicePoints, _AnyHandle):
     """f64 non-uniform FFTs of ``points`` (M doubles in turns, any finite value, reduced mod 1) and ``n_modes`` modes in numpy
     ``fftfreq`` order, ``k = fftfreq(n_modes) * n_modes``, to the relative accuracy ``eps``:
 
@@ -1468,7 +1514,8 @@ class PlannerNufft64(_AnyHandle):
         type 2 (modes -> points)   ``c[j] = sum_m F[m] exp(-+2j pi k[m] x[j])``
 
     with ``-`` for ``Direction.Forward`` and ``+`` for ``Direction.Reverse`` and no scaling.  1 <= n_modes <= 2^28,
-    1 <= M <= 2^30, eps in [1e-14, 1e-1].  The points are host memory (an array or a sequence) and are sorted once here."""
+    1 <= M <= 2^30, eps in [1e-14, 1e-1].  The points are host memory (an array or a sequence) and are sorted once here;
+    :meth:`from_device` takes them from device memory, :meth:`set_points` replaces them."""
 
     _prefix = "nufft"
     _eps = 1e-12
@@ -1477,8 +1524,26 @@ class PlannerNufft64(_AnyHandle):
         x = np.ascontiguousarray(points.detach().cpu().numpy() if _is_torch(points) else points, dtype=np.float64).reshape(-1)
         eps = self._eps if eps is None else float(eps)
         self._new(n_modes, x.ctypes.data_as(C.c_void_p), x.size, eps)
+        self._describe_points(n_modes, x.size, eps)
+
+    @classmethod
+    def from_device(cls, n_modes: int, points, eps: float | None = None, stream=None):
+        """The planner for ``points`` given as a contiguous float64 device tensor, sorted on the device.  ``stream``: a
+        ``torch.cuda.Stream`` whose earlier work produced the points, by default the current one.  Blocks until the planner is
+        built; a point that is not finite is an error and no planner is built.  Any other kind of ``points`` is a
+        :class:`TypeError`."""
+        return cls._from_device(n_modes, (points,), eps, stream)
+
+    def set_points(self, points, stream=None) -> None:
+        """New points for this planner, the same number of them, as a contiguous float64 device tensor: the planner's tables are
+        rewritten in place (a captured graph stays valid and, replayed, transforms at the new points).  Orders itself after the
+        earlier work of ``stream`` (default: the current stream) ONLY -- work on other streams that uses the planner must have
+        finished -- and blocks until done.  A point that is not finite is an error and the planner keeps its old points."""
+        self._set_points((points,), stream)
+
+    def _describe_points(self, n_modes, m, eps):
         self.n = self.n_modes = n_modes
-        self.m = self.m_points = x.size
+        self.m = self.m_points = m
         self.eps = eps
         self.grid_len = int(self._fn("grid_len")(self._h))
         self.width = int(self._fn("width")(self._h))
@@ -1812,7 +1877,7 @@ def nufft3(x, s, c, eps: float | None = None, direction=Direction.Forward):
 # ---------------------------------------------------------------------------------------------
 # non-uniform FFTs of types 1 and 2 in two dimensions (no reference counterpart)
 # ---------------------------------------------------------------------------------------------
-class PlannerNufft2d64(_AnyHandle):
+class PlannerNufft2d64(_DevicePoints, _AnyHandle):
     """f64 non-uniform FFTs of the M points ``(x[j], y[j])`` (doubles in turns, any finite value, reduced mod 1 per coordinate)
     and ``n_modes = (n1, n2)`` modes, row-major, each axis in numpy ``fftfreq`` order (``k1`` pairs with x, ``k2`` with y), to
     the relative accuracy ``eps``:
@@ -1822,7 +1887,8 @@ class PlannerNufft2d64(_AnyHandle):
 
     with ``-`` for ``Direction.Forward`` and ``+`` for ``Direction.Reverse`` and no scaling.  n1, n2 >= 1, the fine grid
     ``grid_len = grid_shape[0] * grid_shape[1] <= 2^28``, 1 <= M <= 2^30, eps in [1e-14, 1e-1].  The points are host memory
-    (arrays or sequences) and are sorted once here."""
+    (arrays or sequences) and are sorted once here; :meth:`from_device` takes them from device memory, :meth:`set_points`
+    replaces them."""
 
     _prefix = "nufft2d"
     _eps = 1e-12
@@ -1834,9 +1900,22 @@ class PlannerNufft2d64(_AnyHandle):
             _check(2)
         eps = self._eps if eps is None else float(eps)
         self._new(n1, n2, px.ctypes.data_as(C.c_void_p), py.ctypes.data_as(C.c_void_p), px.size, eps)
+        self._describe_points((n1, n2), px.size, eps)
+
+    @classmethod
+    def from_device(cls, n_modes, x, y, eps: float | None = None, stream=None):
+        """as :meth:`PlannerNufft64.from_device`, the coordinates as two contiguous float64 device tensors of M values"""
+        return cls._from_device(tuple(n_modes), (x, y), eps, stream)
+
+    def set_points(self, x, y, stream=None) -> None:
+        """as :meth:`PlannerNufft64.set_points`"""
+        self._set_points((x, y), stream)
+
+    def _describe_points(self, n_modes, m, eps):
+        n1, n2 = n_modes
         self.n_modes = (n1, n2)
         self.n = n1 * n2
-        self.m = self.m_points = px.size
+        self.m = self.m_points = m
         self.eps = eps
         self.grid_len = int(self._fn("grid_len")(self._h))
         self.grid_shape = (int(self._fn("grid_rows")(self._h)), int(self._fn("grid_cols")(self._h)))
@@ -2031,7 +2110,7 @@ def nufft2d2(x, y, F, eps: float | None = None, direction=Direction.Forward):
 # ---------------------------------------------------------------------------------------------
 # non-uniform FFTs of types 1 and 2 in three dimensions (no reference counterpart)
 # ---------------------------------------------------------------------------------------------
-class PlannerNufft3d64(_AnyHandle):
+class PlannerNufft3d64(_DevicePoints, _AnyHandle):
     """f64 non-uniform FFTs of the M points ``(x[j], y[j], z[j])`` (doubles in turns, any finite value, reduced mod 1 per coordinate)
     and ``n_modes = (n1, n2, n3)`` modes, row-major, each axis in numpy ``fftfreq`` order (``k1`` pairs with x, ``k2`` with y, ``k3`` with z), to
     the relative accuracy ``eps``:
@@ -2041,7 +2120,8 @@ class PlannerNufft3d64(_AnyHandle):
 
     with ``-`` for ``Direction.Forward`` and ``+`` for ``Direction.Reverse`` and no scaling.  n1, n2, n3 >= 1, the fine grid
     ``grid_len = prod(grid_shape) <= 2^28``, 1 <= M <= 2^30, eps in [1e-14, 1e-1].  The points are host memory
-    (arrays or sequences) and are sorted once here."""
+    (arrays or sequences) and are sorted once here; :meth:`from_device` takes them from device memory, :meth:`set_points`
+    replaces them."""
 
     _prefix = "nufft3d"
     _eps = 1e-12
@@ -2053,9 +2133,22 @@ class PlannerNufft3d64(_AnyHandle):
             _check(2)
         eps = self._eps if eps is None else float(eps)
         self._new(n1, n2, n3, px.ctypes.data_as(C.c_void_p), py.ctypes.data_as(C.c_void_p), pz.ctypes.data_as(C.c_void_p), px.size, eps)
+        self._describe_points((n1, n2, n3), px.size, eps)
+
+    @classmethod
+    def from_device(cls, n_modes, x, y, z, eps: float | None = None, stream=None):
+        """as :meth:`PlannerNufft64.from_device`, the coordinates as three contiguous float64 device tensors of M values"""
+        return cls._from_device(tuple(n_modes), (x, y, z), eps, stream)
+
+    def set_points(self, x, y, z, stream=None) -> None:
+        """as :meth:`PlannerNufft64.set_points`"""
+        self._set_points((x, y, z), stream)
+
+    def _describe_points(self, n_modes, m, eps):
+        n1, n2, n3 = n_modes
         self.n_modes = (n1, n2, n3)
         self.n = n1 * n2 * n3
-        self.m = self.m_points = px.size
+        self.m = self.m_points = m
         self.eps = eps
         self.grid_len = int(self._fn("grid_len")(self._h))
         self.grid_shape = tuple(int(self._fn("grid_dim")(self._h, axis)) for axis in range(3))

@@ -857,6 +857,21 @@ PHAST_CZT_API(32, float)
                                        phast_planner_nufft##SFX **out) try {                                            \
         return nufft_planner_new(n_modes, x_turns, m_points, eps, sizeof(T) == 4, out);                                 \
     } PHAST_CATCH_RC                                                                                                    \
+    int phast_planner_nufft##SFX##_new_dev(size_t n_modes, const double *d_x_turns, size_t m_points, double eps,        \
+                                           void *stream, phast_planner_nufft##SFX **out) try {                          \
+        return nufft_planner_new_dev(n_modes, d_x_turns, m_points, eps, sizeof(T) == 4,                                 \
+                                     static_cast<hipStream_t>(stream), out);                                            \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_planner_nufft##SFX##_set_points_dev(phast_planner_nufft##SFX *p, const double *d_x_turns,                 \
+                                                  size_t m_points, void *stream) try {                                  \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->set_points_dev(d_x_turns, m_points, static_cast<hipStream_t>(stream));                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_planner_nufft##SFX##_time_set_points(phast_planner_nufft##SFX *p, const double *d_x_turns,                \
+                                                   size_t m_points, float *stage_ms, void *stream) try {                \
+        if (!p || !stage_ms) return PHAST_ERR_INVALID_ARG;                                                              \
+        return p->set_points_dev(d_x_turns, m_points, static_cast<hipStream_t>(stream), stage_ms);                      \
+    } PHAST_CATCH_RC                                                                                                    \
     size_t phast_planner_nufft##SFX##_grid_len(const phast_planner_nufft##SFX *p) try {                                 \
         return p ? p->m : 0;                                                                                            \
     } PHAST_CATCH_ZERO                                                                                                  \
@@ -906,6 +921,23 @@ PHAST_NUFFT_API(32, float)
     int phast_planner_nufft2d##SFX##_new(size_t n1, size_t n2, const double *x_turns, const double *y_turns,            \
                                          size_t m_points, double eps, phast_planner_nufft2d##SFX **out) try {           \
         return nufft2d_planner_new(n1, n2, x_turns, y_turns, m_points, eps, sizeof(T) == 4, out);                       \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_planner_nufft2d##SFX##_new_dev(size_t n1, size_t n2, const double *d_x_turns, const double *d_y_turns,    \
+                                             size_t m_points, double eps, void *stream,                                 \
+                                             phast_planner_nufft2d##SFX **out) try {                                    \
+        return nufft2d_planner_new_dev(n1, n2, d_x_turns, d_y_turns, m_points, eps, sizeof(T) == 4,                     \
+                                       static_cast<hipStream_t>(stream), out);                                          \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_planner_nufft2d##SFX##_set_points_dev(phast_planner_nufft2d##SFX *p, const double *d_x_turns,             \
+                                                    const double *d_y_turns, size_t m_points, void *stream) try {       \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->set_points_dev(d_x_turns, d_y_turns, m_points, static_cast<hipStream_t>(stream));                     \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_planner_nufft2d##SFX##_time_set_points(phast_planner_nufft2d##SFX *p, const double *d_x_turns,            \
+                                                     const double *d_y_turns, size_t m_points, float *stage_ms,         \
+                                                     void *stream) try {                                                \
+        if (!p || !stage_ms) return PHAST_ERR_INVALID_ARG;                                                              \
+        return p->set_points_dev(d_x_turns, d_y_turns, m_points, static_cast<hipStream_t>(stream), stage_ms);           \
     } PHAST_CATCH_RC                                                                                                    \
     size_t phast_planner_nufft2d##SFX##_grid_len(const phast_planner_nufft2d##SFX *p) try {                             \
         return p ? p->cells : 0;                                                                                        \
@@ -963,6 +995,25 @@ PHAST_NUFFT2D_API(32, float)
                                          const double *z_turns, size_t m_points, double eps,                            \
                                          phast_planner_nufft3d##SFX **out) try {                                        \
         return nufft3d_planner_new(n1, n2, n3, x_turns, y_turns, z_turns, m_points, eps, sizeof(T) == 4, out);          \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_planner_nufft3d##SFX##_new_dev(size_t n1, size_t n2, size_t n3, const double *d_x_turns,                  \
+                                             const double *d_y_turns, const double *d_z_turns, size_t m_points,         \
+                                             double eps, void *stream, phast_planner_nufft3d##SFX **out) try {          \
+        return nufft3d_planner_new_dev(n1, n2, n3, d_x_turns, d_y_turns, d_z_turns, m_points, eps, sizeof(T) == 4,      \
+                                       static_cast<hipStream_t>(stream), out);                                          \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_planner_nufft3d##SFX##_set_points_dev(phast_planner_nufft3d##SFX *p, const double *d_x_turns,             \
+                                                    const double *d_y_turns, const double *d_z_turns, size_t m_points,  \
+                                                    void *stream) try {                                                 \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->set_points_dev(d_x_turns, d_y_turns, d_z_turns, m_points, static_cast<hipStream_t>(stream));          \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_planner_nufft3d##SFX##_time_set_points(phast_planner_nufft3d##SFX *p, const double *d_x_turns,            \
+                                                     const double *d_y_turns, const double *d_z_turns, size_t m_points, \
+                                                     float *stage_ms, void *stream) try {                               \
+        if (!p || !stage_ms) return PHAST_ERR_INVALID_ARG;                                                              \
+        return p->set_points_dev(d_x_turns, d_y_turns, d_z_turns, m_points, static_cast<hipStream_t>(stream),           \
+                                 stage_ms);                                                                             \
     } PHAST_CATCH_RC                                                                                                    \
     size_t phast_planner_nufft3d##SFX##_grid_len(const phast_planner_nufft3d##SFX *p) try {                             \
         return p ? p->cells : 0;                                                                                        \

@@ -39,11 +39,14 @@ struct CztFrac {
 
 // (v / 2^down) mod 1 on the grid (v finite; down = 1 halves the step).  v = +-mant 2^(e - 53) with mant < 2^53, so the
 // value is mant shifted left by 75 + e - down places of the 128-bit word, wrapped; a negative v is the two's complement.
-inline CztFrac czt_frac(double v, int down) {
-    int e = 0;
-    const double f = std::frexp(std::fabs(v), &e);
-    const unsigned long long mant = (unsigned long long)std::ldexp(f, 53);
-    const long long sh = 75ll + e - down;
+// Plain arithmetic on the bits of the double, so that host and device code share it (nufft_sort.hip): a normal v has
+// mant = 2^52 | fraction field and e = exponent field - 1022; a zero or a subnormal lies far below 2^-128 and is cut to 0.
+PHAST_HD CztFrac czt_frac(double v, int down) {
+    unsigned long long bits = 0;
+    __builtin_memcpy(&bits, &v, sizeof bits);
+    const int field = (int)((bits >> 52) & 0x7ffull);
+    const unsigned long long mant = field ? (bits & 0xfffffffffffffull) | (1ull << 52) : 0;
+    const long long sh = 75ll + (field - 1022) - down;
     CztFrac r{0, 0};
     if (mant != 0 && sh < 128 && sh > -53) {
         if (sh >= 64) {

@@ -51,9 +51,13 @@ inline unsigned long long nufft_grid(unsigned long long n, int w) {
 }
 
 // 1 <= N <= 2^28, 1 <= M <= 2^30, eps in [1e-14, 1e-1] (f64) or [1e-6, 1e-1] (f32), every x_j finite
-inline bool nufft_bad_args(unsigned long long n, unsigned long long m, const double *x, double eps, bool f32) {
+// the part that does not read the points (they may be in device memory: nufft_sort.hpp)
+inline bool nufft_bad_sizes(unsigned long long n, unsigned long long m, const double *x, double eps, bool f32) {
     if (n == 0 || n > kNufftMaxModes || m == 0 || m > kNufftMaxPoints || !x) return true;
-    if (!(eps >= (f32 ? 1e-6 : 1e-14) && eps <= 1e-1)) return true;
+    return !(eps >= (f32 ? 1e-6 : 1e-14) && eps <= 1e-1);
+}
+inline bool nufft_bad_args(unsigned long long n, unsigned long long m, const double *x, double eps, bool f32) {
+    if (nufft_bad_sizes(n, m, x, eps, f32)) return true;
     for (unsigned long long j = 0; j < m; ++j)
         if (!std::isfinite(x[j])) return true;
     return false;
@@ -96,8 +100,9 @@ PHAST_HD unsigned long long nufft_slot(unsigned long long m, unsigned long long 
 }
 
 // a fraction of a turn as a double in [0, 1), TRUNCATED to 53 significant bits (rounding could reach 1.0); the top
-// log2 n_g <= 29 bits -- the cell -- are kept whatever the leading zeros
-inline double nufft_turns(CztFrac f) {
+// log2 n_g <= 29 bits -- the cell -- are kept whatever the leading zeros.  The double is put together from its bits (the 53
+// leading bits of the fraction, the exponent from the count of zeros above them), so host and device code share it
+PHAST_HD double nufft_turns(CztFrac f) {
     unsigned long long hi = f.hi, lo = f.lo;
     int exp2 = 0;
     if (hi == 0) {
@@ -108,7 +113,11 @@ inline double nufft_turns(CztFrac f) {
     if (hi == 0) return 0.0;
     const int lz = __builtin_clzll(hi);
     if (lz) hi = (hi << lz) | (lo >> (64 - lz));
-    return std::ldexp((double)(hi >> 11), exp2 - lz - 53);
+    // (hi >> 11) 2^(exp2 - lz - 53) with hi >> 11 in [2^52, 2^53): the exponent field is 1022 + exp2 - lz >= 895
+    const unsigned long long bits = ((unsigned long long)(1022 + exp2 - lz) << 52) | ((hi >> 11) & 0xfffffffffffffull);
+    double r;
+    __builtin_memcpy(&r, &bits, sizeof r);
+    return r;
 }
 
 // Gauss-Legendre nodes and weights on [-1, 1] (Newton's iteration on P_n from the Chebyshev guess)

@@ -25,13 +25,18 @@ namespace phast {
 constexpr unsigned long long kNufft2dMaxGrid = 1ull << 28;  // G = g1 g2: cell_start stays below 1 GiB, one f64 transform below 8 GiB
 
 // N1, N2 >= 1, G = g1 g2 <= 2^28, 1 <= M <= 2^30, eps in [1e-14, 1e-1] (f64) or [1e-6, 1e-1] (f32), every coordinate finite
-inline bool nufft2d_bad_args(unsigned long long n1, unsigned long long n2, unsigned long long m, const double *x, const double *y,
-                             double eps, bool f32) {
+// the part that does not read the points (they may be in device memory: nufft_sort.hpp)
+inline bool nufft2d_bad_sizes(unsigned long long n1, unsigned long long n2, unsigned long long m, const double *x, const double *y,
+                              double eps, bool f32) {
     if (n1 == 0 || n2 == 0 || n1 > kNufft2dMaxGrid || n2 > kNufft2dMaxGrid) return true;
     if (m == 0 || m > kNufftMaxPoints || !x || !y) return true;
     if (!(eps >= (f32 ? 1e-6 : 1e-14) && eps <= 1e-1)) return true;
     const int w = nufft_width(eps);
-    if (nufft_grid(n1, w) > kNufft2dMaxGrid / nufft_grid(n2, w)) return true;  // both are powers of two <= 2^29
+    return nufft_grid(n1, w) > kNufft2dMaxGrid / nufft_grid(n2, w);  // both are powers of two <= 2^29
+}
+inline bool nufft2d_bad_args(unsigned long long n1, unsigned long long n2, unsigned long long m, const double *x, const double *y,
+                             double eps, bool f32) {
+    if (nufft2d_bad_sizes(n1, n2, m, x, y, eps, f32)) return true;
     for (unsigned long long j = 0; j < m; ++j)
         if (!std::isfinite(x[j]) || !std::isfinite(y[j])) return true;
     return false;

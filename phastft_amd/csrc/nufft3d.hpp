@@ -32,15 +32,20 @@ constexpr unsigned kNufft3dTile1 = 4, kNufft3dTile2 = 8, kNufft3dTile3 = 8;
 constexpr unsigned kNufft3dChunk = 128;
 
 // N_i >= 1, G = g1 g2 g3 <= 2^28, 1 <= M <= 2^30, eps in [1e-14, 1e-1] (f64) or [1e-6, 1e-1] (f32), every coordinate finite
-inline bool nufft3d_bad_args(unsigned long long n1, unsigned long long n2, unsigned long long n3, unsigned long long m, const double *x,
-                             const double *y, const double *z, double eps, bool f32) {
+// the part that does not read the points (they may be in device memory: nufft_sort.hpp)
+inline bool nufft3d_bad_sizes(unsigned long long n1, unsigned long long n2, unsigned long long n3, unsigned long long m, const double *x,
+                              const double *y, const double *z, double eps, bool f32) {
     if (n1 == 0 || n2 == 0 || n3 == 0 || n1 > kNufft3dMaxGrid || n2 > kNufft3dMaxGrid || n3 > kNufft3dMaxGrid) return true;
     if (m == 0 || m > kNufftMaxPoints || !x || !y || !z) return true;
     if (!(eps >= (f32 ? 1e-6 : 1e-14) && eps <= 1e-1)) return true;
     const int w = nufft_width(eps);
     // each is a power of two <= 2^29: neither quotient nor comparison overflows
     const unsigned long long room = kNufft3dMaxGrid / nufft_grid(n1, w);
-    if (room == 0 || nufft_grid(n2, w) > room || nufft_grid(n3, w) > room / nufft_grid(n2, w)) return true;
+    return room == 0 || nufft_grid(n2, w) > room || nufft_grid(n3, w) > room / nufft_grid(n2, w);
+}
+inline bool nufft3d_bad_args(unsigned long long n1, unsigned long long n2, unsigned long long n3, unsigned long long m, const double *x,
+                             const double *y, const double *z, double eps, bool f32) {
+    if (nufft3d_bad_sizes(n1, n2, n3, m, x, y, z, eps, f32)) return true;
     for (unsigned long long j = 0; j < m; ++j)
         if (!std::isfinite(x[j]) || !std::isfinite(y[j]) || !std::isfinite(z[j])) return true;
     return false;

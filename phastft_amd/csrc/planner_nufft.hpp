@@ -1,6 +1,8 @@
 // planner_nufft.hpp -- NufftPlanner<T>: non-uniform FFTs of types 1 and 2 (nufft.hpp) of M points and N modes on an inner
-// Planner<T>(n_g).  Immutable after init: the inner planner, the point set sorted by grid cell (positions, permutation, cell
-// starts) and the N reciprocals 1 / phi^(k) on the device.  What a call mutates is the caller's workspace (_dev calls) or a
+// Planner<T>(n_g).  Immutable after init but for set_points_dev: the inner planner, the point set sorted by grid cell (positions,
+// permutation, cell starts) and the N reciprocals 1 / phi^(k) on the device.  The points come from host memory (init: sorted on
+// the host) or from device memory (init_dev, set_points_dev: sorted on the device, nufft_sort.hpp, to the same bits).  What a
+// transform mutates is the caller's workspace (_dev calls) or a
 // workspace of the inner planner's pool (host-slice calls), so graph capture and concurrent streams and threads need nothing
 // beyond what the engine already does.  Of ConvCore (planner_any.hpp) it uses the inner planner, the single-transform
 // engine plan and the chunk loop; it has no convolution table.
@@ -8,6 +10,7 @@
 
 #include "nufft.hpp"
 #include "planner_any.hpp"
+#include "planner_nufft_sort.hpp"
 
 namespace phast {
 
@@ -31,17 +34,14 @@ template <typename T> struct NufftPlanner : ConvCore<T> {
             if (p) hipFree(p);
     }
 
-    // `x`: M host doubles in turns; the arguments were checked by nufft_bad_args
-    int init(size_t n_modes, const double *x, size_t m_points, double eps_) {
+    // what does not depend on the points: the sizes, the inner planner, 1 / phi^ on the device, and room for the point tables
+    int init_grid(size_t n_modes, size_t m_points, double eps_) {
         modes = n_modes;
         points = m_points;
         eps = eps_;
         w = nufft_width(eps);
         int rc = this->init_core((size_t)nufft_grid(modes, w));
         if (rc) return rc;
-        std::vector<double> xs(points);
-        std::vector<uint32_t> perm(points), cell(m + 1);
-        nufft_bin(x, points, log_m, xs.data(), perm.data(), cell.data());
         // 1 / phi^(k) in double, rounded to T; phi^ is even in k
         std::vector<T> inv(modes);
         const NufftQuad hat(w, m);
@@ -55,11 +55,46 @@ template <typename T> struct NufftPlanner : ConvCore<T> {
         PHAST_HIP(hipMalloc(reinterpret_cast<void **>(&d_perm), points * sizeof(uint32_t)));
         PHAST_HIP(hipMalloc(reinterpret_cast<void **>(&d_cell), (m + 1) * sizeof(uint32_t)));
         PHAST_HIP(hipMalloc(reinterpret_cast<void **>(&d_inv), modes * sizeof(T)));
+        PHAST_HIP(hipMemcpy(d_inv, inv.data(), modes * sizeof(T), hipMemcpyHostToDevice));
+        return PHAST_OK;
+    }
+
+    // `x`: M host doubles in turns; the arguments were checked by nufft_bad_args
+    int init(size_t n_modes, const double *x, size_t m_points, double eps_) {
+        int rc = init_grid(n_modes, m_points, eps_);
+        if (rc) return rc;
+        std::vector<double> xs(points);
+        std::vector<uint32_t> perm(points), cell(m + 1);
+        nufft_bin(x, points, log_m, xs.data(), perm.data(), cell.data());
+        PHAST_ON_DEVICE(device);
         PHAST_HIP(hipMemcpy(d_xs, xs.data(), points * sizeof(double), hipMemcpyHostToDevice));
         PHAST_HIP(hipMemcpy(d_perm, perm.data(), points * sizeof(uint32_t), hipMemcpyHostToDevice));
         PHAST_HIP(hipMemcpy(d_cell, cell.data(), (m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-        PHAST_HIP(hipMemcpy(d_inv, inv.data(), modes * sizeof(T), hipMemcpyHostToDevice));
         return PHAST_OK;
+    }
+
+    // as init, with `d_x`: M doubles in device memory (nufft_sort.hpp), ordered after the earlier work of `s`; blocks.  The
+    // arguments but the points' values were checked by nufft_bad_sizes; PHAST_ERR_INVALID_ARG for a point that is not finite
+    int init_dev(size_t n_modes, const double *d_x, size_t m_points, double eps_, hipStream_t s) {
+        int rc = init_grid(n_modes, m_points, eps_);
+        if (rc) return rc;
+        PHAST_ON_DEVICE(device);
+        return nufft_sort_build(d_x, nullptr, nullptr, points, log_m, 0, 0, d_perm, d_cell, d_xs, nullptr, nullptr, s);
+    }
+
+    // New points for this planner, the same M of them (PHAST_ERR_PLANNER_SIZE otherwise), from device memory: the point tables
+    // are rewritten IN PLACE, at the same addresses, so a HIP graph captured through the planner stays valid and, replayed,
+    // transforms at the new points.  The grid, the width, 1 / phi^, the inner planner and the workspace length do not depend on
+    // the points and are untouched.  The keys, the finiteness check and the sort run into temporaries first: a rejected point set
+    // (PHAST_ERR_INVALID_ARG: a point that is not finite, a null pointer, a stream that is capturing) leaves the planner as it
+    // was.  Blocks until done.  The call orders itself after the earlier work of `s` ONLY: as with free, the caller must have
+    // finished the work on other streams that uses the planner.  ms: nufft_sort_build's
+    int set_points_dev(const double *d_x, size_t m_points, hipStream_t s, float *ms = nullptr) {
+        if (!d_x) return PHAST_ERR_INVALID_ARG;
+        if (m_points != points) return PHAST_ERR_PLANNER_SIZE;
+        PHAST_ON_DEVICE(device);
+        if (nufft_sort_stream_busy(s)) return PHAST_ERR_INVALID_ARG;
+        return nufft_sort_build(d_x, nullptr, nullptr, points, log_m, 0, 0, d_perm, d_cell, d_xs, nullptr, nullptr, s, ms);
     }
 
     size_t workspace_len(size_t batch) const { return 2 * m * batch; }
@@ -269,6 +304,24 @@ template <typename P> static int nufft_planner_new(size_t n_modes, const double 
     auto *p = new (std::nothrow) P();
     if (!p) return PHAST_ERR_ALLOC;
     int rc = p->init(n_modes, x, m_points, eps);
+    if (rc) {
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return PHAST_OK;
+}
+
+// the same from M doubles in device memory, ordered after the earlier work of `s`
+template <typename P>
+static int nufft_planner_new_dev(size_t n_modes, const double *d_x, size_t m_points, double eps, bool f32, hipStream_t s, P **out) {
+    if (!out) return PHAST_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (nufft_bad_sizes(n_modes, m_points, d_x, eps, f32)) return PHAST_ERR_INVALID_ARG;  // before the device is touched
+    if (nufft_sort_stream_busy(s)) return PHAST_ERR_INVALID_ARG;
+    auto *p = new (std::nothrow) P();
+    if (!p) return PHAST_ERR_ALLOC;
+    int rc = p->init_dev(n_modes, d_x, m_points, eps, s);
     if (rc) {
         delete p;
         return rc;

@@ -1,5 +1,5 @@
 // planner_nufft2d.hpp -- Nufft2dPlanner<T>: non-uniform FFTs of types 1 and 2 in two dimensions (nufft2d.hpp) of M points and
-// N1 x N2 modes on an owned NdPlanner<T> of dims (g1, g2).  Immutable after init: the Nd planner, the point set sorted by grid
+// N1 x N2 modes on an owned NdPlanner<T> of dims (g1, g2).  Immutable after init but for set_points_dev: the Nd planner, the point set sorted by grid
 // cell (positions, permutation, cell starts) and the N1 + N2 reciprocals 1 / phi^(k) on the device.  What a call mutates is the
 // caller's workspace (_dev calls) or a device buffer of the call's own (host-slice calls), so graph capture and concurrent
 // streams and threads need nothing beyond what the Nd planner already does.
@@ -10,6 +10,7 @@
 
 #include "nufft2d.hpp"
 #include "planner_nd.hpp"
+#include "planner_nufft_sort.hpp"
 
 namespace phast {
 
@@ -42,8 +43,8 @@ template <typename T> struct Nufft2dPlanner {
         return inv;
     }
 
-    // `x`, `y`: M host doubles in turns; the arguments were checked by nufft2d_bad_args
-    int init(size_t n1_, size_t n2_, const double *x, const double *y, size_t m_points, double eps_) {
+    // what does not depend on the points: the sizes, the Nd planner, 1 / phi^ on the device, and room for the point tables
+    int init_grid(size_t n1_, size_t n2_, size_t m_points, double eps_) {
         n1 = n1_;
         n2 = n2_;
         points = m_points;
@@ -58,9 +59,6 @@ template <typename T> struct Nufft2dPlanner {
         int rc = nd.init(dims, 2);
         if (rc) return rc;
         device = nd.device;
-        std::vector<double> xs(points), ys(points);
-        std::vector<uint32_t> perm(points), cell(cells + 1);
-        nufft2d_bin(x, y, points, log_g1, log_g2, xs.data(), ys.data(), perm.data(), cell.data());
         const std::vector<T> inv1 = inv_table(n1, g1), inv2 = inv_table(n2, g2);
         PHAST_ON_DEVICE(device);
         PHAST_HIP(hipMalloc(reinterpret_cast<void **>(&d_xs), points * sizeof(double)));
@@ -69,13 +67,45 @@ template <typename T> struct Nufft2dPlanner {
         PHAST_HIP(hipMalloc(reinterpret_cast<void **>(&d_cell), (cells + 1) * sizeof(uint32_t)));
         PHAST_HIP(hipMalloc(reinterpret_cast<void **>(&d_inv1), n1 * sizeof(T)));
         PHAST_HIP(hipMalloc(reinterpret_cast<void **>(&d_inv2), n2 * sizeof(T)));
+        PHAST_HIP(hipMemcpy(d_inv1, inv1.data(), n1 * sizeof(T), hipMemcpyHostToDevice));
+        PHAST_HIP(hipMemcpy(d_inv2, inv2.data(), n2 * sizeof(T), hipMemcpyHostToDevice));
+        return PHAST_OK;
+    }
+
+    // `x`, `y`: M host doubles in turns; the arguments were checked by nufft2d_bad_args
+    int init(size_t n1_, size_t n2_, const double *x, const double *y, size_t m_points, double eps_) {
+        int rc = init_grid(n1_, n2_, m_points, eps_);
+        if (rc) return rc;
+        std::vector<double> xs(points), ys(points);
+        std::vector<uint32_t> perm(points), cell(cells + 1);
+        nufft2d_bin(x, y, points, log_g1, log_g2, xs.data(), ys.data(), perm.data(), cell.data());
+        PHAST_ON_DEVICE(device);
         PHAST_HIP(hipMemcpy(d_xs, xs.data(), points * sizeof(double), hipMemcpyHostToDevice));
         PHAST_HIP(hipMemcpy(d_ys, ys.data(), points * sizeof(double), hipMemcpyHostToDevice));
         PHAST_HIP(hipMemcpy(d_perm, perm.data(), points * sizeof(uint32_t), hipMemcpyHostToDevice));
         PHAST_HIP(hipMemcpy(d_cell, cell.data(), (cells + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-        PHAST_HIP(hipMemcpy(d_inv1, inv1.data(), n1 * sizeof(T), hipMemcpyHostToDevice));
-        PHAST_HIP(hipMemcpy(d_inv2, inv2.data(), n2 * sizeof(T), hipMemcpyHostToDevice));
         return PHAST_OK;
+    }
+
+    // as init, with `d_x`, `d_y`: M doubles each in device memory (nufft_sort.hpp), ordered after the earlier work of `s`; blocks.
+    // The arguments but the points' values were checked by nufft2d_bad_sizes; PHAST_ERR_INVALID_ARG for a coordinate that is not
+    // finite
+    int init_dev(size_t n1_, size_t n2_, const double *d_x, const double *d_y, size_t m_points, double eps_, hipStream_t s) {
+        int rc = init_grid(n1_, n2_, m_points, eps_);
+        if (rc) return rc;
+        PHAST_ON_DEVICE(device);
+        return nufft_sort_build(d_x, d_y, nullptr, points, log_g1, log_g2, 0, d_perm, d_cell, d_xs, d_ys, nullptr, s);
+    }
+
+    // new points, the same M of them, from device memory: the rules of NufftPlanner::set_points_dev (planner_nufft.hpp) -- the
+    // tables are rewritten in place, a rejected point set leaves the planner as it was, the call blocks, and it orders itself
+    // after the earlier work of `s` ONLY: the caller must have finished the work on other streams that uses the planner
+    int set_points_dev(const double *d_x, const double *d_y, size_t m_points, hipStream_t s, float *ms = nullptr) {
+        if (!d_x || !d_y) return PHAST_ERR_INVALID_ARG;
+        if (m_points != points) return PHAST_ERR_PLANNER_SIZE;
+        PHAST_ON_DEVICE(device);
+        if (nufft_sort_stream_busy(s)) return PHAST_ERR_INVALID_ARG;
+        return nufft_sort_build(d_x, d_y, nullptr, points, log_g1, log_g2, 0, d_perm, d_cell, d_xs, d_ys, nullptr, s, ms);
     }
 
     size_t workspace_len(size_t batch) const { return 4 * cells * batch; }
@@ -275,6 +305,25 @@ static int nufft2d_planner_new(size_t n1, size_t n2, const double *x, const doub
     auto *p = new (std::nothrow) P();
     if (!p) return PHAST_ERR_ALLOC;
     int rc = p->init(n1, n2, x, y, m_points, eps);
+    if (rc) {
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return PHAST_OK;
+}
+
+// the same from M doubles per coordinate in device memory, ordered after the earlier work of `s`
+template <typename P>
+static int nufft2d_planner_new_dev(size_t n1, size_t n2, const double *d_x, const double *d_y, size_t m_points, double eps, bool f32,
+                                   hipStream_t s, P **out) {
+    if (!out) return PHAST_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (nufft2d_bad_sizes(n1, n2, m_points, d_x, d_y, eps, f32)) return PHAST_ERR_INVALID_ARG;  // before the device is touched
+    if (nufft_sort_stream_busy(s)) return PHAST_ERR_INVALID_ARG;
+    auto *p = new (std::nothrow) P();
+    if (!p) return PHAST_ERR_ALLOC;
+    int rc = p->init_dev(n1, n2, d_x, d_y, m_points, eps, s);
     if (rc) {
         delete p;
         return rc;

@@ -1,5 +1,5 @@
 // planner_nufft3d.hpp -- Nufft3dPlanner<T>: non-uniform FFTs of types 1 and 2 in three dimensions (nufft3d.hpp) of M points and
-// N1 x N2 x N3 modes on an owned NdPlanner<T> of dims (g1, g2, g3).  Immutable after init: the Nd planner, the point set sorted by
+// N1 x N2 x N3 modes on an owned NdPlanner<T> of dims (g1, g2, g3).  Immutable after init but for set_points_dev: the Nd planner, the point set sorted by
 // grid cell (positions, permutation, cell starts) and the N1 + N2 + N3 reciprocals 1 / phi^(k) on the device.  What a call mutates
 // is the caller's workspace (_dev calls) or a device buffer of the call's own (host-slice calls), so graph capture and concurrent
 // streams and threads need nothing beyond what the Nd planner already does.
@@ -11,6 +11,7 @@
 
 #include "nufft3d.hpp"
 #include "planner_nd.hpp"
+#include "planner_nufft_sort.hpp"
 
 namespace phast {
 
@@ -49,8 +50,13 @@ template <typename T> struct Nufft3dPlanner {
         return PHAST_OK;
     }
 
-    // `x`, `y`, `z`: M host doubles in turns; the arguments were checked by nufft3d_bad_args
-    int init(size_t n1_, size_t n2_, size_t n3_, const double *x, const double *y, const double *z, size_t m_points, double eps_) {
+    template <typename E> int room(E **dst, size_t count) {
+        PHAST_HIP(hipMalloc(reinterpret_cast<void **>(dst), count * sizeof(E)));
+        return PHAST_OK;
+    }
+
+    // what does not depend on the points: the sizes, the Nd planner, 1 / phi^ on the device, and room for the point tables
+    int init_grid(size_t n1_, size_t n2_, size_t n3_, size_t m_points, double eps_) {
         n1 = n1_;
         n2 = n2_;
         n3 = n3_;
@@ -68,16 +74,51 @@ template <typename T> struct Nufft3dPlanner {
         int rc = nd.init(dims, 3);
         if (rc) return rc;
         device = nd.device;
+        const std::vector<T> inv1 = inv_table(n1, g1), inv2 = inv_table(n2, g2), inv3 = inv_table(n3, g3);
+        PHAST_ON_DEVICE(device);
+        if ((rc = room(&d_xs, points)) || (rc = room(&d_ys, points)) || (rc = room(&d_zs, points)) || (rc = room(&d_perm, points)) ||
+            (rc = room(&d_cell, cells + 1)) || (rc = upload(&d_inv1, inv1.data(), n1)) || (rc = upload(&d_inv2, inv2.data(), n2)) ||
+            (rc = upload(&d_inv3, inv3.data(), n3)))
+            return rc;
+        return PHAST_OK;
+    }
+
+    // `x`, `y`, `z`: M host doubles in turns; the arguments were checked by nufft3d_bad_args
+    int init(size_t n1_, size_t n2_, size_t n3_, const double *x, const double *y, const double *z, size_t m_points, double eps_) {
+        int rc = init_grid(n1_, n2_, n3_, m_points, eps_);
+        if (rc) return rc;
         std::vector<double> xs(points), ys(points), zs(points);
         std::vector<uint32_t> perm(points), cell(cells + 1);
         nufft3d_bin(x, y, z, points, log_g1, log_g2, log_g3, xs.data(), ys.data(), zs.data(), perm.data(), cell.data());
-        const std::vector<T> inv1 = inv_table(n1, g1), inv2 = inv_table(n2, g2), inv3 = inv_table(n3, g3);
         PHAST_ON_DEVICE(device);
-        if ((rc = upload(&d_xs, xs.data(), points)) || (rc = upload(&d_ys, ys.data(), points)) || (rc = upload(&d_zs, zs.data(), points)) ||
-            (rc = upload(&d_perm, perm.data(), points)) || (rc = upload(&d_cell, cell.data(), cells + 1)) ||
-            (rc = upload(&d_inv1, inv1.data(), n1)) || (rc = upload(&d_inv2, inv2.data(), n2)) || (rc = upload(&d_inv3, inv3.data(), n3)))
-            return rc;
+        PHAST_HIP(hipMemcpy(d_xs, xs.data(), points * sizeof(double), hipMemcpyHostToDevice));
+        PHAST_HIP(hipMemcpy(d_ys, ys.data(), points * sizeof(double), hipMemcpyHostToDevice));
+        PHAST_HIP(hipMemcpy(d_zs, zs.data(), points * sizeof(double), hipMemcpyHostToDevice));
+        PHAST_HIP(hipMemcpy(d_perm, perm.data(), points * sizeof(uint32_t), hipMemcpyHostToDevice));
+        PHAST_HIP(hipMemcpy(d_cell, cell.data(), (cells + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
         return PHAST_OK;
+    }
+
+    // as init, with `d_x`, `d_y`, `d_z`: M doubles each in device memory (nufft_sort.hpp), ordered after the earlier work of `s`;
+    // blocks.  The arguments but the points' values were checked by nufft3d_bad_sizes; PHAST_ERR_INVALID_ARG for a coordinate that
+    // is not finite
+    int init_dev(size_t n1_, size_t n2_, size_t n3_, const double *d_x, const double *d_y, const double *d_z, size_t m_points,
+                 double eps_, hipStream_t s) {
+        int rc = init_grid(n1_, n2_, n3_, m_points, eps_);
+        if (rc) return rc;
+        PHAST_ON_DEVICE(device);
+        return nufft_sort_build(d_x, d_y, d_z, points, log_g1, log_g2, log_g3, d_perm, d_cell, d_xs, d_ys, d_zs, s);
+    }
+
+    // new points, the same M of them, from device memory: the rules of NufftPlanner::set_points_dev (planner_nufft.hpp) -- the
+    // tables are rewritten in place, a rejected point set leaves the planner as it was, the call blocks, and it orders itself
+    // after the earlier work of `s` ONLY: the caller must have finished the work on other streams that uses the planner
+    int set_points_dev(const double *d_x, const double *d_y, const double *d_z, size_t m_points, hipStream_t s, float *ms = nullptr) {
+        if (!d_x || !d_y || !d_z) return PHAST_ERR_INVALID_ARG;
+        if (m_points != points) return PHAST_ERR_PLANNER_SIZE;
+        PHAST_ON_DEVICE(device);
+        if (nufft_sort_stream_busy(s)) return PHAST_ERR_INVALID_ARG;
+        return nufft_sort_build(d_x, d_y, d_z, points, log_g1, log_g2, log_g3, d_perm, d_cell, d_xs, d_ys, d_zs, s, ms);
     }
 
     // elements of T per transform: the two grid planes and the Nd planner's own share (4 G)
@@ -283,6 +324,25 @@ static int nufft3d_planner_new(size_t n1, size_t n2, size_t n3, const double *x,
     auto *p = new (std::nothrow) P();
     if (!p) return PHAST_ERR_ALLOC;
     int rc = p->init(n1, n2, n3, x, y, z, m_points, eps);
+    if (rc) {
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return PHAST_OK;
+}
+
+// the same from M doubles per coordinate in device memory, ordered after the earlier work of `s`
+template <typename P>
+static int nufft3d_planner_new_dev(size_t n1, size_t n2, size_t n3, const double *d_x, const double *d_y, const double *d_z,
+                                   size_t m_points, double eps, bool f32, hipStream_t s, P **out) {
+    if (!out) return PHAST_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (nufft3d_bad_sizes(n1, n2, n3, m_points, d_x, d_y, d_z, eps, f32)) return PHAST_ERR_INVALID_ARG;  // before the device is touched
+    if (nufft_sort_stream_busy(s)) return PHAST_ERR_INVALID_ARG;
+    auto *p = new (std::nothrow) P();
+    if (!p) return PHAST_ERR_ALLOC;
+    int rc = p->init_dev(n1, n2, n3, d_x, d_y, d_z, m_points, eps, s);
     if (rc) {
         delete p;
         return rc;

@@ -219,6 +219,9 @@ extern "C" {
         out_dist: usize, batch: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // non-uniform FFTs of types 1 and 2 (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/nufft.rs)
     pub(crate) fn phast_planner_nufft64_new(n_modes: usize, x_turns: *const f64, m_points: usize, eps: f64, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft64_new_dev(n_modes: usize, d_x_turns: *const f64, m_points: usize, eps: f64, stream: *mut c_void,
+        out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft64_set_points_dev(p: *mut Opaque, d_x_turns: *const f64, m_points: usize, stream: *mut c_void) -> c_int;
     pub(crate) fn phast_planner_nufft64_free(p: *mut Opaque);
     pub(crate) fn phast_planner_nufft64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
     pub(crate) fn phast_planner_nufft64_device_bytes(p: *const Opaque) -> usize;
@@ -240,6 +243,9 @@ extern "C" {
     pub(crate) fn phast_nufft2_64_dev(in_re: *const f64, in_im: *const f64, in_dist: usize, out_re: *mut f64, out_im: *mut f64,
         out_dist: usize, batch: usize, direction: c_int, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
     pub(crate) fn phast_planner_nufft32_new(n_modes: usize, x_turns: *const f64, m_points: usize, eps: f64, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft32_new_dev(n_modes: usize, d_x_turns: *const f64, m_points: usize, eps: f64, stream: *mut c_void,
+        out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft32_set_points_dev(p: *mut Opaque, d_x_turns: *const f64, m_points: usize, stream: *mut c_void) -> c_int;
     pub(crate) fn phast_planner_nufft32_free(p: *mut Opaque);
     pub(crate) fn phast_planner_nufft32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
     pub(crate) fn phast_planner_nufft32_device_bytes(p: *const Opaque) -> usize;
@@ -263,6 +269,10 @@ extern "C" {
     // the same in two dimensions (planner.rs / algorithms/nufft2d.rs)
     pub(crate) fn phast_planner_nufft2d64_new(n1: usize, n2: usize, x_turns: *const f64, y_turns: *const f64, m_points: usize, eps: f64,
         out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft2d64_new_dev(n1: usize, n2: usize, d_x_turns: *const f64, d_y_turns: *const f64, m_points: usize, eps: f64,
+        stream: *mut c_void, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft2d64_set_points_dev(p: *mut Opaque, d_x_turns: *const f64, d_y_turns: *const f64, m_points: usize,
+        stream: *mut c_void) -> c_int;
     pub(crate) fn phast_planner_nufft2d64_free(p: *mut Opaque);
     pub(crate) fn phast_planner_nufft2d64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
     pub(crate) fn phast_planner_nufft2d64_device_bytes(p: *const Opaque) -> usize;
@@ -287,6 +297,10 @@ extern "C" {
         out_dist: usize, batch: usize, direction: c_int, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
     pub(crate) fn phast_planner_nufft2d32_new(n1: usize, n2: usize, x_turns: *const f64, y_turns: *const f64, m_points: usize, eps: f64,
         out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft2d32_new_dev(n1: usize, n2: usize, d_x_turns: *const f64, d_y_turns: *const f64, m_points: usize, eps: f64,
+        stream: *mut c_void, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft2d32_set_points_dev(p: *mut Opaque, d_x_turns: *const f64, d_y_turns: *const f64, m_points: usize,
+        stream: *mut c_void) -> c_int;
     pub(crate) fn phast_planner_nufft2d32_free(p: *mut Opaque);
     pub(crate) fn phast_planner_nufft2d32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
     pub(crate) fn phast_planner_nufft2d32_device_bytes(p: *const Opaque) -> usize;
@@ -313,6 +327,10 @@ extern "C" {
     pub(crate) fn phast_planner_nufft3d64_new(n1: usize, n2: usize, n3: usize, x_turns: *const f64, y_turns: *const f64, z_turns: *const f64,
         m_points: usize, eps: f64,
         out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft3d64_new_dev(n1: usize, n2: usize, n3: usize, d_x_turns: *const f64, d_y_turns: *const f64, d_z_turns: *const f64, m_points: usize, eps: f64,
+        stream: *mut c_void, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft3d64_set_points_dev(p: *mut Opaque, d_x_turns: *const f64, d_y_turns: *const f64, d_z_turns: *const f64, m_points: usize,
+        stream: *mut c_void) -> c_int;
     pub(crate) fn phast_planner_nufft3d64_free(p: *mut Opaque);
     pub(crate) fn phast_planner_nufft3d64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
     pub(crate) fn phast_planner_nufft3d64_device_bytes(p: *const Opaque) -> usize;
@@ -337,6 +355,10 @@ extern "C" {
     pub(crate) fn phast_planner_nufft3d32_new(n1: usize, n2: usize, n3: usize, x_turns: *const f64, y_turns: *const f64, z_turns: *const f64,
         m_points: usize, eps: f64,
         out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft3d32_new_dev(n1: usize, n2: usize, n3: usize, d_x_turns: *const f64, d_y_turns: *const f64, d_z_turns: *const f64, m_points: usize, eps: f64,
+        stream: *mut c_void, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_nufft3d32_set_points_dev(p: *mut Opaque, d_x_turns: *const f64, d_y_turns: *const f64, d_z_turns: *const f64, m_points: usize,
+        stream: *mut c_void) -> c_int;
     pub(crate) fn phast_planner_nufft3d32_free(p: *mut Opaque);
     pub(crate) fn phast_planner_nufft3d32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
     pub(crate) fn phast_planner_nufft3d32_device_bytes(p: *const Opaque) -> usize;

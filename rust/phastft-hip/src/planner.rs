@@ -3,7 +3,7 @@
 //! immutable value any number of callers may borrow (`Send + Sync`, planner.rs:38-39) -- inside the library every
 //! concurrent caller works in a workspace of its own (scratch, staging, stream), so borrowed planners run side by side.
 use crate::ffi::{self, Opaque};
-use std::ffi::c_int;
+use std::ffi::{c_int, c_void};
 
 /// planner.rs:10-16
 #[derive(Copy, Clone)]
@@ -425,10 +425,10 @@ impl_planner_czt!(PlannerCzt32, phast_planner_czt32_new, phast_planner_czt32_fre
                   phast_planner_czt32_workspace_len);
 
 macro_rules! impl_planner_nufft {
-    ($nufft:ident, $new:ident, $free:ident, $grid_len:ident, $width:ident, $ws_len:ident) => {
+    ($nufft:ident, $new:ident, $new_dev:ident, $set_points:ident, $free:ident, $grid_len:ident, $width:ident, $ws_len:ident) => {
         /// An extension beyond PhastFT 0.3.0, whose planners take samples on a grid: non-uniform FFTs of types 1 and 2 of the
         /// points `x` (turns, reduced mod 1) and `n_modes` modes in numpy fftfreq order, to the relative accuracy `eps`.
-        /// Immutable after `new`, like the reference's planners.
+        /// Immutable after `new`, like the reference's planners, but for `set_points_dev` (which takes `&mut self`).
         pub struct $nufft {
             pub(crate) h: *mut Opaque,
             pub(crate) n: usize,
@@ -445,6 +445,28 @@ macro_rules! impl_planner_nufft {
                 let mut h = std::ptr::null_mut();
                 ffi::check(unsafe { ffi::$new(n_modes, x.as_ptr(), x.len(), eps, &mut h) });
                 Self { h, n: n_modes, m: x.len() }
+            }
+            /// The planner for `m_points` points in DEVICE memory (`d_x`: doubles in turns), sorted on the device into the very
+            /// tables `new` builds on the host, ordered after the earlier work of `stream`; blocks until the planner is built.
+            /// Panics with "invalid argument" for the sizes `new` refuses, a null pointer, a stream that is capturing or a point
+            /// that is not finite.
+            ///
+            /// # Safety
+            /// the pointers must be valid device memory of `m_points` doubles and `stream` a HIP stream or null
+            pub unsafe fn from_device(n_modes: usize, d_x: *const f64, m_points: usize, eps: f64, stream: *mut c_void) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(ffi::$new_dev(n_modes, d_x, m_points, eps, stream, &mut h));
+                Self { h, n: n_modes, m: m_points }
+            }
+            /// New points for this planner, the same number of them (another `m_points` panics with "planner size"), from device
+            /// memory: the tables are rewritten in place, so a HIP graph captured through the planner stays valid and, replayed,
+            /// transforms at the new points.  Ordered after the earlier work of `stream` ONLY -- work on other streams that uses
+            /// the planner must have finished -- and blocks until done.  A rejected point set leaves the planner as it was.
+            ///
+            /// # Safety
+            /// as `from_device`
+            pub unsafe fn set_points_dev(&mut self, d_x: *const f64, m_points: usize, stream: *mut c_void) {
+                ffi::check(ffi::$set_points(self.h, d_x, m_points, stream));
             }
             pub fn num_modes(&self) -> usize {
                 self.n
@@ -472,13 +494,15 @@ macro_rules! impl_planner_nufft {
         }
     };
 }
-impl_planner_nufft!(PlannerNufft64, phast_planner_nufft64_new, phast_planner_nufft64_free, phast_planner_nufft64_grid_len,
+impl_planner_nufft!(PlannerNufft64, phast_planner_nufft64_new, phast_planner_nufft64_new_dev,
+                    phast_planner_nufft64_set_points_dev, phast_planner_nufft64_free, phast_planner_nufft64_grid_len,
                     phast_planner_nufft64_width, phast_planner_nufft64_workspace_len);
-impl_planner_nufft!(PlannerNufft32, phast_planner_nufft32_new, phast_planner_nufft32_free, phast_planner_nufft32_grid_len,
+impl_planner_nufft!(PlannerNufft32, phast_planner_nufft32_new, phast_planner_nufft32_new_dev,
+                    phast_planner_nufft32_set_points_dev, phast_planner_nufft32_free, phast_planner_nufft32_grid_len,
                     phast_planner_nufft32_width, phast_planner_nufft32_workspace_len);
 
 macro_rules! impl_planner_nufft2d {
-    ($nufft:ident, $new:ident, $free:ident, $grid_len:ident, $rows:ident, $cols:ident, $width:ident, $ws_len:ident) => {
+    ($nufft:ident, $new:ident, $new_dev:ident, $set_points:ident, $free:ident, $grid_len:ident, $rows:ident, $cols:ident, $width:ident, $ws_len:ident) => {
         /// An extension beyond PhastFT 0.3.0: two-dimensional non-uniform FFTs of types 1 and 2 of the points `(x, y)` (turns,
         /// reduced mod 1 per coordinate) and `n1 x n2` modes, row-major, each axis in numpy fftfreq order (k1 pairs with x, k2
         /// with y), to the relative accuracy `eps`.  Immutable after `new`, like the reference's planners.
@@ -499,6 +523,29 @@ macro_rules! impl_planner_nufft2d {
                 let mut h = std::ptr::null_mut();
                 ffi::check(unsafe { ffi::$new(n_modes.0, n_modes.1, x.as_ptr(), y.as_ptr(), x.len(), eps, &mut h) });
                 Self { h, n: n_modes, m: x.len() }
+            }
+            /// The planner for `m_points` points in DEVICE memory (`d_x`, `d_y`: doubles in turns), sorted on the device into the very
+            /// tables `new` builds on the host, ordered after the earlier work of `stream`; blocks until the planner is built.
+            /// Panics with "invalid argument" for the sizes `new` refuses, a null pointer, a stream that is capturing or a point
+            /// that is not finite.
+            ///
+            /// # Safety
+            /// the pointers must be valid device memory of `m_points` doubles and `stream` a HIP stream or null
+            pub unsafe fn from_device(n_modes: (usize, usize), d_x: *const f64, d_y: *const f64, m_points: usize, eps: f64,
+                                      stream: *mut c_void) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(ffi::$new_dev(n_modes.0, n_modes.1, d_x, d_y, m_points, eps, stream, &mut h));
+                Self { h, n: n_modes, m: m_points }
+            }
+            /// New points for this planner, the same number of them (another `m_points` panics with "planner size"), from device
+            /// memory: the tables are rewritten in place, so a HIP graph captured through the planner stays valid and, replayed,
+            /// transforms at the new points.  Ordered after the earlier work of `stream` ONLY -- work on other streams that uses
+            /// the planner must have finished -- and blocks until done.  A rejected point set leaves the planner as it was.
+            ///
+            /// # Safety
+            /// as `from_device`
+            pub unsafe fn set_points_dev(&mut self, d_x: *const f64, d_y: *const f64, m_points: usize, stream: *mut c_void) {
+                ffi::check(ffi::$set_points(self.h, d_x, d_y, m_points, stream));
             }
             pub fn num_modes(&self) -> (usize, usize) {
                 self.n
@@ -530,15 +577,17 @@ macro_rules! impl_planner_nufft2d {
         }
     };
 }
-impl_planner_nufft2d!(PlannerNufft2d64, phast_planner_nufft2d64_new, phast_planner_nufft2d64_free, phast_planner_nufft2d64_grid_len,
+impl_planner_nufft2d!(PlannerNufft2d64, phast_planner_nufft2d64_new, phast_planner_nufft2d64_new_dev,
+                      phast_planner_nufft2d64_set_points_dev, phast_planner_nufft2d64_free, phast_planner_nufft2d64_grid_len,
                       phast_planner_nufft2d64_grid_rows, phast_planner_nufft2d64_grid_cols, phast_planner_nufft2d64_width,
                       phast_planner_nufft2d64_workspace_len);
-impl_planner_nufft2d!(PlannerNufft2d32, phast_planner_nufft2d32_new, phast_planner_nufft2d32_free, phast_planner_nufft2d32_grid_len,
+impl_planner_nufft2d!(PlannerNufft2d32, phast_planner_nufft2d32_new, phast_planner_nufft2d32_new_dev,
+                      phast_planner_nufft2d32_set_points_dev, phast_planner_nufft2d32_free, phast_planner_nufft2d32_grid_len,
                       phast_planner_nufft2d32_grid_rows, phast_planner_nufft2d32_grid_cols, phast_planner_nufft2d32_width,
                       phast_planner_nufft2d32_workspace_len);
 
 macro_rules! impl_planner_nufft3d {
-    ($nufft:ident, $new:ident, $free:ident, $grid_len:ident, $grid_dim:ident, $width:ident, $ws_len:ident) => {
+    ($nufft:ident, $new:ident, $new_dev:ident, $set_points:ident, $free:ident, $grid_len:ident, $grid_dim:ident, $width:ident, $ws_len:ident) => {
         /// An extension beyond PhastFT 0.3.0: three-dimensional non-uniform FFTs of types 1 and 2 of the points `(x, y, z)`
         /// (turns, reduced mod 1 per coordinate) and `n1 x n2 x n3` modes, row-major, each axis in numpy fftfreq order (k1 pairs
         /// with x, k2 with y, k3 with z), to the relative accuracy `eps`.  Immutable after `new`, like the reference's planners.
@@ -560,6 +609,30 @@ macro_rules! impl_planner_nufft3d {
                 let mut h = std::ptr::null_mut();
                 ffi::check(unsafe { ffi::$new(n_modes.0, n_modes.1, n_modes.2, x.as_ptr(), y.as_ptr(), z.as_ptr(), x.len(), eps, &mut h) });
                 Self { h, n: n_modes, m: x.len() }
+            }
+            /// The planner for `m_points` points in DEVICE memory (`d_x`, `d_y`, `d_z`: doubles in turns), sorted on the device into the very
+            /// tables `new` builds on the host, ordered after the earlier work of `stream`; blocks until the planner is built.
+            /// Panics with "invalid argument" for the sizes `new` refuses, a null pointer, a stream that is capturing or a point
+            /// that is not finite.
+            ///
+            /// # Safety
+            /// the pointers must be valid device memory of `m_points` doubles and `stream` a HIP stream or null
+            pub unsafe fn from_device(n_modes: (usize, usize, usize), d_x: *const f64, d_y: *const f64, d_z: *const f64, m_points: usize,
+                                      eps: f64, stream: *mut c_void) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(ffi::$new_dev(n_modes.0, n_modes.1, n_modes.2, d_x, d_y, d_z, m_points, eps, stream, &mut h));
+                Self { h, n: n_modes, m: m_points }
+            }
+            /// New points for this planner, the same number of them (another `m_points` panics with "planner size"), from device
+            /// memory: the tables are rewritten in place, so a HIP graph captured through the planner stays valid and, replayed,
+            /// transforms at the new points.  Ordered after the earlier work of `stream` ONLY -- work on other streams that uses
+            /// the planner must have finished -- and blocks until done.  A rejected point set leaves the planner as it was.
+            ///
+            /// # Safety
+            /// as `from_device`
+            pub unsafe fn set_points_dev(&mut self, d_x: *const f64, d_y: *const f64, d_z: *const f64, m_points: usize,
+                                         stream: *mut c_void) {
+                ffi::check(ffi::$set_points(self.h, d_x, d_y, d_z, m_points, stream));
             }
             pub fn num_modes(&self) -> (usize, usize, usize) {
                 self.n
@@ -591,10 +664,12 @@ macro_rules! impl_planner_nufft3d {
         }
     };
 }
-impl_planner_nufft3d!(PlannerNufft3d64, phast_planner_nufft3d64_new, phast_planner_nufft3d64_free, phast_planner_nufft3d64_grid_len,
+impl_planner_nufft3d!(PlannerNufft3d64, phast_planner_nufft3d64_new, phast_planner_nufft3d64_new_dev,
+                      phast_planner_nufft3d64_set_points_dev, phast_planner_nufft3d64_free, phast_planner_nufft3d64_grid_len,
                       phast_planner_nufft3d64_grid_dim, phast_planner_nufft3d64_width,
                       phast_planner_nufft3d64_workspace_len);
-impl_planner_nufft3d!(PlannerNufft3d32, phast_planner_nufft3d32_new, phast_planner_nufft3d32_free, phast_planner_nufft3d32_grid_len,
+impl_planner_nufft3d!(PlannerNufft3d32, phast_planner_nufft3d32_new, phast_planner_nufft3d32_new_dev,
+                      phast_planner_nufft3d32_set_points_dev, phast_planner_nufft3d32_free, phast_planner_nufft3d32_grid_len,
                       phast_planner_nufft3d32_grid_dim, phast_planner_nufft3d32_width,
                       phast_planner_nufft3d32_workspace_len);
 
