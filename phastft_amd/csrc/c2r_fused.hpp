@@ -123,7 +123,7 @@ __global__ void __launch_bounds__(1 << (LR + LC - LP)) c2r_first_pass_kernel(con
     constexpr int NT = Body::NT;
     pin_tile_args(a);
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    PHAST_DYNAMIC_LDS(smem);
     T *ex_re = reinterpret_cast<T *>(smem);
     cx *l_twr = reinterpret_cast<cx *>(smem + (size_t)Body::EXCH * sizeof(T) * (Body::PLANE_SEQ ? 1 : 2));
     const typename Body::Shared sh{ex_re, Body::PLANE_SEQ ? ex_re : ex_re + Body::EXCH, l_twr, l_twr};
@@ -131,7 +131,7 @@ __global__ void __launch_bounds__(1 << (LR + LC - LP)) c2r_first_pass_kernel(con
     int tid = threadIdx.x;
     unsigned wave_base = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
     auto fresh_tid = [&]() {  // see tile_fft_kernel
-        asm volatile("" : "+s"(wave_base));
+        PHAST_LAUNDER_SGPR(wave_base);
         return (int)(wave_base | __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
     };
     typename Body::Regs r;

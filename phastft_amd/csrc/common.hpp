@@ -16,6 +16,16 @@
 #ifndef PHAST_DYNAMIC_LDS
 #define PHAST_DYNAMIC_LDS(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
 #endif
+// "this value lives in an SGPR / a VGPR and may have changed": an empty asm statement the compiler cannot see through, with an
+// AMDGPU register constraint that no host compiler accepts.  Macros for the same reason as above: the host emulation of the FFT
+// pass kernels (tests/emu/block_shim.hpp, tests/cpp/pass_emu_test.cpp) defines them away before it includes a kernel header; in
+// every build of the library they are these statements
+#ifndef PHAST_LAUNDER_SGPR
+#define PHAST_LAUNDER_SGPR(x) asm volatile("" : "+s"(x))
+#endif
+#ifndef PHAST_LAUNDER_VGPR
+#define PHAST_LAUNDER_VGPR(x) asm volatile("" : "+v"(x))
+#endif
 
 namespace phast {
 

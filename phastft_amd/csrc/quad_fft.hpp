@@ -252,7 +252,7 @@ template <typename T, bool ONE> __global__ void __launch_bounds__(256) quad_fft_
     using Body = QuadBody<T>;
     using cx = cx_t<T>;
     pin_tile_args(a);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    PHAST_DYNAMIC_LDS(smem);
     using V = typename Body::V;
     V *ex_re = reinterpret_cast<V *>(smem);
     V *ex_im = ex_re + Body::EXCH;

@@ -167,7 +167,7 @@ __global__ void __launch_bounds__(1 << (LR + LC - LP)) r2c_last_pass_kernel(cons
     constexpr int NT = Body::NT;
     pin_tile_args(a);
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    PHAST_DYNAMIC_LDS(smem);
     T *ex_re = reinterpret_cast<T *>(smem);
     cx *l_tw3 = reinterpret_cast<cx *>(smem + (size_t)Body::EXCH * sizeof(T) * (Body::PLANE_SEQ ? 1 : 2));
     cx *l_twr = l_tw3 + (3u << a.tw_bits);
@@ -176,7 +176,7 @@ __global__ void __launch_bounds__(1 << (LR + LC - LP)) r2c_last_pass_kernel(cons
     int tid = threadIdx.x;
     unsigned wave_base = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
     auto fresh_tid = [&]() {  // see tile_fft_kernel
-        asm volatile("" : "+s"(wave_base));
+        PHAST_LAUNDER_SGPR(wave_base);
         return (int)(wave_base | __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
     };
     for (int i = tid; i < Body::TWR; i += NT) l_twr[i] = reinterpret_cast<const cx *>(a.twr)[i];

@@ -215,7 +215,7 @@ __global__ void __launch_bounds__(1 << (LR + LC - LP)) row_fft_kernel(const RowA
     using RB = RowBody<T, LR, LC, LP>;
     using Body = typename RB::Body;
     using cx = cx_t<T>;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    PHAST_DYNAMIC_LDS(smem);
     T *buf = reinterpret_cast<T *>(smem);
     cx *l_twr = reinterpret_cast<cx *>(smem + (size_t)2 * RB::PLANE * sizeof(T));
     cx *l_rtw = l_twr + RB::TWR;  // REAL only: W_{2N} three-level tables
@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(1 << (LR + LC - LP)) row_fft_kernel(const RowA
     auto do_step = [&](auto i) { Body::template step<decltype(i)::value>(sh, tid, r); };
 
     while (t < a.tiles_total) {
-        asm volatile("" : "+v"(tid));  // per-tile address recomputation instead of ~100 hoisted values (tile_fft.hpp)
+        PHAST_LAUNDER_VGPR(tid);  // per-tile address recomputation instead of ~100 hoisted values (tile_fft.hpp)
         __syncthreads();               // the previous tile's readers are done with the LDS buffer (and the tables are in)
         if (REAL && mode == 2) RB::c2r_park(a, t, tid, buf, buf + RB::PLANE, l_rtw);
         else RB::park(buf, buf + RB::PLANE, tid, r);

@@ -450,7 +450,7 @@ __global__ void __launch_bounds__(1 << (LR + LC - LP), 1) tile_fft_kernel(const 
     constexpr int NT = Body::NT;
     pin_tile_args(a);  // all scalar loads of the arguments at once (common.hpp)
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    PHAST_DYNAMIC_LDS(smem);
     T *ex_re = reinterpret_cast<T *>(smem);
     cx *l_tw3 = reinterpret_cast<cx *>(smem + (size_t)Body::EXCH * sizeof(T) * (Body::PLANE_SEQ ? 1 : 2));
     const bool tw_global = Body::tw3_global(a.tw_bits);  // uniform: inter-pass tables read from global memory, not staged
@@ -465,7 +465,7 @@ __global__ void __launch_bounds__(1 << (LR + LC - LP), 1) tile_fft_kernel(const 
     // laundered a VGPR copy of the id once per tile: that VGPR and `col` were what the 32-point f32 kernel spilled.)
     unsigned wave_base = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
     auto fresh_tid = [&]() {
-        asm volatile("" : "+s"(wave_base));
+        PHAST_LAUNDER_SGPR(wave_base);
         return (int)(wave_base | __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
     };
     // Phase stamps exist only in the -DPHAST_TRACE build (tools/trace_tile.py): even behind a uniform branch the

@@ -382,9 +382,9 @@ __global__ void __launch_bounds__((wave_block_threads<T>())) wave_fft_kernel(con
     using cx = cx_t<T>;
     pin_tile_args(a);
     pin_scalars(blocks_total, stagger);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    PHAST_DYNAMIC_LDS(smem);
     const int tid = threadIdx.x, lane = tid & 63;
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) || defined(PHAST_HOST_WAVE_OPS)  // (the latter: tests/emu/block_shim.hpp checks the claim on the host)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform, and the compiler is told so: tile bases live in SGPRs
 #else
     const int wave = tid >> 6;

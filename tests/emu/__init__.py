@@ -13,7 +13,18 @@ twiddle.hip, the digest of fill.hip): a workgroup's threads are fibers that run,
 __syncthreads() to the next; static LDS is a global object and dynamic LDS a heap block, both bounds-checked by ASan.
 `build_block_emulator` builds tests/cpp/block_emu_test.cpp on it (tests/test_block_emulator.py).  It checks LDS and global indices,
 barriers (a missing one gives wrong bits in one of the two orders) and which kernel instantiation a shape reaches; it cannot check
-cross-lane operations, timing, races that both serial orders survive, or the device's own arithmetic.
+timing, races that both serial orders survive, or the device's own arithmetic.
+
+The same shim has lanes and waves: a wave-level operation (v_permlane32/16_swap, wave_barrier, readfirstlane, which aborts on a value
+that is not wave-uniform) is a second rendezvous of the 64 lanes of a wave.  `build_pass_emulator` builds tests/cpp/pass_emu_test.cpp
+on it (tests/test_pass_emulator.py): the six FFT pass kernels (tile, row, fused R2C / C2R, wave, four-wave) as they stand, launched
+through the product's launchers on heap blocks of the planner's sizes, bit for bit against the emulate_* functions in both thread
+orders.  One run launches 432 / 504 / 480 / 560 tile passes (f64 A, f64 B/C, f32 A, f32 B/C: 36 / 36 / 40 / 40 instantiations), 336 / 504
+fused R2C (24 / 36), 420 / 480 fused C2R (35 / 40), 748 small transforms (52 row kernels, 2 one-point), 17 wave (2) and 14 four-wave (2)
+passes per type.  It checks barriers, the LDS carve-up against lds_bytes, table staging, the persistent loop and its prefetch guard, the
+kernels' own pre-twiddle branch and the uniformity claims; of the optional branches tw_global (tables of a 2^28-point transform) did
+NOT run.  It cannot check timing, races that both serial orders survive, the device's own arithmetic, or what the hardware does in a
+swap's inactive lanes.
 """
 from __future__ import annotations
 
@@ -46,6 +57,14 @@ BLOCK_PARTS = ["main", "nd", "bitrev", "twiddle", "digest"]  # BLOCK_PART = inde
 # as SWEEP_FLAGS, without AddressSanitizer's fake stacks (use-after-return): one per fiber, mapped and unmapped for each of the
 # millions of GPU threads a run emulates, they multiply its time; the frames stay on the fibers' own stacks
 BLOCK_FLAGS = SWEEP_FLAGS + ["-fsanitize-address-use-after-return=never"]
+
+# The pass emulator (tests/test_pass_emulator.py): block_shim.hpp with its lanes and waves; tests/cpp/pass_emu_test.cpp #includes
+# the fifteen product units of the FFT pass kernels as they stand, one per translation unit, and launches every pass through the
+# product's own launcher.  PASS_PART = index; the two *_wide units hold one instantiation each and run through their dispatcher's part.
+PASS_SRC = os.path.join(os.path.dirname(HERE), "cpp", "pass_emu_test.cpp")
+PASS_EXE = os.path.join(HERE, "build", "pass_emu_test")
+PASS_PARTS = ["main", "tile_f64_a", "tile_f64_bc", "tile_f64_bc_wide", "tile_f32_a", "tile_f32_bc", "tile_f32_bc_wide", "tile_f64_r2c",
+              "tile_f32_r2c", "tile_f64_c2r", "tile_f32_c2r", "wave_f64", "wave_f32", "quad_f64", "quad_f32", "small_fft"]
 
 
 def build_emulator(force: bool = False) -> str:
@@ -140,4 +159,37 @@ def build_block_emulator(force: bool = False, override_dir: str | None = None, p
         r = subprocess.run([_host_linker(), "-fsanitize=address,undefined", *objs, "-o", exe], capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed for the block emulator:\n{r.stdout}\n{r.stderr}")
+    return exe
+
+
+def build_pass_emulator(force: bool = False, override_dir: str | None = None, parts: tuple = (), out: str | None = None) -> str:
+    """Builds the pass emulator program and returns its path; `override_dir`, `parts` and `out` as build_sweep_emulator's.  A
+    mutated part is compiled at -O0 without debug information -- a fifth of the time of the regular -O1 -g build of a tile unit, and
+    a self-test runs one shape of it."""
+    exe = out or PASS_EXE
+    objdir = os.path.join(HERE, "build")
+    os.makedirs(objdir, exist_ok=True)
+    cpp = os.path.dirname(PASS_SRC)
+    hips = [os.path.join(_b.SRC, f) for f in os.listdir(_b.SRC) if f.endswith(".hip")]
+    deps = [PASS_SRC, BLOCK_SHIM, os.path.join(cpp, "sanitizer_exit.hpp"), os.path.abspath(__file__)] + hips + _b._deps()
+    inc = ["-I", _b.SRC, "-I", _b.INCLUDE, "-I", HERE, "-I", cpp]
+
+    def part(name: str) -> str:
+        k = PASS_PARTS.index(name)
+        mutated = override_dir is not None and name in parts
+        obj = os.path.join(os.path.dirname(exe) if mutated else objdir, f"pass_part{k}.o")
+        if force or mutated or _b._stale(obj, deps):
+            flags = [f for f in BLOCK_FLAGS if f not in ("-O1", "-g")] + ["-O0"] if mutated else BLOCK_FLAGS
+            cmd = [_b.hipcc(), *flags, f"-DPASS_PART={k}", *(["-I", override_dir] if mutated else []), *inc, "-c", PASS_SRC, "-o", obj]
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError(f"hipcc failed for pass part {name}:\n{r.stdout}\n{r.stderr}")
+        return obj
+
+    with cf.ThreadPoolExecutor(min(len(PASS_PARTS), os.cpu_count() or 4, 16)) as ex:
+        objs = list(ex.map(part, PASS_PARTS))
+    if force or override_dir or _b._stale(exe, objs):
+        r = subprocess.run([_host_linker(), "-fsanitize=address,undefined", *objs, "-o", exe], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"link failed for the pass emulator:\n{r.stdout}\n{r.stderr}")
     return exe

@@ -16,13 +16,23 @@
 // LDS (PHAST_DYNAMIC_LDS(name) in common.hpp, `extern __shared__ unsigned char name[]` on the device) is a heap block of exactly
 // the bytes the launch asked for, new for every workgroup and filled with 0xA5.
 //
+// Lanes and waves (the FFT pass kernels: tests/cpp/pass_emu_test.cpp).  The fibers of a workgroup are grouped into waves of 64 by
+// linear thread index, and there is a second kind of rendezvous: a fiber that reaches a wave-level operation yields, and the
+// scheduler resumes it only once every lane of its wave that has not returned has reached the same operation.  On it stand
+// v_permlane32_swap / v_permlane16_swap (the semantics of wave_fft.hpp: a.lanes[32..63] <-> b.lanes[0..31], a.rows{1,3} <->
+// b.rows{0,2}), wave_barrier, readfirstlane -- which ABORTS when the live lanes do not all hold the same value: every use in the
+// kernels claims uniformity -- and mbcnt as the lane number.  The order of the threads (ascending or descending) applies at
+// both levels.  The scheduler aborts, naming kernel, workgroup and wave, when the lanes of one wave sit in different rendezvous
+// or some have returned while others wait at a swap.
+//
 // Limits, stated so that nobody reads more into a green run than it says:
-//   * no cross-lane operations (DPP, permute, readlane, ballot, shuffles): a kernel that uses them does not compile here;
+//   * of the cross-lane operations only the ones above exist (no DPP, ds_permute, readlane, ballot): a kernel that uses another
+//     does not compile here; a swap with inactive lanes, whose result the hardware defines, is refused, not modelled;
 //   * static LDS keeps the bytes of the previous workgroup (and launch), so a read before the write shows as WRONG DATA in the
 //     result, not as an initialisation pattern;
-//   * no timing, no memory model: two threads between the same two barriers never overlap, so a race between them that both
-//     serial orders happen to survive is not seen;
-//   * the device's own arithmetic (rounding of 1.0f / d, sincos) is the host's here.
+//   * no timing, no memory model: two threads between the same two rendezvous never overlap, so a race between them that both
+//     serial orders happen to survive is not seen; fences, s_sleep and s_memtime do nothing;
+//   * the device's own arithmetic (rounding of 1.0f / d, sincos, contraction into FMAs) is the host's here.
 // Nothing here calls into the HIP runtime: the program is linked without it, runs anywhere and never opens a GPU.
 #pragma once
 
@@ -35,6 +45,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <map>
 #include <string>
 #include <tuple>
@@ -60,6 +71,10 @@
 // the one declaration the product cannot keep verbatim (an `extern` array cannot be a heap block): common.hpp defines this
 // macro as today's `extern __shared__ __attribute__((aligned(16))) unsigned char name[]` unless it is defined already
 #define PHAST_DYNAMIC_LDS(name) unsigned char *const name = ::block_shim::dyn_lds
+// common.hpp's empty asm statements with AMDGPU register constraints (they only stop the compiler from keeping values live)
+#define PHAST_LAUNDER_SGPR(x) ((void)(x))
+#define PHAST_LAUNDER_VGPR(x) ((void)(x))
+#define PHAST_HOST_WAVE_OPS 1  // wave_fft.hpp: take the wave index through readfirstlane here too (checked: see below)
 
 namespace block_shim {
 
@@ -72,7 +87,10 @@ inline Order order = kAscending;           // of the threads of a workgroup betw
 inline unsigned char *dyn_lds = nullptr;   // this workgroup's dynamic LDS: exactly the launch's `lds` bytes
 inline unsigned long long launches = 0, workgroups = 0, threads_run = 0, barriers = 0;  // proof that kernels ran here
 inline std::map<std::string, unsigned long long> ran;  // launches per kernel instantiation, by name
+inline std::map<std::string, unsigned long long> ran_in[2];  // ... and per thread order
 inline std::string last_kernel;                        // the instantiation of the latest launch
+inline unsigned force_grid = 0;  // != 0: every launch runs this many workgroups (a launcher that sizes its own grid, shrunken)
+inline unsigned long long wave_ops = 0;  // wave-level rendezvous passed
 
 // "(nd_transpose_narrow<T, NC, true, true>)" launched from "void launch_narrow(...) [T = double, NC = true]" is
 // "nd_transpose_narrow<double, true, true, true>": the template parameters of the launching function, which the compiler
@@ -163,7 +181,13 @@ struct Fiber {
     void *fake = nullptr;  // AddressSanitizer's fake stack of this fiber while it is switched out
     Idx tid{};
     bool done = false, waiting = false;
+    int wave_op = 0;          // != 0: waits at this wave-level operation (WaveOp)
+    unsigned wa = 0, wb = 0;  // its operands on the way in, its results on the way out
 };
+enum WaveOp { kNoOp = 0, kWaveBarrier = 1, kFirstLane = 2, kSwap32 = 3, kSwap16 = 4 };
+inline const char *wave_op_name(int op) {
+    return op == kWaveBarrier ? "wave_barrier" : op == kFirstLane ? "readfirstlane" : op == kSwap32 ? "permlane32_swap" : op == kSwap16 ? "permlane16_swap" : "none";
+}
 inline std::vector<Fiber> fibers;  // stacks are mapped once and reused by every workgroup
 inline Context sched_ctx;
 inline void *sched_fake = nullptr;
@@ -208,6 +232,70 @@ inline void barrier() {
     cur->waiting = true;
     to_scheduler(false);
 }
+struct Swapped {
+    unsigned v[2];
+    unsigned operator[](int i) const { return v[i]; }
+};
+inline Swapped wave_rendezvous(int op, unsigned a, unsigned b) {
+    Fiber *self = cur;
+    self->wave_op = op;
+    self->wa = a;
+    self->wb = b;
+    to_scheduler(false);
+    return Swapped{{self->wa, self->wb}};
+}
+inline int lane_id() { return (int)((cur - fibers.data()) & 63); }
+[[noreturn]] inline void wave_abort(unsigned wave, const char *what) {
+    std::fflush(stdout);
+    std::fprintf(stderr, "block_shim: %s, workgroup (%u, %u, %u), wave %u: %s\n", last_kernel.c_str(), block_idx.x, block_idx.y, block_idx.z,
+                 wave, what);
+    std::fflush(stderr);
+    std::abort();
+}
+// every live lane of wave `w` waits: at the workgroup barrier (false), or all at ONE wave-level operation, which is performed
+// and the lanes released (true)
+inline bool resolve_wave(unsigned w, unsigned nthreads) {
+    const unsigned lo = w * 64, hi = std::min(lo + 64, nthreads);
+    int op = -1;
+    unsigned live = 0;
+    for (unsigned t = lo; t < hi; ++t) {
+        const Fiber &f = fibers[t];
+        if (f.done) continue;
+        ++live;
+        const int here = f.waiting ? kNoOp : f.wave_op;
+        if (op >= 0 && here != op) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "divergence: lane %u waits at %s, an earlier lane at %s", t - lo, f.waiting ? "__syncthreads" : wave_op_name(here),
+                          op == kNoOp ? "__syncthreads" : wave_op_name(op));
+            wave_abort(w, msg);
+        }
+        op = here;
+    }
+    if (!live || op == kNoOp) return false;
+    if (op == kSwap32 || op == kSwap16) {
+        if (live != 64) wave_abort(w, "divergence: some lanes have returned (or the wave is partial) while others wait at a swap");
+        Fiber *l = &fibers[lo];
+        const unsigned half = op == kSwap32 ? 32 : 16;  // a.upper <-> b.lower of every pair of `half`-lane groups
+        for (unsigned g = 0; g < 64; g += 2 * half)
+            for (unsigned i = g; i < g + half; ++i) std::swap(l[i].wb, l[i + half].wa);
+    } else if (op == kFirstLane) {
+        unsigned first = 0;
+        bool have = false;
+        for (unsigned t = lo; t < hi; ++t) {
+            Fiber &f = fibers[t];
+            if (f.done) continue;
+            if (!have) first = f.wa, have = true;
+            if (f.wa != first) {
+                char msg[160];
+                std::snprintf(msg, sizeof msg, "readfirstlane of a value that is not wave-uniform: lane %u holds %u, the first live lane %u", t - lo, f.wa, first);
+                wave_abort(w, msg);
+            }
+        }
+    }
+    for (unsigned t = lo; t < hi; ++t) fibers[t].wave_op = kNoOp;
+    ++wave_ops;
+    return true;
+}
 
 inline void run_workgroup(unsigned nthreads) {
     if (fibers.size() < nthreads) {
@@ -226,25 +314,30 @@ inline void run_workgroup(unsigned nthreads) {
                 Fiber &f = fibers[t];
                 f.tid = {tx, ty, tz};
                 f.done = f.waiting = false;
+                f.wave_op = kNoOp;
                 f.fake = nullptr;
                 context_init(f.ctx, f.stack, fiber_main);
             }
     unsigned live = nthreads;
     while (live) {
-        bool waited = false;
         for (unsigned k = 0; k < nthreads; ++k) {
             Fiber &f = fibers[order == kAscending ? k : nthreads - 1 - k];
-            if (f.done) continue;
-            f.waiting = false;
+            if (f.done || f.waiting || f.wave_op) continue;
             cur = &f;
             thread_idx = f.tid;
             start_switch(&sched_fake, f.stack, kStackBytes);
             context_switch(sched_ctx, f.ctx);
             finish_switch(sched_fake, nullptr, nullptr);
             if (f.done) --live;
-            waited |= f.waiting;
         }
-        if (waited) ++barriers;  // a barrier that every live thread of the workgroup has now passed
+        // every live thread now waits.  Waves whose lanes all wait at one wave-level operation go on; when there is none, the
+        // whole workgroup stands at __syncthreads()
+        bool released = false;
+        for (unsigned w = 0; w * 64 < nthreads; ++w) released |= resolve_wave(w, nthreads);
+        if (!released && live) {
+            ++barriers;  // a barrier that every live thread of the workgroup has now passed
+            for (unsigned t = 0; t < nthreads; ++t) fibers[t].waiting = false;
+        }
     }
     cur = nullptr;
 }
@@ -253,7 +346,17 @@ template <typename K, typename... A>
 inline void launch(const char *text, const char *where, K kernel, dim3 grid, dim3 block, size_t lds, A... args) {
     ++launches;
     last_kernel = instantiation(text, where);
+    if (last_kernel.find(" in ") != std::string::npos) {  // a function pointer variable: the second, third .. function it has held are #1, #2 ..
+        static std::map<std::string, std::vector<const void *>> held;
+        std::vector<const void *> &h = held[last_kernel];
+        const void *fn = reinterpret_cast<const void *>(kernel);
+        size_t at = std::find(h.begin(), h.end(), fn) - h.begin();
+        if (at == h.size()) h.push_back(fn);
+        if (at) last_kernel.insert(last_kernel.find(" in "), "#" + std::to_string(at));
+    }
     ++ran[last_kernel];
+    ++ran_in[order][last_kernel];
+    if (force_grid) grid = dim3(force_grid);
     grid_dim = {grid.x, grid.y, grid.z};
     block_dim = {block.x, block.y, block.z};
     const unsigned nthreads = block.x * block.y * block.z;
@@ -284,7 +387,8 @@ inline void launch(const char *text, const char *where, K kernel, dim3 grid, dim
 }
 
 inline void print_counters() {
-    std::printf("  launches %llu  workgroups %llu  threads %llu  barriers %llu\n", launches, workgroups, threads_run, barriers);
+    std::printf("  launches %llu  workgroups %llu  threads %llu  barriers %llu  wave operations %llu\n", launches, workgroups, threads_run, barriers,
+                wave_ops);
 }
 
 }  // namespace block_shim
@@ -297,6 +401,10 @@ inline void print_counters() {
 #undef hipLaunchKernelGGL
 #define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...)                                                        \
     ::block_shim::launch(#kernel, __PRETTY_FUNCTION__, kernel, dim3(grid), dim3(block), (size_t)(lds), __VA_ARGS__)
+#undef hipExtLaunchKernelGGL
+#define hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, e0, e1, flags, ...)                                      \
+    ::block_shim::launch(#kernel, __PRETTY_FUNCTION__, kernel, dim3(grid), dim3(block), (size_t)(lds), __VA_ARGS__)
+#define hipFuncGetAttributes(attr, func) ((void)(attr), (void)(func), hipErrorInvalidValue)  // (the launchers' occupancy query: not here)
 #define hipGetLastError() (hipSuccess)  // the runtime's own answers 100 (no device) on a machine without one
 // raise_lds_limit (common.hpp) succeeds without the runtime: device 0, and the attribute is taken as set
 #define hipGetDevice(p) (*(p) = 0, hipSuccess)
@@ -311,3 +419,40 @@ inline unsigned __brev(unsigned x) {
     return ((x & 0xaaaaaaaau) >> 1) | ((x & 0x55555555u) << 1);
 }
 inline void __syncthreads() { ::block_shim::barrier(); }
+
+// ---- wave-level operations (see the head of this file) ----
+#define __builtin_amdgcn_permlane32_swap(a, b, fi, bc) ::block_shim::wave_rendezvous(::block_shim::kSwap32, (a), (b))
+#define __builtin_amdgcn_permlane16_swap(a, b, fi, bc) ::block_shim::wave_rendezvous(::block_shim::kSwap16, (a), (b))
+#define __builtin_amdgcn_wave_barrier() ((void)::block_shim::wave_rendezvous(::block_shim::kWaveBarrier, 0u, 0u))
+#define __builtin_amdgcn_readfirstlane(x) ((int)::block_shim::wave_rendezvous(::block_shim::kFirstLane, (unsigned)(x), 0u)[0])
+#define __builtin_amdgcn_mbcnt_lo(mask, x) ((x) + (unsigned)std::min(::block_shim::lane_id(), 32))      /* mask = ~0u in the kernels */
+#define __builtin_amdgcn_mbcnt_hi(mask, x) ((x) + (unsigned)std::max(::block_shim::lane_id() - 32, 0))
+#define __builtin_amdgcn_fence(...) ((void)0)
+#define __builtin_amdgcn_s_sleep(x) ((void)0)
+#define __builtin_amdgcn_s_memtime() (0ull)
+inline int __double2loint(double x) {
+    unsigned long long u;
+    std::memcpy(&u, &x, 8);
+    return (int)(unsigned)u;
+}
+inline int __double2hiint(double x) {
+    unsigned long long u;
+    std::memcpy(&u, &x, 8);
+    return (int)(unsigned)(u >> 32);
+}
+inline double __hiloint2double(int hi, int lo) {
+    const unsigned long long u = ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+    double x;
+    std::memcpy(&x, &u, 8);
+    return x;
+}
+inline unsigned __float_as_uint(float x) {
+    unsigned u;
+    std::memcpy(&u, &x, 4);
+    return u;
+}
+inline float __uint_as_float(unsigned u) {
+    float x;
+    std::memcpy(&x, &u, 4);
+    return x;
+}
