@@ -1875,9 +1875,51 @@ def nufft3(x, s, c, eps: float | None = None, direction=Direction.Forward):
 
 
 # ---------------------------------------------------------------------------------------------
-# non-uniform FFTs of types 1 and 2 in two dimensions (no reference counterpart)
+# non-uniform FFTs of types 1 and 2 in two and three dimensions (no reference counterpart)
 # ---------------------------------------------------------------------------------------------
-class PlannerNufft2d64(_DevicePoints, _AnyHandle):
+class _PlannerNufftNd(_DevicePoints, _AnyHandle):
+    """what the planners of two and three dimensions share: phast_planner_nufft{_rank}d{_sfx}_*"""
+
+    _eps = 1e-12
+    _rank = 0
+
+    def _init(self, n_modes, coords, eps):
+        shape = tuple(int(v) for v in n_modes)
+        if len(shape) != self._rank:
+            raise ValueError(f"n_modes: need {self._rank} mode counts, not {len(shape)}")
+        pts = [np.ascontiguousarray(v.detach().cpu().numpy() if _is_torch(v) else v, dtype=np.float64).reshape(-1) for v in coords]
+        if any(p.size != pts[0].size for p in pts):
+            _check(2)
+        eps = self._eps if eps is None else float(eps)
+        self._new(*shape, *(p.ctypes.data_as(C.c_void_p) for p in pts), pts[0].size, eps)
+        self._describe_points(shape, pts[0].size, eps)
+
+    def _describe_points(self, n_modes, m, eps):
+        self.n_modes = tuple(n_modes)
+        self.n = int(np.prod(self.n_modes, dtype=np.int64))
+        self.m = self.m_points = m
+        self.eps = eps
+        self.grid_len = int(self._fn("grid_len")(self._h))
+        if self._rank == 2:
+            self.grid_shape = (int(self._fn("grid_rows")(self._h)), int(self._fn("grid_cols")(self._h)))
+        else:
+            self.grid_shape = tuple(int(self._fn("grid_dim")(self._h, axis)) for axis in range(self._rank))
+        self.width = int(self._fn("width")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` transforms works in: 4 G batch, G = ``grid_len``.  A smaller workspace of
+        at least ``workspace_len(1)`` runs the batch in chunks."""
+        return self._workspace_len(batch)
+
+    def time_stages(self, type: int, in_re, in_im, out_re, out_im, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (spread or pre, the transform of the grid, deconvolve or interpolate) of a
+        Forward call of ``type`` 1 or 2 of ``batch`` transforms at the natural distances on device tensors (measurement hook)"""
+        bufs = [_Slice(_flat(in_re), self._dtype, "in_re"), _NULL if in_im is None else _Slice(_flat(in_im), self._dtype, "in_im"),
+                _Slice(_flat(out_re), self._dtype, "out_re"), _Slice(_flat(out_im), self._dtype, "out_im")]
+        return self._time("time_stages", bufs, (type, batch), batch, workspace, reps)[:3]
+
+
+class PlannerNufft2d64(_PlannerNufftNd):
     """f64 non-uniform FFTs of the M points ``(x[j], y[j])`` (doubles in turns, any finite value, reduced mod 1 per coordinate)
     and ``n_modes = (n1, n2)`` modes, row-major, each axis in numpy ``fftfreq`` order (``k1`` pairs with x, ``k2`` with y), to
     the relative accuracy ``eps``:
@@ -1891,16 +1933,10 @@ class PlannerNufft2d64(_DevicePoints, _AnyHandle):
     replaces them."""
 
     _prefix = "nufft2d"
-    _eps = 1e-12
+    _rank = 2
 
     def __init__(self, n_modes, x, y, eps: float | None = None):
-        n1, n2 = (int(v) for v in n_modes)
-        px, py = (np.ascontiguousarray(v.detach().cpu().numpy() if _is_torch(v) else v, dtype=np.float64).reshape(-1) for v in (x, y))
-        if px.size != py.size:
-            _check(2)
-        eps = self._eps if eps is None else float(eps)
-        self._new(n1, n2, px.ctypes.data_as(C.c_void_p), py.ctypes.data_as(C.c_void_p), px.size, eps)
-        self._describe_points((n1, n2), px.size, eps)
+        self._init(n_modes, (x, y), eps)
 
     @classmethod
     def from_device(cls, n_modes, x, y, eps: float | None = None, stream=None):
@@ -1910,28 +1946,6 @@ class PlannerNufft2d64(_DevicePoints, _AnyHandle):
     def set_points(self, x, y, stream=None) -> None:
         """as :meth:`PlannerNufft64.set_points`"""
         self._set_points((x, y), stream)
-
-    def _describe_points(self, n_modes, m, eps):
-        n1, n2 = n_modes
-        self.n_modes = (n1, n2)
-        self.n = n1 * n2
-        self.m = self.m_points = m
-        self.eps = eps
-        self.grid_len = int(self._fn("grid_len")(self._h))
-        self.grid_shape = (int(self._fn("grid_rows")(self._h)), int(self._fn("grid_cols")(self._h)))
-        self.width = int(self._fn("width")(self._h))
-
-    def workspace_len(self, batch: int = 1) -> int:
-        """Elements of T a device call of ``batch`` transforms works in: 4 G batch, G = ``grid_len``.  A smaller workspace of
-        at least 4 G runs the batch in chunks."""
-        return self._workspace_len(batch)
-
-    def time_stages(self, type: int, in_re, in_im, out_re, out_im, batch: int = 1, workspace=None, reps: int = 10):
-        """Average HIP-event milliseconds of (spread or pre, the 2-D transform of the grid, deconvolve or interpolate) of a
-        Forward call of ``type`` 1 or 2 of ``batch`` transforms at the natural distances on device tensors (measurement hook)"""
-        bufs = [_Slice(_flat(in_re), self._dtype, "in_re"), _NULL if in_im is None else _Slice(_flat(in_im), self._dtype, "in_im"),
-                _Slice(_flat(out_re), self._dtype, "out_re"), _Slice(_flat(out_im), self._dtype, "out_im")]
-        return self._time("time_stages", bufs, (type, batch), batch, workspace, reps)[:3]
 
 
 class PlannerNufft2d32(PlannerNufft2d64):
@@ -1943,174 +1957,7 @@ class PlannerNufft2d32(PlannerNufft2d64):
     _eps = 1e-6
 
 
-def _nufft2d_batched(t, x_re, x_im, planner, direction, out, work, stream):
-    import torch
-
-    want = torch.float64 if planner._dtype == np.float64 else torch.float32
-    n1, n2 = planner.n_modes
-
-    def plane(v, what, modes):
-        """(transforms, distance, batched) of a point-side or mode-side plane"""
-        if not _is_torch(v) or v.device.type != "cuda" or v.dtype != want:
-            raise TypeError(f"{what}: need a {want} device tensor")
-        per = n1 * n2 if modes else planner.m_points
-        if modes and (v.dim() == 3 or (v.dim() == 2 and tuple(v.shape) == (n1, n2))):  # (batch, N1, N2) or (N1, N2)
-            ok = tuple(v.shape[-2:]) == (n1, n2) and (n2 == 1 or v.stride(-1) == 1) and (n1 == 1 or v.stride(-2) == n2)
-            batched = v.dim() == 3
-        else:  # (batch, per) or (per,)
-            ok = v.dim() in (1, 2) and v.shape[-1] == per and (per == 1 or v.stride(-1) == 1)
-            batched = v.dim() == 2
-        if not ok:
-            shapes = f"(batch, {n1}, {n2}), ({n1}, {n2}), (batch, {per}) or ({per},)" if modes else f"(batch, {per}) or ({per},)"
-            raise ValueError(f"{what}: need shape {shapes} with a contiguous last axis, not {tuple(v.shape)}")
-        rows = v.shape[0] if batched else 1
-        dist = v.stride(0) if batched and rows > 1 else per
-        if dist < per:
-            raise ValueError(f"{what}: rows overlap")
-        return rows, dist, batched
-
-    batch, in_dist, batched = plane(x_re, "x_re", t == 2)
-    if x_im is not None and (plane(x_im, "x_im", t == 2) != (batch, in_dist, batched) or x_im.shape != x_re.shape):
-        raise ValueError("x_im: need the shape and the strides of x_re")
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        if out is None:
-            shape = ((batch,) if batched else ()) + ((n1, n2) if t == 1 else (planner.m_points,))
-            out = (torch.empty(shape, dtype=want, device=x_re.device), torch.empty(shape, dtype=want, device=x_re.device))
-        out_re, out_im = out
-        rows, out_dist, _ = plane(out_re, "out_re", t == 1)
-        if rows != batch or plane(out_im, "out_im", t == 1)[:2] != (batch, out_dist) or out_im.shape != out_re.shape:
-            raise ValueError("out: need a pair of tensors of one row per transform with equal shapes and strides")
-        ws = _any_workspace(planner, batch, work)
-        _check(_call(f"phast_nufft2d{t}_{planner._sfx}_dev", x_re.data_ptr(), None if x_im is None else x_im.data_ptr(), in_dist,
-                     out_re.data_ptr(), out_im.data_ptr(), out_dist, batch, int(direction), planner._h, ws.ptr, ws.len,
-                     _stream()))
-    return out_re, out_im
-
-
-def nufft2d1_batched(c_re, c_im, planner, direction=Direction.Forward, out=None, work=None, stream=None):
-    """Device-resident batch of two-dimensional type 1 transforms (points -> modes) through one planner: ``c_re`` (and ``c_im``,
-    or ``None`` for real data) are torch device tensors of shape ``(batch, M)`` or ``(M,)`` of the planner's type whose last axis
-    is contiguous; returns ``(out_re, out_im)`` of shape ``(batch, n1, n2)`` or ``(n1, n2)``.  ``out``: such a pair to write
-    into, of shape ``(batch, n1, n2)``, ``(n1, n2)`` or flat, ``(batch, n1 n2)`` or ``(n1 n2,)``, with a contiguous last axis
-    (it must not overlap the input or ``work``); ``work``: a device tensor of at least ``planner.workspace_len(1)`` elements
-    (fewer than ``planner.workspace_len(batch)`` runs the batch in chunks), by default one from torch's allocator; ``stream``: a
-    ``torch.cuda.Stream``, by default the current one."""
-    return _nufft2d_batched(1, c_re, c_im, planner, direction, out, work, stream)
-
-
-def nufft2d2_batched(f_re, f_im, planner, direction=Direction.Forward, out=None, work=None, stream=None):
-    """Device-resident batch of two-dimensional type 2 transforms (modes -> points): as :func:`nufft2d1_batched` with inputs of
-    the mode-side shapes and outputs of M values per transform"""
-    return _nufft2d_batched(2, f_re, f_im, planner, direction, out, work, stream)
-
-
-def _nufft2d_host(t, sfx, dtype, in_re, in_im, out_re, out_im, direction, planner=None, x=None, y=None, n_modes=None, eps=None):
-    a = _Slice(_flat(in_re), dtype, "in_re")
-    b = _NULL if in_im is None else _Slice(_flat(in_im), dtype, "in_im")
-    o_re, o_im = _Slice(_flat(out_re), dtype, "out_re"), _Slice(_flat(out_im), dtype, "out_im")
-    if _same_place(*(s for s in (a, b, o_re, o_im) if s is not _NULL)):
-        raise TypeError(f"nufft2d{t}_{sfx} takes host arrays (nufft2d{t}_batched takes device tensors)")
-    if (b is not _NULL and b.len != a.len) or o_re.len != o_im.len:
-        _check(2)
-    if planner is not None:
-        _check(_call(f"phast_nufft2d{t}_{sfx}_with_planner", a.ptr, b.ptr, a.len, o_re.ptr, o_im.ptr, o_re.len, int(direction),
-                     planner._h))
-        return
-    px, py = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (x, y))
-    if len(n_modes) != 2:
-        raise ValueError(f"nufft2d{t}_{sfx}: the mode-side arrays need shape (n1, n2), not {tuple(n_modes)}")
-    n1, n2 = (int(v) for v in n_modes)
-    n_in, n_out = (px.size, n1 * n2) if t == 1 else (n1 * n2, px.size)
-    if px.size != py.size or a.len != n_in or o_re.len != n_out:
-        _check(2)
-    _check(_call(f"phast_nufft2d{t}_{sfx}", px.ctypes.data_as(C.c_void_p), py.ctypes.data_as(C.c_void_p), px.size, a.ptr, b.ptr,
-                 o_re.ptr, o_im.ptr, n1, n2, float(eps), int(direction)))
-
-
-def nufft2d1_64(x, y, c_re, c_im, out_re, out_im, eps: float = 1e-12, direction=Direction.Forward) -> None:
-    """f64 two-dimensional type 1 transform of one host vector of M values at the points ``(x, y)`` (``c_im`` may be ``None``:
-    real data) into host arrays of shape ``(n1, n2)``, through a planner of its own (blocking)"""
-    _nufft2d_host(1, "64", np.float64, c_re, c_im, out_re, out_im, direction, x=x, y=y, n_modes=np.shape(out_re), eps=eps)
-
-
-def nufft2d1_32(x, y, c_re, c_im, out_re, out_im, eps: float = 1e-6, direction=Direction.Forward) -> None:
-    """f32 twin of :func:`nufft2d1_64`"""
-    _nufft2d_host(1, "32", np.float32, c_re, c_im, out_re, out_im, direction, x=x, y=y, n_modes=np.shape(out_re), eps=eps)
-
-
-def nufft2d2_64(x, y, f_re, f_im, out_re, out_im, eps: float = 1e-12, direction=Direction.Forward) -> None:
-    """f64 two-dimensional type 2 transform of one host array of shape ``(n1, n2)`` into host arrays of M values at the points
-    ``(x, y)`` (blocking)"""
-    _nufft2d_host(2, "64", np.float64, f_re, f_im, out_re, out_im, direction, x=x, y=y, n_modes=np.shape(f_re), eps=eps)
-
-
-def nufft2d2_32(x, y, f_re, f_im, out_re, out_im, eps: float = 1e-6, direction=Direction.Forward) -> None:
-    """f32 twin of :func:`nufft2d2_64`"""
-    _nufft2d_host(2, "32", np.float32, f_re, f_im, out_re, out_im, direction, x=x, y=y, n_modes=np.shape(f_re), eps=eps)
-
-
-def nufft2d1_64_with_planner(c_re, c_im, out_re, out_im, planner: PlannerNufft2d64, direction=Direction.Forward) -> None:
-    _nufft2d_host(1, "64", np.float64, c_re, c_im, out_re, out_im, direction, planner)
-
-
-def nufft2d1_32_with_planner(c_re, c_im, out_re, out_im, planner: PlannerNufft2d32, direction=Direction.Forward) -> None:
-    _nufft2d_host(1, "32", np.float32, c_re, c_im, out_re, out_im, direction, planner)
-
-
-def nufft2d2_64_with_planner(f_re, f_im, out_re, out_im, planner: PlannerNufft2d64, direction=Direction.Forward) -> None:
-    _nufft2d_host(2, "64", np.float64, f_re, f_im, out_re, out_im, direction, planner)
-
-
-def nufft2d2_32_with_planner(f_re, f_im, out_re, out_im, planner: PlannerNufft2d32, direction=Direction.Forward) -> None:
-    _nufft2d_host(2, "32", np.float32, f_re, f_im, out_re, out_im, direction, planner)
-
-
-def _nufft2d(t, x, y, v, n_modes, eps, direction):
-    import torch
-
-    kinds = {torch.float64: (PlannerNufft2d64, torch.float64), torch.complex128: (PlannerNufft2d64, torch.float64),
-             torch.float32: (PlannerNufft2d32, torch.float32), torch.complex64: (PlannerNufft2d32, torch.float32)}
-    if not _is_torch(v) or v.device.type != "cuda" or v.dtype not in kinds or v.dim() < (1 if t == 1 else 2):
-        raise TypeError("need a float64, float32, complex128 or complex64 device tensor of at least one axis (points) or two (modes)")
-    cls, real = kinds[v.dtype]
-    planner = cls(n_modes, x, y, eps)
-    n1, n2 = planner.n_modes
-    tail_in, tail_out = ((planner.m_points,), (n1, n2)) if t == 1 else ((n1, n2), (planner.m_points,))
-    if tuple(v.shape[-len(tail_in):]) != tail_in:
-        raise ValueError(f"the last axes are {tuple(v.shape[-len(tail_in):])}, the transform takes {tail_in}")
-    lead = tuple(v.shape[:-len(tail_in)])
-    n_in, n_out = int(np.prod(tail_in)), int(np.prod(tail_out))
-    rows = v.reshape(-1, n_in)
-    if v.is_complex():
-        x_re, x_im = rows.real.contiguous(), rows.imag.contiguous()
-    else:
-        x_re, x_im = rows.contiguous(), None
-    out = torch.empty((2, rows.shape[0], n_out), dtype=real, device=v.device)
-    if rows.shape[0]:
-        _nufft2d_batched(t, x_re, x_im, planner, direction, (out[0], out[1]), None, None)
-        torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
-    return torch.complex(out[0], out[1]).reshape(lead + tail_out)
-
-
-def nufft2d1(x, y, c, n_modes, eps: float | None = None, direction=Direction.Forward):
-    """Two-dimensional type 1 non-uniform FFT of a real or complex device tensor ``c`` over its last axis (M values at the
-    points ``(x, y)``, in turns) into ``n_modes = (n1, n2)`` modes in ``fftfreq`` order: a new complex tensor of shape
-    ``c.shape[:-1] + (n1, n2)``.  float64 / complex128 run in f64 (eps defaults to 1e-12), float32 / complex64 in f32 (1e-6)."""
-    return _nufft2d(1, x, y, c, n_modes, eps, direction)
-
-
-def nufft2d2(x, y, F, eps: float | None = None, direction=Direction.Forward):
-    """Two-dimensional type 2 non-uniform FFT of a real or complex device tensor ``F`` of modes over its last two axes, evaluated
-    at the points ``(x, y)`` (in turns): a new complex tensor of shape ``F.shape[:-2] + (len(x),)``"""
-    if not _is_torch(F) or F.dim() < 2:
-        raise TypeError("need a device tensor of at least two axes")
-    return _nufft2d(2, x, y, F, tuple(F.shape[-2:]), eps, direction)
-
-
-# ---------------------------------------------------------------------------------------------
-# non-uniform FFTs of types 1 and 2 in three dimensions (no reference counterpart)
-# ---------------------------------------------------------------------------------------------
-class PlannerNufft3d64(_DevicePoints, _AnyHandle):
+class PlannerNufft3d64(_PlannerNufftNd):
     """f64 non-uniform FFTs of the M points ``(x[j], y[j], z[j])`` (doubles in turns, any finite value, reduced mod 1 per coordinate)
     and ``n_modes = (n1, n2, n3)`` modes, row-major, each axis in numpy ``fftfreq`` order (``k1`` pairs with x, ``k2`` with y, ``k3`` with z), to
     the relative accuracy ``eps``:
@@ -2124,16 +1971,10 @@ class PlannerNufft3d64(_DevicePoints, _AnyHandle):
     replaces them."""
 
     _prefix = "nufft3d"
-    _eps = 1e-12
+    _rank = 3
 
     def __init__(self, n_modes, x, y, z, eps: float | None = None):
-        n1, n2, n3 = (int(v) for v in n_modes)
-        px, py, pz = (np.ascontiguousarray(v.detach().cpu().numpy() if _is_torch(v) else v, dtype=np.float64).reshape(-1) for v in (x, y, z))
-        if px.size != py.size or px.size != pz.size:
-            _check(2)
-        eps = self._eps if eps is None else float(eps)
-        self._new(n1, n2, n3, px.ctypes.data_as(C.c_void_p), py.ctypes.data_as(C.c_void_p), pz.ctypes.data_as(C.c_void_p), px.size, eps)
-        self._describe_points((n1, n2, n3), px.size, eps)
+        self._init(n_modes, (x, y, z), eps)
 
     @classmethod
     def from_device(cls, n_modes, x, y, z, eps: float | None = None, stream=None):
@@ -2143,28 +1984,6 @@ class PlannerNufft3d64(_DevicePoints, _AnyHandle):
     def set_points(self, x, y, z, stream=None) -> None:
         """as :meth:`PlannerNufft64.set_points`"""
         self._set_points((x, y, z), stream)
-
-    def _describe_points(self, n_modes, m, eps):
-        n1, n2, n3 = n_modes
-        self.n_modes = (n1, n2, n3)
-        self.n = n1 * n2 * n3
-        self.m = self.m_points = m
-        self.eps = eps
-        self.grid_len = int(self._fn("grid_len")(self._h))
-        self.grid_shape = tuple(int(self._fn("grid_dim")(self._h, axis)) for axis in range(3))
-        self.width = int(self._fn("width")(self._h))
-
-    def workspace_len(self, batch: int = 1) -> int:
-        """Elements of T a device call of ``batch`` transforms works in: 4 G batch, G = ``grid_len``.  A smaller workspace of
-        at least ``workspace_len(1)`` runs the batch in chunks."""
-        return self._workspace_len(batch)
-
-    def time_stages(self, type: int, in_re, in_im, out_re, out_im, batch: int = 1, workspace=None, reps: int = 10):
-        """Average HIP-event milliseconds of (spread or pre, the 3-D transform of the grid, deconvolve or interpolate) of a
-        Forward call of ``type`` 1 or 2 of ``batch`` transforms at the natural distances on device tensors (measurement hook)"""
-        bufs = [_Slice(_flat(in_re), self._dtype, "in_re"), _NULL if in_im is None else _Slice(_flat(in_im), self._dtype, "in_im"),
-                _Slice(_flat(out_re), self._dtype, "out_re"), _Slice(_flat(out_im), self._dtype, "out_im")]
-        return self._time("time_stages", bufs, (type, batch), batch, workspace, reps)[:3]
 
 
 class PlannerNufft3d32(PlannerNufft3d64):
@@ -2176,26 +1995,29 @@ class PlannerNufft3d32(PlannerNufft3d64):
     _eps = 1e-6
 
 
-def _nufft3d_batched(t, x_re, x_im, planner, direction, out, work, stream):
+def _nufft_nd_batched(rank, t, x_re, x_im, planner, direction, out, work, stream):
     import torch
 
     want = torch.float64 if planner._dtype == np.float64 else torch.float32
-    n1, n2, n3 = planner.n_modes
+    nm = tuple(planner.n_modes)
+    if len(nm) != rank:
+        raise ValueError(f"nufft{rank}d{t}_batched: need a planner of {rank} dimensions, not of {len(nm)}")
+    row_major = [int(np.prod(nm[i + 1:], dtype=np.int64)) for i in range(rank)]  # the stride of axis i of a mode-side array
 
     def plane(v, what, modes):
         """(transforms, distance, batched) of a point-side or mode-side plane"""
         if not _is_torch(v) or v.device.type != "cuda" or v.dtype != want:
             raise TypeError(f"{what}: need a {want} device tensor")
-        per = n1 * n2 * n3 if modes else planner.m_points
-        if modes and (v.dim() == 4 or (v.dim() == 3 and tuple(v.shape) == (n1, n2, n3))):  # (batch, N1, N2, N3) or (N1, N2, N3)
-            ok = (tuple(v.shape[-3:]) == (n1, n2, n3) and (n3 == 1 or v.stride(-1) == 1) and (n2 == 1 or v.stride(-2) == n3)
-                  and (n1 == 1 or v.stride(-3) == n2 * n3))
-            batched = v.dim() == 4
+        per = planner.n if modes else planner.m_points
+        if modes and (v.dim() == rank + 1 or (v.dim() == rank and tuple(v.shape) == nm)):  # (batch, N1, .., ND) or (N1, .., ND)
+            ok = tuple(v.shape[-rank:]) == nm and all(nm[i] == 1 or v.stride(i - rank) == row_major[i] for i in range(rank))
+            batched = v.dim() == rank + 1
         else:  # (batch, per) or (per,)
             ok = v.dim() in (1, 2) and v.shape[-1] == per and (per == 1 or v.stride(-1) == 1)
             batched = v.dim() == 2
         if not ok:
-            shapes = f"(batch, {n1}, {n2}, {n3}), ({n1}, {n2}, {n3}), (batch, {per}) or ({per},)" if modes else f"(batch, {per}) or ({per},)"
+            dims = ", ".join(str(k) for k in nm)
+            shapes = f"(batch, {dims}), ({dims}), (batch, {per}) or ({per},)" if modes else f"(batch, {per}) or ({per},)"
             raise ValueError(f"{what}: need shape {shapes} with a contiguous last axis, not {tuple(v.shape)}")
         rows = v.shape[0] if batched else 1
         dist = v.stride(0) if batched and rows > 1 else per
@@ -2208,17 +2030,34 @@ def _nufft3d_batched(t, x_re, x_im, planner, direction, out, work, stream):
         raise ValueError("x_im: need the shape and the strides of x_re")
     with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
         if out is None:
-            shape = ((batch,) if batched else ()) + ((n1, n2, n3) if t == 1 else (planner.m_points,))
+            shape = ((batch,) if batched else ()) + (nm if t == 1 else (planner.m_points,))
             out = (torch.empty(shape, dtype=want, device=x_re.device), torch.empty(shape, dtype=want, device=x_re.device))
         out_re, out_im = out
         rows, out_dist, _ = plane(out_re, "out_re", t == 1)
         if rows != batch or plane(out_im, "out_im", t == 1)[:2] != (batch, out_dist) or out_im.shape != out_re.shape:
             raise ValueError("out: need a pair of tensors of one row per transform with equal shapes and strides")
         ws = _any_workspace(planner, batch, work)
-        _check(_call(f"phast_nufft3d{t}_{planner._sfx}_dev", x_re.data_ptr(), None if x_im is None else x_im.data_ptr(), in_dist,
+        _check(_call(f"phast_nufft{rank}d{t}_{planner._sfx}_dev", x_re.data_ptr(), None if x_im is None else x_im.data_ptr(), in_dist,
                      out_re.data_ptr(), out_im.data_ptr(), out_dist, batch, int(direction), planner._h, ws.ptr, ws.len,
                      _stream()))
     return out_re, out_im
+
+
+def nufft2d1_batched(c_re, c_im, planner, direction=Direction.Forward, out=None, work=None, stream=None):
+    """Device-resident batch of two-dimensional type 1 transforms (points -> modes) through one planner: ``c_re`` (and ``c_im``,
+    or ``None`` for real data) are torch device tensors of shape ``(batch, M)`` or ``(M,)`` of the planner's type whose last axis
+    is contiguous; returns ``(out_re, out_im)`` of shape ``(batch, n1, n2)`` or ``(n1, n2)``.  ``out``: such a pair to write
+    into, of shape ``(batch, n1, n2)``, ``(n1, n2)`` or flat, ``(batch, n1 n2)`` or ``(n1 n2,)``, with a contiguous last axis
+    (it must not overlap the input or ``work``); ``work``: a device tensor of at least ``planner.workspace_len(1)`` elements
+    (fewer than ``planner.workspace_len(batch)`` runs the batch in chunks), by default one from torch's allocator; ``stream``: a
+    ``torch.cuda.Stream``, by default the current one."""
+    return _nufft_nd_batched(2, 1, c_re, c_im, planner, direction, out, work, stream)
+
+
+def nufft2d2_batched(f_re, f_im, planner, direction=Direction.Forward, out=None, work=None, stream=None):
+    """Device-resident batch of two-dimensional type 2 transforms (modes -> points): as :func:`nufft2d1_batched` with inputs of
+    the mode-side shapes and outputs of M values per transform"""
+    return _nufft_nd_batched(2, 2, f_re, f_im, planner, direction, out, work, stream)
 
 
 def nufft3d1_batched(c_re, c_im, planner, direction=Direction.Forward, out=None, work=None, stream=None):
@@ -2229,87 +2068,134 @@ def nufft3d1_batched(c_re, c_im, planner, direction=Direction.Forward, out=None,
     (it must not overlap the input or ``work``); ``work``: a device tensor of at least ``planner.workspace_len(1)`` elements
     (fewer than ``planner.workspace_len(batch)`` runs the batch in chunks), by default one from torch's allocator; ``stream``: a
     ``torch.cuda.Stream``, by default the current one."""
-    return _nufft3d_batched(1, c_re, c_im, planner, direction, out, work, stream)
+    return _nufft_nd_batched(3, 1, c_re, c_im, planner, direction, out, work, stream)
 
 
 def nufft3d2_batched(f_re, f_im, planner, direction=Direction.Forward, out=None, work=None, stream=None):
     """Device-resident batch of three-dimensional type 2 transforms (modes -> points): as :func:`nufft3d1_batched` with inputs of
     the mode-side shapes and outputs of M values per transform"""
-    return _nufft3d_batched(2, f_re, f_im, planner, direction, out, work, stream)
+    return _nufft_nd_batched(3, 2, f_re, f_im, planner, direction, out, work, stream)
 
 
-def _nufft3d_host(t, sfx, dtype, in_re, in_im, out_re, out_im, direction, planner=None, x=None, y=None, z=None, n_modes=None, eps=None):
+def _nufft_nd_host(rank, t, sfx, dtype, in_re, in_im, out_re, out_im, direction, planner=None, coords=None, n_modes=None, eps=None):
     a = _Slice(_flat(in_re), dtype, "in_re")
     b = _NULL if in_im is None else _Slice(_flat(in_im), dtype, "in_im")
     o_re, o_im = _Slice(_flat(out_re), dtype, "out_re"), _Slice(_flat(out_im), dtype, "out_im")
+    name = f"nufft{rank}d{t}"
     if _same_place(*(s for s in (a, b, o_re, o_im) if s is not _NULL)):
-        raise TypeError(f"nufft3d{t}_{sfx} takes host arrays (nufft3d{t}_batched takes device tensors)")
+        raise TypeError(f"{name}_{sfx} takes host arrays ({name}_batched takes device tensors)")
     if (b is not _NULL and b.len != a.len) or o_re.len != o_im.len:
         _check(2)
     if planner is not None:
-        _check(_call(f"phast_nufft3d{t}_{sfx}_with_planner", a.ptr, b.ptr, a.len, o_re.ptr, o_im.ptr, o_re.len, int(direction),
+        _check(_call(f"phast_{name}_{sfx}_with_planner", a.ptr, b.ptr, a.len, o_re.ptr, o_im.ptr, o_re.len, int(direction),
                      planner._h))
         return
-    px, py, pz = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (x, y, z))
-    if len(n_modes) != 3:
-        raise ValueError(f"nufft3d{t}_{sfx}: the mode-side arrays need shape (n1, n2, n3), not {tuple(n_modes)}")
-    n1, n2, n3 = (int(v) for v in n_modes)
-    n_in, n_out = (px.size, n1 * n2 * n3) if t == 1 else (n1 * n2 * n3, px.size)
-    if px.size != py.size or px.size != pz.size or a.len != n_in or o_re.len != n_out:
+    pts = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in coords]
+    if len(n_modes) != rank:
+        want = ", ".join(f"n{i + 1}" for i in range(rank))
+        raise ValueError(f"{name}_{sfx}: the mode-side arrays need shape ({want}), not {tuple(n_modes)}")
+    shape = tuple(int(v) for v in n_modes)
+    m, n = pts[0].size, int(np.prod(shape, dtype=np.int64))
+    n_in, n_out = (m, n) if t == 1 else (n, m)
+    if any(p.size != m for p in pts) or a.len != n_in or o_re.len != n_out:
         _check(2)
-    _check(_call(f"phast_nufft3d{t}_{sfx}", px.ctypes.data_as(C.c_void_p), py.ctypes.data_as(C.c_void_p), pz.ctypes.data_as(C.c_void_p), px.size,
-                 a.ptr, b.ptr, o_re.ptr, o_im.ptr, n1, n2, n3, float(eps), int(direction)))
+    _check(_call(f"phast_{name}_{sfx}", *(p.ctypes.data_as(C.c_void_p) for p in pts), m, a.ptr, b.ptr, o_re.ptr, o_im.ptr, *shape,
+                 float(eps), int(direction)))
+
+
+def nufft2d1_64(x, y, c_re, c_im, out_re, out_im, eps: float = 1e-12, direction=Direction.Forward) -> None:
+    """f64 two-dimensional type 1 transform of one host vector of M values at the points ``(x, y)`` (``c_im`` may be ``None``:
+    real data) into host arrays of shape ``(n1, n2)``, through a planner of its own (blocking)"""
+    _nufft_nd_host(2, 1, "64", np.float64, c_re, c_im, out_re, out_im, direction, coords=(x, y), n_modes=np.shape(out_re), eps=eps)
+
+
+def nufft2d1_32(x, y, c_re, c_im, out_re, out_im, eps: float = 1e-6, direction=Direction.Forward) -> None:
+    """f32 twin of :func:`nufft2d1_64`"""
+    _nufft_nd_host(2, 1, "32", np.float32, c_re, c_im, out_re, out_im, direction, coords=(x, y), n_modes=np.shape(out_re), eps=eps)
+
+
+def nufft2d2_64(x, y, f_re, f_im, out_re, out_im, eps: float = 1e-12, direction=Direction.Forward) -> None:
+    """f64 two-dimensional type 2 transform of one host array of shape ``(n1, n2)`` into host arrays of M values at the points
+    ``(x, y)`` (blocking)"""
+    _nufft_nd_host(2, 2, "64", np.float64, f_re, f_im, out_re, out_im, direction, coords=(x, y), n_modes=np.shape(f_re), eps=eps)
+
+
+def nufft2d2_32(x, y, f_re, f_im, out_re, out_im, eps: float = 1e-6, direction=Direction.Forward) -> None:
+    """f32 twin of :func:`nufft2d2_64`"""
+    _nufft_nd_host(2, 2, "32", np.float32, f_re, f_im, out_re, out_im, direction, coords=(x, y), n_modes=np.shape(f_re), eps=eps)
+
+
+def nufft2d1_64_with_planner(c_re, c_im, out_re, out_im, planner: PlannerNufft2d64, direction=Direction.Forward) -> None:
+    _nufft_nd_host(2, 1, "64", np.float64, c_re, c_im, out_re, out_im, direction, planner)
+
+
+def nufft2d1_32_with_planner(c_re, c_im, out_re, out_im, planner: PlannerNufft2d32, direction=Direction.Forward) -> None:
+    _nufft_nd_host(2, 1, "32", np.float32, c_re, c_im, out_re, out_im, direction, planner)
+
+
+def nufft2d2_64_with_planner(f_re, f_im, out_re, out_im, planner: PlannerNufft2d64, direction=Direction.Forward) -> None:
+    _nufft_nd_host(2, 2, "64", np.float64, f_re, f_im, out_re, out_im, direction, planner)
+
+
+def nufft2d2_32_with_planner(f_re, f_im, out_re, out_im, planner: PlannerNufft2d32, direction=Direction.Forward) -> None:
+    _nufft_nd_host(2, 2, "32", np.float32, f_re, f_im, out_re, out_im, direction, planner)
 
 
 def nufft3d1_64(x, y, z, c_re, c_im, out_re, out_im, eps: float = 1e-12, direction=Direction.Forward) -> None:
     """f64 three-dimensional type 1 transform of one host vector of M values at the points ``(x, y, z)`` (``c_im`` may be ``None``:
     real data) into host arrays of shape ``(n1, n2, n3)``, through a planner of its own (blocking)"""
-    _nufft3d_host(1, "64", np.float64, c_re, c_im, out_re, out_im, direction, x=x, y=y, z=z, n_modes=np.shape(out_re), eps=eps)
+    _nufft_nd_host(3, 1, "64", np.float64, c_re, c_im, out_re, out_im, direction, coords=(x, y, z), n_modes=np.shape(out_re), eps=eps)
 
 
 def nufft3d1_32(x, y, z, c_re, c_im, out_re, out_im, eps: float = 1e-6, direction=Direction.Forward) -> None:
     """f32 twin of :func:`nufft3d1_64`"""
-    _nufft3d_host(1, "32", np.float32, c_re, c_im, out_re, out_im, direction, x=x, y=y, z=z, n_modes=np.shape(out_re), eps=eps)
+    _nufft_nd_host(3, 1, "32", np.float32, c_re, c_im, out_re, out_im, direction, coords=(x, y, z), n_modes=np.shape(out_re), eps=eps)
 
 
 def nufft3d2_64(x, y, z, f_re, f_im, out_re, out_im, eps: float = 1e-12, direction=Direction.Forward) -> None:
     """f64 three-dimensional type 2 transform of one host array of shape ``(n1, n2, n3)`` into host arrays of M values at the points
     ``(x, y)`` (blocking)"""
-    _nufft3d_host(2, "64", np.float64, f_re, f_im, out_re, out_im, direction, x=x, y=y, z=z, n_modes=np.shape(f_re), eps=eps)
+    _nufft_nd_host(3, 2, "64", np.float64, f_re, f_im, out_re, out_im, direction, coords=(x, y, z), n_modes=np.shape(f_re), eps=eps)
 
 
 def nufft3d2_32(x, y, z, f_re, f_im, out_re, out_im, eps: float = 1e-6, direction=Direction.Forward) -> None:
     """f32 twin of :func:`nufft3d2_64`"""
-    _nufft3d_host(2, "32", np.float32, f_re, f_im, out_re, out_im, direction, x=x, y=y, z=z, n_modes=np.shape(f_re), eps=eps)
+    _nufft_nd_host(3, 2, "32", np.float32, f_re, f_im, out_re, out_im, direction, coords=(x, y, z), n_modes=np.shape(f_re), eps=eps)
 
 
 def nufft3d1_64_with_planner(c_re, c_im, out_re, out_im, planner: PlannerNufft3d64, direction=Direction.Forward) -> None:
-    _nufft3d_host(1, "64", np.float64, c_re, c_im, out_re, out_im, direction, planner)
+    _nufft_nd_host(3, 1, "64", np.float64, c_re, c_im, out_re, out_im, direction, planner)
 
 
 def nufft3d1_32_with_planner(c_re, c_im, out_re, out_im, planner: PlannerNufft3d32, direction=Direction.Forward) -> None:
-    _nufft3d_host(1, "32", np.float32, c_re, c_im, out_re, out_im, direction, planner)
+    _nufft_nd_host(3, 1, "32", np.float32, c_re, c_im, out_re, out_im, direction, planner)
 
 
 def nufft3d2_64_with_planner(f_re, f_im, out_re, out_im, planner: PlannerNufft3d64, direction=Direction.Forward) -> None:
-    _nufft3d_host(2, "64", np.float64, f_re, f_im, out_re, out_im, direction, planner)
+    _nufft_nd_host(3, 2, "64", np.float64, f_re, f_im, out_re, out_im, direction, planner)
 
 
 def nufft3d2_32_with_planner(f_re, f_im, out_re, out_im, planner: PlannerNufft3d32, direction=Direction.Forward) -> None:
-    _nufft3d_host(2, "32", np.float32, f_re, f_im, out_re, out_im, direction, planner)
+    _nufft_nd_host(3, 2, "32", np.float32, f_re, f_im, out_re, out_im, direction, planner)
 
 
-def _nufft3d(t, x, y, z, v, n_modes, eps, direction):
+def _nufft_nd(t, coords, v, n_modes, eps, direction):
     import torch
 
-    kinds = {torch.float64: (PlannerNufft3d64, torch.float64), torch.complex128: (PlannerNufft3d64, torch.float64),
-             torch.float32: (PlannerNufft3d32, torch.float32), torch.complex64: (PlannerNufft3d32, torch.float32)}
-    if not _is_torch(v) or v.device.type != "cuda" or v.dtype not in kinds or v.dim() < (1 if t == 1 else 3):
-        raise TypeError("need a float64, float32, complex128 or complex64 device tensor of at least one axis (points) or three (modes)")
+    rank = len(coords)
+    word = {2: "two", 3: "three"}[rank]
+    if t == 2:  # the modes are the last `rank` axes of v
+        if not _is_torch(v) or v.dim() < rank:
+            raise TypeError(f"need a device tensor of at least {word} axes")
+        n_modes = tuple(v.shape[-rank:])
+    p64, p32 = {2: (PlannerNufft2d64, PlannerNufft2d32), 3: (PlannerNufft3d64, PlannerNufft3d32)}[rank]
+    kinds = {torch.float64: (p64, torch.float64), torch.complex128: (p64, torch.float64),
+             torch.float32: (p32, torch.float32), torch.complex64: (p32, torch.float32)}
+    if not _is_torch(v) or v.device.type != "cuda" or v.dtype not in kinds or v.dim() < (1 if t == 1 else rank):
+        raise TypeError(f"need a float64, float32, complex128 or complex64 device tensor of at least one axis (points) or {word} (modes)")
     cls, real = kinds[v.dtype]
-    planner = cls(n_modes, x, y, z, eps)
-    n1, n2, n3 = planner.n_modes
-    tail_in, tail_out = ((planner.m_points,), (n1, n2, n3)) if t == 1 else ((n1, n2, n3), (planner.m_points,))
+    planner = cls(n_modes, *coords, eps)
+    tail_in, tail_out = ((planner.m_points,), planner.n_modes) if t == 1 else (planner.n_modes, (planner.m_points,))
     if tuple(v.shape[-len(tail_in):]) != tail_in:
         raise ValueError(f"the last axes are {tuple(v.shape[-len(tail_in):])}, the transform takes {tail_in}")
     lead = tuple(v.shape[:-len(tail_in)])
@@ -2321,24 +2207,35 @@ def _nufft3d(t, x, y, z, v, n_modes, eps, direction):
         x_re, x_im = rows.contiguous(), None
     out = torch.empty((2, rows.shape[0], n_out), dtype=real, device=v.device)
     if rows.shape[0]:
-        _nufft3d_batched(t, x_re, x_im, planner, direction, (out[0], out[1]), None, None)
+        _nufft_nd_batched(rank, t, x_re, x_im, planner, direction, (out[0], out[1]), None, None)
         torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
     return torch.complex(out[0], out[1]).reshape(lead + tail_out)
+
+
+def nufft2d1(x, y, c, n_modes, eps: float | None = None, direction=Direction.Forward):
+    """Two-dimensional type 1 non-uniform FFT of a real or complex device tensor ``c`` over its last axis (M values at the
+    points ``(x, y)``, in turns) into ``n_modes = (n1, n2)`` modes in ``fftfreq`` order: a new complex tensor of shape
+    ``c.shape[:-1] + (n1, n2)``.  float64 / complex128 run in f64 (eps defaults to 1e-12), float32 / complex64 in f32 (1e-6)."""
+    return _nufft_nd(1, (x, y), c, n_modes, eps, direction)
+
+
+def nufft2d2(x, y, F, eps: float | None = None, direction=Direction.Forward):
+    """Two-dimensional type 2 non-uniform FFT of a real or complex device tensor ``F`` of modes over its last two axes, evaluated
+    at the points ``(x, y)`` (in turns): a new complex tensor of shape ``F.shape[:-2] + (len(x),)``"""
+    return _nufft_nd(2, (x, y), F, None, eps, direction)
 
 
 def nufft3d1(x, y, z, c, n_modes, eps: float | None = None, direction=Direction.Forward):
     """Three-dimensional type 1 non-uniform FFT of a real or complex device tensor ``c`` over its last axis (M values at the
     points ``(x, y, z)``, in turns) into ``n_modes = (n1, n2, n3)`` modes in ``fftfreq`` order: a new complex tensor of shape
     ``c.shape[:-1] + (n1, n2, n3)``.  float64 / complex128 run in f64 (eps defaults to 1e-12), float32 / complex64 in f32 (1e-6)."""
-    return _nufft3d(1, x, y, z, c, n_modes, eps, direction)
+    return _nufft_nd(1, (x, y, z), c, n_modes, eps, direction)
 
 
 def nufft3d2(x, y, z, F, eps: float | None = None, direction=Direction.Forward):
     """Three-dimensional type 2 non-uniform FFT of a real or complex device tensor ``F`` of modes over its last three axes, evaluated
     at the points ``(x, y, z)`` (in turns): a new complex tensor of shape ``F.shape[:-3] + (len(x),)``"""
-    if not _is_torch(F) or F.dim() < 3:
-        raise TypeError("need a device tensor of at least three axes")
-    return _nufft3d(2, x, y, z, F, tuple(F.shape[-3:]), eps, direction)
+    return _nufft_nd(2, (x, y, z), F, None, eps, direction)
 
 
 # ---------------------------------------------------------------------------------------------

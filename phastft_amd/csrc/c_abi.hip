@@ -22,8 +22,7 @@
 #include "planner_czt.hpp"
 #include "planner_nufft.hpp"
 #include "planner_nd.hpp"
-#include "planner_nufft2d.hpp"
-#include "planner_nufft3d.hpp"
+#include "planner_nufft_nd.hpp"
 #include "planner_nufft_t3.hpp"
 
 // ================================================================================================
@@ -49,10 +48,10 @@ struct phast_planner_czt64 : CztPlanner<double> {};
 struct phast_planner_czt32 : CztPlanner<float> {};
 struct phast_planner_nufft64 : NufftPlanner<double> {};
 struct phast_planner_nufft32 : NufftPlanner<float> {};
-struct phast_planner_nufft2d64 : Nufft2dPlanner<double> {};
-struct phast_planner_nufft2d32 : Nufft2dPlanner<float> {};
-struct phast_planner_nufft3d64 : Nufft3dPlanner<double> {};
-struct phast_planner_nufft3d32 : Nufft3dPlanner<float> {};
+struct phast_planner_nufft2d64 : NufftNdPlanner<double, 2> {};
+struct phast_planner_nufft2d32 : NufftNdPlanner<float, 2> {};
+struct phast_planner_nufft3d64 : NufftNdPlanner<double, 3> {};
+struct phast_planner_nufft3d32 : NufftNdPlanner<float, 3> {};
 struct phast_planner_nufft_t3_64 : NufftT3Planner<double> {};
 struct phast_planner_nufft_t3_32 : NufftT3Planner<float> {};
 struct phast_planner_nd64 : NdPlanner<double> {};
@@ -828,29 +827,52 @@ PHAST_CONV_API(32, f32, float)
 PHAST_CZT_API(64, double)
 PHAST_CZT_API(32, float)
 
-// Non-uniform FFTs of types 1 and 2 (planner_nufft.hpp): the lengths, eps and the points are checked before the device is
-// touched; the one-shot forms build a planner of their own for the call.  TYPE 1: points -> modes, 2: modes -> points
-#define PHAST_NUFFT_CALLS(SFX, T, TYPE)                                                                                 \
-    int phast_nufft##TYPE##_##SFX(const double *x_turns, size_t m_points, const T *in_re, const T *in_im, T *out_re,    \
-                                  T *out_im, size_t n_modes, double eps, int direction) try {                           \
-        if (!in_re || !out_re || !out_im) return PHAST_ERR_INVALID_ARG;                                                 \
-        phast_planner_nufft##SFX *p = nullptr;                                                                          \
-        int rc = nufft_planner_new(n_modes, x_turns, m_points, eps, sizeof(T) == 4, &p);                                \
-        if (rc) return rc;                                                                                              \
-        std::unique_ptr<phast_planner_nufft##SFX> own(p);                                                               \
-        return p->nufft_host(TYPE, direction, in_re, in_im, p->in_len(TYPE), out_re, out_im, p->out_len(TYPE));         \
-    } PHAST_CATCH_RC                                                                                                    \
-    int phast_nufft##TYPE##_##SFX##_with_planner(const T *in_re, const T *in_im, size_t in_len, T *out_re, T *out_im,   \
-                                                 size_t out_len, int direction, const phast_planner_nufft##SFX *p) try {\
+// Non-uniform FFTs of types 1 and 2 (planner_nufft.hpp, planner_nufft_nd.hpp): the lengths, eps and the points are checked before
+// the device is touched; the one-shot forms build a planner of their own for the call.  TYPE 1: points -> modes, 2: modes ->
+// points.  What lists neither coordinates nor mode counts is the same for every rank: H = nufft, nufft2d, nufft3d
+#define PHAST_NUFFT_RANK_CALLS(H, SFX, T, TYPE)                                                                         \
+    int phast_##H##TYPE##_##SFX##_with_planner(const T *in_re, const T *in_im, size_t in_len, T *out_re, T *out_im,     \
+                                               size_t out_len, int direction, const phast_planner_##H##SFX *p) try {    \
         if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
         return p->nufft_host(TYPE, direction, in_re, in_im, in_len, out_re, out_im, out_len);                           \
     } PHAST_CATCH_RC                                                                                                    \
-    int phast_nufft##TYPE##_##SFX##_dev(const T *d_in_re, const T *d_in_im, size_t in_dist, T *d_out_re, T *d_out_im,   \
-                                        size_t out_dist, size_t batch, int direction, const phast_planner_nufft##SFX *p,\
-                                        T *d_work, size_t work_len, void *stream) try {                                 \
+    int phast_##H##TYPE##_##SFX##_dev(const T *d_in_re, const T *d_in_im, size_t in_dist, T *d_out_re, T *d_out_im,     \
+                                      size_t out_dist, size_t batch, int direction, const phast_planner_##H##SFX *p,    \
+                                      T *d_work, size_t work_len, void *stream) try {                                   \
         if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
         return p->nufft_dev(TYPE, direction, d_in_re, d_in_im, in_dist, d_out_re, d_out_im, out_dist, batch, d_work,    \
                             work_len, static_cast<hipStream_t>(stream));                                                \
+    } PHAST_CATCH_RC
+#define PHAST_NUFFT_RANK_API(H, SFX, T)                                                                                 \
+    size_t phast_planner_##H##SFX##_grid_len(const phast_planner_##H##SFX *p) try {                                     \
+        return p ? p->grid_len() : 0;                                                                                   \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_##H##SFX##_width(const phast_planner_##H##SFX *p) try {                                           \
+        return p ? p->w : 0;                                                                                            \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_##H##SFX##_time_stages(const phast_planner_##H##SFX *p, const T *d_in_re, const T *d_in_im,       \
+                                             T *d_out_re, T *d_out_im, int type, size_t batch, T *d_work,               \
+                                             size_t work_len, int reps, float *stage_ms, void *stream) try {            \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(type, d_in_re, d_in_im, d_out_re, d_out_im, batch, d_work, work_len, reps, stage_ms,      \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    PHAST_NUFFT_RANK_CALLS(H, SFX, T, 1)                                                                                \
+    PHAST_NUFFT_RANK_CALLS(H, SFX, T, 2)
+// the body of every rank's one-shot form: NEW builds the planner p
+#define PHAST_NUFFT_ONE_SHOT(H, SFX, TYPE, NEW)                                                                         \
+    if (!in_re || !out_re || !out_im) return PHAST_ERR_INVALID_ARG;                                                     \
+    phast_planner_##H##SFX *p = nullptr;                                                                                \
+    int rc = NEW;                                                                                                       \
+    if (rc) return rc;                                                                                                  \
+    std::unique_ptr<phast_planner_##H##SFX> own(p);                                                                     \
+    return p->nufft_host(TYPE, direction, in_re, in_im, p->in_len(TYPE), out_re, out_im, p->out_len(TYPE));
+
+// one dimension
+#define PHAST_NUFFT_CALLS(SFX, T, TYPE)                                                                                 \
+    int phast_nufft##TYPE##_##SFX(const double *x_turns, size_t m_points, const T *in_re, const T *in_im, T *out_re,    \
+                                  T *out_im, size_t n_modes, double eps, int direction) try {                           \
+        PHAST_NUFFT_ONE_SHOT(nufft, SFX, TYPE, nufft_planner_new(n_modes, x_turns, m_points, eps, sizeof(T) == 4, &p))  \
     } PHAST_CATCH_RC
 #define PHAST_NUFFT_API(SFX, T)                                                                                         \
     int phast_planner_nufft##SFX##_new(size_t n_modes, const double *x_turns, size_t m_points, double eps,              \
@@ -872,166 +894,92 @@ PHAST_CZT_API(32, float)
         if (!p || !stage_ms) return PHAST_ERR_INVALID_ARG;                                                              \
         return p->set_points_dev(d_x_turns, m_points, static_cast<hipStream_t>(stream), stage_ms);                      \
     } PHAST_CATCH_RC                                                                                                    \
-    size_t phast_planner_nufft##SFX##_grid_len(const phast_planner_nufft##SFX *p) try {                                 \
-        return p ? p->m : 0;                                                                                            \
-    } PHAST_CATCH_ZERO                                                                                                  \
-    int phast_planner_nufft##SFX##_width(const phast_planner_nufft##SFX *p) try {                                       \
-        return p ? p->w : 0;                                                                                            \
-    } PHAST_CATCH_ZERO                                                                                                  \
-    int phast_planner_nufft##SFX##_time_stages(const phast_planner_nufft##SFX *p, const T *d_in_re, const T *d_in_im,   \
-                                               T *d_out_re, T *d_out_im, int type, size_t batch, T *d_work,             \
-                                               size_t work_len, int reps, float *stage_ms, void *stream) try {          \
-        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
-        return p->time_stages(type, d_in_re, d_in_im, d_out_re, d_out_im, batch, d_work, work_len, reps, stage_ms,      \
-                              static_cast<hipStream_t>(stream));                                                        \
-    } PHAST_CATCH_RC                                                                                                    \
+    PHAST_NUFFT_RANK_API(nufft, SFX, T)                                                                                 \
     PHAST_NUFFT_CALLS(SFX, T, 1)                                                                                        \
     PHAST_NUFFT_CALLS(SFX, T, 2)
 PHAST_NUFFT_API(64, double)
 PHAST_NUFFT_API(32, float)
 
-// Non-uniform FFTs of types 1 and 2 in two dimensions (planner_nufft2d.hpp): the same rules, (n1, n2) where the 1-D forms have
-// n_modes and (x, y) where they have x
+// two dimensions: the same rules, (n1, n2) where the 1-D forms have n_modes and (x, y) where they have x
 #define PHAST_NUFFT2D_CALLS(SFX, T, TYPE)                                                                               \
     int phast_nufft2d##TYPE##_##SFX(const double *x_turns, const double *y_turns, size_t m_points, const T *in_re,      \
                                     const T *in_im, T *out_re, T *out_im, size_t n1, size_t n2, double eps,             \
                                     int direction) try {                                                                \
-        if (!in_re || !out_re || !out_im) return PHAST_ERR_INVALID_ARG;                                                 \
-        phast_planner_nufft2d##SFX *p = nullptr;                                                                        \
-        int rc = nufft2d_planner_new(n1, n2, x_turns, y_turns, m_points, eps, sizeof(T) == 4, &p);                      \
-        if (rc) return rc;                                                                                              \
-        std::unique_ptr<phast_planner_nufft2d##SFX> own(p);                                                             \
-        return p->nufft_host(TYPE, direction, in_re, in_im, p->in_len(TYPE), out_re, out_im, p->out_len(TYPE));         \
-    } PHAST_CATCH_RC                                                                                                    \
-    int phast_nufft2d##TYPE##_##SFX##_with_planner(const T *in_re, const T *in_im, size_t in_len, T *out_re, T *out_im, \
-                                                   size_t out_len, int direction,                                       \
-                                                   const phast_planner_nufft2d##SFX *p) try {                           \
-        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
-        return p->nufft_host(TYPE, direction, in_re, in_im, in_len, out_re, out_im, out_len);                           \
-    } PHAST_CATCH_RC                                                                                                    \
-    int phast_nufft2d##TYPE##_##SFX##_dev(const T *d_in_re, const T *d_in_im, size_t in_dist, T *d_out_re, T *d_out_im, \
-                                          size_t out_dist, size_t batch, int direction,                                 \
-                                          const phast_planner_nufft2d##SFX *p, T *d_work, size_t work_len,              \
-                                          void *stream) try {                                                           \
-        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
-        return p->nufft_dev(TYPE, direction, d_in_re, d_in_im, in_dist, d_out_re, d_out_im, out_dist, batch, d_work,    \
-                            work_len, static_cast<hipStream_t>(stream));                                                \
+        PHAST_NUFFT_ONE_SHOT(nufft2d, SFX, TYPE,                                                                        \
+                             nufft_nd_planner_new({n1, n2}, {x_turns, y_turns}, m_points, eps, sizeof(T) == 4, &p))     \
     } PHAST_CATCH_RC
 #define PHAST_NUFFT2D_API(SFX, T)                                                                                       \
     int phast_planner_nufft2d##SFX##_new(size_t n1, size_t n2, const double *x_turns, const double *y_turns,            \
                                          size_t m_points, double eps, phast_planner_nufft2d##SFX **out) try {           \
-        return nufft2d_planner_new(n1, n2, x_turns, y_turns, m_points, eps, sizeof(T) == 4, out);                       \
+        return nufft_nd_planner_new({n1, n2}, {x_turns, y_turns}, m_points, eps, sizeof(T) == 4, out);                  \
     } PHAST_CATCH_RC                                                                                                    \
     int phast_planner_nufft2d##SFX##_new_dev(size_t n1, size_t n2, const double *d_x_turns, const double *d_y_turns,    \
                                              size_t m_points, double eps, void *stream,                                 \
                                              phast_planner_nufft2d##SFX **out) try {                                    \
-        return nufft2d_planner_new_dev(n1, n2, d_x_turns, d_y_turns, m_points, eps, sizeof(T) == 4,                     \
-                                       static_cast<hipStream_t>(stream), out);                                          \
+        return nufft_nd_planner_new_dev({n1, n2}, {d_x_turns, d_y_turns}, m_points, eps, sizeof(T) == 4,                \
+                                        static_cast<hipStream_t>(stream), out);                                         \
     } PHAST_CATCH_RC                                                                                                    \
     int phast_planner_nufft2d##SFX##_set_points_dev(phast_planner_nufft2d##SFX *p, const double *d_x_turns,             \
                                                     const double *d_y_turns, size_t m_points, void *stream) try {       \
         if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
-        return p->set_points_dev(d_x_turns, d_y_turns, m_points, static_cast<hipStream_t>(stream));                     \
+        return p->set_points_dev({d_x_turns, d_y_turns}, m_points, static_cast<hipStream_t>(stream));                   \
     } PHAST_CATCH_RC                                                                                                    \
     int phast_planner_nufft2d##SFX##_time_set_points(phast_planner_nufft2d##SFX *p, const double *d_x_turns,            \
                                                      const double *d_y_turns, size_t m_points, float *stage_ms,         \
                                                      void *stream) try {                                                \
         if (!p || !stage_ms) return PHAST_ERR_INVALID_ARG;                                                              \
-        return p->set_points_dev(d_x_turns, d_y_turns, m_points, static_cast<hipStream_t>(stream), stage_ms);           \
+        return p->set_points_dev({d_x_turns, d_y_turns}, m_points, static_cast<hipStream_t>(stream), stage_ms);         \
     } PHAST_CATCH_RC                                                                                                    \
-    size_t phast_planner_nufft2d##SFX##_grid_len(const phast_planner_nufft2d##SFX *p) try {                             \
-        return p ? p->cells : 0;                                                                                        \
-    } PHAST_CATCH_ZERO                                                                                                  \
     size_t phast_planner_nufft2d##SFX##_grid_rows(const phast_planner_nufft2d##SFX *p) try {                            \
-        return p ? p->g1 : 0;                                                                                           \
+        return p ? p->g[0] : 0;                                                                                         \
     } PHAST_CATCH_ZERO                                                                                                  \
     size_t phast_planner_nufft2d##SFX##_grid_cols(const phast_planner_nufft2d##SFX *p) try {                            \
-        return p ? p->g2 : 0;                                                                                           \
+        return p ? p->g[1] : 0;                                                                                         \
     } PHAST_CATCH_ZERO                                                                                                  \
-    int phast_planner_nufft2d##SFX##_width(const phast_planner_nufft2d##SFX *p) try {                                   \
-        return p ? p->w : 0;                                                                                            \
-    } PHAST_CATCH_ZERO                                                                                                  \
-    int phast_planner_nufft2d##SFX##_time_stages(const phast_planner_nufft2d##SFX *p, const T *d_in_re,                 \
-                                                 const T *d_in_im, T *d_out_re, T *d_out_im, int type, size_t batch,    \
-                                                 T *d_work, size_t work_len, int reps, float *stage_ms,                 \
-                                                 void *stream) try {                                                    \
-        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
-        return p->time_stages(type, d_in_re, d_in_im, d_out_re, d_out_im, batch, d_work, work_len, reps, stage_ms,      \
-                              static_cast<hipStream_t>(stream));                                                        \
-    } PHAST_CATCH_RC                                                                                                    \
+    PHAST_NUFFT_RANK_API(nufft2d, SFX, T)                                                                               \
     PHAST_NUFFT2D_CALLS(SFX, T, 1)                                                                                      \
     PHAST_NUFFT2D_CALLS(SFX, T, 2)
 PHAST_NUFFT2D_API(64, double)
 PHAST_NUFFT2D_API(32, float)
 
-// Non-uniform FFTs of types 1 and 2 in three dimensions (planner_nufft3d.hpp): the same rules, (n1, n2, n3) and (x, y, z)
+// three dimensions: (n1, n2, n3) and (x, y, z)
 #define PHAST_NUFFT3D_CALLS(SFX, T, TYPE)                                                                               \
     int phast_nufft3d##TYPE##_##SFX(const double *x_turns, const double *y_turns, const double *z_turns,                \
                                     size_t m_points, const T *in_re, const T *in_im, T *out_re, T *out_im, size_t n1,   \
                                     size_t n2, size_t n3, double eps, int direction) try {                              \
-        if (!in_re || !out_re || !out_im) return PHAST_ERR_INVALID_ARG;                                                 \
-        phast_planner_nufft3d##SFX *p = nullptr;                                                                        \
-        int rc = nufft3d_planner_new(n1, n2, n3, x_turns, y_turns, z_turns, m_points, eps, sizeof(T) == 4, &p);         \
-        if (rc) return rc;                                                                                              \
-        std::unique_ptr<phast_planner_nufft3d##SFX> own(p);                                                             \
-        return p->nufft_host(TYPE, direction, in_re, in_im, p->in_len(TYPE), out_re, out_im, p->out_len(TYPE));         \
-    } PHAST_CATCH_RC                                                                                                    \
-    int phast_nufft3d##TYPE##_##SFX##_with_planner(const T *in_re, const T *in_im, size_t in_len, T *out_re, T *out_im, \
-                                                   size_t out_len, int direction,                                       \
-                                                   const phast_planner_nufft3d##SFX *p) try {                           \
-        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
-        return p->nufft_host(TYPE, direction, in_re, in_im, in_len, out_re, out_im, out_len);                           \
-    } PHAST_CATCH_RC                                                                                                    \
-    int phast_nufft3d##TYPE##_##SFX##_dev(const T *d_in_re, const T *d_in_im, size_t in_dist, T *d_out_re, T *d_out_im, \
-                                          size_t out_dist, size_t batch, int direction,                                 \
-                                          const phast_planner_nufft3d##SFX *p, T *d_work, size_t work_len,              \
-                                          void *stream) try {                                                           \
-        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
-        return p->nufft_dev(TYPE, direction, d_in_re, d_in_im, in_dist, d_out_re, d_out_im, out_dist, batch, d_work,    \
-                            work_len, static_cast<hipStream_t>(stream));                                                \
+        PHAST_NUFFT_ONE_SHOT(nufft3d, SFX, TYPE,                                                                        \
+                             nufft_nd_planner_new({n1, n2, n3}, {x_turns, y_turns, z_turns}, m_points, eps,             \
+                                                  sizeof(T) == 4, &p))                                                  \
     } PHAST_CATCH_RC
 #define PHAST_NUFFT3D_API(SFX, T)                                                                                       \
     int phast_planner_nufft3d##SFX##_new(size_t n1, size_t n2, size_t n3, const double *x_turns, const double *y_turns, \
                                          const double *z_turns, size_t m_points, double eps,                            \
                                          phast_planner_nufft3d##SFX **out) try {                                        \
-        return nufft3d_planner_new(n1, n2, n3, x_turns, y_turns, z_turns, m_points, eps, sizeof(T) == 4, out);          \
+        return nufft_nd_planner_new({n1, n2, n3}, {x_turns, y_turns, z_turns}, m_points, eps, sizeof(T) == 4, out);     \
     } PHAST_CATCH_RC                                                                                                    \
     int phast_planner_nufft3d##SFX##_new_dev(size_t n1, size_t n2, size_t n3, const double *d_x_turns,                  \
                                              const double *d_y_turns, const double *d_z_turns, size_t m_points,         \
                                              double eps, void *stream, phast_planner_nufft3d##SFX **out) try {          \
-        return nufft3d_planner_new_dev(n1, n2, n3, d_x_turns, d_y_turns, d_z_turns, m_points, eps, sizeof(T) == 4,      \
-                                       static_cast<hipStream_t>(stream), out);                                          \
+        return nufft_nd_planner_new_dev({n1, n2, n3}, {d_x_turns, d_y_turns, d_z_turns}, m_points, eps, sizeof(T) == 4, \
+                                        static_cast<hipStream_t>(stream), out);                                         \
     } PHAST_CATCH_RC                                                                                                    \
     int phast_planner_nufft3d##SFX##_set_points_dev(phast_planner_nufft3d##SFX *p, const double *d_x_turns,             \
                                                     const double *d_y_turns, const double *d_z_turns, size_t m_points,  \
                                                     void *stream) try {                                                 \
         if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
-        return p->set_points_dev(d_x_turns, d_y_turns, d_z_turns, m_points, static_cast<hipStream_t>(stream));          \
+        return p->set_points_dev({d_x_turns, d_y_turns, d_z_turns}, m_points, static_cast<hipStream_t>(stream));        \
     } PHAST_CATCH_RC                                                                                                    \
     int phast_planner_nufft3d##SFX##_time_set_points(phast_planner_nufft3d##SFX *p, const double *d_x_turns,            \
                                                      const double *d_y_turns, const double *d_z_turns, size_t m_points, \
                                                      float *stage_ms, void *stream) try {                               \
         if (!p || !stage_ms) return PHAST_ERR_INVALID_ARG;                                                              \
-        return p->set_points_dev(d_x_turns, d_y_turns, d_z_turns, m_points, static_cast<hipStream_t>(stream),           \
+        return p->set_points_dev({d_x_turns, d_y_turns, d_z_turns}, m_points, static_cast<hipStream_t>(stream),         \
                                  stage_ms);                                                                             \
     } PHAST_CATCH_RC                                                                                                    \
-    size_t phast_planner_nufft3d##SFX##_grid_len(const phast_planner_nufft3d##SFX *p) try {                             \
-        return p ? p->cells : 0;                                                                                        \
-    } PHAST_CATCH_ZERO                                                                                                  \
     size_t phast_planner_nufft3d##SFX##_grid_dim(const phast_planner_nufft3d##SFX *p, int axis) try {                   \
-        return !p ? 0 : axis == 0 ? p->g1 : axis == 1 ? p->g2 : axis == 2 ? p->g3 : 0;                                  \
+        return p && axis >= 0 && axis < 3 ? p->g[axis] : 0;                                                             \
     } PHAST_CATCH_ZERO                                                                                                  \
-    int phast_planner_nufft3d##SFX##_width(const phast_planner_nufft3d##SFX *p) try {                                   \
-        return p ? p->w : 0;                                                                                            \
-    } PHAST_CATCH_ZERO                                                                                                  \
-    int phast_planner_nufft3d##SFX##_time_stages(const phast_planner_nufft3d##SFX *p, const T *d_in_re,                 \
-                                                 const T *d_in_im, T *d_out_re, T *d_out_im, int type, size_t batch,    \
-                                                 T *d_work, size_t work_len, int reps, float *stage_ms,                 \
-                                                 void *stream) try {                                                    \
-        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
-        return p->time_stages(type, d_in_re, d_in_im, d_out_re, d_out_im, batch, d_work, work_len, reps, stage_ms,      \
-                              static_cast<hipStream_t>(stream));                                                        \
-    } PHAST_CATCH_RC                                                                                                    \
+    PHAST_NUFFT_RANK_API(nufft3d, SFX, T)                                                                               \
     PHAST_NUFFT3D_CALLS(SFX, T, 1)                                                                                      \
     PHAST_NUFFT3D_CALLS(SFX, T, 2)
 PHAST_NUFFT3D_API(64, double)

@@ -8,9 +8,8 @@
 // engine plan and the chunk loop; it has no convolution table.
 #pragma once
 
-#include "nufft.hpp"
 #include "planner_any.hpp"
-#include "planner_nufft_sort.hpp"
+#include "planner_nufft_common.hpp"
 
 namespace phast {
 
@@ -42,14 +41,7 @@ template <typename T> struct NufftPlanner : ConvCore<T> {
         w = nufft_width(eps);
         int rc = this->init_core((size_t)nufft_grid(modes, w));
         if (rc) return rc;
-        // 1 / phi^(k) in double, rounded to T; phi^ is even in k
-        std::vector<T> inv(modes);
-        const NufftQuad hat(w, m);
-        for (size_t k = 0; k <= modes / 2; ++k) {
-            const T r = (T)(1.0 / hat((long long)k));
-            if (k < (modes + 1) / 2) inv[k] = r;
-            if (k > 0) inv[modes - k] = r;
-        }
+        const std::vector<T> inv = nufft_inv_table<T>(w, modes, m);
         PHAST_ON_DEVICE(device);
         PHAST_HIP(hipMalloc(reinterpret_cast<void **>(&d_xs), points * sizeof(double)));
         PHAST_HIP(hipMalloc(reinterpret_cast<void **>(&d_perm), points * sizeof(uint32_t)));
@@ -98,6 +90,7 @@ template <typename T> struct NufftPlanner : ConvCore<T> {
     }
 
     size_t workspace_len(size_t batch) const { return 2 * m * batch; }
+    size_t grid_len() const { return m; }
     size_t table_bytes() const { return points * (sizeof(double) + sizeof(uint32_t)) + (m + 1) * sizeof(uint32_t) + modes * sizeof(T); }
     size_t device_bytes() const { return table_bytes() + (inner ? inner->device_bytes() : 0); }
     std::string describe() const {
@@ -210,29 +203,10 @@ template <typename T> struct NufftPlanner : ConvCore<T> {
         });
     }
 
-    // [p, p + len) and [q, q + qlen) share an element
-    static bool overlap(const T *p, size_t len, const T *q, size_t qlen) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-        return p && q && a < b + qlen * sizeof(T) && b < a + len * sizeof(T);
-    }
-
     int check_dev(int type, int direction, const T *d_in_re, const T *d_in_im, size_t in_dist, const T *d_out_re,
                   const T *d_out_im, size_t out_dist, size_t batch, const T *d_work, size_t work_len) const {
-        if (!d_in_re || !d_out_re || !d_out_im) return PHAST_ERR_INVALID_ARG;  // d_in_im may be null: real data
-        if (direction != PHAST_FORWARD && direction != PHAST_REVERSE) return PHAST_ERR_INVALID_ARG;
-        const size_t ni = in_len(type), no = out_len(type);
-        if (batch > 1 && (in_dist < ni || out_dist < no)) return PHAST_ERR_INVALID_ARG;
-        if (batch && (!d_work || work_len < 2 * m)) return PHAST_ERR_INVALID_ARG;
-        if (batch) {  // the output is written while later chunks still read the input and the workspace
-            const size_t in_span = (batch - 1) * (batch > 1 ? in_dist : 0) + ni, out_span = (batch - 1) * (batch > 1 ? out_dist : 0) + no;
-            for (const T *o : {d_out_re, d_out_im})
-                if (overlap(o, out_span, d_in_re, in_span) || overlap(o, out_span, d_in_im, in_span) ||
-                    overlap(o, out_span, d_work, work_len))
-                    return PHAST_ERR_INVALID_ARG;
-            if (overlap(d_out_re, out_span, d_out_im, out_span)) return PHAST_ERR_INVALID_ARG;
-            if (overlap(d_work, work_len, d_in_re, in_span) || overlap(d_work, work_len, d_in_im, in_span)) return PHAST_ERR_INVALID_ARG;
-        }
-        return PHAST_OK;
+        return nufft_check_dev(direction, d_in_re, d_in_im, in_dist, in_len(type), d_out_re, d_out_im, out_dist, out_len(type), batch,
+                               d_work, work_len, 2 * m);
     }
 
     // device pointers, asynchronous on `s`
@@ -298,36 +272,13 @@ template <typename T> struct NufftPlanner : ConvCore<T> {
 };
 
 template <typename P> static int nufft_planner_new(size_t n_modes, const double *x, size_t m_points, double eps, bool f32, P **out) {
-    if (!out) return PHAST_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (nufft_bad_args(n_modes, m_points, x, eps, f32)) return PHAST_ERR_INVALID_ARG;  // before the device is touched
-    auto *p = new (std::nothrow) P();
-    if (!p) return PHAST_ERR_ALLOC;
-    int rc = p->init(n_modes, x, m_points, eps);
-    if (rc) {
-        delete p;
-        return rc;
-    }
-    *out = p;
-    return PHAST_OK;
+    return nufft_planner_make(out, [&] { return nufft_bad_args(n_modes, m_points, x, eps, f32); }, n_modes, x, m_points, eps);
 }
 
 // the same from M doubles in device memory, ordered after the earlier work of `s`
 template <typename P>
 static int nufft_planner_new_dev(size_t n_modes, const double *d_x, size_t m_points, double eps, bool f32, hipStream_t s, P **out) {
-    if (!out) return PHAST_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (nufft_bad_sizes(n_modes, m_points, d_x, eps, f32)) return PHAST_ERR_INVALID_ARG;  // before the device is touched
-    if (nufft_sort_stream_busy(s)) return PHAST_ERR_INVALID_ARG;
-    auto *p = new (std::nothrow) P();
-    if (!p) return PHAST_ERR_ALLOC;
-    int rc = p->init_dev(n_modes, d_x, m_points, eps, s);
-    if (rc) {
-        delete p;
-        return rc;
-    }
-    *out = p;
-    return PHAST_OK;
+    return nufft_planner_make_dev(out, [&] { return nufft_bad_sizes(n_modes, m_points, d_x, eps, f32); }, s, n_modes, d_x, m_points, eps);
 }
 
 }  // namespace phast

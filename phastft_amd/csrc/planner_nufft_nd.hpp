@@ -1,53 +1,91 @@
-// planner_nufft3d.hpp -- Nufft3dPlanner<T>: non-uniform FFTs of types 1 and 2 in three dimensions (nufft3d.hpp) of M points and
-// N1 x N2 x N3 modes on an owned NdPlanner<T> of dims (g1, g2, g3).  Immutable after init but for set_points_dev: the Nd planner, the point set sorted by
-// grid cell (positions, permutation, cell starts) and the N1 + N2 + N3 reciprocals 1 / phi^(k) on the device.  What a call mutates
-// is the caller's workspace (_dev calls) or a device buffer of the call's own (host-slice calls), so graph capture and concurrent
-// streams and threads need nothing beyond what the Nd planner already does.
+// planner_nufft_nd.hpp -- NufftNdPlanner<T, D>: non-uniform FFTs of types 1 and 2 in D = 2 or 3 dimensions (nufft2d.hpp,
+// nufft3d.hpp) of M points and N1 x .. x ND modes on an owned NdPlanner<T> of dims (g1, .., gD).  Immutable after init but for
+// set_points_dev: the Nd planner, the point set sorted by grid cell (positions, permutation, cell starts) and the N1 + .. + ND
+// reciprocals 1 / phi^(k) on the device.  What a call mutates is the caller's workspace (_dev calls) or a device buffer of the
+// call's own (host-slice calls), so graph capture and concurrent streams and threads need nothing beyond what the Nd planner
+// already does.  The kernels differ by rank; NufftRank<D> below is all that the planner knows of that.
 //
 // Workspace (elements of T) of a chunk of c transforms: c re grids, c im grids, then what the Nd planner asks for c arrays of
-// (g1, g2, g3) (its transposed copies, 2 c G: every axis is a power of two, so there is no Bluestein part): per() = 4 G per
-// transform, G = g1 g2 g3, read from the Nd planner and not assumed.
+// (g1, .., gD) (its transposed copies, 2 c G: every axis is a power of two, so there is no Bluestein part): per() = 4 G per
+// transform, G = g1 .. gD, read from the Nd planner and not assumed.
 #pragma once
 
+#include "nufft2d.hpp"
 #include "nufft3d.hpp"
 #include "planner_nd.hpp"
-#include "planner_nufft_sort.hpp"
+#include "planner_nufft_common.hpp"
 
 namespace phast {
 
-template <typename T> struct Nufft3dPlanner {
-    size_t n1 = 0, n2 = 0, n3 = 0, points = 0;  // N1, N2, N3, M
-    size_t g1 = 0, g2 = 0, g3 = 0, cells = 0;   // the fine grid and G = g1 g2 g3
-    unsigned log_g1 = 0, log_g2 = 0, log_g3 = 0;
+// What depends on the rank: the kernels' argument struct and launcher, the host's binning and the argument checks.  n, x, lg,
+// xs, inv: D entries each, axis 1 first
+template <size_t D> struct NufftRank;
+template <> struct NufftRank<2> {
+    using Args = Nufft2dArgs;
+    static constexpr const char *name = "nufft2d";
+    static bool bad_sizes(const size_t *n, const double *const *x, size_t m, double eps, bool f32) {
+        return nufft2d_bad_sizes(n[0], n[1], m, x[0], x[1], eps, f32);
+    }
+    static bool bad_args(const size_t *n, const double *const *x, size_t m, double eps, bool f32) {
+        return nufft2d_bad_args(n[0], n[1], m, x[0], x[1], eps, f32);
+    }
+    static void bin(const double *const *x, size_t m, const unsigned *lg, double *const *xs, uint32_t *perm, uint32_t *cell) {
+        nufft2d_bin(x[0], x[1], m, lg[0], lg[1], xs[0], xs[1], perm, cell);
+    }
+    static void axes(Args &a, const size_t *n, const unsigned *lg, double *const *xs, const void *const *inv) {
+        a.xs = xs[0], a.ys = xs[1];
+        a.inv1 = inv[0], a.inv2 = inv[1];
+        a.n1 = n[0], a.n2 = n[1];
+        a.log_g1 = lg[0], a.log_g2 = lg[1];
+    }
+    template <typename T> static hipError_t launch(int kind, bool vec, const Args &a, hipStream_t s) {
+        return launch_nufft2d<T>(kind, vec, a, s);
+    }
+};
+template <> struct NufftRank<3> {
+    using Args = Nufft3dArgs;
+    static constexpr const char *name = "nufft3d";
+    static bool bad_sizes(const size_t *n, const double *const *x, size_t m, double eps, bool f32) {
+        return nufft3d_bad_sizes(n[0], n[1], n[2], m, x[0], x[1], x[2], eps, f32);
+    }
+    static bool bad_args(const size_t *n, const double *const *x, size_t m, double eps, bool f32) {
+        return nufft3d_bad_args(n[0], n[1], n[2], m, x[0], x[1], x[2], eps, f32);
+    }
+    static void bin(const double *const *x, size_t m, const unsigned *lg, double *const *xs, uint32_t *perm, uint32_t *cell) {
+        nufft3d_bin(x[0], x[1], x[2], m, lg[0], lg[1], lg[2], xs[0], xs[1], xs[2], perm, cell);
+    }
+    static void axes(Args &a, const size_t *n, const unsigned *lg, double *const *xs, const void *const *inv) {
+        a.xs = xs[0], a.ys = xs[1], a.zs = xs[2];
+        a.inv1 = inv[0], a.inv2 = inv[1], a.inv3 = inv[2];
+        a.n1 = n[0], a.n2 = n[1], a.n3 = n[2];
+        a.log_g1 = lg[0], a.log_g2 = lg[1], a.log_g3 = lg[2];
+    }
+    template <typename T> static hipError_t launch(int kind, bool vec, const Args &a, hipStream_t s) {
+        return launch_nufft3d<T>(kind, vec, a, s);
+    }
+};
+
+template <typename T, size_t D> struct NufftNdPlanner {
+    static_assert(D == 2 || D == 3, "the kernels exist for two and three dimensions");
+    using Rank = NufftRank<D>;
+    size_t n[D] = {}, g[D] = {};  // the modes N_i and the fine grid g_i
+    size_t cells = 0, points = 0;  // G = g1 .. gD, M
+    unsigned log_g[D] = {};
     int w = 0, device = -1;
     double eps = 0;
     NdPlanner<T> nd;
-    double *d_xs = nullptr, *d_ys = nullptr, *d_zs = nullptr;
+    double *d_coord[D] = {};  // the sorted positions per axis
     uint32_t *d_perm = nullptr, *d_cell = nullptr;
-    T *d_inv1 = nullptr, *d_inv2 = nullptr, *d_inv3 = nullptr;
+    T *d_inv[D] = {};
 
-    ~Nufft3dPlanner() {
+    ~NufftNdPlanner() {
         DeviceGuard on(device);
-        for (void *p : {(void *)d_xs, (void *)d_ys, (void *)d_zs, (void *)d_perm, (void *)d_cell, (void *)d_inv1, (void *)d_inv2, (void *)d_inv3})
-            if (p) hipFree(p);
-    }
-
-    // 1 / phi^(k) of an axis of n modes on g grid points in double, rounded to T; phi^ is even in k
-    std::vector<T> inv_table(size_t n, size_t g) const {
-        std::vector<T> inv(n);
-        const NufftQuad hat(w, g);
-        for (size_t k = 0; k <= n / 2; ++k) {
-            const T r = (T)(1.0 / hat((long long)k));
-            if (k < (n + 1) / 2) inv[k] = r;
-            if (k > 0) inv[n - k] = r;
+        for (size_t i = 0; i < D; ++i) {
+            if (d_coord[i]) hipFree(d_coord[i]);
+            if (d_inv[i]) hipFree(d_inv[i]);
         }
-        return inv;
-    }
-
-    template <typename E> int upload(E **dst, const E *src, size_t count) {
-        PHAST_HIP(hipMalloc(reinterpret_cast<void **>(dst), count * sizeof(E)));
-        PHAST_HIP(hipMemcpy(*dst, src, count * sizeof(E), hipMemcpyHostToDevice));
-        return PHAST_OK;
+        for (void *p : {(void *)d_perm, (void *)d_cell})
+            if (p) hipFree(p);
     }
 
     template <typename E> int room(E **dst, size_t count) {
@@ -56,85 +94,104 @@ template <typename T> struct Nufft3dPlanner {
     }
 
     // what does not depend on the points: the sizes, the Nd planner, 1 / phi^ on the device, and room for the point tables
-    int init_grid(size_t n1_, size_t n2_, size_t n3_, size_t m_points, double eps_) {
-        n1 = n1_;
-        n2 = n2_;
-        n3 = n3_;
+    int init_grid(const size_t (&n_)[D], size_t m_points, double eps_) {
         points = m_points;
         eps = eps_;
         w = nufft_width(eps);
-        g1 = (size_t)nufft_grid(n1, w);
-        g2 = (size_t)nufft_grid(n2, w);
-        g3 = (size_t)nufft_grid(n3, w);
-        cells = g1 * g2 * g3;
-        log_g1 = ilog2(g1);
-        log_g2 = ilog2(g2);
-        log_g3 = ilog2(g3);
-        const size_t dims[3] = {g1, g2, g3};
-        int rc = nd.init(dims, 3);
+        cells = 1;
+        for (size_t i = 0; i < D; ++i) {
+            n[i] = n_[i];
+            g[i] = (size_t)nufft_grid(n[i], w);
+            log_g[i] = ilog2(g[i]);
+            cells *= g[i];
+        }
+        int rc = nd.init(g, D);
         if (rc) return rc;
         device = nd.device;
-        const std::vector<T> inv1 = inv_table(n1, g1), inv2 = inv_table(n2, g2), inv3 = inv_table(n3, g3);
+        std::vector<T> inv[D];
+        for (size_t i = 0; i < D; ++i) inv[i] = nufft_inv_table<T>(w, n[i], g[i]);
         PHAST_ON_DEVICE(device);
-        if ((rc = room(&d_xs, points)) || (rc = room(&d_ys, points)) || (rc = room(&d_zs, points)) || (rc = room(&d_perm, points)) ||
-            (rc = room(&d_cell, cells + 1)) || (rc = upload(&d_inv1, inv1.data(), n1)) || (rc = upload(&d_inv2, inv2.data(), n2)) ||
-            (rc = upload(&d_inv3, inv3.data(), n3)))
-            return rc;
+        for (size_t i = 0; i < D; ++i)
+            if ((rc = room(&d_coord[i], points))) return rc;
+        if ((rc = room(&d_perm, points)) || (rc = room(&d_cell, cells + 1))) return rc;
+        for (size_t i = 0; i < D; ++i) {
+            if ((rc = room(&d_inv[i], n[i]))) return rc;
+            PHAST_HIP(hipMemcpy(d_inv[i], inv[i].data(), n[i] * sizeof(T), hipMemcpyHostToDevice));
+        }
         return PHAST_OK;
     }
 
-    // `x`, `y`, `z`: M host doubles in turns; the arguments were checked by nufft3d_bad_args
-    int init(size_t n1_, size_t n2_, size_t n3_, const double *x, const double *y, const double *z, size_t m_points, double eps_) {
-        int rc = init_grid(n1_, n2_, n3_, m_points, eps_);
+    // `x`: per axis M host doubles in turns; the arguments were checked by Rank::bad_args
+    int init(const size_t (&n_)[D], const double *const (&x)[D], size_t m_points, double eps_) {
+        int rc = init_grid(n_, m_points, eps_);
         if (rc) return rc;
-        std::vector<double> xs(points), ys(points), zs(points);
+        std::vector<double> xs[D];
+        double *xp[D];
+        for (size_t i = 0; i < D; ++i) {
+            xs[i].resize(points);
+            xp[i] = xs[i].data();
+        }
         std::vector<uint32_t> perm(points), cell(cells + 1);
-        nufft3d_bin(x, y, z, points, log_g1, log_g2, log_g3, xs.data(), ys.data(), zs.data(), perm.data(), cell.data());
+        Rank::bin(x, points, log_g, xp, perm.data(), cell.data());
         PHAST_ON_DEVICE(device);
-        PHAST_HIP(hipMemcpy(d_xs, xs.data(), points * sizeof(double), hipMemcpyHostToDevice));
-        PHAST_HIP(hipMemcpy(d_ys, ys.data(), points * sizeof(double), hipMemcpyHostToDevice));
-        PHAST_HIP(hipMemcpy(d_zs, zs.data(), points * sizeof(double), hipMemcpyHostToDevice));
+        for (size_t i = 0; i < D; ++i) PHAST_HIP(hipMemcpy(d_coord[i], xp[i], points * sizeof(double), hipMemcpyHostToDevice));
         PHAST_HIP(hipMemcpy(d_perm, perm.data(), points * sizeof(uint32_t), hipMemcpyHostToDevice));
         PHAST_HIP(hipMemcpy(d_cell, cell.data(), (cells + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
         return PHAST_OK;
     }
 
-    // as init, with `d_x`, `d_y`, `d_z`: M doubles each in device memory (nufft_sort.hpp), ordered after the earlier work of `s`;
-    // blocks.  The arguments but the points' values were checked by nufft3d_bad_sizes; PHAST_ERR_INVALID_ARG for a coordinate that
-    // is not finite
-    int init_dev(size_t n1_, size_t n2_, size_t n3_, const double *d_x, const double *d_y, const double *d_z, size_t m_points,
-                 double eps_, hipStream_t s) {
-        int rc = init_grid(n1_, n2_, n3_, m_points, eps_);
+    // the point tables from `d_x`: per axis M doubles in device memory (nufft_sort.hpp; its third axis is absent in 2-D)
+    int sort_points(const double *const (&d_x)[D], hipStream_t s, float *ms) {
+        return nufft_sort_build(d_x[0], d_x[1], D > 2 ? d_x[D - 1] : nullptr, points, log_g[0], log_g[1], D > 2 ? log_g[D - 1] : 0,
+                                d_perm, d_cell, d_coord[0], d_coord[1], D > 2 ? d_coord[D - 1] : nullptr, s, ms);
+    }
+
+    // as init, with the points in device memory, ordered after the earlier work of `s`; blocks.  The arguments but the points'
+    // values were checked by Rank::bad_sizes; PHAST_ERR_INVALID_ARG for a coordinate that is not finite
+    int init_dev(const size_t (&n_)[D], const double *const (&d_x)[D], size_t m_points, double eps_, hipStream_t s) {
+        int rc = init_grid(n_, m_points, eps_);
         if (rc) return rc;
         PHAST_ON_DEVICE(device);
-        return nufft_sort_build(d_x, d_y, d_z, points, log_g1, log_g2, log_g3, d_perm, d_cell, d_xs, d_ys, d_zs, s);
+        return sort_points(d_x, s, nullptr);
     }
 
     // new points, the same M of them, from device memory: the rules of NufftPlanner::set_points_dev (planner_nufft.hpp) -- the
     // tables are rewritten in place, a rejected point set leaves the planner as it was, the call blocks, and it orders itself
     // after the earlier work of `s` ONLY: the caller must have finished the work on other streams that uses the planner
-    int set_points_dev(const double *d_x, const double *d_y, const double *d_z, size_t m_points, hipStream_t s, float *ms = nullptr) {
-        if (!d_x || !d_y || !d_z) return PHAST_ERR_INVALID_ARG;
+    int set_points_dev(const double *const (&d_x)[D], size_t m_points, hipStream_t s, float *ms = nullptr) {
+        for (const double *p : d_x)
+            if (!p) return PHAST_ERR_INVALID_ARG;
         if (m_points != points) return PHAST_ERR_PLANNER_SIZE;
         PHAST_ON_DEVICE(device);
         if (nufft_sort_stream_busy(s)) return PHAST_ERR_INVALID_ARG;
-        return nufft_sort_build(d_x, d_y, d_z, points, log_g1, log_g2, log_g3, d_perm, d_cell, d_xs, d_ys, d_zs, s, ms);
+        return sort_points(d_x, s, ms);
     }
 
     // elements of T per transform: the two grid planes and the Nd planner's own share (4 G)
     size_t per() const { return 2 * cells + nd.workspace_len(1); }
     size_t workspace_len(size_t batch) const { return per() * batch; }
+    size_t grid_len() const { return cells; }
+    size_t modes() const {
+        size_t all = 1;
+        for (size_t ni : n) all *= ni;
+        return all;
+    }
     size_t table_bytes() const {
-        return points * (3 * sizeof(double) + sizeof(uint32_t)) + (cells + 1) * sizeof(uint32_t) + (n1 + n2 + n3) * sizeof(T);
+        size_t inv = 0;
+        for (size_t ni : n) inv += ni;
+        return points * (D * sizeof(double) + sizeof(uint32_t)) + (cells + 1) * sizeof(uint32_t) + inv * sizeof(T);
     }
     size_t device_bytes() const { return table_bytes() + nd.device_bytes(); }
     std::string describe() const {
         char f[48];
         std::snprintf(f, sizeof f, " eps=%.3g w=%d", eps, w);
-        return "nufft3d N=" + std::to_string(n1) + "x" + std::to_string(n2) + "x" + std::to_string(n3) + " M=" + std::to_string(points) + f +
-               " grid=" + std::to_string(g1) + "x" + std::to_string(g2) + "x" + std::to_string(g3) + ": " + nd.describe();
+        auto by = [](const size_t (&v)[D]) {
+            std::string s = std::to_string(v[0]);
+            for (size_t i = 1; i < D; ++i) s += "x" + std::to_string(v[i]);
+            return s;
+        };
+        return std::string(Rank::name) + " N=" + by(n) + " M=" + std::to_string(points) + f + " grid=" + by(g) + ": " + nd.describe();
     }
-    size_t modes() const { return n1 * n2 * n3; }
     size_t in_len(int type) const { return type == 1 ? points : modes(); }
     size_t out_len(int type) const { return type == 1 ? modes() : points; }
 
@@ -148,24 +205,15 @@ template <typename T> struct Nufft3dPlanner {
         // 16-byte accesses: aligned planes and workspace, and the transforms' planes a multiple of the group apart (one
         // transform has no distance to meet)
         auto vec = [&](const T *re, const T *im, size_t dist) { return al(re) && al(im) && al(wk) && (c == 1 || dist % V == 0); };
-        Nufft3dArgs a{};
-        a.xs = d_xs;
-        a.ys = d_ys;
-        a.zs = d_zs;
+        typename Rank::Args a{};
+        const void *inv[D];
+        for (size_t i = 0; i < D; ++i) inv[i] = d_inv[i];
+        Rank::axes(a, n, log_g, d_coord, inv);
         a.perm = d_perm;
         a.cell_start = d_cell;
-        a.inv1 = d_inv1;
-        a.inv2 = d_inv2;
-        a.inv3 = d_inv3;
         a.in_dist = in_dist;
         a.out_dist = out_dist;
-        a.n1 = n1;
-        a.n2 = n2;
-        a.n3 = n3;
         a.m = points;
-        a.log_g1 = log_g1;
-        a.log_g2 = log_g2;
-        a.log_g3 = log_g3;
         a.w = w;
         if (ev) PHAST_HIP(hipEventRecord(ev[0], s));
         a.in_re = x_re;
@@ -173,11 +221,11 @@ template <typename T> struct Nufft3dPlanner {
         a.out_re = w_re;
         a.out_im = w_im;
         if (type == 1) {
-            a.groups = c * cells;  // a tile of 256 grid points per workgroup
-            PHAST_HIP(launch_nufft3d<T>(0, false, a, s));
+            a.groups = c * cells;
+            PHAST_HIP(Rank::template launch<T>(0, false, a, s));
         } else {
             a.groups = c * (cells / V);
-            PHAST_HIP(launch_nufft3d<T>(2, vec(x_re, x_im, in_dist), a, s));
+            PHAST_HIP(Rank::template launch<T>(2, vec(x_re, x_im, in_dist), a, s));
         }
         if (ev) PHAST_HIP(hipEventRecord(ev[1], s));
         // always the Forward transform (Reverse of the Nd planner scales by 1 / G).  Reverse by the swap trick: the FFT of
@@ -191,12 +239,12 @@ template <typename T> struct Nufft3dPlanner {
         a.out_re = o_re;
         a.out_im = o_im;
         if (type == 1) {
-            a.gpt = (unsigned)(n1 * n2 * ((n3 + V - 1) / V));
+            a.gpt = (unsigned)(modes() / n[D - 1] * ((n[D - 1] + V - 1) / V));  // sweeps along the last axis
             a.groups = c * a.gpt;
-            PHAST_HIP(launch_nufft3d<T>(3, vec(o_re, o_im, out_dist), a, s));
+            PHAST_HIP(Rank::template launch<T>(3, vec(o_re, o_im, out_dist), a, s));
         } else {
             a.groups = c * points;
-            PHAST_HIP(launch_nufft3d<T>(1, false, a, s));
+            PHAST_HIP(Rank::template launch<T>(1, false, a, s));
         }
         if (ev) PHAST_HIP(hipEventRecord(ev[3], s));
         return PHAST_OK;
@@ -218,30 +266,10 @@ template <typename T> struct Nufft3dPlanner {
         return PHAST_OK;
     }
 
-    // [p, p + len) and [q, q + qlen) share an element
-    static bool overlap(const T *p, size_t len, const T *q, size_t qlen) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-        return p && q && a < b + qlen * sizeof(T) && b < a + len * sizeof(T);
-    }
-
-    // the rules and return codes of NufftPlanner::check_dev
     int check_dev(int type, int direction, const T *d_in_re, const T *d_in_im, size_t in_dist, const T *d_out_re,
                   const T *d_out_im, size_t out_dist, size_t batch, const T *d_work, size_t work_len) const {
-        if (!d_in_re || !d_out_re || !d_out_im) return PHAST_ERR_INVALID_ARG;  // d_in_im may be null: real data
-        if (direction != PHAST_FORWARD && direction != PHAST_REVERSE) return PHAST_ERR_INVALID_ARG;
-        const size_t ni = in_len(type), no = out_len(type);
-        if (batch > 1 && (in_dist < ni || out_dist < no)) return PHAST_ERR_INVALID_ARG;
-        if (batch && (!d_work || work_len < per())) return PHAST_ERR_INVALID_ARG;
-        if (batch) {  // the output is written while later chunks still read the input and the workspace
-            const size_t in_span = (batch - 1) * (batch > 1 ? in_dist : 0) + ni, out_span = (batch - 1) * (batch > 1 ? out_dist : 0) + no;
-            for (const T *o : {d_out_re, d_out_im})
-                if (overlap(o, out_span, d_in_re, in_span) || overlap(o, out_span, d_in_im, in_span) ||
-                    overlap(o, out_span, d_work, work_len))
-                    return PHAST_ERR_INVALID_ARG;
-            if (overlap(d_out_re, out_span, d_out_im, out_span)) return PHAST_ERR_INVALID_ARG;
-            if (overlap(d_work, work_len, d_in_re, in_span) || overlap(d_work, work_len, d_in_im, in_span)) return PHAST_ERR_INVALID_ARG;
-        }
-        return PHAST_OK;
+        return nufft_check_dev(direction, d_in_re, d_in_im, in_dist, in_len(type), d_out_re, d_out_im, out_dist, out_len(type), batch,
+                               d_work, work_len, per());
     }
 
     // device pointers, asynchronous on `s`: no allocation, no synchronisation
@@ -280,8 +308,8 @@ template <typename T> struct Nufft3dPlanner {
         return PHAST_OK;
     }
 
-    // measurement hook: ms[0..2] = average milliseconds of the three stages (spread or pre, the 3-D transform of the grid,
-    // deconvolve or interpolate) over `reps` Forward calls of one chunk (work_len >= workspace_len(batch)) at the natural
+    // measurement hook: ms[0..2] = average milliseconds of the three stages (spread or pre, the D-dimensional transform of the
+    // grid, deconvolve or interpolate) over `reps` Forward calls of one chunk (work_len >= workspace_len(batch)) at the natural
     // distances; ms[3] and ms[4] are 0 (the timer of the any-length planners has five slots); blocks
     int time_stages(int type, const T *d_in_re, const T *d_in_im, T *d_out_re, T *d_out_im, size_t batch, T *d_work,
                     size_t work_len, int reps, float *ms, hipStream_t s) const {
@@ -315,40 +343,15 @@ template <typename T> struct Nufft3dPlanner {
     }
 };
 
-template <typename P>
-static int nufft3d_planner_new(size_t n1, size_t n2, size_t n3, const double *x, const double *y, const double *z, size_t m_points,
-                               double eps, bool f32, P **out) {
-    if (!out) return PHAST_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (nufft3d_bad_args(n1, n2, n3, m_points, x, y, z, eps, f32)) return PHAST_ERR_INVALID_ARG;  // before the device is touched
-    auto *p = new (std::nothrow) P();
-    if (!p) return PHAST_ERR_ALLOC;
-    int rc = p->init(n1, n2, n3, x, y, z, m_points, eps);
-    if (rc) {
-        delete p;
-        return rc;
-    }
-    *out = p;
-    return PHAST_OK;
+// P over NufftNdPlanner<T, D> from host points (n: the mode counts, x: a pointer per coordinate); D comes from the two lists
+template <typename P, size_t D>
+static int nufft_nd_planner_new(const size_t (&n)[D], const double *const (&x)[D], size_t m_points, double eps, bool f32, P **out) {
+    return nufft_planner_make(out, [&] { return NufftRank<D>::bad_args(n, x, m_points, eps, f32); }, n, x, m_points, eps);
 }
-
-// the same from M doubles per coordinate in device memory, ordered after the earlier work of `s`
-template <typename P>
-static int nufft3d_planner_new_dev(size_t n1, size_t n2, size_t n3, const double *d_x, const double *d_y, const double *d_z,
-                                   size_t m_points, double eps, bool f32, hipStream_t s, P **out) {
-    if (!out) return PHAST_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (nufft3d_bad_sizes(n1, n2, n3, m_points, d_x, d_y, d_z, eps, f32)) return PHAST_ERR_INVALID_ARG;  // before the device is touched
-    if (nufft_sort_stream_busy(s)) return PHAST_ERR_INVALID_ARG;
-    auto *p = new (std::nothrow) P();
-    if (!p) return PHAST_ERR_ALLOC;
-    int rc = p->init_dev(n1, n2, n3, d_x, d_y, d_z, m_points, eps, s);
-    if (rc) {
-        delete p;
-        return rc;
-    }
-    *out = p;
-    return PHAST_OK;
+template <typename P, size_t D>
+static int nufft_nd_planner_new_dev(const size_t (&n)[D], const double *const (&d_x)[D], size_t m_points, double eps, bool f32,
+                                    hipStream_t s, P **out) {
+    return nufft_planner_make_dev(out, [&] { return NufftRank<D>::bad_sizes(n, d_x, m_points, eps, f32); }, s, n, d_x, m_points, eps);
 }
 
 }  // namespace phast

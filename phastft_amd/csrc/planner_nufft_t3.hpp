@@ -138,7 +138,7 @@ template <typename T> struct NufftT3Planner {
         if (batch && (!d_work || work_len < workspace_len(1))) return PHAST_ERR_INVALID_ARG;
         if (batch) {  // the output is written while later chunks still read the input and the workspace
             const size_t in_span = (batch - 1) * (batch > 1 ? in_dist : 0) + ni, out_span = (batch - 1) * (batch > 1 ? out_dist : 0) + no;
-            auto overlap = NufftPlanner<T>::overlap;
+            auto overlap = nufft_overlap<T>;
             for (const T *o : {d_out_re, d_out_im})
                 if (overlap(o, out_span, d_in_re, in_span) || overlap(o, out_span, d_in_im, in_span) ||
                     overlap(o, out_span, d_work, work_len))
