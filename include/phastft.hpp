@@ -24,6 +24,8 @@
 //                                                            istft_f64/f32_with_planner, enum PadMode -- torch.stft / istft
 //   (none: no convolution upstream)                          class PlannerConv64/32, conv_f64/f32_with_planner, enum ConvMode --
 //                                                            scipy.signal.convolve / correlate by overlap-save
+//   (none: no convolution upstream)                          class PlannerConvNd64/32, convnd_f64/f32_with_planner -- the same of
+//                                                            arrays of rank 1 .. 3, by overlap-save along every axis
 //   (none: whole spectra only upstream)                      class PlannerCzt64/32, czt_64/32[_with_planner] -- the chirp-Z transform
 //                                                            on the unit circle (scipy.signal.czt / zoom_fft)
 //   (none: samples on a grid only upstream)                  class PlannerNufft64/32, nufft1_64/32[_with_planner],
@@ -564,6 +566,71 @@ PHASTFT_PLANNER_CONV(PlannerConv32, phast_planner_conv32, 32, float)
 PHASTFT_CONV(f64, double, PlannerConv64)
 PHASTFT_CONV(f32, float, PlannerConv32)
 #undef PHASTFT_CONV
+
+// ---- overlap-save convolution and correlation of real arrays of rank 1 .. 3 (no reference counterpart; scipy.signal.convolve /
+// correlate of N-d arrays) ----
+#define PHASTFT_PLANNER_CONVND(NAME, CT, SFX, T)                                                                 \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* row-major arrays of `signal_shape`, `taps` of `taps_shape` (the same rank); block: empty = automatic, or one \
+           entry per axis (0: automatic) */                                                                      \
+        NAME(const std::vector<std::size_t> &signal_shape, const std::vector<std::size_t> &taps_shape, Slice<const T> taps, \
+             ConvMode mode = ConvMode::Full, bool correlate = false, const std::vector<std::size_t> &block = {})  \
+            : rank_(signal_shape.size()) {                                                                       \
+            std::size_t k = 1;                                                                                   \
+            for (std::size_t v : taps_shape) k *= v;                                                             \
+            if (taps_shape.size() != rank_ || (!block.empty() && block.size() != rank_) || (rank_ && taps.len != k)) \
+                check(PHAST_ERR_INVALID_ARG);                                                                    \
+            check(phast_planner_convnd##SFX##_new(signal_shape.data(), taps_shape.data(), rank_, taps.ptr,       \
+                                                  static_cast<int>(mode), correlate ? 1 : 0,                     \
+                                                  block.empty() ? nullptr : block.data(), &h_));                 \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_), rank_(o.rank_) { o.h_ = nullptr; }                                   \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_convnd##SFX##_free(h_);                                                        \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_convnd##SFX##_describe(h_, &s[0], s.size()));                                    \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_convnd##SFX##_device_bytes(h_); }                \
+        std::size_t out_len() const { return phast_planner_convnd##SFX##_out_len(h_); }                          \
+        std::vector<std::size_t> out_shape() const {                                                             \
+            std::vector<std::size_t> d(rank_);                                                                   \
+            check(phast_planner_convnd##SFX##_out_dims(h_, d.data(), rank_));                                    \
+            return d;                                                                                            \
+        }                                                                                                        \
+        std::vector<std::size_t> block() const {                                                                 \
+            std::vector<std::size_t> d(rank_);                                                                   \
+            check(phast_planner_convnd##SFX##_block(h_, d.data(), rank_));                                       \
+            return d;                                                                                            \
+        }                                                                                                        \
+        std::size_t tiles() const { return phast_planner_convnd##SFX##_tiles(h_); }                              \
+        /* elements of T a _dev call of `batch` arrays works in; workspace_min: the least a call runs in */      \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_convnd##SFX##_workspace_len(h_, batch); } \
+        std::size_t workspace_min() const { return phast_planner_convnd##SFX##_workspace_min(h_); }              \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+        std::size_t rank_ = 0;                                                                                   \
+    };
+PHASTFT_PLANNER_CONVND(PlannerConvNd64, phast_planner_convnd64, 64, double)
+PHASTFT_PLANNER_CONVND(PlannerConvNd32, phast_planner_convnd32, 32, float)
+#undef PHASTFT_PLANNER_CONVND
+
+// one host array of the planner's shape -> its out_len() output samples (row-major, out_shape()); blocking
+#define PHASTFT_CONVND(FS, T, P)                                                                                 \
+    inline void convnd_##FS##_with_planner(Slice<const T> signal, Slice<T> output, const P &planner) {           \
+        check(phast_convnd_##FS##_with_planner(signal.ptr, signal.len, output.ptr, output.len, planner.get()));  \
+    }
+PHASTFT_CONVND(f64, double, PlannerConvNd64)
+PHASTFT_CONVND(f32, float, PlannerConvNd32)
+#undef PHASTFT_CONVND
 
 // ---- the chirp-Z transform on the unit circle and the zoom FFT (no reference counterpart; scipy.signal.czt / zoom_fft) ----
 #define PHASTFT_PLANNER_CZT(NAME, CT, SFX)                                                                       \

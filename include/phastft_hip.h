@@ -572,6 +572,72 @@ int phast_conv_f32_dev(const float *d_signal, float *d_out, size_t signal_len, s
 int phast_planner_conv32_time_stages(const phast_planner_conv32 *p, const float *d_signal, float *d_out, size_t batch, float *d_work,
                                      size_t work_len, int reps, float *stage_ms, void *stream);
 
+/* ---- overlap-save convolution and correlation of real ARRAYS of rank 1 .. 3 (no reference counterpart; scipy.signal.convolve /
+ * correlate(x, h, mode, method="direct") of N-d arrays).  x is a row-major array [L_0 .. L_{r-1}], h one of the
+ * same rank [K_0 .. K_{r-1}], both real:
+ *     full[t] = sum_j g[j] x[t - j], t_i in [0, L_i + K_i - 1); g = h (flip = 0) or h reversed along every axis (flip = 1:
+ *     correlation); out[i] = full[t0 + i], with t0_i and out_i per axis by the PHAST_CONV_* rules above (VALID needs
+ *     L_i >= K_i on every axis; K_i > L_i is legal in FULL and SAME).
+ * The array is cut into tiles of block[i] = B_i >= K_i points per axis that overlap by K_i - 1; a tile is one R2C of the tile
+ * shape on the phast_planner_r2c_nd* engine, called unchanged, a multiply by the filter's spectrum (built once in double by
+ * _new) and one C2R, and yields S_i = B_i - K_i + 1 output samples per axis; _tiles is prod ceil(out_i / S_i).  `block` null,
+ * or block[i] = 0, picks B_i: the smallest power of two >= max(4 (K_i - 1), floor), floor = 1024 where one axis counts and 64
+ * where two or three do, or the smallest power of two >= out_i + K_i - 1 where that is smaller (_block tells).  An axis with
+ * L_i = K_i = 1 does not count: it is dropped (the last one stays if nothing else does) and its block is 1.
+ * _new takes rank 1 .. 3, 1 <= L_i, K_i <= 2^29, K_i <= B_i <= 2^29, prod L <= 2^30, prod out <= 2^30, prod B <= 2^28, `taps` a
+ * host pointer to prod K values (row-major), flip 0 or 1: anything else is PHAST_ERR_INVALID_ARG before the device is touched.
+ * _out_len is prod out; _out_dims and _block fill `rank` values (the planner's rank, or PHAST_ERR_INVALID_ARG).
+ *
+ * The caller's device workspace holds phast_planner_convnd*_workspace_len(p, batch) elements of T; any work_len >=
+ * _workspace_min(p) (one tile) runs the call in chunks of whole tiles, a null or shorter one is PHAST_ERR_INVALID_ARG.
+ * _dev calls: asynchronous on `stream`; `batch` arrays at sig_dist >= prod L, their outputs at out_dist >= prod out, all through
+ * the planner's one filter; pointers need element alignment only; the arrays are never written and nothing is written outside
+ * the prod out elements of an output.  A signal_len that is not prod L is PHAST_ERR_PLANNER_SIZE, a host output that is not
+ * prod out long PHAST_ERR_LEN_MISMATCH.  The planner is immutable and holds no per-call state.  An output sample comes from
+ * exactly one tile: the bits of an array do not depend on the batch, the chunking, the pointer alignment, the stream or graph
+ * replay wherever the tile transform's do not (two or more tile axes longer than 1; or one that is not a power of two, or a
+ * power of two up to 4096).  Host-slice calls take one array, stage through the device and block. */
+typedef struct phast_planner_convnd64 phast_planner_convnd64; /* PlannerConvNd64 */
+int phast_planner_convnd64_new(const size_t *signal_dims, const size_t *tap_dims, size_t rank, const double *taps, int mode, int flip,
+                               const size_t *block, phast_planner_convnd64 **out);
+void phast_planner_convnd64_free(phast_planner_convnd64 *p);
+int phast_planner_convnd64_describe(const phast_planner_convnd64 *p, char *buf, size_t buf_len);
+size_t phast_planner_convnd64_device_bytes(const phast_planner_convnd64 *p);
+size_t phast_planner_convnd64_out_len(const phast_planner_convnd64 *p);
+int phast_planner_convnd64_out_dims(const phast_planner_convnd64 *p, size_t *dims, size_t rank);
+int phast_planner_convnd64_block(const phast_planner_convnd64 *p, size_t *dims, size_t rank);
+size_t phast_planner_convnd64_tiles(const phast_planner_convnd64 *p);
+size_t phast_planner_convnd64_workspace_len(const phast_planner_convnd64 *p, size_t batch);
+size_t phast_planner_convnd64_workspace_min(const phast_planner_convnd64 *p);
+int phast_convnd_f64_with_planner(const double *signal, size_t signal_len, double *output, size_t output_len,
+                                  const phast_planner_convnd64 *planner);
+int phast_convnd_f64_dev(const double *d_signal, double *d_out, size_t signal_len, size_t batch, size_t sig_dist, size_t out_dist,
+                         const phast_planner_convnd64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/convnd_rate.py): stage_ms[5] = average milliseconds of the tile sweep, the R2C, the spectrum sweep,
+ * the C2R and the save sweep over `reps` calls of `batch` arrays at distances prod L and prod out in ONE chunk (work_len >=
+ * phast_planner_convnd*_workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_convnd64_time_stages(const phast_planner_convnd64 *p, const double *d_signal, double *d_out, size_t batch,
+                                       double *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_convnd32 phast_planner_convnd32; /* PlannerConvNd32 */
+int phast_planner_convnd32_new(const size_t *signal_dims, const size_t *tap_dims, size_t rank, const float *taps, int mode, int flip,
+                               const size_t *block, phast_planner_convnd32 **out);
+void phast_planner_convnd32_free(phast_planner_convnd32 *p);
+int phast_planner_convnd32_describe(const phast_planner_convnd32 *p, char *buf, size_t buf_len);
+size_t phast_planner_convnd32_device_bytes(const phast_planner_convnd32 *p);
+size_t phast_planner_convnd32_out_len(const phast_planner_convnd32 *p);
+int phast_planner_convnd32_out_dims(const phast_planner_convnd32 *p, size_t *dims, size_t rank);
+int phast_planner_convnd32_block(const phast_planner_convnd32 *p, size_t *dims, size_t rank);
+size_t phast_planner_convnd32_tiles(const phast_planner_convnd32 *p);
+size_t phast_planner_convnd32_workspace_len(const phast_planner_convnd32 *p, size_t batch);
+size_t phast_planner_convnd32_workspace_min(const phast_planner_convnd32 *p);
+int phast_convnd_f32_with_planner(const float *signal, size_t signal_len, float *output, size_t output_len,
+                                  const phast_planner_convnd32 *planner);
+int phast_convnd_f32_dev(const float *d_signal, float *d_out, size_t signal_len, size_t batch, size_t sig_dist, size_t out_dist,
+                         const phast_planner_convnd32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook: as phast_planner_convnd64_time_stages */
+int phast_planner_convnd32_time_stages(const phast_planner_convnd32 *p, const float *d_signal, float *d_out, size_t batch,
+                                       float *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
+
 /* ---- the chirp-Z transform on the unit circle and the zoom FFT (no reference counterpart; scipy.signal.czt / zoom_fft;
  * DESIGN.md §17).  N input points x, M output points, `start` and `step` finite doubles in turns (cycles per sample):
  *     X[k] = sum_{n < N} x[n] exp(-2 pi i n (start + k step)),  k < M

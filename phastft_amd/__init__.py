@@ -26,6 +26,8 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
                                                     stft_f64/f32_with_planner, istft_f64/f32_with_planner
     (none: no convolution)                          PlannerConv64/32, conv_batched, conv_f64/f32_with_planner,
                                                     fftconvolve, correlate
+    (none: no convolution)                          PlannerConvNd64/32, convnd_batched, convnd_f64/f32_with_planner,
+                                                    fftconvolve_nd, correlate_nd
     (none: whole spectra only)                      PlannerCzt64/32, czt_batched, czt_64/32[_with_planner], czt, zoom_fft
     (none: samples on a grid only)                  PlannerNufft64/32, nufft1_batched, nufft2_batched,
                                                     nufft1_64/32[_with_planner], nufft2_64/32[_with_planner], nufft1, nufft2
@@ -85,6 +87,8 @@ __all__ = [
     "istft_f64_with_planner", "istft_f32_with_planner",
     "PlannerConv64", "PlannerConv32", "conv_batched", "conv_f64_with_planner", "conv_f32_with_planner", "fftconvolve",
     "correlate",
+    "PlannerConvNd64", "PlannerConvNd32", "convnd_batched", "convnd_f64_with_planner", "convnd_f32_with_planner",
+    "fftconvolve_nd", "correlate_nd",
     "PlannerCzt64", "PlannerCzt32", "czt_batched", "czt_64", "czt_32", "czt_64_with_planner", "czt_32_with_planner", "czt",
     "zoom_fft",
     "PlannerNufft64", "PlannerNufft32", "nufft1_batched", "nufft2_batched", "nufft1_64", "nufft1_32", "nufft2_64", "nufft2_32",
@@ -1291,6 +1295,129 @@ def fftconvolve(x, h, mode: str = "full"):
 def correlate(x, h, mode: str = "full"):
     """``scipy.signal.correlate(x, h, mode)`` of one real device tensor with the template ``h``: a new device tensor"""
     return _convolve(x, h, mode, True)
+
+
+# ---------------------------------------------------------------------------------------------
+# overlap-save convolution and correlation of real arrays of rank 1 .. 3 (no reference counterpart; scipy.signal.convolve /
+# correlate of N-d arrays)
+# ---------------------------------------------------------------------------------------------
+class PlannerConvNd64(_AnyHandle):
+    """f64 convolution (``correlate=True``: cross-correlation) of row-major arrays of ``signal_shape`` (rank 1 .. 3) with the real
+    ``taps`` of the same rank: ``scipy.signal.convolve(x, taps, mode, method="direct")`` / ``scipy.signal.correlate(...)``.
+    ``mode``: ``"full"``, ``"same"`` or ``"valid"`` (needs L_i >= K_i on every axis).  The array runs in overlapping tiles of
+    ``block`` points per axis, each one R2C of the tile shape, one multiply by the filter's spectrum and one C2R; ``block=None``,
+    or a 0 in it, picks a power of two per axis from the taps, any other value must be at least the taps' extent."""
+
+    _prefix = "convnd"
+
+    def __init__(self, signal_shape, taps, mode: str = "full", correlate: bool = False, block=None):
+        if mode not in _CONV_MODES:
+            raise ValueError(f"mode must be 'full', 'same' or 'valid', not {mode!r}")
+        if _is_torch(taps):
+            taps = taps.detach().cpu().numpy()
+        h = np.ascontiguousarray(taps, dtype=self._dtype)
+        self.signal_shape = tuple(int(d) for d in signal_shape)
+        rank = len(self.signal_shape)
+        if h.ndim != rank:
+            raise ValueError(f"the taps have rank {h.ndim}, the arrays rank {rank}")
+        if block is not None and len(tuple(block)) != rank:
+            raise ValueError(f"block needs one entry per axis ({rank}), or None")
+        blk = None if block is None else _dims(block)[0]
+        self._new(_dims(self.signal_shape)[0], _dims(h.shape)[0], rank, h.ctypes.data_as(C.c_void_p), _CONV_MODES[mode],
+                  bool(correlate), blk)
+        self.n = self.signal_len = int(np.prod(self.signal_shape, dtype=np.int64))
+        self.taps_shape, self.mode, self.correlate = tuple(h.shape), mode, bool(correlate)
+        self.out_len = int(self._fn("out_len")(self._h))
+        self.out_shape = self._dims_of("out_dims")
+        self.block = self._dims_of("block")
+        self.tiles = int(self._fn("tiles")(self._h))
+
+    def _dims_of(self, name: str):
+        rank = len(self.signal_shape)
+        d = (C.c_size_t * rank)()
+        _check(self._fn(name)(self._h, d, rank))
+        return tuple(int(v) for v in d)
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` arrays works in.  A smaller workspace of at least ``workspace_min()``
+        (one tile) runs the call in chunks of whole tiles."""
+        return self._workspace_len(batch)
+
+    def workspace_min(self) -> int:
+        return int(self._fn("workspace_min")(self._h))
+
+    def time_stages(self, signal, out, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (tile sweep, R2C, spectrum sweep, C2R, save sweep) of a call of ``batch``
+        arrays at distances prod L and ``out_len`` on device tensors (measurement hook)"""
+        x, y = _Slice(_flat(signal), self._dtype, "signal"), _Slice(_flat(out), self._dtype, "out")
+        return self._time("time_stages", (x, y), (batch,), batch, workspace, reps)
+
+
+class PlannerConvNd32(PlannerConvNd64):
+    """f32 twin of :class:`PlannerConvNd64` (the filter's spectrum is built in f64 and rounded)"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def convnd_batched(signal, out, planner, batch: int, sig_dist: int | None = None, out_dist: int | None = None,
+                   workspace=None) -> None:
+    """Device-resident batch of N-d convolutions through one planner's filter: array b at ``b*sig_dist`` elements (default
+    prod L, any distance >= that), its output at ``b*out_dist`` (default ``planner.out_len``, any distance >= that).
+    ``workspace``: a device tensor of the planner's type of at least ``planner.workspace_min()`` elements (fewer than
+    ``planner.workspace_len(batch)`` runs the tiles in chunks); by default one from torch's allocator."""
+    dtype, fs = planner._dtype, "f64" if planner._dtype == np.float64 else "f32"
+    x, y = _Slice(_flat(signal), dtype, "signal"), _Slice(_flat(out), dtype, "out")
+    if not _same_place(x, y):
+        raise TypeError("convnd_batched needs device tensors")
+    n, m = planner.signal_len, planner.out_len
+    sig_dist = n if sig_dist is None else sig_dist
+    out_dist = m if out_dist is None else out_dist
+    _need("signal", x.len, batch, sig_dist, n)
+    _need("out", y.len, batch, out_dist, m)
+    ws = _any_workspace(planner, batch, workspace)
+    _check(_call(f"phast_convnd_{fs}_dev", x.ptr, y.ptr, n, batch, sig_dist, out_dist, planner._h, ws.ptr, ws.len, _stream()))
+
+
+def _convnd_host(fs, dtype, signal, out, planner):
+    x, y = _Slice(_flat(signal), dtype, "signal"), _Slice(_flat(out), dtype, "out")
+    if _same_place(x, y):
+        raise TypeError(f"convnd_{fs}_with_planner takes host arrays (convnd_batched takes device tensors)")
+    _check(_call(f"phast_convnd_{fs}_with_planner", x.ptr, x.len, y.ptr, y.len, planner._h))
+
+
+def convnd_f64_with_planner(signal, out, planner: PlannerConvNd64) -> None:
+    """f64 convolution of one host array of ``signal_shape`` into a host array of ``planner.out_shape`` (blocking)"""
+    _convnd_host("f64", np.float64, signal, out, planner)
+
+
+def convnd_f32_with_planner(signal, out, planner: PlannerConvNd32) -> None:
+    """f32 twin of :func:`convnd_f64_with_planner`"""
+    _convnd_host("f32", np.float32, signal, out, planner)
+
+
+def _convolve_nd(x, h, mode, correlate):
+    import torch
+
+    if not _is_torch(x) or x.device.type != "cuda" or x.dtype not in (torch.float64, torch.float32):
+        raise TypeError("need a float64 or float32 device tensor")
+    x = x.contiguous()
+    planner = (PlannerConvNd64 if x.dtype == torch.float64 else PlannerConvNd32)(tuple(x.shape), h, mode, correlate)
+    out = torch.empty(planner.out_shape, dtype=x.dtype, device=x.device)
+    convnd_batched(x, out, planner, 1)
+    torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+    return out
+
+
+def fftconvolve_nd(x, h, mode: str = "full"):
+    """``scipy.signal.fftconvolve(x, h, mode)`` of one real device tensor of rank 1 .. 3 with the taps ``h`` of the same rank (an
+    array or a tensor), by overlap-save along every axis through a planner of its own: a new device tensor of the output's shape"""
+    return _convolve_nd(x, h, mode, False)
+
+
+def correlate_nd(x, h, mode: str = "full"):
+    """``scipy.signal.correlate(x, h, mode)`` of one real device tensor of rank 1 .. 3 with the template ``h``: a new device tensor"""
+    return _convolve_nd(x, h, mode, True)
 
 
 # ---------------------------------------------------------------------------------------------

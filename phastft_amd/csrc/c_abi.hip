@@ -19,6 +19,7 @@
 #include "planner_dct.hpp"
 #include "planner_stft.hpp"
 #include "planner_conv.hpp"
+#include "planner_convnd.hpp"
 #include "planner_czt.hpp"
 #include "planner_nufft.hpp"
 #include "planner_nd.hpp"
@@ -44,6 +45,8 @@ struct phast_planner_stft64 : StftPlanner<double> {};
 struct phast_planner_stft32 : StftPlanner<float> {};
 struct phast_planner_conv64 : ConvPlanner<double> {};
 struct phast_planner_conv32 : ConvPlanner<float> {};
+struct phast_planner_convnd64 : ConvNdPlanner<double> {};
+struct phast_planner_convnd32 : ConvNdPlanner<float> {};
 struct phast_planner_czt64 : CztPlanner<double> {};
 struct phast_planner_czt32 : CztPlanner<float> {};
 struct phast_planner_nufft64 : NufftPlanner<double> {};
@@ -552,6 +555,7 @@ PHAST_HANDLE_API(conv64) PHAST_HANDLE_API(conv32) PHAST_HANDLE_API(czt64) PHAST_
 PHAST_HANDLE_API(nufft64) PHAST_HANDLE_API(nufft32) PHAST_HANDLE_API(nufft2d64) PHAST_HANDLE_API(nufft2d32)
 PHAST_HANDLE_API(nufft3d64) PHAST_HANDLE_API(nufft3d32) PHAST_HANDLE_API(nufft_t3_64) PHAST_HANDLE_API(nufft_t3_32)
 PHAST_HANDLE_API(nd64) PHAST_HANDLE_API(nd32) PHAST_HANDLE_API(r2c_nd64) PHAST_HANDLE_API(r2c_nd32)
+PHAST_HANDLE_API(convnd64) PHAST_HANDLE_API(convnd32)
 
 // Arbitrary lengths (Bluestein, planner_any.hpp): arguments are checked before the device is touched
 #define PHAST_ANY_API(SFX, T)                                                                                           \
@@ -786,6 +790,54 @@ PHAST_STFT_API(32, f32, float)
     } PHAST_CATCH_RC
 PHAST_CONV_API(64, f64, double)
 PHAST_CONV_API(32, f32, float)
+
+// Overlap-save convolution and correlation of real arrays of rank 1 .. 3 (planner_convnd.hpp): every argument rule and a wrong
+// length come back before the device is touched
+#define PHAST_CONVND_API(SFX, FS, T)                                                                                    \
+    int phast_planner_convnd##SFX##_new(const size_t *signal_dims, const size_t *tap_dims, size_t rank, const T *taps,  \
+                                        int mode, int flip, const size_t *block, phast_planner_convnd##SFX **out) try { \
+        return convnd_planner_new<T>(signal_dims, tap_dims, rank, taps, mode, flip, block, out);                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_convnd##SFX##_out_len(const phast_planner_convnd##SFX *p) try {                                \
+        return p ? p->out_pts : 0;                                                                                      \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_convnd##SFX##_out_dims(const phast_planner_convnd##SFX *p, size_t *dims, size_t rank) try {       \
+        if (!p || !dims || rank != p->rank) return PHAST_ERR_INVALID_ARG;                                               \
+        p->out_dims(dims);                                                                                              \
+        return PHAST_OK;                                                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_planner_convnd##SFX##_block(const phast_planner_convnd##SFX *p, size_t *dims, size_t rank) try {          \
+        if (!p || !dims || rank != p->rank) return PHAST_ERR_INVALID_ARG;                                               \
+        p->block(dims);                                                                                                 \
+        return PHAST_OK;                                                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_convnd##SFX##_tiles(const phast_planner_convnd##SFX *p) try {                                  \
+        return p ? p->tiles : 0;                                                                                        \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_convnd##SFX##_workspace_min(const phast_planner_convnd##SFX *p) try {                          \
+        return p ? p->workspace_min() : 0;                                                                              \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_convnd##SFX##_time_stages(const phast_planner_convnd##SFX *p, const T *d_signal, T *d_out,        \
+                                                size_t batch, T *d_work, size_t work_len, int reps, float *stage_ms,    \
+                                                void *stream) try {                                                     \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(d_signal, d_out, batch, d_work, work_len, reps, stage_ms,                                 \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_convnd_##FS##_with_planner(const T *signal, size_t signal_len, T *out, size_t out_len,                    \
+                                         const phast_planner_convnd##SFX *p) try {                                      \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(signal, signal_len, out, out_len);                                                               \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_convnd_##FS##_dev(const T *d_signal, T *d_out, size_t signal_len, size_t batch, size_t sig_dist,          \
+                                size_t out_dist, const phast_planner_convnd##SFX *p, T *d_work, size_t work_len,        \
+                                void *stream) try {                                                                     \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(d_signal, d_out, signal_len, batch, sig_dist, out_dist, d_work, work_len,                         \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC
+PHAST_CONVND_API(64, f64, double)
+PHAST_CONVND_API(32, f32, float)
 
 // The chirp-Z transform on the unit circle (planner_czt.hpp): the lengths and the two doubles are checked before the device
 // is touched; the one-shot form builds a planner of its own for the call

@@ -3,6 +3,7 @@
 //! does upstream (benches/bit_reversal.rs:3).
 pub mod bravo;
 pub mod conv;
+pub mod convnd;
 pub mod czt;
 pub mod dit;
 pub mod nufft;

@@ -188,6 +188,41 @@ extern "C" {
         planner: *const Opaque) -> c_int;
     pub(crate) fn phast_conv_f32_dev(signal: *const f32, out: *mut f32, signal_len: usize, batch: usize, sig_dist: usize,
         out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // overlap-save convolution and correlation of arrays of rank 1 .. 3 (an extension: planner.rs / algorithms/convnd.rs)
+    pub(crate) fn phast_planner_convnd64_new(signal_dims: *const usize, tap_dims: *const usize, rank: usize, taps: *const f64,
+        mode: c_int, flip: c_int, block: *const usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_convnd64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_convnd64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_convnd64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_convnd64_out_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_convnd64_out_dims(p: *const Opaque, dims: *mut usize, rank: usize) -> c_int;
+    pub(crate) fn phast_planner_convnd64_block(p: *const Opaque, dims: *mut usize, rank: usize) -> c_int;
+    pub(crate) fn phast_planner_convnd64_tiles(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_convnd64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_convnd64_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_convnd64_time_stages(p: *const Opaque, signal: *const f64, out: *mut f64, batch: usize,
+        work: *mut f64, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_convnd_f64_with_planner(signal: *const f64, signal_len: usize, out: *mut f64, out_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_convnd_f64_dev(signal: *const f64, out: *mut f64, signal_len: usize, batch: usize, sig_dist: usize,
+        out_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_convnd32_new(signal_dims: *const usize, tap_dims: *const usize, rank: usize, taps: *const f32,
+        mode: c_int, flip: c_int, block: *const usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_convnd32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_convnd32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_convnd32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_convnd32_out_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_convnd32_out_dims(p: *const Opaque, dims: *mut usize, rank: usize) -> c_int;
+    pub(crate) fn phast_planner_convnd32_block(p: *const Opaque, dims: *mut usize, rank: usize) -> c_int;
+    pub(crate) fn phast_planner_convnd32_tiles(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_convnd32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_convnd32_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_convnd32_time_stages(p: *const Opaque, signal: *const f32, out: *mut f32, batch: usize,
+        work: *mut f32, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_convnd_f32_with_planner(signal: *const f32, signal_len: usize, out: *mut f32, out_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_convnd_f32_dev(signal: *const f32, out: *mut f32, signal_len: usize, batch: usize, sig_dist: usize,
+        out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // the chirp-Z transform on the unit circle (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/czt.rs)
     pub(crate) fn phast_planner_czt64_new(n: usize, m: usize, step: f64, start: f64, out: *mut *mut Opaque) -> c_int;
     pub(crate) fn phast_planner_czt64_free(p: *mut Opaque);

@@ -58,6 +58,9 @@ pub use planner::{PadMode, PlannerStft32, PlannerStft64};
 // overlap-save convolution and correlation of real signals (an extension beyond PhastFT 0.3.0)
 pub use algorithms::conv::{conv_f32_dev, conv_f32_with_planner, conv_f64_dev, conv_f64_with_planner};
 pub use planner::{ConvMode, PlannerConv32, PlannerConv64};
+// ... and of real arrays of rank 1 .. 3, by overlap-save along every axis
+pub use algorithms::convnd::{convnd_f32_dev, convnd_f32_with_planner, convnd_f64_dev, convnd_f64_with_planner};
+pub use planner::{PlannerConvNd32, PlannerConvNd64};
 // the chirp-Z transform on the unit circle and the zoom FFT (an extension beyond PhastFT 0.3.0)
 pub use algorithms::czt::{czt_32, czt_32_dev, czt_32_with_planner, czt_64, czt_64_dev, czt_64_with_planner};
 pub use planner::{PlannerCzt32, PlannerCzt64};

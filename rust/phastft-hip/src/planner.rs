@@ -376,6 +376,81 @@ impl_planner_conv!(PlannerConv32, f32, phast_planner_conv32_new, phast_planner_c
                    phast_planner_conv32_block, phast_planner_conv32_segments, phast_planner_conv32_workspace_len,
                    phast_planner_conv32_workspace_min);
 
+macro_rules! impl_planner_convnd {
+    ($conv:ident, $t:ty, $new:ident, $free:ident, $out_len:ident, $out_dims:ident, $block:ident, $tiles:ident, $ws_len:ident,
+     $ws_min:ident) => {
+        /// An extension beyond PhastFT 0.3.0: convolution (`correlate`: cross-correlation) of real row-major arrays of rank
+        /// 1 .. 3 with the planner's taps of the same rank, by overlap-save along every axis (scipy.signal.convolve /
+        /// correlate with method = "direct"): one N-d R2C, one spectrum multiply and one N-d C2R per tile of `block` points
+        /// per axis.  Immutable after `new`, like the reference's planners.
+        pub struct $conv {
+            pub(crate) h: *mut Opaque,
+            pub(crate) signal_len: usize,
+            rank: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in
+        // device buffers of its own (host-slice calls)
+        unsafe impl Send for $conv {}
+        unsafe impl Sync for $conv {}
+        impl $conv {
+            /// `taps`: row-major, `taps_shape` of the rank of `signal_shape`; `block`: `None`, or one entry per axis (0 picks
+            /// that axis' block from the taps).  Panics with "invalid argument" unless the rank is 1 .. 3, every extent is
+            /// 1 ..= 2^29, `signal_shape[i] >= taps_shape[i]` with `ConvMode::Valid`, `taps_shape[i] <= block[i] <= 2^29`, the
+            /// array and the output hold at most 2^30 points and a tile at most 2^28
+            pub fn new(signal_shape: &[usize], taps_shape: &[usize], taps: &[$t], mode: ConvMode, correlate: bool,
+                       block: Option<&[usize]>) -> Self {
+                let rank = signal_shape.len();
+                assert!(taps_shape.len() == rank && block.map_or(true, |b| b.len() == rank), "invalid argument");
+                assert!(taps.len() == taps_shape.iter().product::<usize>(), "invalid argument");
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe {
+                    ffi::$new(signal_shape.as_ptr(), taps_shape.as_ptr(), rank, taps.as_ptr(), mode as c_int, correlate as c_int,
+                              block.map_or(std::ptr::null(), |b| b.as_ptr()), &mut h)
+                });
+                Self { h, signal_len: signal_shape.iter().product(), rank }
+            }
+            pub fn signal_len(&self) -> usize {
+                self.signal_len
+            }
+            pub fn out_len(&self) -> usize {
+                unsafe { ffi::$out_len(self.h) }
+            }
+            pub fn out_shape(&self) -> Vec<usize> {
+                let mut d = vec![0usize; self.rank];
+                ffi::check(unsafe { ffi::$out_dims(self.h, d.as_mut_ptr(), self.rank) });
+                d
+            }
+            pub fn block(&self) -> Vec<usize> {
+                let mut d = vec![0usize; self.rank];
+                ffi::check(unsafe { ffi::$block(self.h, d.as_mut_ptr(), self.rank) });
+                d
+            }
+            pub fn tiles(&self) -> usize {
+                unsafe { ffi::$tiles(self.h) }
+            }
+            /// elements of the workspace a device call of `batch` arrays works in
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+            /// the least workspace a call runs in: one tile
+            pub fn workspace_min(&self) -> usize {
+                unsafe { ffi::$ws_min(self.h) }
+            }
+        }
+        impl Drop for $conv {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_convnd!(PlannerConvNd64, f64, phast_planner_convnd64_new, phast_planner_convnd64_free, phast_planner_convnd64_out_len,
+                     phast_planner_convnd64_out_dims, phast_planner_convnd64_block, phast_planner_convnd64_tiles,
+                     phast_planner_convnd64_workspace_len, phast_planner_convnd64_workspace_min);
+impl_planner_convnd!(PlannerConvNd32, f32, phast_planner_convnd32_new, phast_planner_convnd32_free, phast_planner_convnd32_out_len,
+                     phast_planner_convnd32_out_dims, phast_planner_convnd32_block, phast_planner_convnd32_tiles,
+                     phast_planner_convnd32_workspace_len, phast_planner_convnd32_workspace_min);
+
 macro_rules! impl_planner_czt {
     ($czt:ident, $new:ident, $free:ident, $conv_len:ident, $ws_len:ident) => {
         /// An extension beyond PhastFT 0.3.0, whose planners give whole spectra: the chirp-Z transform on the unit circle
