@@ -14,9 +14,6 @@
 
 namespace phast {
 
-template <typename T> struct NufftReal { typedef double type; };
-template <> struct NufftReal<float> { typedef float type; };
-
 // g[b n_g + l] = sum_j phi(2 (l - n_g x_j) / w) c[b in_dist + j] over the points of the cells l - h .. l + h - 1 (mod n_g),
 // h = ceil(w / 2), in cell order and sorted order.  REAL: no imaginary plane
 template <typename T, bool REAL>
@@ -28,7 +25,7 @@ __global__ void __launch_bounds__(256) nufft_spread_kernel(NufftArgs a) {
     const unsigned long long b = g >> a.log_g, l = g & mask;
     const T *cr = (const T *)a.in_re + b * a.in_dist;
     const T *ci = REAL ? nullptr : (const T *)a.in_im + b * a.in_dist;
-    const long long h = (a.w + 1) / 2, half = (long long)(grid >> 1);
+    const long long h = (a.w + 1) / 2;
     const double dgrid = (double)grid, two_over_w = 2.0 / a.w;
     const R beta = (R)nufft_beta(a.w);
     const unsigned long long lo = (l - (unsigned long long)h) & mask;  // the first cell; 2h <= n_g cells from there
@@ -41,9 +38,7 @@ __global__ void __launch_bounds__(256) nufft_spread_kernel(NufftArgs a) {
         for (uint32_t i = i0; i < i1; ++i) {
             double t;
             const long long q = nufft_cell(a.xs[i], dgrid, &t);
-            // l - q in [-n_g / 2, n_g / 2): the signed distance of the two cells around the ring
-            const long long dq = (long long)(((unsigned long long)((long long)l - q + half)) & mask) - half;
-            const R k = nufft_weight<R>(dq, t, two_over_w, beta);
+            const R k = nufft_weight<R>(nufft_ring(l, q, mask), t, two_over_w, beta);
             const uint32_t j = a.perm[i];
             sr += k * (R)cr[j];
             if (!REAL) si += k * (R)ci[j];

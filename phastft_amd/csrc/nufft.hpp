@@ -224,5 +224,15 @@ struct NufftArgs {
 // the caller's planes AND the workspace allow 16-byte accesses)
 template <typename T> hipError_t launch_nufft(int kind, bool vec, const NufftArgs &a, hipStream_t stream);
 
+// the type the kernel values and the sums of spread and interpolate are formed in
+template <typename T> struct NufftReal { typedef double type; };
+template <> struct NufftReal<float> { typedef float type; };
+
+// the signed distance l - q of two cells around a ring of mask + 1 cells, in [-(mask + 1) / 2, (mask + 1) / 2)
+__device__ inline long long nufft_ring(unsigned long long l, long long q, unsigned long long mask) {
+    const long long half = (long long)((mask + 1) >> 1);
+    return (long long)(((unsigned long long)((long long)l - q + half)) & mask) - half;
+}
+
 }  // namespace phast
 #endif

@@ -1,6 +1,6 @@
-// nufft_sort.hpp -- the point tables of the non-uniform FFT planners (nufft.hpp, nufft2d.hpp, nufft3d.hpp) built on the device from
-// coordinates in device memory: the same perm, cell_start and sorted positions as nufft_bin, nufft2d_bin and
-// nufft3d_bin give on the host, bit for bit.  Three stages, shared by one, two and three dimensions and by f64 and f32 (the points
+// nufft_sort.hpp -- the point tables of the non-uniform FFT planners (nufft.hpp, nufft_nd.hpp) built on the device from
+// coordinates in device memory: the same perm, cell_start and sorted positions as nufft_bin and
+// nufft_nd_bin give on the host, bit for bit.  Three stages, shared by one, two and three dimensions and by f64 and f32 (the points
 // are doubles in both):
 //
 //     keys     one thread per point: the combined cell (((q1 << log_g2) | q2) << log_g3) | q3, q_i the top log_g_i bits of

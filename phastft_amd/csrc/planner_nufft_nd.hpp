@@ -1,73 +1,22 @@
-// planner_nufft_nd.hpp -- NufftNdPlanner<T, D>: non-uniform FFTs of types 1 and 2 in D = 2 or 3 dimensions (nufft2d.hpp,
-// nufft3d.hpp) of M points and N1 x .. x ND modes on an owned NdPlanner<T> of dims (g1, .., gD).  Immutable after init but for
-// set_points_dev: the Nd planner, the point set sorted by grid cell (positions, permutation, cell starts) and the N1 + .. + ND
+// planner_nufft_nd.hpp -- NufftNdPlanner<T, D>: non-uniform FFTs of types 1 and 2 in D = 2 or 3 dimensions (nufft_nd.hpp) of
+// M points and N1 x .. x ND modes on an owned NdPlanner<T> of dims (g1, .., gD).  Immutable after init but for set_points_dev: the Nd planner, the point set sorted by grid cell (positions, permutation, cell starts) and the N1 + .. + ND
 // reciprocals 1 / phi^(k) on the device.  What a call mutates is the caller's workspace (_dev calls) or a device buffer of the
 // call's own (host-slice calls), so graph capture and concurrent streams and threads need nothing beyond what the Nd planner
-// already does.  The kernels differ by rank; NufftRank<D> below is all that the planner knows of that.
+// already does.  The checks, the binning, the kernels' arguments and their launcher are generic in D too.
 //
 // Workspace (elements of T) of a chunk of c transforms: c re grids, c im grids, then what the Nd planner asks for c arrays of
 // (g1, .., gD) (its transposed copies, 2 c G: every axis is a power of two, so there is no Bluestein part): per() = 4 G per
 // transform, G = g1 .. gD, read from the Nd planner and not assumed.
 #pragma once
 
-#include "nufft2d.hpp"
-#include "nufft3d.hpp"
+#include "nufft_nd.hpp"
 #include "planner_nd.hpp"
 #include "planner_nufft_common.hpp"
 
 namespace phast {
 
-// What depends on the rank: the kernels' argument struct and launcher, the host's binning and the argument checks.  n, x, lg,
-// xs, inv: D entries each, axis 1 first
-template <size_t D> struct NufftRank;
-template <> struct NufftRank<2> {
-    using Args = Nufft2dArgs;
-    static constexpr const char *name = "nufft2d";
-    static bool bad_sizes(const size_t *n, const double *const *x, size_t m, double eps, bool f32) {
-        return nufft2d_bad_sizes(n[0], n[1], m, x[0], x[1], eps, f32);
-    }
-    static bool bad_args(const size_t *n, const double *const *x, size_t m, double eps, bool f32) {
-        return nufft2d_bad_args(n[0], n[1], m, x[0], x[1], eps, f32);
-    }
-    static void bin(const double *const *x, size_t m, const unsigned *lg, double *const *xs, uint32_t *perm, uint32_t *cell) {
-        nufft2d_bin(x[0], x[1], m, lg[0], lg[1], xs[0], xs[1], perm, cell);
-    }
-    static void axes(Args &a, const size_t *n, const unsigned *lg, double *const *xs, const void *const *inv) {
-        a.xs = xs[0], a.ys = xs[1];
-        a.inv1 = inv[0], a.inv2 = inv[1];
-        a.n1 = n[0], a.n2 = n[1];
-        a.log_g1 = lg[0], a.log_g2 = lg[1];
-    }
-    template <typename T> static hipError_t launch(int kind, bool vec, const Args &a, hipStream_t s) {
-        return launch_nufft2d<T>(kind, vec, a, s);
-    }
-};
-template <> struct NufftRank<3> {
-    using Args = Nufft3dArgs;
-    static constexpr const char *name = "nufft3d";
-    static bool bad_sizes(const size_t *n, const double *const *x, size_t m, double eps, bool f32) {
-        return nufft3d_bad_sizes(n[0], n[1], n[2], m, x[0], x[1], x[2], eps, f32);
-    }
-    static bool bad_args(const size_t *n, const double *const *x, size_t m, double eps, bool f32) {
-        return nufft3d_bad_args(n[0], n[1], n[2], m, x[0], x[1], x[2], eps, f32);
-    }
-    static void bin(const double *const *x, size_t m, const unsigned *lg, double *const *xs, uint32_t *perm, uint32_t *cell) {
-        nufft3d_bin(x[0], x[1], x[2], m, lg[0], lg[1], lg[2], xs[0], xs[1], xs[2], perm, cell);
-    }
-    static void axes(Args &a, const size_t *n, const unsigned *lg, double *const *xs, const void *const *inv) {
-        a.xs = xs[0], a.ys = xs[1], a.zs = xs[2];
-        a.inv1 = inv[0], a.inv2 = inv[1], a.inv3 = inv[2];
-        a.n1 = n[0], a.n2 = n[1], a.n3 = n[2];
-        a.log_g1 = lg[0], a.log_g2 = lg[1], a.log_g3 = lg[2];
-    }
-    template <typename T> static hipError_t launch(int kind, bool vec, const Args &a, hipStream_t s) {
-        return launch_nufft3d<T>(kind, vec, a, s);
-    }
-};
-
 template <typename T, size_t D> struct NufftNdPlanner {
     static_assert(D == 2 || D == 3, "the kernels exist for two and three dimensions");
-    using Rank = NufftRank<D>;
     size_t n[D] = {}, g[D] = {};  // the modes N_i and the fine grid g_i
     size_t cells = 0, points = 0;  // G = g1 .. gD, M
     unsigned log_g[D] = {};
@@ -121,7 +70,7 @@ template <typename T, size_t D> struct NufftNdPlanner {
         return PHAST_OK;
     }
 
-    // `x`: per axis M host doubles in turns; the arguments were checked by Rank::bad_args
+    // `x`: per axis M host doubles in turns; the arguments were checked by nufft_nd_bad_args
     int init(const size_t (&n_)[D], const double *const (&x)[D], size_t m_points, double eps_) {
         int rc = init_grid(n_, m_points, eps_);
         if (rc) return rc;
@@ -132,7 +81,7 @@ template <typename T, size_t D> struct NufftNdPlanner {
             xp[i] = xs[i].data();
         }
         std::vector<uint32_t> perm(points), cell(cells + 1);
-        Rank::bin(x, points, log_g, xp, perm.data(), cell.data());
+        nufft_nd_bin<D>(x, points, log_g, xp, perm.data(), cell.data());
         PHAST_ON_DEVICE(device);
         for (size_t i = 0; i < D; ++i) PHAST_HIP(hipMemcpy(d_coord[i], xp[i], points * sizeof(double), hipMemcpyHostToDevice));
         PHAST_HIP(hipMemcpy(d_perm, perm.data(), points * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -147,7 +96,7 @@ template <typename T, size_t D> struct NufftNdPlanner {
     }
 
     // as init, with the points in device memory, ordered after the earlier work of `s`; blocks.  The arguments but the points'
-    // values were checked by Rank::bad_sizes; PHAST_ERR_INVALID_ARG for a coordinate that is not finite
+    // values were checked by nufft_nd_bad_sizes; PHAST_ERR_INVALID_ARG for a coordinate that is not finite
     int init_dev(const size_t (&n_)[D], const double *const (&d_x)[D], size_t m_points, double eps_, hipStream_t s) {
         int rc = init_grid(n_, m_points, eps_);
         if (rc) return rc;
@@ -190,7 +139,7 @@ template <typename T, size_t D> struct NufftNdPlanner {
             for (size_t i = 1; i < D; ++i) s += "x" + std::to_string(v[i]);
             return s;
         };
-        return std::string(Rank::name) + " N=" + by(n) + " M=" + std::to_string(points) + f + " grid=" + by(g) + ": " + nd.describe();
+        return "nufft" + std::to_string(D) + "d N=" + by(n) + " M=" + std::to_string(points) + f + " grid=" + by(g) + ": " + nd.describe();
     }
     size_t in_len(int type) const { return type == 1 ? points : modes(); }
     size_t out_len(int type) const { return type == 1 ? modes() : points; }
@@ -205,10 +154,13 @@ template <typename T, size_t D> struct NufftNdPlanner {
         // 16-byte accesses: aligned planes and workspace, and the transforms' planes a multiple of the group apart (one
         // transform has no distance to meet)
         auto vec = [&](const T *re, const T *im, size_t dist) { return al(re) && al(im) && al(wk) && (c == 1 || dist % V == 0); };
-        typename Rank::Args a{};
-        const void *inv[D];
-        for (size_t i = 0; i < D; ++i) inv[i] = d_inv[i];
-        Rank::axes(a, n, log_g, d_coord, inv);
+        NufftNdArgs<D> a{};
+        for (size_t i = 0; i < D; ++i) {
+            a.xs[i] = d_coord[i];
+            a.inv[i] = d_inv[i];
+            a.n[i] = n[i];
+            a.log_g[i] = log_g[i];
+        }
         a.perm = d_perm;
         a.cell_start = d_cell;
         a.in_dist = in_dist;
@@ -222,10 +174,10 @@ template <typename T, size_t D> struct NufftNdPlanner {
         a.out_im = w_im;
         if (type == 1) {
             a.groups = c * cells;
-            PHAST_HIP(Rank::template launch<T>(0, false, a, s));
+            PHAST_HIP((launch_nufft_nd<T, D>(0, false, a, s)));
         } else {
             a.groups = c * (cells / V);
-            PHAST_HIP(Rank::template launch<T>(2, vec(x_re, x_im, in_dist), a, s));
+            PHAST_HIP((launch_nufft_nd<T, D>(2, vec(x_re, x_im, in_dist), a, s)));
         }
         if (ev) PHAST_HIP(hipEventRecord(ev[1], s));
         // always the Forward transform (Reverse of the Nd planner scales by 1 / G).  Reverse by the swap trick: the FFT of
@@ -241,10 +193,10 @@ template <typename T, size_t D> struct NufftNdPlanner {
         if (type == 1) {
             a.gpt = (unsigned)(modes() / n[D - 1] * ((n[D - 1] + V - 1) / V));  // sweeps along the last axis
             a.groups = c * a.gpt;
-            PHAST_HIP(Rank::template launch<T>(3, vec(o_re, o_im, out_dist), a, s));
+            PHAST_HIP((launch_nufft_nd<T, D>(3, vec(o_re, o_im, out_dist), a, s)));
         } else {
             a.groups = c * points;
-            PHAST_HIP(Rank::template launch<T>(1, false, a, s));
+            PHAST_HIP((launch_nufft_nd<T, D>(1, false, a, s)));
         }
         if (ev) PHAST_HIP(hipEventRecord(ev[3], s));
         return PHAST_OK;
@@ -346,12 +298,12 @@ template <typename T, size_t D> struct NufftNdPlanner {
 // P over NufftNdPlanner<T, D> from host points (n: the mode counts, x: a pointer per coordinate); D comes from the two lists
 template <typename P, size_t D>
 static int nufft_nd_planner_new(const size_t (&n)[D], const double *const (&x)[D], size_t m_points, double eps, bool f32, P **out) {
-    return nufft_planner_make(out, [&] { return NufftRank<D>::bad_args(n, x, m_points, eps, f32); }, n, x, m_points, eps);
+    return nufft_planner_make(out, [&] { return nufft_nd_bad_args<D>(n, x, m_points, eps, f32); }, n, x, m_points, eps);
 }
 template <typename P, size_t D>
 static int nufft_nd_planner_new_dev(const size_t (&n)[D], const double *const (&d_x)[D], size_t m_points, double eps, bool f32,
                                     hipStream_t s, P **out) {
-    return nufft_planner_make_dev(out, [&] { return NufftRank<D>::bad_sizes(n, d_x, m_points, eps, f32); }, s, n, d_x, m_points, eps);
+    return nufft_planner_make_dev(out, [&] { return nufft_nd_bad_sizes<D>(n, d_x, m_points, eps, f32); }, s, n, d_x, m_points, eps);
 }
 
 }  // namespace phast

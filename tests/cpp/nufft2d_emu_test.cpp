@@ -1,8 +1,10 @@
-// nufft2d_emu_test.cpp -- the four kernels of the two-dimensional non-uniform FFT (csrc/nufft2d.hip), run on the host under
-// AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_nufft2d_emulator.py builds and runs it; tests/emu/sweep_shim.hpp
-// turns a launch into a serial loop).  One translation unit with its own main, linked without the HIP runtime.  nufft2d.hip is
-// #included as it stands and every kernel is driven through launch_nufft2d with arguments built as planner_nufft2d.hpp builds
-// them, from tables made by nufft2d.hpp's own nufft2d_bin.
+// nufft2d_emu_test.cpp -- the four kernels of the two-dimensional non-uniform FFT (csrc/nufft_nd.hip at D = 2), run on the host
+// under AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_nufft2d_emulator.py builds and runs it).  The unit also holds
+// the tiled spread of three dimensions (__shared__, __syncthreads), so the program stands on tests/emu/block_shim.hpp, where a
+// workgroup's threads are fibers, and every case runs in BOTH thread orders, ascending and descending.  One translation unit with
+// its own main, linked without the HIP runtime.  nufft_nd.hip is #included as it stands and every kernel is driven through
+// launch_nufft_nd<T, 2> with arguments built as planner_nufft_nd.hpp builds them, from tables made by nufft_nd.hpp's own
+// nufft_nd_bin.
 //
 // Buffers: every plane, table and workspace is a heap allocation of exactly the bytes the contract covers; an "unaligned"
 // buffer is one element longer and used from element 1.  Workspaces written by a kernel start as NaN, caller outputs as a
@@ -20,9 +22,17 @@
 // the edge may fall on either side: it is allowed e^{-beta} (1 + beta) |value| more.
 #include <hip/hip_runtime.h>
 
-#include "sweep_shim.hpp"
+#include "block_shim.hpp"
 
-#include "nufft2d.hip"
+#include <cmath>
+// any_len.hpp's chirp() (on nufft_nd.hip's include path, never called by its kernels) names the device's sincospi: a host
+// overload so that the header compiles here
+inline void sincospi(double t, double *s, double *c) {
+    *s = std::sin(3.141592653589793238462643383279502884 * t);
+    *c = std::cos(3.141592653589793238462643383279502884 * t);
+}
+
+#include "nufft_nd.hip"
 
 #include <cstdarg>
 #include <cstdio>
@@ -54,7 +64,7 @@ template <> struct Fp<float> {
 int g_fails = 0;
 unsigned long long g_compared = 0;
 double g_worst[4] = {0, 0, 0, 0};
-const char *const kKernel[4] = {"nufft2d_spread_kernel", "nufft2d_interp_kernel", "nufft2d_pre_kernel", "nufft2d_deconv_kernel"};
+const char *const kKernel[4] = {"nufft_nd_spread_kernel", "nufft_nd_interp_kernel", "nufft_nd_pre_kernel", "nufft_nd_deconv_kernel"};
 char g_case[256] = "";
 
 void fail(int kind, const char *fmt, ...) {
@@ -128,7 +138,10 @@ struct Tables {
         while (((size_t)1 << log_g1) < g1) ++log_g1;
         while (((size_t)1 << log_g2) < g2) ++log_g2;
         const std::vector<double> x = make_coordinate(m, g1, 0), y = make_coordinate(m, g2, 1);
-        nufft2d_bin(x.data(), y.data(), m, log_g1, log_g2, xs.p, ys.p, perm.p, cell.p);
+        const double *const in[2] = {x.data(), y.data()};
+        const unsigned log_g[2] = {log_g1, log_g2};
+        double *const sorted[2] = {xs.p, ys.p};
+        nufft_nd_bin<2>(in, m, log_g, sorted, perm.p, cell.p);
     }
 };
 
@@ -149,19 +162,21 @@ template <typename T> void compare(int kind, const char *what, size_t idx, const
     if (!(err <= gate)) fail(kind, "%s[%zu] = %.17Lg, want %.17Lg: error %.3Lg > gate %.3Lg", what, idx, (ld)*got, want, err, gate);
 }
 
-template <typename T> Nufft2dArgs args_of(const Tables &t, const T *inv1, const T *inv2) {
-    Nufft2dArgs a{};
-    a.xs = t.xs.p;
-    a.ys = t.ys.p;
+template <typename T> NufftNdArgs<2> args_of(const Tables &t, const T *inv1, const T *inv2) {
+    NufftNdArgs<2> a{};
+    const double *const xs[2] = {t.xs.p, t.ys.p};
+    const T *const inv[2] = {inv1, inv2};
+    const size_t n[2] = {t.n1, t.n2};
+    const unsigned log_g[2] = {t.log_g1, t.log_g2};
+    for (size_t i = 0; i < 2; ++i) {
+        a.xs[i] = xs[i];
+        a.inv[i] = inv[i];
+        a.n[i] = n[i];
+        a.log_g[i] = log_g[i];
+    }
     a.perm = t.perm.p;
     a.cell_start = t.cell.p;
-    a.inv1 = inv1;
-    a.inv2 = inv2;
-    a.n1 = t.n1;
-    a.n2 = t.n2;
     a.m = t.m;
-    a.log_g1 = t.log_g1;
-    a.log_g2 = t.log_g2;
     a.w = t.w;
     return a;
 }
@@ -200,8 +215,8 @@ template <typename T> void run_case(const Tables &t, const Weights &w1, const We
     Buf<T> inv1(t.n1), inv2(t.n2);
     for (size_t i = 0; i < t.n1; ++i) inv1[i] = (T)(1.5L + 0.5L * rnd(3, i));
     for (size_t i = 0; i < t.n2; ++i) inv2[i] = (T)(1.25L + 0.25L * rnd(4, i));
-    std::snprintf(g_case, sizeof g_case, "%s N=%zux%zu M=%zu w=%d grid=%zux%zu batch=%zu dist %zu/%zu planes+%zu work+%zu%s", Fp<T>::name(),
-                  t.n1, t.n2, m, t.w, t.g1, g2, batch, pd, fd, plane_off, wk_off, real ? " real" : "");
+    std::snprintf(g_case, sizeof g_case, "%s %s N=%zux%zu M=%zu w=%d grid=%zux%zu batch=%zu dist %zu/%zu planes+%zu work+%zu%s", Fp<T>::name(),
+                  block_shim::order == block_shim::kAscending ? "ascending" : "descending", t.n1, t.n2, m, t.w, t.g1, g2, batch, pd, fd, plane_off, wk_off, real ? " real" : "");
     // the pairs (l1, l2, i) of the support, grouped by point: per point the axis-1 and axis-2 terms
     std::vector<std::vector<const Weights::Term *>> by1(m), by2(m);
     for (const auto &a : w1.terms) by1[a.i].push_back(&a);
@@ -212,14 +227,14 @@ template <typename T> void run_case(const Tables &t, const Weights &w1, const We
         fill_random(cr, 11);
         fill_random(ci, 12);
         fill_sentinel(wk);
-        Nufft2dArgs a = args_of<T>(t, inv1.p, inv2.p);
+        NufftNdArgs<2> a = args_of<T>(t, inv1.p, inv2.p);
         a.in_re = cr.p;
         a.in_im = real ? nullptr : ci.p;
         a.out_re = wk.p;
         a.out_im = wk.p + batch * G;
         a.in_dist = pd;
         a.groups = batch * G;
-        if (launch_nufft2d<T>(0, false, a, nullptr) != hipSuccess) fail(0, "the launcher failed");
+        if (launch_nufft_nd<T, 2>(0, false, a, nullptr) != hipSuccess) fail(0, "the launcher failed");
         for (size_t b = 0; b < batch; ++b) {
             std::vector<ld> sr(G, 0), si(G, 0), gr(G, 0), gi(G, 0);
             std::vector<size_t> terms(G, 0);
@@ -248,14 +263,14 @@ template <typename T> void run_case(const Tables &t, const Weights &w1, const We
         fill_random(wk, 21);
         fill_sentinel(orr);
         fill_sentinel(oi);
-        Nufft2dArgs a = args_of<T>(t, inv1.p, inv2.p);
+        NufftNdArgs<2> a = args_of<T>(t, inv1.p, inv2.p);
         a.in_re = wk.p;
         a.in_im = wk.p + batch * G;
         a.out_re = orr.p;
         a.out_im = oi.p;
         a.out_dist = pd;
         a.groups = batch * m;
-        if (launch_nufft2d<T>(1, false, a, nullptr) != hipSuccess) fail(1, "the launcher failed");
+        if (launch_nufft_nd<T, 2>(1, false, a, nullptr) != hipSuccess) fail(1, "the launcher failed");
         std::vector<char> named(orr.n, 0);
         for (size_t b = 0; b < batch; ++b)
             for (size_t i = 0; i < m; ++i) {
@@ -286,7 +301,7 @@ template <typename T> void run_case(const Tables &t, const Weights &w1, const We
         fill_random(fr, 31);
         fill_random(fi, 32);
         fill_sentinel(wk);
-        Nufft2dArgs a = args_of<T>(t, inv1.p, inv2.p);
+        NufftNdArgs<2> a = args_of<T>(t, inv1.p, inv2.p);
         a.in_re = fr.p;
         a.in_im = real ? nullptr : fi.p;
         a.out_re = wk.p;
@@ -294,7 +309,7 @@ template <typename T> void run_case(const Tables &t, const Weights &w1, const We
         a.in_dist = fd;
         a.groups = batch * (G / V);
         const bool vec = al(fr.p) && (real || al(fi.p)) && al(wk.p) && fd % V == 0;
-        if (launch_nufft2d<T>(2, vec, a, nullptr) != hipSuccess) fail(2, "the launcher failed");
+        if (launch_nufft_nd<T, 2>(2, vec, a, nullptr) != hipSuccess) fail(2, "the launcher failed");
         for (size_t b = 0; b < batch; ++b) {
             std::vector<char> named(G, 0);
             for (size_t i1 = 0; i1 < t.n1; ++i1)
@@ -320,7 +335,7 @@ template <typename T> void run_case(const Tables &t, const Weights &w1, const We
         fill_random(wk, 41);
         fill_sentinel(orr);
         fill_sentinel(oi);
-        Nufft2dArgs a = args_of<T>(t, inv1.p, inv2.p);
+        NufftNdArgs<2> a = args_of<T>(t, inv1.p, inv2.p);
         a.in_re = wk.p;
         a.in_im = wk.p + batch * G;
         a.out_re = orr.p;
@@ -329,7 +344,7 @@ template <typename T> void run_case(const Tables &t, const Weights &w1, const We
         a.gpt = (unsigned)(t.n1 * ((t.n2 + V - 1) / V));
         a.groups = batch * a.gpt;
         const bool vec = al(orr.p) && al(oi.p) && al(wk.p) && fd % V == 0;
-        if (launch_nufft2d<T>(3, vec, a, nullptr) != hipSuccess) fail(3, "the launcher failed");
+        if (launch_nufft_nd<T, 2>(3, vec, a, nullptr) != hipSuccess) fail(3, "the launcher failed");
         for (size_t b = 0; b < batch; ++b)
             for (size_t i1 = 0; i1 < t.n1; ++i1)
                 for (size_t i2 = 0; i2 < t.n2; ++i2) {
@@ -350,17 +365,21 @@ template <typename T> void run_all() {
     for (const auto &s : shapes) {
         const Tables t(s[0], s[1], s[2], (int)s[3]);
         const Weights w1(t.xs.p, t.m, t.g1, t.w, Fp<T>::u), w2(t.ys.p, t.m, t.g2, t.w, Fp<T>::u);
-        for (size_t batch : {(size_t)1, (size_t)3}) {
-            run_case<T>(t, w1, w2, batch, 0, 0, false);
-            run_case<T>(t, w1, w2, batch, 1, 0, false);  // caller planes at element alignment (buf[1:])
-            run_case<T>(t, w1, w2, batch, 0, 1, false);  // the workspace at element alignment
-            run_case<T>(t, w1, w2, batch, 0, 0, true);   // no imaginary input plane
-            run_case<T>(t, w1, w2, batch, 1, 0, true);
-            if (batch > 1) {  // distances that are multiples of the group: the vector variants of the sweeps in a batch
-                run_case<T>(t, w1, w2, batch, 0, 0, false, true);
-                run_case<T>(t, w1, w2, batch, 0, 0, true, true);
+        for (block_shim::Order order : {block_shim::kAscending, block_shim::kDescending}) {
+            block_shim::order = order;
+            for (size_t batch : {(size_t)1, (size_t)3}) {
+                run_case<T>(t, w1, w2, batch, 0, 0, false);
+                run_case<T>(t, w1, w2, batch, 1, 0, false);  // caller planes at element alignment (buf[1:])
+                run_case<T>(t, w1, w2, batch, 0, 1, false);  // the workspace at element alignment
+                run_case<T>(t, w1, w2, batch, 0, 0, true);   // no imaginary input plane
+                run_case<T>(t, w1, w2, batch, 1, 0, true);
+                if (batch > 1) {  // distances that are multiples of the group: the vector variants of the sweeps in a batch
+                    run_case<T>(t, w1, w2, batch, 0, 0, false, true);
+                    run_case<T>(t, w1, w2, batch, 0, 0, true, true);
+                }
             }
         }
+        block_shim::order = block_shim::kAscending;
     }
 }
 
@@ -369,8 +388,8 @@ template <typename T> void run_all() {
 int main() {
     run_all<double>();
     run_all<float>();
-    for (int k = 0; k < 4; ++k) std::printf("  %-22s worst error / gate %.3f\n", kKernel[k], g_worst[k]);
-    std::printf("launches %llu threads %llu elements %llu\n", sweep_shim::launches, sweep_shim::threads_run, g_compared);
+    for (int k = 0; k < 4; ++k) std::printf("  %-23s worst error / gate %.3f\n", kKernel[k], g_worst[k]);
+    std::printf("launches %llu threads %llu elements %llu\n", block_shim::launches, block_shim::threads_run, g_compared);
     std::printf("nufft2d: %s (%d failures)\n", g_fails ? "FAILED" : "ok", g_fails);
     phast_test_exit(g_fails ? 1 : 0);
 }

@@ -1,11 +1,11 @@
-// nufft3d_emu_test.cpp -- the four kernels of the three-dimensional non-uniform FFT (csrc/nufft3d.hip), run on the host under
+// nufft3d_emu_test.cpp -- the four kernels of the three-dimensional non-uniform FFT (csrc/nufft_nd.hip at D = 3), run on the host under
 // AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_nufft3d_emulator.py builds and runs it).  The spread kernel stages
 // points through LDS between barriers, so the program stands on tests/emu/block_shim.hpp: a workgroup's threads are fibers that
 // run from one __syncthreads() to the next in ascending or in descending order, and every case runs in BOTH orders -- a thread
 // that reads LDS another has not yet written, or overwrites LDS another has not yet read, gets wrong bits in one of them.  One
-// translation unit with its own main, linked without the HIP runtime.  nufft3d.hip is #included as it stands and every kernel is
-// driven through launch_nufft3d with arguments built as planner_nufft3d.hpp builds them, from tables made by nufft3d.hpp's own
-// nufft3d_bin.
+// translation unit with its own main, linked without the HIP runtime.  nufft_nd.hip is #included as it stands and every kernel is
+// driven through launch_nufft_nd<T, 3> with arguments built as planner_nufft_nd.hpp builds them, from tables made by
+// nufft_nd.hpp's own nufft_nd_bin.
 //
 // Buffers: every plane, table and workspace is a heap allocation of exactly the bytes the contract covers; an "unaligned"
 // buffer is one element longer and used from element 1.  Workspaces written by a kernel start as NaN, caller outputs as a
@@ -29,14 +29,14 @@
 #include "block_shim.hpp"
 
 #include <cmath>
-// any_len.hpp's chirp() (on nufft3d.hip's include path, never called by its kernels) names the device's sincospi: a host
+// any_len.hpp's chirp() (on nufft_nd.hip's include path, never called by its kernels) names the device's sincospi: a host
 // overload so that the header compiles here
 inline void sincospi(double t, double *s, double *c) {
     *s = std::sin(3.141592653589793238462643383279502884 * t);
     *c = std::cos(3.141592653589793238462643383279502884 * t);
 }
 
-#include "nufft3d.hip"
+#include "nufft_nd.hip"
 
 #include <cstdarg>
 #include <cstdio>
@@ -68,7 +68,7 @@ template <> struct Fp<float> {
 int g_fails = 0;
 unsigned long long g_compared = 0;
 double g_worst[4] = {0, 0, 0, 0};
-const char *const kKernel[4] = {"nufft3d_spread_kernel", "nufft3d_interp_kernel", "nufft3d_pre_kernel", "nufft3d_deconv_kernel"};
+const char *const kKernel[4] = {"nufft_nd_spread_kernel", "nufft_nd_interp_kernel", "nufft_nd_pre_kernel", "nufft_nd_deconv_kernel"};
 char g_case[320] = "";
 
 void fail(int kind, const char *fmt, ...) {
@@ -147,7 +147,9 @@ struct Tables {
             while (((size_t)1 << log_g[i]) < g[i]) ++log_g[i];
         const std::vector<double> x = make_coordinate(m, g[0], 0, clump), y = make_coordinate(m, g[1], 1, clump),
                                   z = make_coordinate(m, g[2], 2, clump);
-        nufft3d_bin(x.data(), y.data(), z.data(), m, log_g[0], log_g[1], log_g[2], xs.p, ys.p, zs.p, perm.p, cell.p);
+        const double *const in[3] = {x.data(), y.data(), z.data()};
+        double *const sorted[3] = {xs.p, ys.p, zs.p};
+        nufft_nd_bin<3>(in, m, log_g, sorted, perm.p, cell.p);
         if (clump) {  // the case is what it says: one cell holds every point
             size_t most = 0;
             for (size_t q = 0; q < cells; ++q) most = std::max<size_t>(most, cell.p[q + 1] - cell.p[q]);
@@ -174,23 +176,19 @@ template <typename T> void compare(int kind, const char *what, size_t idx, const
     if (!(err <= gate)) fail(kind, "%s[%zu] = %.17Lg, want %.17Lg: error %.3Lg > gate %.3Lg", what, idx, (ld)*got, want, err, gate);
 }
 
-template <typename T> Nufft3dArgs args_of(const Tables &t, const T *inv1, const T *inv2, const T *inv3) {
-    Nufft3dArgs a{};
-    a.xs = t.xs.p;
-    a.ys = t.ys.p;
-    a.zs = t.zs.p;
+template <typename T> NufftNdArgs<3> args_of(const Tables &t, const T *inv1, const T *inv2, const T *inv3) {
+    NufftNdArgs<3> a{};
+    const double *const xs[3] = {t.xs.p, t.ys.p, t.zs.p};
+    const T *const inv[3] = {inv1, inv2, inv3};
+    for (size_t i = 0; i < 3; ++i) {
+        a.xs[i] = xs[i];
+        a.inv[i] = inv[i];
+        a.n[i] = t.n[i];
+        a.log_g[i] = t.log_g[i];
+    }
     a.perm = t.perm.p;
     a.cell_start = t.cell.p;
-    a.inv1 = inv1;
-    a.inv2 = inv2;
-    a.inv3 = inv3;
-    a.n1 = t.n[0];
-    a.n2 = t.n[1];
-    a.n3 = t.n[2];
     a.m = t.m;
-    a.log_g1 = t.log_g[0];
-    a.log_g2 = t.log_g[1];
-    a.log_g3 = t.log_g[2];
     a.w = t.w;
     return a;
 }
@@ -243,14 +241,14 @@ void run_case(const Tables &t, const Weights &w1, const Weights &w2, const Weigh
         fill_random(cr, 11);
         fill_random(ci, 12);
         fill_sentinel(wk);
-        Nufft3dArgs a = args_of<T>(t, inv1.p, inv2.p, inv3.p);
+        NufftNdArgs<3> a = args_of<T>(t, inv1.p, inv2.p, inv3.p);
         a.in_re = cr.p;
         a.in_im = real ? nullptr : ci.p;
         a.out_re = wk.p;
         a.out_im = wk.p + batch * G;
         a.in_dist = pd;
         a.groups = batch * G;
-        if (launch_nufft3d<T>(0, false, a, nullptr) != hipSuccess) fail(0, "the launcher failed");
+        if (launch_nufft_nd<T, 3>(0, false, a, nullptr) != hipSuccess) fail(0, "the launcher failed");
         for (size_t b = 0; b < batch; ++b) {
             std::vector<ld> sr(G, 0), si(G, 0), gr(G, 0), gi(G, 0);
             std::vector<size_t> terms(G, 0);
@@ -280,14 +278,14 @@ void run_case(const Tables &t, const Weights &w1, const Weights &w2, const Weigh
         fill_random(wk, 21);
         fill_sentinel(orr);
         fill_sentinel(oi);
-        Nufft3dArgs a = args_of<T>(t, inv1.p, inv2.p, inv3.p);
+        NufftNdArgs<3> a = args_of<T>(t, inv1.p, inv2.p, inv3.p);
         a.in_re = wk.p;
         a.in_im = wk.p + batch * G;
         a.out_re = orr.p;
         a.out_im = oi.p;
         a.out_dist = pd;
         a.groups = batch * m;
-        if (launch_nufft3d<T>(1, false, a, nullptr) != hipSuccess) fail(1, "the launcher failed");
+        if (launch_nufft_nd<T, 3>(1, false, a, nullptr) != hipSuccess) fail(1, "the launcher failed");
         std::vector<char> named(orr.n, 0);
         for (size_t b = 0; b < batch; ++b)
             for (size_t i = 0; i < m; ++i) {
@@ -319,7 +317,7 @@ void run_case(const Tables &t, const Weights &w1, const Weights &w2, const Weigh
         fill_random(fr, 31);
         fill_random(fi, 32);
         fill_sentinel(wk);
-        Nufft3dArgs a = args_of<T>(t, inv1.p, inv2.p, inv3.p);
+        NufftNdArgs<3> a = args_of<T>(t, inv1.p, inv2.p, inv3.p);
         a.in_re = fr.p;
         a.in_im = real ? nullptr : fi.p;
         a.out_re = wk.p;
@@ -327,7 +325,7 @@ void run_case(const Tables &t, const Weights &w1, const Weights &w2, const Weigh
         a.in_dist = fd;
         a.groups = batch * (G / V);
         const bool vec = al(fr.p) && (real || al(fi.p)) && al(wk.p) && (batch == 1 || fd % V == 0);
-        if (launch_nufft3d<T>(2, vec, a, nullptr) != hipSuccess) fail(2, "the launcher failed");
+        if (launch_nufft_nd<T, 3>(2, vec, a, nullptr) != hipSuccess) fail(2, "the launcher failed");
         for (size_t b = 0; b < batch; ++b) {
             std::vector<char> named(G, 0);
             for (size_t i1 = 0; i1 < t.n[0]; ++i1)
@@ -354,7 +352,7 @@ void run_case(const Tables &t, const Weights &w1, const Weights &w2, const Weigh
         fill_random(wk, 41);
         fill_sentinel(orr);
         fill_sentinel(oi);
-        Nufft3dArgs a = args_of<T>(t, inv1.p, inv2.p, inv3.p);
+        NufftNdArgs<3> a = args_of<T>(t, inv1.p, inv2.p, inv3.p);
         a.in_re = wk.p;
         a.in_im = wk.p + batch * G;
         a.out_re = orr.p;
@@ -363,7 +361,7 @@ void run_case(const Tables &t, const Weights &w1, const Weights &w2, const Weigh
         a.gpt = (unsigned)(t.n[0] * t.n[1] * ((t.n[2] + V - 1) / V));
         a.groups = batch * a.gpt;
         const bool vec = al(orr.p) && al(oi.p) && al(wk.p) && (batch == 1 || fd % V == 0);
-        if (launch_nufft3d<T>(3, vec, a, nullptr) != hipSuccess) fail(3, "the launcher failed");
+        if (launch_nufft_nd<T, 3>(3, vec, a, nullptr) != hipSuccess) fail(3, "the launcher failed");
         for (size_t b = 0; b < batch; ++b)
             for (size_t i1 = 0; i1 < t.n[0]; ++i1)
                 for (size_t i2 = 0; i2 < t.n[1]; ++i2)
@@ -425,7 +423,7 @@ int main(int argc, char **argv) {
     }
     if (f64) run_all<double>();
     if (f32) run_all<float>();
-    for (int k = 0; k < 4; ++k) std::printf("  %-22s worst error / gate %.3f\n", kKernel[k], g_worst[k]);
+    for (int k = 0; k < 4; ++k) std::printf("  %-23s worst error / gate %.3f\n", kKernel[k], g_worst[k]);
     std::printf("chunk %u ", kNufft3dChunk);
     std::printf("launches %llu threads %llu barriers %llu elements %llu\n", block_shim::launches, block_shim::threads_run, block_shim::barriers, g_compared);
     std::printf("nufft3d: %s (%d failures)\n", g_fails ? "FAILED" : "ok", g_fails);

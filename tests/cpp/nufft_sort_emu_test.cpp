@@ -9,7 +9,7 @@
 // Buffers: the coordinates, the two key and two index arrays, the histogram (nufft_sort_hist_len entries), the flag and the
 // tables are heap allocations of exactly the bytes the contract covers.
 //
-// The reference is the host path itself: nufft_bin, nufft2d_bin and nufft3d_bin on the same points.  perm, cell_start and
+// The reference is the host path itself: nufft_bin and nufft_nd_bin on the same points.  perm, cell_start and
 // xs / ys / zs must be EQUAL, bit for bit.
 //
 // Point sets: (u) uniform in [-3, 3); (c) clumped, every point within 1e-7 of 0.3; (d) duplicates, five distinct values; (e)
@@ -34,8 +34,7 @@ inline void sincospi(double t, double *s, double *c) {
 
 #include "nufft_sort.hip"
 
-#include "nufft2d.hpp"
-#include "nufft3d.hpp"
+#include "nufft_nd.hpp"
 
 #include <cstdarg>
 #include <cstdio>
@@ -146,12 +145,14 @@ void run_case(unsigned dims, const unsigned (&lg)[3], size_t m, char set, block_
     // the host path
     std::vector<double> rxs(m), rys(m), rzs(m);
     std::vector<uint32_t> rperm(m), rcell(cells + 1);
+    const double *const xin[3] = {x.p, y.p, z.p};
+    double *const rs[3] = {rxs.data(), rys.data(), rzs.data()};
     if (dims == 1)
         nufft_bin(x.p, m, lg[0], rxs.data(), rperm.data(), rcell.data());
     else if (dims == 2)
-        nufft2d_bin(x.p, y.p, m, lg[0], lg[1], rxs.data(), rys.data(), rperm.data(), rcell.data());
+        nufft_nd_bin<2>(xin, m, lg, rs, rperm.data(), rcell.data());
     else
-        nufft3d_bin(x.p, y.p, z.p, m, lg[0], lg[1], lg[2], rxs.data(), rys.data(), rzs.data(), rperm.data(), rcell.data());
+        nufft_nd_bin<3>(xin, m, lg, rs, rperm.data(), rcell.data());
     // the device path
     Buf<uint32_t> k0(m), k1(m), i0(m), i1(m), hist(nufft_sort_hist_len(m)), flag(1), perm(m), cell(cells + 1);
     Buf<double> xs(m), ys(dims > 1 ? m : 0), zs(dims > 2 ? m : 0);

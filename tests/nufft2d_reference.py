@@ -125,7 +125,7 @@ class Reference:
 
 
 # ---------------------------------------------------------------------------------------------
-# the schedule of csrc/nufft2d.hpp in numpy
+# the schedule of csrc/nufft_nd.hpp (D = 2) in numpy
 # ---------------------------------------------------------------------------------------------
 def model(t: int, x, y, v, n1: int, n2: int, eps: float, direction: int = FORWARD, dt=np.float64):
     """type t of the values v (flat) through spread / pre, numpy's 2-D FFT of the (g1, g2) grid and deconvolve / interpolate;

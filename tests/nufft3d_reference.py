@@ -133,7 +133,7 @@ class Reference:
 
 
 # ---------------------------------------------------------------------------------------------
-# the schedule of csrc/nufft3d.hpp in numpy
+# the schedule of csrc/nufft_nd.hpp (D = 3) in numpy
 # ---------------------------------------------------------------------------------------------
 def model(t: int, x, y, z, v, n1: int, n2: int, n3: int, eps: float, direction: int = FORWARD, dt=np.float64):
     """type t of the values v (flat) through spread / pre, numpy's 3-D FFT of the (g1, g2, g3) grid and deconvolve /

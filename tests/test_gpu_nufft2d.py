@@ -1,4 +1,4 @@
-"""Two-dimensional non-uniform FFTs of types 1 and 2 on the MI355X (csrc/nufft2d.hip, csrc/planner_nufft2d.hpp) against
+"""Two-dimensional non-uniform FFTs of types 1 and 2 on the MI355X (csrc/nufft_nd.hip, csrc/planner_nufft_nd.hpp) against
 tests/nufft2d_reference.py, the direct sum in long double with exact phases, on inputs that are exact in both types.
 
 The gate (tests/test_nufft2d_cpu.py: nufft2d_gate): C_EPS_2D * eps + tests/tolerances.py's formula on log2 G, G = g1 g2, for the

@@ -1,4 +1,4 @@
-"""Three-dimensional non-uniform FFTs of types 1 and 2 on the MI355X (csrc/nufft3d.hip, csrc/planner_nufft3d.hpp) against
+"""Three-dimensional non-uniform FFTs of types 1 and 2 on the MI355X (csrc/nufft_nd.hip, csrc/planner_nufft_nd.hpp) against
 tests/nufft3d_reference.py, the direct sum in long double with exact phases, on inputs that are exact in both types.
 
 The gate (tests/test_nufft3d_cpu.py: nufft3d_gate): C_EPS_3D * eps + tests/tolerances.py's formula on log2 G, G = g1 g2 g3, for

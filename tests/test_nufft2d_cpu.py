@@ -1,4 +1,4 @@
-"""The two-dimensional non-uniform FFT (csrc/nufft2d.hpp, csrc/planner_nufft2d.hpp) without a GPU: the host half of nufft2d.hpp
+"""The two-dimensional non-uniform FFT (csrc/nufft_nd.hpp, csrc/planner_nufft_nd.hpp) without a GPU: the host half of nufft_nd.hpp
 compiled with plain g++ (tests/cpp/nufft2d_test.cpp) and held against Python integers -- the argument rule and the binning by
 the combined cell; a numpy model of the schedule against tests/nufft2d_reference.py at every shape of tests/test_gpu_nufft2d.py
 (the CPU leg of the gate); the new C ABI exported and listed, with every argument rule returned before the device is touched.
@@ -168,7 +168,7 @@ def binning_points(g1, g2, count=2000):
 
 @pytest.mark.parametrize("logs", [(3, 3), (3, 6), (7, 4)], ids=lambda s: f"{s[0]}_{s[1]}")
 def test_binning(helpers, logs):
-    """nufft2d_bin against a numpy stable argsort of the combined cell q1 g2 + q2, q_i = floor(frac(coordinate) g_i) with frac
+    """nufft_nd_bin<2> against a numpy stable argsort of the combined cell q1 g2 + q2, q_i = floor(frac(coordinate) g_i) with frac
     exact in Python integers: the permutation, the cell starts and the kept positions (in the same cell, below 1)"""
     log_g1, log_g2 = logs
     g1, g2 = 1 << log_g1, 1 << log_g2

@@ -1,4 +1,4 @@
-"""The three-dimensional non-uniform FFT (csrc/nufft3d.hpp, csrc/planner_nufft3d.hpp) without a GPU: the host half of nufft3d.hpp
+"""The three-dimensional non-uniform FFT (csrc/nufft_nd.hpp, csrc/planner_nufft_nd.hpp) without a GPU: the host half of nufft_nd.hpp
 compiled with plain g++ (tests/cpp/nufft3d_test.cpp) and held against Python integers -- the argument rule and the binning by
 the combined cell; a numpy model of the schedule against tests/nufft3d_reference.py at every shape of tests/test_gpu_nufft3d.py;
 the new C ABI exported and listed, with every argument rule returned before the device is touched.
@@ -224,7 +224,7 @@ def binning_points(gs, count=2000):
 
 @pytest.mark.parametrize("logs", [(3, 3, 3), (3, 5, 4), (6, 3, 4)], ids=lambda s: f"{s[0]}_{s[1]}_{s[2]}")
 def test_binning(helpers, logs):
-    """nufft3d_bin against a numpy stable argsort of the combined cell (q1 g2 + q2) g3 + q3, q_i = floor(frac(coordinate) g_i)
+    """nufft_nd_bin<3> against a numpy stable argsort of the combined cell (q1 g2 + q2) g3 + q3, q_i = floor(frac(coordinate) g_i)
     with frac exact in Python integers: the permutation, the cell starts and the kept positions (in the same cell, below 1)"""
     gs = tuple(1 << v for v in logs)
     pts = binning_points(gs)

@@ -1,6 +1,6 @@
 """The kernels that build the NUFFT planners' point tables on the device (csrc/nufft_sort.hip: keys, histogram, scan, scatter,
 tables) run thread by thread ON THE HOST under AddressSanitizer and UndefinedBehaviorSanitizer -- no GPU, no HIP runtime -- and
-must give perm, cell_start and xs / ys / zs EQUAL to the host path's (nufft_bin, nufft2d_bin, nufft3d_bin), bit for bit.
+must give perm, cell_start and xs / ys / zs EQUAL to the host path's (nufft_bin, nufft_nd_bin), bit for bit.
 
 tests/cpp/nufft_sort_emu_test.cpp is a stand-alone program on tests/emu/block_shim.hpp (a workgroup's threads are fibers that
 meet at __syncthreads()), built with tests.emu.BLOCK_FLAGS and linked by the toolchain's clang++ without the HIP runtime.  It
