@@ -22,6 +22,8 @@
 //                                                            dst_f64/f32[_with_planner], enum Norm -- types II and III, any N >= 1
 //   (none: no short-time transforms upstream)                class PlannerStft64/32, stft_f64/f32_with_planner,
 //                                                            istft_f64/f32_with_planner, enum PadMode -- torch.stft / istft
+//   (none: no lapped transforms upstream)                    class PlannerMdct64/32, mdct_f64/f32_with_planner,
+//                                                            imdct_f64/f32_with_planner
 //   (none: no convolution upstream)                          class PlannerConv64/32, conv_f64/f32_with_planner, enum ConvMode --
 //                                                            scipy.signal.convolve / correlate by overlap-save
 //   (none: no convolution upstream)                          class PlannerConvNd64/32, convnd_f64/f32_with_planner -- the same of
@@ -518,6 +520,55 @@ PHASTFT_PLANNER_STFT(PlannerStft32, phast_planner_stft32, 32, float)
 PHASTFT_STFT(f64, double, PlannerStft64)
 PHASTFT_STFT(f32, float, PlannerStft32)
 #undef PHASTFT_STFT
+
+// ---- the modified discrete cosine transform and its inverse (no reference counterpart, and none in torch or scipy) ----
+#define PHASTFT_PLANNER_MDCT(NAME, CT, SFX, T)                                                                   \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* `n` coefficients (even) per frame of 2 n samples; `window`: 2 n values, or empty for the sine window */ \
+        NAME(std::size_t signal_len, std::size_t n, Slice<const T> window = Slice<const T>(nullptr, 0), bool padded = true) { \
+            if (window.len && window.len != 2 * n) check(PHAST_ERR_INVALID_ARG);                                 \
+            check(phast_planner_mdct##SFX##_new(signal_len, n, window.len ? window.ptr : nullptr, padded ? 1 : 0, &h_)); \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }                                                   \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_mdct##SFX##_free(h_);                                                          \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_mdct##SFX##_describe(h_, &s[0], s.size()));                                      \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_mdct##SFX##_device_bytes(h_); }                  \
+        std::size_t frames() const { return phast_planner_mdct##SFX##_frames(h_); }                              \
+        /* how far the window is from perfect reconstruction: 0 for sine, Vorbis and Kaiser-Bessel-derived windows */ \
+        double tdac_defect() const { return phast_planner_mdct##SFX##_tdac_defect(h_); }                         \
+        /* elements of T a _dev call of `batch` signals works in; workspace_min: the least a call runs in */     \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_mdct##SFX##_workspace_len(h_, batch); } \
+        std::size_t workspace_min(bool inverse = false) const { return phast_planner_mdct##SFX##_workspace_min(h_, inverse); } \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+    };
+PHASTFT_PLANNER_MDCT(PlannerMdct64, phast_planner_mdct64, 64, double)
+PHASTFT_PLANNER_MDCT(PlannerMdct32, phast_planner_mdct32, 32, float)
+#undef PHASTFT_PLANNER_MDCT
+
+// one host signal of L samples <-> frames * n coefficients (frame-major); blocking
+#define PHASTFT_MDCT(FS, T, P)                                                                                   \
+    inline void mdct_##FS##_with_planner(Slice<const T> signal, Slice<T> coefs, const P &planner) {              \
+        check(phast_mdct_##FS##_with_planner(signal.ptr, signal.len, coefs.ptr, coefs.len, planner.get()));      \
+    }                                                                                                            \
+    inline void imdct_##FS##_with_planner(Slice<const T> coefs, Slice<T> signal, const P &planner) {             \
+        check(phast_imdct_##FS##_with_planner(coefs.ptr, coefs.len, signal.ptr, signal.len, planner.get()));     \
+    }
+PHASTFT_MDCT(f64, double, PlannerMdct64)
+PHASTFT_MDCT(f32, float, PlannerMdct32)
+#undef PHASTFT_MDCT
 
 // ---- overlap-save convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve / correlate) ----
 enum class ConvMode : int { Full = PHAST_CONV_FULL, Same = PHAST_CONV_SAME, Valid = PHAST_CONV_VALID };

@@ -504,6 +504,78 @@ int phast_istft_f32_dev(const float *d_re, const float *d_im, float *d_signal, s
 int phast_planner_stft32_time_stages(const phast_planner_stft32 *p, int inverse, float *d_signal, float *d_re, float *d_im, size_t batch,
                                      float *d_work, size_t work_len, int reps, float *stage_ms, void *stream);
 
+/* ---- the modified discrete cosine transform and its inverse (no reference counterpart, and none in torch or scipy; DESIGN.md
+ * §24).  N coefficients per frame, N even, 2 <= N <= 2^29 (an odd N is PHAST_ERR_INVALID_ARG: no codec uses one, and it would
+ * need a 2N-point inner transform); frame length 2N, hop N; window w[0..2N): host doubles (64) or floats (32) given at _new
+ * and held as T on the device, NULL for the sine window sin(pi (n + 1/2) / (2N)).  h = N / 2.
+ *     forward  For frame t of a signal x[0..L), zero outside [0, L), with s_t = (t - padded) N:
+ *                  X_t[k] = sum_{n=0}^{2N-1} w[n] x[s_t + n] cos(pi/N (n + 1/2 + N/2)(k + 1/2)),  k = 0 .. N-1
+ *              There is no scale on the forward transform.
+ *     frames   padded = 1: F = ceil(L / N) + 1 and L >= 1; every sample lies in exactly two frames.
+ *              padded = 0: F = floor(L / N) - 1, L >= 2N is required, and the tail beyond (F + 1) N is not read.
+ *              The coefficients are [batch][F][N], row-major and packed, as the STFT's planes are.
+ *     inverse  With y_t[n] = (2/N) w[n] sum_k X_t[k] cos(pi/N (n + 1/2 + N/2)(k + 1/2)), out[s] = sum_t y_t[s - s_t] for
+ *              0 <= s < L.  There is no division by an envelope (an MDCT cannot be normalised after the fact).  Every output
+ *              sample has at most two source frames; a sample with one (padded = 0: s < N or s >= F N) gets that one term,
+ *              a sample with none is written as 0.
+ * Perfect reconstruction: if w[n]^2 + w[n+N]^2 = 1 and w[2N-1-n] = w[n], then imdct(mdct(x)) = x on all of [0, L) for
+ * padded = 1 and on [N, F N) for padded = 0.  _tdac_defect is max(max_n |w[n]^2 + w[n+N]^2 - 1|, max_n |w[n] - w[2N-1-n]|),
+ * computed once at _new in double from the values given (for NULL: from the sine window before it is rounded to T).  The
+ * planner never refuses a window: an analysis-only caller may pass any.
+ * _new takes 1 <= L <= 2^29, frames N <= 2^30 and padded in {0, 1}; anything else is PHAST_ERR_INVALID_ARG before the device
+ * is touched.
+ *
+ * One complex transform of h points per frame (the phast_planner_any* engine, called unchanged) between two O(frames N)
+ * sweeps: the fold of 2N windowed samples to N and a DCT-IV of N, whose two twiddle sets are device tables built at _new.
+ * The caller's device workspace holds phast_planner_mdct*_workspace_len(p, batch) elements of T.  The forward call runs any
+ * work_len >= _workspace_min(p, 0) (one frame) in chunks of whole frames, the inverse any work_len >= _workspace_min(p, 1)
+ * (one signal's frames) in chunks of whole signals; a null or shorter one is PHAST_ERR_INVALID_ARG.  _dev calls: asynchronous
+ * on `stream`; `batch` signals at sig_dist >= L, coefficients packed, pointers need element alignment only; the inputs of
+ * both calls are never written, and in place is not offered (the shapes differ).  A signal_len that is not the planner's is
+ * PHAST_ERR_PLANNER_SIZE, host coefficients that are not frames * N long PHAST_ERR_LEN_MISMATCH.  The planner is immutable and
+ * holds no per-call state.  The overlap-add is a gather without atomics.  Host-slice calls take one signal, stage through the
+ * device and block. */
+typedef struct phast_planner_mdct64 phast_planner_mdct64; /* PlannerMdct64 */
+int phast_planner_mdct64_new(size_t signal_len, size_t n, const double *window, int padded, phast_planner_mdct64 **out);
+void phast_planner_mdct64_free(phast_planner_mdct64 *p);
+int phast_planner_mdct64_describe(const phast_planner_mdct64 *p, char *buf, size_t buf_len);
+size_t phast_planner_mdct64_device_bytes(const phast_planner_mdct64 *p);
+size_t phast_planner_mdct64_frames(const phast_planner_mdct64 *p);
+size_t phast_planner_mdct64_workspace_len(const phast_planner_mdct64 *p, size_t batch);
+size_t phast_planner_mdct64_workspace_min(const phast_planner_mdct64 *p, int inverse);
+double phast_planner_mdct64_tdac_defect(const phast_planner_mdct64 *p);
+int phast_mdct_f64_with_planner(const double *signal, size_t signal_len, double *coefs, size_t coefs_len, const phast_planner_mdct64 *planner);
+int phast_imdct_f64_with_planner(const double *coefs, size_t coefs_len, double *signal, size_t signal_len, const phast_planner_mdct64 *planner);
+int phast_mdct_f64_dev(const double *d_signal, double *d_coefs, size_t signal_len, size_t batch, size_t sig_dist,
+                       const phast_planner_mdct64 *planner, double *d_work, size_t work_len, void *stream);
+int phast_imdct_f64_dev(const double *d_coefs, double *d_signal, size_t signal_len, size_t batch, size_t sig_dist,
+                        const phast_planner_mdct64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/mdct_rate.py): stage_ms[3] = average milliseconds of the pre sweep, of the complex transform and of
+ * the post sweep (inverse = 1: the post and the overlap-add sweeps together) over `reps` calls of `batch` signals at distance
+ * L in ONE chunk (work_len >= phast_planner_mdct*_workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_mdct64_time_stages(const phast_planner_mdct64 *p, int inverse, double *d_signal, double *d_coefs, size_t batch, double *d_work, size_t work_len,
+                                     int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_mdct32 phast_planner_mdct32; /* PlannerMdct32 */
+int phast_planner_mdct32_new(size_t signal_len, size_t n, const float *window, int padded, phast_planner_mdct32 **out);
+void phast_planner_mdct32_free(phast_planner_mdct32 *p);
+int phast_planner_mdct32_describe(const phast_planner_mdct32 *p, char *buf, size_t buf_len);
+size_t phast_planner_mdct32_device_bytes(const phast_planner_mdct32 *p);
+size_t phast_planner_mdct32_frames(const phast_planner_mdct32 *p);
+size_t phast_planner_mdct32_workspace_len(const phast_planner_mdct32 *p, size_t batch);
+size_t phast_planner_mdct32_workspace_min(const phast_planner_mdct32 *p, int inverse);
+double phast_planner_mdct32_tdac_defect(const phast_planner_mdct32 *p);
+int phast_mdct_f32_with_planner(const float *signal, size_t signal_len, float *coefs, size_t coefs_len, const phast_planner_mdct32 *planner);
+int phast_imdct_f32_with_planner(const float *coefs, size_t coefs_len, float *signal, size_t signal_len, const phast_planner_mdct32 *planner);
+int phast_mdct_f32_dev(const float *d_signal, float *d_coefs, size_t signal_len, size_t batch, size_t sig_dist,
+                       const phast_planner_mdct32 *planner, float *d_work, size_t work_len, void *stream);
+int phast_imdct_f32_dev(const float *d_coefs, float *d_signal, size_t signal_len, size_t batch, size_t sig_dist,
+                        const phast_planner_mdct32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/mdct_rate.py): stage_ms[3] = average milliseconds of the pre sweep, of the complex transform and of
+ * the post sweep (inverse = 1: the post and the overlap-add sweeps together) over `reps` calls of `batch` signals at distance
+ * L in ONE chunk (work_len >= phast_planner_mdct*_workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_mdct32_time_stages(const phast_planner_mdct32 *p, int inverse, float *d_signal, float *d_coefs, size_t batch, float *d_work, size_t work_len,
+                                     int reps, float *stage_ms, void *stream);
+
 /* ---- overlap-save FIR convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve /
  * correlate(x, h, mode, method="direct")).  Signal x of L samples, K taps h, both real:
  *     full[t] = sum_j g[j] x[t - j], t in [0, L + K - 1); g = h (flip = 0: convolution) or g[j] = h[K - 1 - j] (flip = 1:

@@ -24,6 +24,9 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
                                                     dct_batched, dst_batched, idct, idst
     (none: no short-time transforms)                PlannerStft64/32, stft_batched, istft_batched,
                                                     stft_f64/f32_with_planner, istft_f64/f32_with_planner
+    (none: no lapped transforms)                    PlannerMdct64/32, mdct_batched, imdct_batched,
+                                                    mdct_f64/f32_with_planner, imdct_f64/f32_with_planner, mdct, imdct,
+                                                    mdct_window
     (none: no convolution)                          PlannerConv64/32, conv_batched, conv_f64/f32_with_planner,
                                                     fftconvolve, correlate
     (none: no convolution)                          PlannerConvNd64/32, convnd_batched, convnd_f64/f32_with_planner,
@@ -85,6 +88,8 @@ __all__ = [
     "dst_f64_with_planner", "dst_f32_with_planner", "dct_batched", "dst_batched", "idct", "idst",
     "PlannerStft64", "PlannerStft32", "stft_batched", "istft_batched", "stft_f64_with_planner", "stft_f32_with_planner",
     "istft_f64_with_planner", "istft_f32_with_planner",
+    "PlannerMdct64", "PlannerMdct32", "mdct_batched", "imdct_batched", "mdct_f64_with_planner", "mdct_f32_with_planner",
+    "imdct_f64_with_planner", "imdct_f32_with_planner", "mdct", "imdct", "mdct_window",
     "PlannerConv64", "PlannerConv32", "conv_batched", "conv_f64_with_planner", "conv_f32_with_planner", "fftconvolve",
     "correlate",
     "PlannerConvNd64", "PlannerConvNd32", "convnd_batched", "convnd_f64_with_planner", "convnd_f32_with_planner",
@@ -1185,6 +1190,175 @@ def istft_f64_with_planner(in_re, in_im, signal, planner: PlannerStft64) -> None
 def istft_f32_with_planner(in_re, in_im, signal, planner: PlannerStft32) -> None:
     """f32 twin of :func:`istft_f64_with_planner`"""
     _stft_host("istft", "f32", np.float32, in_re, in_im, signal, planner)
+
+
+# ---------------------------------------------------------------------------------------------
+# the modified discrete cosine transform and its inverse (no reference counterpart, and none in torch or scipy)
+# ---------------------------------------------------------------------------------------------
+def mdct_window(name: str, n: int, dtype=np.float64, alpha: float = 4.0):
+    """The 2N values of a window that reconstructs perfectly (w[j]^2 + w[j+N]^2 = 1, symmetric), as a numpy array of ``dtype``:
+    ``"sine"`` sin(pi (j + 1/2) / (2N)), ``"vorbis"`` sin(pi/2 sin^2(pi (j + 1/2) / (2N))) or ``"kbd"``, the
+    Kaiser-Bessel-derived window of ``alpha`` (the running sum of a Kaiser window of N + 1 points, beta = pi alpha)."""
+    if n < 1:
+        raise ValueError(f"n must be positive, not {n}")
+    pi = np.longdouble("3.14159265358979323846264338327950288")
+    t = (np.arange(n, dtype=np.longdouble) + 0.5) / (2 * n)  # the rising half; the other half mirrors it
+    if name == "sine":
+        half = np.sin(pi * t)
+    elif name == "vorbis":
+        half = np.sin(pi / 2 * np.sin(pi * t) ** 2)
+    elif name == "kbd":
+        j = np.arange(n + 1, dtype=np.float64)
+        k = np.i0(np.pi * alpha * np.sqrt(1.0 - (2.0 * j / n - 1.0) ** 2)).astype(np.longdouble)
+        half = np.sqrt(np.cumsum(k[:n]) / np.sum(k))
+    else:
+        raise ValueError(f"window must be 'sine', 'vorbis' or 'kbd', not {name!r}")
+    return np.concatenate([half, half[::-1]]).astype(dtype)
+
+
+class PlannerMdct64(_AnyHandle):
+    """f64 MDCT / inverse MDCT of signals of ``signal_len`` samples: ``n`` coefficients (even) per frame of ``2 n`` samples,
+    hop ``n``, times ``window`` (``2 n`` values; None: the sine window).  ``padded``: the signal is framed from ``-n`` on, so
+    that every sample lies in two frames (``ceil(L / n) + 1`` frames) and a window with ``tdac_defect`` 0 reconstructs all of
+    it; without, ``floor(L / n) - 1`` frames from sample 0 on reconstruct ``[n, frames * n)``.  Coefficients are (frames, n),
+    row-major.  The forward transform is unscaled, the inverse carries 2 / n."""
+
+    _prefix = "mdct"
+
+    def __init__(self, signal_len: int, n: int, window=None, padded: bool = True):
+        wp = None
+        if window is not None:
+            if _is_torch(window):
+                window = window.detach().cpu().numpy()
+            w = np.ascontiguousarray(window, dtype=self._dtype).reshape(-1)
+            if w.size != 2 * n:
+                raise ValueError(f"window: {w.size} values for 2 n = {2 * n}")
+            wp = w.ctypes.data_as(C.c_void_p)
+        self._new(signal_len, n, wp, bool(padded))
+        self.signal_len, self.n, self.padded = signal_len, n, bool(padded)
+        self.frames = int(self._fn("frames")(self._h))
+        self.tdac_defect = float(self._fn("tdac_defect")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` signals works in.  A smaller workspace runs the batch in chunks: of
+        whole frames forward (at least ``workspace_min()``), of whole signals for the inverse (``workspace_min(True)``)."""
+        return self._workspace_len(batch)
+
+    def workspace_min(self, inverse: bool = False) -> int:
+        return int(self._fn("workspace_min")(self._h, bool(inverse)))
+
+    def time_stages(self, signal, coefs, inverse: bool = False, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (the pre sweep, the complex transform, the post sweep -- with the overlap-add
+        for the inverse) of a call of ``batch`` signals at distance L on device tensors (measurement hook)"""
+        x, c = _Slice(signal, self._dtype, "signal"), _Slice(coefs, self._dtype, "coefs")
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 3)()
+        _check(self._fn("time_stages")(self._h, bool(inverse), x.ptr, c.ptr, batch, ws.ptr, ws.len, reps, ms, _stream()))
+        return [float(v) for v in ms]
+
+
+class PlannerMdct32(PlannerMdct64):
+    """f32 twin of :class:`PlannerMdct64`"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def _mdct_batched(inverse, signal, coefs, planner, batch, sig_dist, workspace):
+    dtype, fs = planner._dtype, "f64" if planner._dtype == np.float64 else "f32"
+    x, c = _Slice(signal, dtype, "signal"), _Slice(coefs, dtype, "coefs")
+    name = "imdct" if inverse else "mdct"
+    if not _same_place(x, c):
+        raise TypeError(f"{name}_batched needs device tensors")
+    n, pts = planner.signal_len, planner.frames * planner.n
+    sig_dist = n if sig_dist is None else sig_dist
+    _need("signal", x.len, batch, sig_dist, n)
+    _need("coefs", c.len, batch, pts, pts)
+    ws = _any_workspace(planner, batch, workspace)
+    args = (c.ptr, x.ptr) if inverse else (x.ptr, c.ptr)
+    _check(_call(f"phast_{name}_{fs}_dev", *args, n, batch, sig_dist, planner._h, ws.ptr, ws.len, _stream()))
+
+
+def mdct_batched(signal, coefs, planner, batch: int, sig_dist: int | None = None, workspace=None) -> None:
+    """Device-resident batch of MDCTs: signal b at ``b*sig_dist`` (default L, any distance >= L); coefficient k of frame t of
+    signal b at ``(b*frames + t)*n + k``.  ``workspace``: a device tensor of the planner's type of at least
+    ``planner.workspace_min()`` elements (fewer than ``planner.workspace_len(batch)`` runs the frames in chunks); by default
+    one from torch's allocator.  The signal is not written."""
+    _mdct_batched(False, signal, coefs, planner, batch, sig_dist, workspace)
+
+
+def imdct_batched(coefs, signal, planner, batch: int, sig_dist: int | None = None, workspace=None) -> None:
+    """Device-resident batch of inverse MDCTs by windowed overlap-add: the inverse of :func:`mdct_batched` where the planner's
+    window has ``tdac_defect`` 0.  ``workspace``: at least ``planner.workspace_min(True)`` elements (one signal's frames).
+    The coefficients are not written; every sample of [0, L) is (0 where no frame holds it)."""
+    _mdct_batched(True, signal, coefs, planner, batch, sig_dist, workspace)
+
+
+def _mdct_host(name, fs, dtype, a, b, planner):
+    sl = [_Slice(t, dtype, w) for t, w in zip((a, b), ("signal", "coefs") if name == "mdct" else ("coefs", "signal"))]
+    if _same_place(*sl):
+        raise TypeError(f"{name}_{fs}_with_planner takes host arrays ({name}_batched takes device tensors)")
+    _check(_call(f"phast_{name}_{fs}_with_planner", *(v for s in sl for v in (s.ptr, s.len)), planner._h))
+
+
+def mdct_f64_with_planner(signal, coefs, planner: PlannerMdct64) -> None:
+    """f64 MDCT of one host signal of L samples into a host array of frames * n coefficients (blocking)"""
+    _mdct_host("mdct", "f64", np.float64, signal, coefs, planner)
+
+
+def mdct_f32_with_planner(signal, coefs, planner: PlannerMdct32) -> None:
+    """f32 twin of :func:`mdct_f64_with_planner`"""
+    _mdct_host("mdct", "f32", np.float32, signal, coefs, planner)
+
+
+def imdct_f64_with_planner(coefs, signal, planner: PlannerMdct64) -> None:
+    """f64 inverse MDCT of a host array of frames * n coefficients into one host signal of L samples (blocking)"""
+    _mdct_host("imdct", "f64", np.float64, coefs, signal, planner)
+
+
+def imdct_f32_with_planner(coefs, signal, planner: PlannerMdct32) -> None:
+    """f32 twin of :func:`imdct_f64_with_planner`"""
+    _mdct_host("imdct", "f32", np.float32, coefs, signal, planner)
+
+
+def _mdct_planner(t, length, n, window, padded):
+    import torch
+
+    if not _is_torch(t) or t.device.type != "cuda" or t.dtype not in (torch.float64, torch.float32):
+        raise TypeError("need a float64 or float32 device tensor")
+    dtype = np.float64 if t.dtype == torch.float64 else np.float32
+    if isinstance(window, str):
+        window = mdct_window(window, n, dtype)
+    return (PlannerMdct64 if dtype == np.float64 else PlannerMdct32)(length, n, window, padded)
+
+
+def mdct(x, n: int, window="sine", padded: bool = True):
+    """The MDCT of one real device tensor of L samples with ``n`` coefficients per frame, through a planner of its own: a new
+    device tensor of shape (frames, n).  ``window``: a name for :func:`mdct_window` or ``2 n`` values."""
+    import torch
+
+    planner = _mdct_planner(x, x.numel(), n, window, padded)
+    out = torch.empty(planner.frames * n, dtype=x.dtype, device=x.device)
+    mdct_batched(x.contiguous().reshape(-1), out, planner, 1)
+    torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+    return out.reshape(planner.frames, n)
+
+
+def imdct(X, length: int, window="sine", padded: bool = True):
+    """The inverse MDCT of one (frames, n) device tensor into a new device tensor of ``length`` samples: ``x`` again for
+    ``X = mdct(x, n, window, padded)`` and a window of :func:`mdct_window`."""
+    import torch
+
+    if X.dim() != 2:
+        raise ValueError("imdct needs a (frames, n) tensor")
+    n = X.shape[1]
+    planner = _mdct_planner(X, length, n, window, padded)
+    if planner.frames != X.shape[0]:
+        raise ValueError(f"{X.shape[0]} frames, but length = {length} with n = {n} has {planner.frames}")
+    out = torch.empty(length, dtype=X.dtype, device=X.device)
+    imdct_batched(X.contiguous().reshape(-1), out, planner, 1)
+    torch.cuda.current_stream().synchronize()
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

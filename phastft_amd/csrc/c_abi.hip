@@ -17,6 +17,7 @@
 #include "planner_any.hpp"
 #include "planner_any_real.hpp"
 #include "planner_dct.hpp"
+#include "planner_mdct.hpp"
 #include "planner_stft.hpp"
 #include "planner_conv.hpp"
 #include "planner_convnd.hpp"
@@ -43,6 +44,8 @@ struct phast_planner_dct64 : DctPlanner<double> {};
 struct phast_planner_dct32 : DctPlanner<float> {};
 struct phast_planner_stft64 : StftPlanner<double> {};
 struct phast_planner_stft32 : StftPlanner<float> {};
+struct phast_planner_mdct64 : MdctPlanner<double> {};
+struct phast_planner_mdct32 : MdctPlanner<float> {};
 struct phast_planner_conv64 : ConvPlanner<double> {};
 struct phast_planner_conv32 : ConvPlanner<float> {};
 struct phast_planner_convnd64 : ConvNdPlanner<double> {};
@@ -555,7 +558,7 @@ PHAST_HANDLE_API(conv64) PHAST_HANDLE_API(conv32) PHAST_HANDLE_API(czt64) PHAST_
 PHAST_HANDLE_API(nufft64) PHAST_HANDLE_API(nufft32) PHAST_HANDLE_API(nufft2d64) PHAST_HANDLE_API(nufft2d32)
 PHAST_HANDLE_API(nufft3d64) PHAST_HANDLE_API(nufft3d32) PHAST_HANDLE_API(nufft_t3_64) PHAST_HANDLE_API(nufft_t3_32)
 PHAST_HANDLE_API(nd64) PHAST_HANDLE_API(nd32) PHAST_HANDLE_API(r2c_nd64) PHAST_HANDLE_API(r2c_nd32)
-PHAST_HANDLE_API(convnd64) PHAST_HANDLE_API(convnd32)
+PHAST_HANDLE_API(convnd64) PHAST_HANDLE_API(convnd32) PHAST_HANDLE_API(mdct64) PHAST_HANDLE_API(mdct32)
 
 // Arbitrary lengths (Bluestein, planner_any.hpp): arguments are checked before the device is touched
 #define PHAST_ANY_API(SFX, T)                                                                                           \
@@ -749,6 +752,53 @@ PHAST_DCT_API(32, f32, float)
     } PHAST_CATCH_RC
 PHAST_STFT_API(64, f64, double)
 PHAST_STFT_API(32, f32, float)
+
+// The MDCT and its inverse (planner_mdct.hpp): every argument rule and a wrong length come back before the device is touched
+#define PHAST_MDCT_API(SFX, FS, T)                                                                                      \
+    int phast_planner_mdct##SFX##_new(size_t signal_len, size_t n, const T *window, int padded,                         \
+                                      phast_planner_mdct##SFX **out) try {                                              \
+        return mdct_planner_new<T>(signal_len, n, window, padded, out);                                                 \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_mdct##SFX##_frames(const phast_planner_mdct##SFX *p) try {                                     \
+        return p ? p->frames : 0;                                                                                       \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_mdct##SFX##_workspace_min(const phast_planner_mdct##SFX *p, int inverse) try {                 \
+        return p ? p->workspace_min(inverse != 0) : 0;                                                                  \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    double phast_planner_mdct##SFX##_tdac_defect(const phast_planner_mdct##SFX *p) try {                                \
+        return p ? p->tdac_defect : 0.0;                                                                                \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_mdct##SFX##_time_stages(const phast_planner_mdct##SFX *p, int inverse, T *d_signal, T *d_coefs,   \
+                                              size_t batch, T *d_work, size_t work_len, int reps, float *stage_ms,      \
+                                              void *stream) try {                                                       \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(inverse != 0, d_signal, d_coefs, batch, d_work, work_len, reps, stage_ms,                 \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_mdct_##FS##_with_planner(const T *signal, size_t signal_len, T *coefs, size_t coefs_len,                  \
+                                       const phast_planner_mdct##SFX *p) try {                                          \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(false, signal, signal_len, coefs, coefs_len);                                                    \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_imdct_##FS##_with_planner(const T *coefs, size_t coefs_len, T *signal, size_t signal_len,                 \
+                                        const phast_planner_mdct##SFX *p) try {                                         \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(true, coefs, coefs_len, signal, signal_len);                                                     \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_mdct_##FS##_dev(const T *d_signal, T *d_coefs, size_t signal_len, size_t batch, size_t sig_dist,          \
+                              const phast_planner_mdct##SFX *p, T *d_work, size_t work_len, void *stream) try {         \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->mdct_dev(d_signal, d_coefs, signal_len, batch, sig_dist, d_work, work_len,                            \
+                           static_cast<hipStream_t>(stream));                                                           \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_imdct_##FS##_dev(const T *d_coefs, T *d_signal, size_t signal_len, size_t batch, size_t sig_dist,         \
+                               const phast_planner_mdct##SFX *p, T *d_work, size_t work_len, void *stream) try {        \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->imdct_dev(d_coefs, d_signal, signal_len, batch, sig_dist, d_work, work_len,                           \
+                            static_cast<hipStream_t>(stream));                                                          \
+    } PHAST_CATCH_RC
+PHAST_MDCT_API(64, f64, double)
+PHAST_MDCT_API(32, f32, float)
 
 // Overlap-save convolution and correlation of real signals (planner_conv.hpp): every argument rule and a wrong length come
 // back before the device is touched

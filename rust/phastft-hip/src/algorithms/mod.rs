@@ -6,6 +6,7 @@ pub mod conv;
 pub mod convnd;
 pub mod czt;
 pub mod dit;
+pub mod mdct;
 pub mod nufft;
 pub mod nufft2d;
 pub mod nufft3d;

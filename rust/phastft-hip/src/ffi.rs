@@ -155,6 +155,43 @@ extern "C" {
         planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     pub(crate) fn phast_istft_f32_dev(re: *const f32, im: *const f32, signal: *mut f32, signal_len: usize, batch: usize,
         sig_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // the MDCT and its inverse (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/mdct.rs)
+    pub(crate) fn phast_planner_mdct64_new(signal_len: usize, n: usize, window: *const f64, padded: c_int, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_mdct64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_mdct64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_mdct64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_mdct64_frames(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_mdct64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_mdct64_workspace_min(p: *const Opaque, inverse: c_int) -> usize;
+    pub(crate) fn phast_planner_mdct64_tdac_defect(p: *const Opaque) -> f64;
+    pub(crate) fn phast_planner_mdct64_time_stages(p: *const Opaque, inverse: c_int, signal: *mut f64, coefs: *mut f64, batch: usize,
+        work: *mut f64, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_mdct_f64_with_planner(signal: *const f64, signal_len: usize, coefs: *mut f64, coefs_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_imdct_f64_with_planner(coefs: *const f64, coefs_len: usize, signal: *mut f64, signal_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_mdct_f64_dev(signal: *const f64, coefs: *mut f64, signal_len: usize, batch: usize, sig_dist: usize,
+        planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_imdct_f64_dev(coefs: *const f64, signal: *mut f64, signal_len: usize, batch: usize, sig_dist: usize,
+        planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_mdct32_new(signal_len: usize, n: usize, window: *const f32, padded: c_int, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_mdct32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_mdct32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_mdct32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_mdct32_frames(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_mdct32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_mdct32_workspace_min(p: *const Opaque, inverse: c_int) -> usize;
+    pub(crate) fn phast_planner_mdct32_tdac_defect(p: *const Opaque) -> f64;
+    pub(crate) fn phast_planner_mdct32_time_stages(p: *const Opaque, inverse: c_int, signal: *mut f32, coefs: *mut f32, batch: usize,
+        work: *mut f32, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_mdct_f32_with_planner(signal: *const f32, signal_len: usize, coefs: *mut f32, coefs_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_imdct_f32_with_planner(coefs: *const f32, coefs_len: usize, signal: *mut f32, signal_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_mdct_f32_dev(signal: *const f32, coefs: *mut f32, signal_len: usize, batch: usize, sig_dist: usize,
+        planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_imdct_f32_dev(coefs: *const f32, signal: *mut f32, signal_len: usize, batch: usize, sig_dist: usize,
+        planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // overlap-save convolution and correlation (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/conv.rs)
     pub(crate) fn phast_planner_conv64_new(signal_len: usize, taps: *const f64, num_taps: usize, mode: c_int, flip: c_int,
         block: usize, out: *mut *mut Opaque) -> c_int;

@@ -55,6 +55,12 @@ pub use algorithms::stft::{
     stft_f64_dev, stft_f64_with_planner,
 };
 pub use planner::{PadMode, PlannerStft32, PlannerStft64};
+// the modified discrete cosine transform and its inverse (an extension beyond PhastFT 0.3.0)
+pub use algorithms::mdct::{
+    imdct_f32_dev, imdct_f32_with_planner, imdct_f64_dev, imdct_f64_with_planner, mdct_f32_dev, mdct_f32_with_planner,
+    mdct_f64_dev, mdct_f64_with_planner,
+};
+pub use planner::{PlannerMdct32, PlannerMdct64};
 // overlap-save convolution and correlation of real signals (an extension beyond PhastFT 0.3.0)
 pub use algorithms::conv::{conv_f32_dev, conv_f32_with_planner, conv_f64_dev, conv_f64_with_planner};
 pub use planner::{ConvMode, PlannerConv32, PlannerConv64};

@@ -310,6 +310,68 @@ impl_planner_stft!(PlannerStft32, f32, phast_planner_stft32_new, phast_planner_s
                    phast_planner_stft32_bins, phast_planner_stft32_workspace_len, phast_planner_stft32_workspace_min,
                    phast_planner_stft32_envelope_min);
 
+macro_rules! impl_planner_mdct {
+    ($mdct:ident, $t:ty, $new:ident, $free:ident, $frames:ident, $ws_len:ident, $ws_min:ident, $defect:ident) => {
+        /// An extension beyond PhastFT 0.3.0: the modified discrete cosine transform of signals of `signal_len` samples and
+        /// its inverse by windowed overlap-add: `n` coefficients (even) per frame of `2 n` samples, hop `n`; one complex
+        /// transform of `n / 2` per frame between two sweeps.  Immutable after `new`, like the reference's planners.
+        pub struct $mdct {
+            pub(crate) h: *mut Opaque,
+            pub(crate) signal_len: usize,
+            pub(crate) n: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in
+        // device buffers of its own (host-slice calls)
+        unsafe impl Send for $mdct {}
+        unsafe impl Sync for $mdct {}
+        impl $mdct {
+            /// `window`: `2 n` values, or `None` for the sine window.  `padded`: frames from sample `-n` on, so that every
+            /// sample lies in two.  Panics with "invalid argument" unless n is even, 2 <= n <= 2^29, 1 <= signal_len <=
+            /// 2^29, signal_len >= 2 n without `padded`, and frames * n <= 2^30
+            pub fn new(signal_len: usize, n: usize, window: Option<&[$t]>, padded: bool) -> Self {
+                if let Some(w) = window {
+                    assert_eq!(w.len(), 2 * n, "invalid argument");
+                }
+                let mut h = std::ptr::null_mut();
+                let w = window.map_or(std::ptr::null(), |w| w.as_ptr());
+                ffi::check(unsafe { ffi::$new(signal_len, n, w, padded as c_int, &mut h) });
+                Self { h, signal_len, n }
+            }
+            pub fn signal_len(&self) -> usize {
+                self.signal_len
+            }
+            pub fn n(&self) -> usize {
+                self.n
+            }
+            pub fn frames(&self) -> usize {
+                unsafe { ffi::$frames(self.h) }
+            }
+            /// how far the window is from perfect reconstruction (0 for the sine, Vorbis and Kaiser-Bessel-derived windows);
+            /// reported, never refused
+            pub fn tdac_defect(&self) -> f64 {
+                unsafe { ffi::$defect(self.h) }
+            }
+            /// elements of the workspace a device call of `batch` signals works in
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+            /// the least workspace a call runs in: one frame forward, one signal's frames for the inverse
+            pub fn workspace_min(&self, inverse: bool) -> usize {
+                unsafe { ffi::$ws_min(self.h, inverse as c_int) }
+            }
+        }
+        impl Drop for $mdct {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_mdct!(PlannerMdct64, f64, phast_planner_mdct64_new, phast_planner_mdct64_free, phast_planner_mdct64_frames,
+                   phast_planner_mdct64_workspace_len, phast_planner_mdct64_workspace_min, phast_planner_mdct64_tdac_defect);
+impl_planner_mdct!(PlannerMdct32, f32, phast_planner_mdct32_new, phast_planner_mdct32_free, phast_planner_mdct32_frames,
+                   phast_planner_mdct32_workspace_len, phast_planner_mdct32_workspace_min, phast_planner_mdct32_tdac_defect);
+
 /// Which part of the full convolution a planner yields (PHAST_CONV_* of the C ABI)
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum ConvMode {
