@@ -24,6 +24,8 @@
 //                                                            istft_f64/f32_with_planner, enum PadMode -- torch.stft / istft
 //   (none: no lapped transforms upstream)                    class PlannerMdct64/32, mdct_f64/f32_with_planner,
 //                                                            imdct_f64/f32_with_planner
+//   (none: no spectral estimation upstream)                  class PlannerPsd64/32, psd_f64/f32_with_planner,
+//                                                            csd_f64/f32_with_planner
 //   (none: no convolution upstream)                          class PlannerConv64/32, conv_f64/f32_with_planner, enum ConvMode --
 //                                                            scipy.signal.convolve / correlate by overlap-save
 //   (none: no convolution upstream)                          class PlannerConvNd64/32, convnd_f64/f32_with_planner -- the same of
@@ -569,6 +571,68 @@ PHASTFT_PLANNER_MDCT(PlannerMdct32, phast_planner_mdct32, 32, float)
 PHASTFT_MDCT(f64, double, PlannerMdct64)
 PHASTFT_MDCT(f32, float, PlannerMdct32)
 #undef PHASTFT_MDCT
+
+// ---- Welch spectral estimation (no reference counterpart; scipy.signal.welch / csd / spectrogram) ----
+enum class Detrend : int { None = PHAST_DETREND_NONE, Constant = PHAST_DETREND_CONSTANT };
+enum class PsdScaling : int { Density = PHAST_PSD_DENSITY, Spectrum = PHAST_PSD_SPECTRUM };
+#define PHASTFT_PLANNER_PSD(NAME, CT, SFX, T)                                                                    \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* segments of `nperseg` samples `hop` apart, zero-padded to `nfft`; `window`: nperseg doubles, or empty for Hann */ \
+        NAME(std::size_t signal_len, std::size_t nperseg, std::size_t hop, std::size_t nfft,                     \
+             Slice<const double> window = Slice<const double>(nullptr, 0), Detrend detrend = Detrend::Constant,  \
+             PsdScaling scaling = PsdScaling::Density, double fs = 1.0) {                                        \
+            if (window.len && window.len != nperseg) check(PHAST_ERR_INVALID_ARG);                               \
+            check(phast_planner_psd##SFX##_new(signal_len, nperseg, hop, nfft, window.len ? window.ptr : nullptr, \
+                                               static_cast<int>(detrend), static_cast<int>(scaling), fs, &h_));  \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }                                                   \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_psd##SFX##_free(h_);                                                           \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_psd##SFX##_describe(h_, &s[0], s.size()));                                       \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_psd##SFX##_device_bytes(h_); }                   \
+        std::size_t segments() const { return phast_planner_psd##SFX##_segments(h_); }                           \
+        std::size_t bins() const { return phast_planner_psd##SFX##_bins(h_); }                                   \
+        /* frames per slab of the sum over frames: a function of segments() and bins() alone */                  \
+        std::size_t slab() const { return phast_planner_psd##SFX##_slab(h_); }                                   \
+        /* elements of T a _dev call of `batch` signals (cross: pairs) works in; workspace_min: the least a call runs in */ \
+        std::size_t workspace_len(std::size_t batch = 1, bool cross = false) const {                             \
+            return phast_planner_psd##SFX##_workspace_len(h_, batch, cross);                                     \
+        }                                                                                                        \
+        std::size_t workspace_min(bool cross = false) const { return phast_planner_psd##SFX##_workspace_min(h_, cross); } \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+    };
+PHASTFT_PLANNER_PSD(PlannerPsd64, phast_planner_psd64, 64, double)
+PHASTFT_PLANNER_PSD(PlannerPsd32, phast_planner_psd32, 32, float)
+#undef PHASTFT_PLANNER_PSD
+
+// one host signal (csd: one pair) of L samples -> bins values, or segments * bins frame-major for average = false; blocking.
+// csd: P_xy = <conj(X) Y> in two planes; pxx and pyy may be empty
+#define PHASTFT_PSD(FS, T, P)                                                                                    \
+    inline void psd_##FS##_with_planner(Slice<const T> signal, Slice<T> out, const P &planner, bool average = true) { \
+        check(phast_psd_##FS##_with_planner(signal.ptr, signal.len, out.ptr, out.len, average ? 1 : 0, planner.get())); \
+    }                                                                                                            \
+    inline void csd_##FS##_with_planner(Slice<const T> x, Slice<const T> y, Slice<T> out_re, Slice<T> out_im, const P &planner, \
+                                        Slice<T> pxx = Slice<T>(nullptr, 0), Slice<T> pyy = Slice<T>(nullptr, 0), \
+                                        bool average = true) {                                                   \
+        check(phast_csd_##FS##_with_planner(x.ptr, x.len, y.ptr, y.len, out_re.ptr, out_re.len, out_im.ptr, out_im.len, \
+                                            pxx.len ? pxx.ptr : nullptr, pxx.len, pyy.len ? pyy.ptr : nullptr, pyy.len, \
+                                            average ? 1 : 0, planner.get()));                                    \
+    }
+PHASTFT_PSD(f64, double, PlannerPsd64)
+PHASTFT_PSD(f32, float, PlannerPsd32)
+#undef PHASTFT_PSD
 
 // ---- overlap-save convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve / correlate) ----
 enum class ConvMode : int { Full = PHAST_CONV_FULL, Same = PHAST_CONV_SAME, Valid = PHAST_CONV_VALID };

@@ -576,6 +576,92 @@ int phast_imdct_f32_dev(const float *d_coefs, float *d_signal, size_t signal_len
 int phast_planner_mdct32_time_stages(const phast_planner_mdct32 *p, int inverse, float *d_signal, float *d_coefs, size_t batch, float *d_work, size_t work_len,
                                      int reps, float *stage_ms, void *stream);
 
+/* ---- Welch spectral estimation: welch, csd, spectrogram (no reference counterpart; scipy.signal.welch / csd / spectrogram
+ * with return_onesided = True, mode = "psd", boundary = None, padded = False).
+ *     sizes     L samples per signal, P = nperseg, H = hop = nperseg - noverlap, F = nfft; 1 <= H <= P <= F <= 2^29,
+ *               P <= L <= 2^29.  Segments S = 1 + floor((L - P) / H); the tail beyond the last segment is not read.
+ *               bins = floor(F / 2) + 1.  fd = F rounded up to 16 bytes; S fd <= 2^30.
+ *     window    P host values (double for both types); NULL: Hann, scipy.signal.get_window("hann", P), the periodic form,
+ *               built on the host in long double.
+ *     segment   r_f[j] = w[j] (x[f H + j] - m_f) for j < P, and 0 for P <= j < F.  m_f is the mean of the P samples of the
+ *               segment for detrend = PHAST_DETREND_CONSTANT (scipy's default) and 0 for PHAST_DETREND_NONE.  X_f = rfft_F(r_f).
+ *     scale     PHAST_PSD_DENSITY: sigma = 1 / (fs sum w^2).  PHAST_PSD_SPECTRUM: sigma = 1 / (sum w)^2.  sigma is computed at
+ *               _new in double from the values given; a window whose sum w^2 (density) or sum w (spectrum) is 0, and
+ *               fs <= 0, are PHAST_ERR_INVALID_ARG.
+ *     one side  c_k = 2 for every bin, but c_0 = 1 and c_{F/2} = 1 when F is even.
+ *     auto      P_xx[k] = sigma c_k (1/S) sum_f |X_f[k]|^2
+ *     cross     P_xy[k] = sigma c_k (1/S) sum_f conj(X_f[k]) Y_f[k] (scipy's csd convention), two planes: re and im.  The cross
+ *               call also returns P_xx and P_yy from the same pass where d_pxx / d_pyy are not NULL (coherence needs all three).
+ *     average   1: the outputs are [batch][bins], packed.  0 (spectrogram): no sum over f and no 1/S; the outputs are
+ *               frame-major, [batch][S][bins], laid out as the STFT's planes (scipy.signal.spectrogram returns the transpose).
+ * Numerics: m_f is accumulated and kept in double for both types -- as the segment's first sample and the double mean of the
+ * differences from it, so that an offset of the signal costs nothing --, x - m_f is formed in double, multiplied by w and
+ * then rounded to T.  The sums over frames are formed and carried in double, partial sums in the workspace included, and rounded
+ * to T once, at the final store: the f32 error does not grow with S.  The frames of a signal are summed in slabs of
+ * _slab(p) frames (a function of S and bins alone), every sum in ascending frame order, without atomics: the result's bits
+ * do not depend on the batch, on work_len, on the stream or on a graph replay wherever the real transform's do not (F not a
+ * power of two; powers of two up to 4096).
+ * Out of scope: linear detrend, average = "median", two-sided output, complex input, scipy's boundary / padded extension,
+ * modes other than psd, one window per signal of a batch.
+ * The caller's device workspace holds phast_planner_psd*_workspace_len(p, batch, cross) elements of T (cross = 1: for the
+ * phast_csd_* calls): all frames of the batch in one chunk, their spectrum planes, the means, the partial rows and the real
+ * planner's own workspace.  Any work_len >= _workspace_min(p, cross) runs the flattened (signal, frame) index in chunks of
+ * whole frames.  Signal b starts at d_x + b sig_dist (sig_dist >= L; batch 1 ignores it).  The inputs are not written.
+ * Every argument rule is checked before the device is touched; the codes are the STFT's.  The *_with_planner forms take host
+ * slices of one signal (out_len = bins, or S bins for average = 0), stage through a device buffer of their own and block. */
+#define PHAST_DETREND_NONE 0
+#define PHAST_DETREND_CONSTANT 1
+#define PHAST_PSD_DENSITY 0
+#define PHAST_PSD_SPECTRUM 1
+typedef struct phast_planner_psd64 phast_planner_psd64; /* PlannerPsd64 */
+int phast_planner_psd64_new(size_t signal_len, size_t nperseg, size_t hop, size_t nfft, const double *window, int detrend, int scaling, double fs,
+                             phast_planner_psd64 **out);
+void phast_planner_psd64_free(phast_planner_psd64 *p);
+int phast_planner_psd64_describe(const phast_planner_psd64 *p, char *buf, size_t buf_len);
+size_t phast_planner_psd64_device_bytes(const phast_planner_psd64 *p);
+size_t phast_planner_psd64_segments(const phast_planner_psd64 *p);
+size_t phast_planner_psd64_bins(const phast_planner_psd64 *p);
+size_t phast_planner_psd64_slab(const phast_planner_psd64 *p); /* Q: the frames per slab of the sum over frames */
+size_t phast_planner_psd64_workspace_len(const phast_planner_psd64 *p, size_t batch, int cross);
+size_t phast_planner_psd64_workspace_min(const phast_planner_psd64 *p, int cross);
+int phast_psd_f64_with_planner(const double *signal, size_t signal_len, double *out, size_t out_len, int average, const phast_planner_psd64 *planner);
+int phast_csd_f64_with_planner(const double *x, size_t x_len, const double *y, size_t y_len, double *out_re, size_t re_len, double *out_im, size_t im_len,
+                              double *pxx, size_t pxx_len, double *pyy, size_t pyy_len, int average, const phast_planner_psd64 *planner);
+int phast_psd_f64_dev(const double *d_x, double *d_out, size_t signal_len, size_t batch, size_t sig_dist, int average,
+                     const phast_planner_psd64 *planner, double *d_work, size_t work_len, void *stream);
+int phast_csd_f64_dev(const double *d_x, const double *d_y, double *d_out_re, double *d_out_im, double *d_pxx, double *d_pyy, size_t signal_len, size_t batch,
+                     size_t sig_dist, int average, const phast_planner_psd64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/psd_rate.py): stage_ms[3] = average milliseconds of the mean and frame sweeps, of the real transform
+ * and of the accumulate and final sweeps (average = 0: the point sweep) over `reps` auto-spectrum calls of `batch` signals at
+ * distance L in ONE chunk (work_len >= phast_planner_psd*_workspace_len(p, batch, 0)).  slab: 0, or the frames per slab to sum
+ * with instead of _slab(p) (not less than it; slab = segments is one slab: what the slab rule buys).  Blocks until done. */
+int phast_planner_psd64_time_stages(const phast_planner_psd64 *p, double *d_signal, double *d_out, size_t batch, int average, size_t slab, double *d_work, size_t work_len,
+                                     int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_psd32 phast_planner_psd32; /* PlannerPsd32 */
+int phast_planner_psd32_new(size_t signal_len, size_t nperseg, size_t hop, size_t nfft, const double *window, int detrend, int scaling, double fs,
+                             phast_planner_psd32 **out);
+void phast_planner_psd32_free(phast_planner_psd32 *p);
+int phast_planner_psd32_describe(const phast_planner_psd32 *p, char *buf, size_t buf_len);
+size_t phast_planner_psd32_device_bytes(const phast_planner_psd32 *p);
+size_t phast_planner_psd32_segments(const phast_planner_psd32 *p);
+size_t phast_planner_psd32_bins(const phast_planner_psd32 *p);
+size_t phast_planner_psd32_slab(const phast_planner_psd32 *p); /* Q: the frames per slab of the sum over frames */
+size_t phast_planner_psd32_workspace_len(const phast_planner_psd32 *p, size_t batch, int cross);
+size_t phast_planner_psd32_workspace_min(const phast_planner_psd32 *p, int cross);
+int phast_psd_f32_with_planner(const float *signal, size_t signal_len, float *out, size_t out_len, int average, const phast_planner_psd32 *planner);
+int phast_csd_f32_with_planner(const float *x, size_t x_len, const float *y, size_t y_len, float *out_re, size_t re_len, float *out_im, size_t im_len,
+                              float *pxx, size_t pxx_len, float *pyy, size_t pyy_len, int average, const phast_planner_psd32 *planner);
+int phast_psd_f32_dev(const float *d_x, float *d_out, size_t signal_len, size_t batch, size_t sig_dist, int average,
+                     const phast_planner_psd32 *planner, float *d_work, size_t work_len, void *stream);
+int phast_csd_f32_dev(const float *d_x, const float *d_y, float *d_out_re, float *d_out_im, float *d_pxx, float *d_pyy, size_t signal_len, size_t batch,
+                     size_t sig_dist, int average, const phast_planner_psd32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/psd_rate.py): stage_ms[3] = average milliseconds of the mean and frame sweeps, of the real transform
+ * and of the accumulate and final sweeps (average = 0: the point sweep) over `reps` auto-spectrum calls of `batch` signals at
+ * distance L in ONE chunk (work_len >= phast_planner_psd*_workspace_len(p, batch, 0)).  slab: 0, or the frames per slab to sum
+ * with instead of _slab(p) (not less than it; slab = segments is one slab: what the slab rule buys).  Blocks until done. */
+int phast_planner_psd32_time_stages(const phast_planner_psd32 *p, float *d_signal, float *d_out, size_t batch, int average, size_t slab, float *d_work, size_t work_len,
+                                     int reps, float *stage_ms, void *stream);
+
 /* ---- overlap-save FIR convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve /
  * correlate(x, h, mode, method="direct")).  Signal x of L samples, K taps h, both real:
  *     full[t] = sum_j g[j] x[t - j], t in [0, L + K - 1); g = h (flip = 0: convolution) or g[j] = h[K - 1 - j] (flip = 1:

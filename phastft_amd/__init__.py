@@ -27,6 +27,9 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
     (none: no lapped transforms)                    PlannerMdct64/32, mdct_batched, imdct_batched,
                                                     mdct_f64/f32_with_planner, imdct_f64/f32_with_planner, mdct, imdct,
                                                     mdct_window
+    (none: no spectral estimation)                  PlannerPsd64/32, psd_batched, csd_batched,
+                                                    psd_f64/f32_with_planner, csd_f64/f32_with_planner, welch, csd,
+                                                    spectrogram, periodogram, coherence
     (none: no convolution)                          PlannerConv64/32, conv_batched, conv_f64/f32_with_planner,
                                                     fftconvolve, correlate
     (none: no convolution)                          PlannerConvNd64/32, convnd_batched, convnd_f64/f32_with_planner,
@@ -90,6 +93,8 @@ __all__ = [
     "istft_f64_with_planner", "istft_f32_with_planner",
     "PlannerMdct64", "PlannerMdct32", "mdct_batched", "imdct_batched", "mdct_f64_with_planner", "mdct_f32_with_planner",
     "imdct_f64_with_planner", "imdct_f32_with_planner", "mdct", "imdct", "mdct_window",
+    "PlannerPsd64", "PlannerPsd32", "psd_batched", "csd_batched", "psd_f64_with_planner", "psd_f32_with_planner",
+    "csd_f64_with_planner", "csd_f32_with_planner", "welch", "csd", "spectrogram", "periodogram", "coherence",
     "PlannerConv64", "PlannerConv32", "conv_batched", "conv_f64_with_planner", "conv_f32_with_planner", "fftconvolve",
     "correlate",
     "PlannerConvNd64", "PlannerConvNd32", "convnd_batched", "convnd_f64_with_planner", "convnd_f32_with_planner",
@@ -1359,6 +1364,283 @@ def imdct(X, length: int, window="sine", padded: bool = True):
     imdct_batched(X.contiguous().reshape(-1), out, planner, 1)
     torch.cuda.current_stream().synchronize()
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Welch spectral estimation (no reference counterpart; scipy.signal.welch / csd / spectrogram / periodogram / coherence)
+# ---------------------------------------------------------------------------------------------
+_DETRENDS = {"constant": 1, "none": 0}
+_SCALINGS = {"density": 0, "spectrum": 1}
+
+
+def _detrend_code(detrend) -> int:
+    if detrend is None or detrend is False:
+        return 0
+    if isinstance(detrend, str) and detrend in _DETRENDS:
+        return _DETRENDS[detrend]
+    raise ValueError(f"detrend must be 'constant', 'none', False or None, not {detrend!r} (linear detrending is out of scope)")
+
+
+def _psd_window(window, nperseg: int):
+    """the ``nperseg`` window values as float64, or None for the Hann window the library builds itself"""
+    if window is None or (isinstance(window, str) and window in ("hann", "hanning")):
+        return None
+    if isinstance(window, str) and window in ("boxcar", "box", "ones", "rect", "rectangular"):
+        return np.ones(nperseg, np.float64)
+    if isinstance(window, (str, tuple, float, int)):
+        try:
+            from scipy.signal import get_window
+        except ImportError:
+            raise ValueError(f"window {window!r}: without scipy only 'hann', 'boxcar' and arrays are accepted") from None
+        return np.ascontiguousarray(get_window(window, nperseg), dtype=np.float64)
+    if _is_torch(window):
+        window = window.detach().cpu().numpy()
+    w = np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
+    if w.size != nperseg:
+        raise ValueError(f"window: {w.size} values for nperseg = {nperseg}")
+    return w
+
+
+class PlannerPsd64(_AnyHandle):
+    """f64 Welch spectral estimation of signals of ``signal_len`` samples, with scipy.signal's definitions: segments of
+    ``nperseg`` samples ``hop`` apart (None: ``nperseg - nperseg // 2``, scipy's default overlap), each less its mean
+    (``detrend="constant"``; ``"none"``, False or None: as it is), times ``window`` (``nperseg`` values, a torch tensor, or a
+    name: any that ``scipy.signal.get_window`` takes if scipy imports, else ``"hann"`` or ``"boxcar"``; None: Hann),
+    zero-padded to ``nfft`` (None: ``nperseg``) and transformed.  ``scaling``: ``"density"`` (V^2/Hz at sampling rate ``fs``)
+    or ``"spectrum"`` (V^2).  One-sided: ``bins = nfft // 2 + 1``.  ``segments`` frames per signal; the sums over them run
+    in slabs of ``slab`` frames."""
+
+    _prefix = "psd"
+
+    def __init__(self, signal_len: int, nperseg: int, hop: int | None = None, nfft: int | None = None, window=None,
+                 detrend="constant", scaling: str = "density", fs: float = 1.0):
+        det = _detrend_code(detrend)
+        if scaling not in _SCALINGS:
+            raise ValueError(f"scaling must be 'density' or 'spectrum', not {scaling!r}")
+        hop = nperseg - nperseg // 2 if hop is None else hop
+        nfft = nperseg if nfft is None else nfft
+        w = _psd_window(window, nperseg)
+        self._new(signal_len, nperseg, hop, nfft, None if w is None else w.ctypes.data_as(C.c_void_p), det, _SCALINGS[scaling],
+                  float(fs))
+        self.n = self.signal_len = signal_len
+        self.nperseg, self.hop, self.nfft, self.fs = nperseg, hop, nfft, float(fs)
+        self.detrend, self.scaling = "constant" if det else "none", scaling
+        self.segments = int(self._fn("segments")(self._h))
+        self.bins = int(self._fn("bins")(self._h))
+        self.slab = int(self._fn("slab")(self._h))
+
+    def frequencies(self):
+        """the ``bins`` sample frequencies, as numpy.fft.rfftfreq(nfft, 1 / fs)"""
+        return np.fft.rfftfreq(self.nfft, 1 / self.fs)
+
+    def times(self):
+        """the ``segments`` segment centres, as scipy.signal.spectrogram's"""
+        return (np.arange(self.segments, dtype=np.float64) * self.hop + self.nperseg / 2) / self.fs
+
+    def workspace_len(self, batch: int = 1, cross: bool = False) -> int:
+        """Elements of T a device call of ``batch`` signals (``cross``: pairs of signals, :func:`csd_batched`) works in.  A
+        smaller workspace of at least ``workspace_min(cross)`` runs the frames in chunks, to the same bits."""
+        return int(self._fn("workspace_len")(self._h, batch, bool(cross)))
+
+    def workspace_min(self, cross: bool = False) -> int:
+        return int(self._fn("workspace_min")(self._h, bool(cross)))
+
+    def time_stages(self, signal, out, batch: int = 1, average: bool = True, workspace=None, reps: int = 10, slab: int = 0):
+        """Average HIP-event milliseconds of (the mean and frame sweeps, the real transform, the accumulate and final sweeps)
+        of an auto-spectrum call of ``batch`` signals at distance L on device tensors (measurement hook).  ``slab``: the frames
+        per slab to sum with instead of the planner's (not fewer; ``segments``: one slab)"""
+        x, o = _Slice(signal, self._dtype, "signal"), _Slice(out, self._dtype, "out")
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 3)()
+        _check(self._fn("time_stages")(self._h, x.ptr, o.ptr, batch, bool(average), slab, ws.ptr, ws.len, reps, ms, _stream()))
+        return [float(v) for v in ms]
+
+
+class PlannerPsd32(PlannerPsd64):
+    """f32 twin of :class:`PlannerPsd64` (the window, the means and the sums over frames stay in double)"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def _psd_workspace(planner, batch, cross, workspace):
+    if workspace is None:
+        import torch
+
+        workspace = torch.empty(max(1, planner.workspace_len(batch, cross)),
+                                dtype=torch.float64 if planner._dtype == np.float64 else torch.float32, device="cuda")
+    return _any_workspace(planner, batch, workspace)
+
+
+def psd_batched(signal, out, planner, batch: int, average: bool = True, sig_dist: int | None = None, workspace=None) -> None:
+    """Device-resident batch of Welch auto spectra: signal b at ``b*sig_dist`` (default L, any distance >= L); bin k of signal
+    b at ``b*bins + k`` of ``out``.  ``average=False`` (the spectrogram): bin k of segment f of signal b at
+    ``(b*segments + f)*bins + k``.  ``workspace``: a device tensor of the planner's type of at least
+    ``planner.workspace_min()`` elements; by default one of ``planner.workspace_len(batch)`` from torch's allocator.  The
+    signal is not written."""
+    dtype, fs = planner._dtype, "f64" if planner._dtype == np.float64 else "f32"
+    x, o = _Slice(signal, dtype, "signal"), _Slice(out, dtype, "out")
+    if not _same_place(x, o):
+        raise TypeError("psd_batched needs device tensors")
+    n, pts = planner.signal_len, planner.bins * (1 if average else planner.segments)
+    sig_dist = n if sig_dist is None else sig_dist
+    _need("signal", x.len, batch, sig_dist, n)
+    _need("out", o.len, batch, pts, pts)
+    ws = _psd_workspace(planner, batch, False, workspace)
+    _check(_call(f"phast_psd_{fs}_dev", x.ptr, o.ptr, n, batch, sig_dist, bool(average), planner._h, ws.ptr, ws.len, _stream()))
+
+
+def csd_batched(x, y, out_re, out_im, planner, batch: int, pxx=None, pyy=None, average: bool = True,
+                sig_dist: int | None = None, workspace=None) -> None:
+    """Device-resident batch of Welch cross spectra P_xy = <conj(X) Y> (scipy.signal.csd's convention) into the planes
+    ``out_re`` and ``out_im``, laid out as :func:`psd_batched`'s ``out``; ``pxx`` and ``pyy``, where given, receive the two auto
+    spectra from the same pass.  ``workspace``: at least ``planner.workspace_min(True)`` elements."""
+    dtype, fs = planner._dtype, "f64" if planner._dtype == np.float64 else "f32"
+    names = ("x", "y", "out_re", "out_im", "pxx", "pyy")
+    sl = [None if t is None else _Slice(t, dtype, w) for t, w in zip((x, y, out_re, out_im, pxx, pyy), names)]
+    if any(v is None for v in sl[:4]):
+        raise TypeError("csd_batched needs x, y, out_re and out_im")
+    if not _same_place(*(v for v in sl if v is not None)):
+        raise TypeError("csd_batched needs device tensors")
+    n, pts = planner.signal_len, planner.bins * (1 if average else planner.segments)
+    sig_dist = n if sig_dist is None else sig_dist
+    for v, w in zip(sl, names):
+        if v is not None:
+            _need(w, v.len, batch, *((sig_dist, n) if w in ("x", "y") else (pts, pts)))
+    ws = _psd_workspace(planner, batch, True, workspace)
+    _check(_call(f"phast_csd_{fs}_dev", *(None if v is None else v.ptr for v in sl), n, batch, sig_dist, bool(average),
+                 planner._h, ws.ptr, ws.len, _stream()))
+
+
+def _psd_host(fs, dtype, arrays, names, average, planner):
+    sl = [None if t is None else _Slice(t, dtype, w) for t, w in zip(arrays, names)]
+    if _same_place(*(v for v in sl if v is not None)):
+        raise TypeError(f"the *_{fs}_with_planner forms take host arrays (psd_batched / csd_batched take device tensors)")
+    return [x for v in sl for x in ((None, 0) if v is None else (v.ptr, v.len))]
+
+
+def psd_f64_with_planner(signal, out, planner: PlannerPsd64, average: bool = True) -> None:
+    """f64 Welch auto spectrum of one host signal of L samples into a host array of bins (``average=False``: segments * bins)
+    values (blocking)"""
+    _check(_call("phast_psd_f64_with_planner", *_psd_host("f64", np.float64, (signal, out), ("signal", "out"), average, planner),
+                 bool(average), planner._h))
+
+
+def psd_f32_with_planner(signal, out, planner: PlannerPsd32, average: bool = True) -> None:
+    """f32 twin of :func:`psd_f64_with_planner`"""
+    _check(_call("phast_psd_f32_with_planner", *_psd_host("f32", np.float32, (signal, out), ("signal", "out"), average, planner),
+                 bool(average), planner._h))
+
+
+_CSD_NAMES = ("x", "y", "out_re", "out_im", "pxx", "pyy")
+
+
+def csd_f64_with_planner(x, y, out_re, out_im, planner: PlannerPsd64, pxx=None, pyy=None, average: bool = True) -> None:
+    """f64 Welch cross spectrum of one pair of host signals into host planes (blocking); ``pxx``, ``pyy``: the auto spectra"""
+    _check(_call("phast_csd_f64_with_planner", *_psd_host("f64", np.float64, (x, y, out_re, out_im, pxx, pyy), _CSD_NAMES, average,
+                                                          planner), bool(average), planner._h))
+
+
+def csd_f32_with_planner(x, y, out_re, out_im, planner: PlannerPsd32, pxx=None, pyy=None, average: bool = True) -> None:
+    """f32 twin of :func:`csd_f64_with_planner`"""
+    _check(_call("phast_csd_f32_with_planner", *_psd_host("f32", np.float32, (x, y, out_re, out_im, pxx, pyy), _CSD_NAMES, average,
+                                                          planner), bool(average), planner._h))
+
+
+def _psd_setup(x, fs, window, nperseg, noverlap, nfft, detrend, scaling, overlap_div=2):
+    """the planner, the batch and the leading shape for a device tensor whose last axis is time"""
+    import torch
+
+    if not _is_torch(x) or x.device.type != "cuda" or x.dtype not in (torch.float64, torch.float32) or x.dim() < 1:
+        raise TypeError("need a float64 or float32 device tensor")
+    length = x.shape[-1]
+    nperseg = 256 if nperseg is None else int(nperseg)
+    if nperseg > length:
+        import warnings
+
+        warnings.warn(f"nperseg = {nperseg} is greater than input length = {length}, using nperseg = {length}", stacklevel=3)
+        nperseg = length
+    noverlap = nperseg // overlap_div if noverlap is None else int(noverlap)
+    if not 0 <= noverlap < nperseg:
+        raise ValueError("noverlap must be less than nperseg")
+    nfft = nperseg if nfft is None else int(nfft)
+    if nfft < nperseg:
+        raise ValueError("nfft must be greater than or equal to nperseg")
+    cls = PlannerPsd64 if x.dtype == torch.float64 else PlannerPsd32
+    planner = cls(length, nperseg, nperseg - noverlap, nfft, window, detrend, scaling, fs)
+    batch = x.numel() // length
+    return planner, batch, tuple(x.shape[:-1])
+
+
+def _psd_freqs(planner, x):
+    import torch
+
+    return torch.as_tensor(planner.frequencies(), dtype=x.dtype, device=x.device)
+
+
+def welch(x, fs: float = 1.0, window="hann", nperseg: int | None = 256, noverlap: int | None = None, nfft: int | None = None,
+          detrend="constant", scaling: str = "density"):
+    """scipy.signal.welch over the last axis of a real device tensor, through a planner of its own: ``(freqs, Pxx)`` as new
+    device tensors, ``Pxx`` of shape ``x.shape[:-1] + (bins,)``.  ``nperseg`` greater than the length is clamped to it, with
+    scipy's warning."""
+    import torch
+
+    planner, batch, lead = _psd_setup(x, fs, window, nperseg, noverlap, nfft, detrend, scaling)
+    out = torch.empty(batch * planner.bins, dtype=x.dtype, device=x.device)
+    psd_batched(x.contiguous().reshape(-1), out, planner, batch)
+    torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+    return _psd_freqs(planner, x), out.reshape(lead + (planner.bins,))
+
+
+def _csd_run(x, y, fs, window, nperseg, noverlap, nfft, detrend, scaling, autos):
+    import torch
+
+    if not _is_torch(y) or y.shape != x.shape or y.dtype != x.dtype or y.device != x.device:
+        raise TypeError("x and y must be device tensors of one shape and type")
+    planner, batch, lead = _psd_setup(x, fs, window, nperseg, noverlap, nfft, detrend, scaling)
+    outs = [torch.empty(batch * planner.bins, dtype=x.dtype, device=x.device) for _ in range(4 if autos else 2)]
+    csd_batched(x.contiguous().reshape(-1), y.contiguous().reshape(-1), outs[0], outs[1], planner, batch, *outs[2:])
+    torch.cuda.current_stream().synchronize()
+    return _psd_freqs(planner, x), [o.reshape(lead + (planner.bins,)) for o in outs]
+
+
+def csd(x, y, fs: float = 1.0, window="hann", nperseg: int | None = 256, noverlap: int | None = None, nfft: int | None = None,
+        detrend="constant", scaling: str = "density"):
+    """scipy.signal.csd over the last axis of two real device tensors of one shape: ``(freqs, Pxy)``, ``Pxy`` complex"""
+    import torch
+
+    freqs, (re, im) = _csd_run(x, y, fs, window, nperseg, noverlap, nfft, detrend, scaling, False)
+    return freqs, torch.complex(re, im)
+
+
+def coherence(x, y, fs: float = 1.0, window="hann", nperseg: int | None = 256, noverlap: int | None = None,
+              nfft: int | None = None, detrend="constant"):
+    """scipy.signal.coherence: ``(freqs, |Pxy|^2 / (Pxx Pyy))`` from one cross call (the last step is elementwise on bins
+    values)"""
+    freqs, (re, im, pxx, pyy) = _csd_run(x, y, fs, window, nperseg, noverlap, nfft, detrend, "density", True)
+    return freqs, (re * re + im * im) / (pxx * pyy)
+
+
+def spectrogram(x, fs: float = 1.0, window="hann", nperseg: int | None = 256, noverlap: int | None = None,
+                nfft: int | None = None, detrend="constant", scaling: str = "density"):
+    """scipy.signal.spectrogram with ``mode="psd"`` over the last axis of a real device tensor: ``(freqs, times, Sxx)``, ``Sxx``
+    of shape ``x.shape[:-1] + (bins, segments)`` (a transposed view of the frame-major result).  ``noverlap`` defaults to
+    ``nperseg // 8`` as scipy's does; the default window here is Hann, not scipy's Tukey(0.25), which needs scipy."""
+    import torch
+
+    planner, batch, lead = _psd_setup(x, fs, window, nperseg, noverlap, nfft, detrend, scaling, overlap_div=8)
+    out = torch.empty(batch * planner.segments * planner.bins, dtype=x.dtype, device=x.device)
+    psd_batched(x.contiguous().reshape(-1), out, planner, batch, average=False)
+    torch.cuda.current_stream().synchronize()
+    times = torch.as_tensor(planner.times(), dtype=x.dtype, device=x.device)
+    return _psd_freqs(planner, x), times, out.reshape(lead + (planner.segments, planner.bins)).transpose(-1, -2)
+
+
+def periodogram(x, fs: float = 1.0, window="boxcar", nfft: int | None = None, detrend="constant", scaling: str = "density"):
+    """scipy.signal.periodogram over the last axis: one segment of all L samples"""
+    if not _is_torch(x) or x.dim() < 1:
+        raise TypeError("need a float64 or float32 device tensor")
+    return welch(x, fs, window, x.shape[-1], 0, nfft, detrend, scaling)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 #include "planner_any_real.hpp"
 #include "planner_dct.hpp"
 #include "planner_mdct.hpp"
+#include "planner_psd.hpp"
 #include "planner_stft.hpp"
 #include "planner_conv.hpp"
 #include "planner_convnd.hpp"
@@ -46,6 +47,8 @@ struct phast_planner_stft64 : StftPlanner<double> {};
 struct phast_planner_stft32 : StftPlanner<float> {};
 struct phast_planner_mdct64 : MdctPlanner<double> {};
 struct phast_planner_mdct32 : MdctPlanner<float> {};
+struct phast_planner_psd64 : PsdPlanner<double> {};
+struct phast_planner_psd32 : PsdPlanner<float> {};
 struct phast_planner_conv64 : ConvPlanner<double> {};
 struct phast_planner_conv32 : ConvPlanner<float> {};
 struct phast_planner_convnd64 : ConvNdPlanner<double> {};
@@ -799,6 +802,76 @@ PHAST_STFT_API(32, f32, float)
     } PHAST_CATCH_RC
 PHAST_MDCT_API(64, f64, double)
 PHAST_MDCT_API(32, f32, float)
+
+// Welch spectral estimation (planner_psd.hpp): every argument rule and a wrong length come back before the device is touched
+#define PHAST_PSD_API(SFX, FS, T)                                                                                       \
+    int phast_planner_psd##SFX##_new(size_t signal_len, size_t nperseg, size_t hop, size_t nfft, const double *window,  \
+                                     int detrend, int scaling, double fs, phast_planner_psd##SFX **out) try {           \
+        return psd_planner_new<T>(signal_len, nperseg, hop, nfft, window, detrend, scaling, fs, out);                   \
+    } PHAST_CATCH_RC                                                                                                    \
+    void phast_planner_psd##SFX##_free(phast_planner_psd##SFX *p) try { delete p; } PHAST_CATCH_VOID                    \
+    int phast_planner_psd##SFX##_describe(const phast_planner_psd##SFX *p, char *buf, size_t len) try {                 \
+        if (!p || !buf || !len) return PHAST_ERR_INVALID_ARG;                                                           \
+        std::snprintf(buf, len, "%s", p->describe().c_str());                                                           \
+        return PHAST_OK;                                                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_psd##SFX##_device_bytes(const phast_planner_psd##SFX *p) try {                                 \
+        return p ? p->device_bytes() : 0;                                                                               \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_psd##SFX##_segments(const phast_planner_psd##SFX *p) try {                                     \
+        return p ? p->frames : 0;                                                                                       \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_psd##SFX##_bins(const phast_planner_psd##SFX *p) try {                                         \
+        return p ? p->bins : 0;                                                                                         \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_psd##SFX##_slab(const phast_planner_psd##SFX *p) try {                                         \
+        return p ? p->q : 0;                                                                                            \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_psd##SFX##_workspace_len(const phast_planner_psd##SFX *p, size_t batch, int cross) try {       \
+        return p ? p->workspace_len(batch, cross != 0) : 0;                                                             \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_psd##SFX##_workspace_min(const phast_planner_psd##SFX *p, int cross) try {                     \
+        return p ? p->workspace_min(cross != 0) : 0;                                                                    \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_psd##SFX##_time_stages(const phast_planner_psd##SFX *p, T *d_signal, T *d_out, size_t batch,      \
+                                             int average, size_t slab, T *d_work, size_t work_len, int reps,            \
+                                             float *stage_ms, void *stream) try {                                       \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(d_signal, d_out, batch, average, slab, d_work, work_len, reps, stage_ms,                  \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_psd_##FS##_with_planner(const T *signal, size_t signal_len, T *out, size_t out_len, int average,          \
+                                      const phast_planner_psd##SFX *p) try {                                            \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        T *o[4] = {out, nullptr, nullptr, nullptr};                                                                     \
+        const size_t n[4] = {out_len, 0, 0, 0};                                                                         \
+        return p->host(signal, signal_len, nullptr, 0, o, n, average);                                                  \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_csd_##FS##_with_planner(const T *x, size_t x_len, const T *y, size_t y_len, T *out_re, size_t re_len,     \
+                                      T *out_im, size_t im_len, T *pxx, size_t pxx_len, T *pyy, size_t pyy_len,         \
+                                      int average, const phast_planner_psd##SFX *p) try {                               \
+        if (!p || !y) return PHAST_ERR_INVALID_ARG;                                                                     \
+        T *o[4] = {out_re, out_im, pxx, pyy};                                                                           \
+        const size_t n[4] = {re_len, im_len, pxx_len, pyy_len};                                                         \
+        return p->host(x, x_len, y, y_len, o, n, average);                                                              \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_psd_##FS##_dev(const T *d_x, T *d_out, size_t signal_len, size_t batch, size_t sig_dist, int average,     \
+                             const phast_planner_psd##SFX *p, T *d_work, size_t work_len, void *stream) try {           \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        T *o[4] = {d_out, nullptr, nullptr, nullptr};                                                                   \
+        return p->run(d_x, nullptr, o, signal_len, batch, sig_dist, average, d_work, work_len,                          \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_csd_##FS##_dev(const T *d_x, const T *d_y, T *d_out_re, T *d_out_im, T *d_pxx, T *d_pyy,                  \
+                             size_t signal_len, size_t batch, size_t sig_dist, int average,                             \
+                             const phast_planner_psd##SFX *p, T *d_work, size_t work_len, void *stream) try {           \
+        if (!p || !d_y) return PHAST_ERR_INVALID_ARG;                                                                   \
+        T *o[4] = {d_out_re, d_out_im, d_pxx, d_pyy};                                                                   \
+        return p->run(d_x, d_y, o, signal_len, batch, sig_dist, average, d_work, work_len,                              \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC
+PHAST_PSD_API(64, f64, double)
+PHAST_PSD_API(32, f32, float)
 
 // Overlap-save convolution and correlation of real signals (planner_conv.hpp): every argument rule and a wrong length come
 // back before the device is touched

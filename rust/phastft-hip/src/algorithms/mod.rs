@@ -7,6 +7,7 @@ pub mod convnd;
 pub mod czt;
 pub mod dit;
 pub mod mdct;
+pub mod psd;
 pub mod nufft;
 pub mod nufft2d;
 pub mod nufft3d;

@@ -192,6 +192,51 @@ extern "C" {
         planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     pub(crate) fn phast_imdct_f32_dev(coefs: *const f32, signal: *mut f32, signal_len: usize, batch: usize, sig_dist: usize,
         planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // Welch spectral estimation (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/psd.rs)
+    pub(crate) fn phast_planner_psd64_new(signal_len: usize, nperseg: usize, hop: usize, nfft: usize, window: *const f64, detrend: c_int,
+        scaling: c_int, fs: f64, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_psd64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_psd64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_psd64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_psd64_segments(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_psd64_bins(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_psd64_slab(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_psd64_workspace_len(p: *const Opaque, batch: usize, cross: c_int) -> usize;
+    pub(crate) fn phast_planner_psd64_workspace_min(p: *const Opaque, cross: c_int) -> usize;
+    pub(crate) fn phast_planner_psd64_time_stages(p: *const Opaque, signal: *mut f64, out: *mut f64, batch: usize, average: c_int,
+        slab: usize, work: *mut f64, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_psd_f64_with_planner(signal: *const f64, signal_len: usize, out: *mut f64, out_len: usize, average: c_int,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_csd_f64_with_planner(x: *const f64, x_len: usize, y: *const f64, y_len: usize, out_re: *mut f64, re_len: usize,
+        out_im: *mut f64, im_len: usize, pxx: *mut f64, pxx_len: usize, pyy: *mut f64, pyy_len: usize, average: c_int,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_psd_f64_dev(x: *const f64, out: *mut f64, signal_len: usize, batch: usize, sig_dist: usize, average: c_int,
+        planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_csd_f64_dev(x: *const f64, y: *const f64, out_re: *mut f64, out_im: *mut f64, pxx: *mut f64, pyy: *mut f64,
+        signal_len: usize, batch: usize, sig_dist: usize, average: c_int, planner: *const Opaque, work: *mut f64, work_len: usize,
+        stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_psd32_new(signal_len: usize, nperseg: usize, hop: usize, nfft: usize, window: *const f64, detrend: c_int,
+        scaling: c_int, fs: f64, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_psd32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_psd32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_psd32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_psd32_segments(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_psd32_bins(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_psd32_slab(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_psd32_workspace_len(p: *const Opaque, batch: usize, cross: c_int) -> usize;
+    pub(crate) fn phast_planner_psd32_workspace_min(p: *const Opaque, cross: c_int) -> usize;
+    pub(crate) fn phast_planner_psd32_time_stages(p: *const Opaque, signal: *mut f32, out: *mut f32, batch: usize, average: c_int,
+        slab: usize, work: *mut f32, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_psd_f32_with_planner(signal: *const f32, signal_len: usize, out: *mut f32, out_len: usize, average: c_int,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_csd_f32_with_planner(x: *const f32, x_len: usize, y: *const f32, y_len: usize, out_re: *mut f32, re_len: usize,
+        out_im: *mut f32, im_len: usize, pxx: *mut f32, pxx_len: usize, pyy: *mut f32, pyy_len: usize, average: c_int,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_psd_f32_dev(x: *const f32, out: *mut f32, signal_len: usize, batch: usize, sig_dist: usize, average: c_int,
+        planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_csd_f32_dev(x: *const f32, y: *const f32, out_re: *mut f32, out_im: *mut f32, pxx: *mut f32, pyy: *mut f32,
+        signal_len: usize, batch: usize, sig_dist: usize, average: c_int, planner: *const Opaque, work: *mut f32, work_len: usize,
+        stream: *mut c_void) -> c_int;
     // overlap-save convolution and correlation (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/conv.rs)
     pub(crate) fn phast_planner_conv64_new(signal_len: usize, taps: *const f64, num_taps: usize, mode: c_int, flip: c_int,
         block: usize, out: *mut *mut Opaque) -> c_int;

@@ -61,6 +61,12 @@ pub use algorithms::mdct::{
     mdct_f64_dev, mdct_f64_with_planner,
 };
 pub use planner::{PlannerMdct32, PlannerMdct64};
+// Welch spectral estimation: welch, csd, spectrogram (an extension beyond PhastFT 0.3.0)
+pub use algorithms::psd::{
+    csd_f32_dev, csd_f32_with_planner, csd_f64_dev, csd_f64_with_planner, psd_f32_dev, psd_f32_with_planner, psd_f64_dev,
+    psd_f64_with_planner,
+};
+pub use planner::{Detrend, PlannerPsd32, PlannerPsd64, PsdScaling};
 // overlap-save convolution and correlation of real signals (an extension beyond PhastFT 0.3.0)
 pub use algorithms::conv::{conv_f32_dev, conv_f32_with_planner, conv_f64_dev, conv_f64_with_planner};
 pub use planner::{ConvMode, PlannerConv32, PlannerConv64};

@@ -372,6 +372,83 @@ impl_planner_mdct!(PlannerMdct64, f64, phast_planner_mdct64_new, phast_planner_m
 impl_planner_mdct!(PlannerMdct32, f32, phast_planner_mdct32_new, phast_planner_mdct32_free, phast_planner_mdct32_frames,
                    phast_planner_mdct32_workspace_len, phast_planner_mdct32_workspace_min, phast_planner_mdct32_tdac_defect);
 
+/// How a segment is detrended before it is windowed (PHAST_DETREND_* of the C ABI)
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Detrend {
+    None = 0,
+    Constant = 1,
+}
+/// The scale of a spectral estimate (PHAST_PSD_* of the C ABI): V^2 / Hz or V^2
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum PsdScaling {
+    Density = 0,
+    Spectrum = 1,
+}
+
+macro_rules! impl_planner_psd {
+    ($psd:ident, $new:ident, $free:ident, $segments:ident, $bins:ident, $slab:ident, $ws_len:ident, $ws_min:ident) => {
+        /// An extension beyond PhastFT 0.3.0: Welch spectral estimation of signals of `signal_len` samples with
+        /// scipy.signal's definitions (welch, csd, spectrogram): segments of `nperseg` samples `hop` apart, detrended,
+        /// windowed, zero-padded to `nfft` and transformed; one-sided, `nfft / 2 + 1` bins.  Immutable after `new`.
+        pub struct $psd {
+            pub(crate) h: *mut Opaque,
+            pub(crate) signal_len: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in
+        // device buffers of its own (host-slice calls)
+        unsafe impl Send for $psd {}
+        unsafe impl Sync for $psd {}
+        impl $psd {
+            /// `window`: `nperseg` values, or `None` for the periodic Hann window.  Panics with "invalid argument" unless
+            /// 1 <= hop <= nperseg <= nfft <= 2^29, nperseg <= signal_len <= 2^29, segments * nfft <= 2^30, fs > 0 and
+            /// the window's sum of squares (density) or sum (spectrum) is not zero
+            #[allow(clippy::too_many_arguments)]
+            pub fn new(signal_len: usize, nperseg: usize, hop: usize, nfft: usize, window: Option<&[f64]>, detrend: Detrend,
+                       scaling: PsdScaling, fs: f64) -> Self {
+                if let Some(w) = window {
+                    assert_eq!(w.len(), nperseg, "invalid argument");
+                }
+                let mut h = std::ptr::null_mut();
+                let w = window.map_or(std::ptr::null(), |w| w.as_ptr());
+                ffi::check(unsafe { ffi::$new(signal_len, nperseg, hop, nfft, w, detrend as c_int, scaling as c_int, fs, &mut h) });
+                Self { h, signal_len }
+            }
+            pub fn signal_len(&self) -> usize {
+                self.signal_len
+            }
+            pub fn segments(&self) -> usize {
+                unsafe { ffi::$segments(self.h) }
+            }
+            pub fn bins(&self) -> usize {
+                unsafe { ffi::$bins(self.h) }
+            }
+            /// frames per slab of the sum over frames: a function of `segments()` and `bins()` alone
+            pub fn slab(&self) -> usize {
+                unsafe { ffi::$slab(self.h) }
+            }
+            /// elements of the workspace a device call of `batch` signals (`cross`: pairs of signals) works in
+            pub fn workspace_len(&self, batch: usize, cross: bool) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch, cross as c_int) }
+            }
+            /// the least workspace a call runs in: one frame (`cross`: one frame of each signal)
+            pub fn workspace_min(&self, cross: bool) -> usize {
+                unsafe { ffi::$ws_min(self.h, cross as c_int) }
+            }
+        }
+        impl Drop for $psd {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_psd!(PlannerPsd64, phast_planner_psd64_new, phast_planner_psd64_free, phast_planner_psd64_segments,
+                  phast_planner_psd64_bins, phast_planner_psd64_slab, phast_planner_psd64_workspace_len,
+                  phast_planner_psd64_workspace_min);
+impl_planner_psd!(PlannerPsd32, phast_planner_psd32_new, phast_planner_psd32_free, phast_planner_psd32_segments,
+                  phast_planner_psd32_bins, phast_planner_psd32_slab, phast_planner_psd32_workspace_len,
+                  phast_planner_psd32_workspace_min);
+
 /// Which part of the full convolution a planner yields (PHAST_CONV_* of the C ABI)
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum ConvMode {
