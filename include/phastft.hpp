@@ -26,6 +26,8 @@
 //                                                            imdct_f64/f32_with_planner
 //   (none: no spectral estimation upstream)                  class PlannerPsd64/32, psd_f64/f32_with_planner,
 //                                                            csd_f64/f32_with_planner
+//   (none: no spectra of uneven samples upstream)            class PlannerLomb64/32, lombscargle_f64/f32_with_planner,
+//                                                            enum LombNorm -- scipy.signal.lombscargle
 //   (none: no convolution upstream)                          class PlannerConv64/32, conv_f64/f32_with_planner, enum ConvMode --
 //                                                            scipy.signal.convolve / correlate by overlap-save
 //   (none: no convolution upstream)                          class PlannerConvNd64/32, convnd_f64/f32_with_planner -- the same of
@@ -633,6 +635,62 @@ PHASTFT_PLANNER_PSD(PlannerPsd32, phast_planner_psd32, 32, float)
 PHASTFT_PSD(f64, double, PlannerPsd64)
 PHASTFT_PSD(f32, float, PlannerPsd32)
 #undef PHASTFT_PSD
+
+// ---- the Lomb-Scargle periodogram of unevenly spaced samples (no reference counterpart; scipy.signal.lombscargle) ----
+enum class LombNorm : int { Power = PHAST_LOMB_POWER, Normalize = PHAST_LOMB_NORMALIZE, Amplitude = PHAST_LOMB_AMPLITUDE };
+#define PHASTFT_PLANNER_LOMB(NAME, CT, SFX, T)                                                                   \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* M times, K frequencies in cycles per unit of time; `weights`: M doubles >= 0, or empty for equal weights */ \
+        NAME(Slice<const double> times, Slice<const double> freqs, Slice<const double> weights = Slice<const double>(nullptr, 0), \
+             bool floating_mean = false, double eps = sizeof(T) == 4 ? 1e-6 : 1e-12)                             \
+            : m_(times.len), k_(freqs.len) {                                                                     \
+            if (weights.len && weights.len != times.len) check(PHAST_ERR_INVALID_ARG);                           \
+            check(phast_planner_lomb##SFX##_new(times.ptr, times.len, freqs.ptr, freqs.len,                      \
+                                                weights.len ? weights.ptr : nullptr, floating_mean ? 1 : 0, eps, &h_)); \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_), m_(o.m_), k_(o.k_) { o.h_ = nullptr; }                               \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_lomb##SFX##_free(h_);                                                          \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_lomb##SFX##_describe(h_, &s[0], s.size()));                                      \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t points() const { return m_; }                                                                \
+        std::size_t freqs() const { return k_; }                                                                 \
+        std::size_t device_bytes() const { return phast_planner_lomb##SFX##_device_bytes(h_); }                  \
+        /* points per slab of the two reductions: a function of points() alone */                                \
+        std::size_t slab() const { return phast_planner_lomb##SFX##_slab(h_); }                                  \
+        std::size_t grid_len() const { return phast_planner_lomb##SFX##_grid_len(h_); }                          \
+        /* elements of T a _dev call of `batch` signals works in; workspace_min: the least a call runs in */     \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_lomb##SFX##_workspace_len(h_, batch); } \
+        std::size_t workspace_min() const { return phast_planner_lomb##SFX##_workspace_min(h_); }                \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+        std::size_t m_ = 0, k_ = 0;                                                                              \
+    };
+PHASTFT_PLANNER_LOMB(PlannerLomb64, phast_planner_lomb64, 64, double)
+PHASTFT_PLANNER_LOMB(PlannerLomb32, phast_planner_lomb32, 32, float)
+#undef PHASTFT_PLANNER_LOMB
+
+// one host signal of M values -> K values; blocking.  Amplitude: the real parts into `out`, the imaginary parts into `out_im`
+// (required for it, unused otherwise)
+#define PHASTFT_LOMB(FS, T, P)                                                                                   \
+    inline void lombscargle_##FS##_with_planner(Slice<const T> y, Slice<T> out, const P &planner,                \
+                                                LombNorm normalize = LombNorm::Power, Slice<T> out_im = Slice<T>(nullptr, 0)) { \
+        check(phast_lombscargle_##FS##_with_planner(y.ptr, y.len, out.ptr, out.len, out_im.len ? out_im.ptr : nullptr, \
+                                                    out_im.len, static_cast<int>(normalize), planner.get()));    \
+    }
+PHASTFT_LOMB(f64, double, PlannerLomb64)
+PHASTFT_LOMB(f32, float, PlannerLomb32)
+#undef PHASTFT_LOMB
 
 // ---- overlap-save convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve / correlate) ----
 enum class ConvMode : int { Full = PHAST_CONV_FULL, Same = PHAST_CONV_SAME, Valid = PHAST_CONV_VALID };

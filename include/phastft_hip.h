@@ -662,6 +662,78 @@ int phast_csd_f32_dev(const float *d_x, const float *d_y, float *d_out_re, float
 int phast_planner_psd32_time_stages(const phast_planner_psd32 *p, float *d_signal, float *d_out, size_t batch, int average, size_t slab, float *d_work, size_t work_len,
                                      int reps, float *stage_ms, void *stream);
 
+/* ---- the generalised Lomb-Scargle periodogram of unevenly spaced samples (no reference counterpart;
+ * scipy.signal.lombscargle, 1.15).  M times t_j and K frequencies f_k (host doubles, f in cycles per unit of t:
+ * scipy's angular freqs over 2 pi), optional weights w_j >= 0 with sum w > 0 (normalised to sum 1; NULL: 1 / M),
+ * floating_mean (0 / 1), fixed at _new; the values y_j per call.  With phi = 2 pi f_k t_j:
+ *     tables    A0 = sum w e^{i phi} = C + i S, A2 = sum w e^{2 i phi} = C2 + i S2; CC = (1 + C2) / 2, SS = (1 - C2) / 2,
+ *               CS = S2 / 2; floating mean: CC -= C^2, SS -= S^2, CS -= C S; tau = atan2(2 CS, CC - SS) / 2;
+ *               CCt = (1 + C2 cos 2 tau + S2 sin 2 tau) / 2, SSt = 1 - CCt; floating mean: CCt -= (C cos tau + S sin tau)^2,
+ *               SSt -= (S cos tau - C sin tau)^2; both clamped from below at finfo(T).epsneg, as scipy does
+ *     signal    Y = sum w y (floating mean; else 0), A1 = sum w (y - Y) e^{i phi}; YC = Re A1 cos tau + Im A1 sin tau,
+ *               YS = Im A1 cos tau - Re A1 sin tau, a = YC / CCt, b = YS / SSt, P = 2 (a YC + b YS)
+ *     PHAST_LOMB_POWER: P M / 4.  PHAST_LOMB_NORMALIZE: P / (2 YY), YY = sum w (y - Y)^2.  PHAST_LOMB_AMPLITUDE: the complex
+ *               (a + i b) e^{i tau} into out_re and out_im; out_im is required for amplitude only and not written otherwise.
+ * A call is one type-3 transform (Reverse, eps) of the real strengths T(w (y - Y)) between new sweeps; the tables are built at
+ * _new in double for both types by temporary f64 type-3 transforms of the weights at f and at 2 f, and rounded to T.
+ * Numerics: Y is accumulated and kept in double for both types -- as the signal's first value plus the weighted mean of the
+ * differences from it -- and taken off BEFORE the transform, so that an offset of the signal costs nothing; YY likewise.  The
+ * points of a signal are summed in slabs of _slab(p) points (a function of M alone), every sum in a fixed order, without
+ * atomics: the result's bits do not depend on the batch, on work_len, on alignment, on the stream or on a graph replay.
+ * _new refuses with PHAST_ERR_INVALID_ARG, before the device is touched: NULL t or freqs, M or K outside 1 .. 2^30, a
+ * non-finite t, f or w, a negative w, sum w <= 0, eps outside the type-3 planner's range for the type, and a type-3 grid --
+ * of (t, f) or of (t, 2 f) -- above that planner's limit.
+ * Out of scope: times in device memory, a fast path for times on a grid, multi-term models, false-alarm probabilities.
+ * The caller's device workspace holds phast_planner_lomb*_workspace_len(p, batch) elements of T: the strengths, A1's planes,
+ * the type-3 workspace and the doubles of the reductions of all signals in one chunk.  Any work_len >= _workspace_min(p) runs
+ * the batch in chunks of whole signals.  Signal b starts at d_y + b sig_dist (>= M), its results at d_out + b out_dist (>= K);
+ * batch 1 ignores both.  The inputs are not written.  The *_with_planner forms take host slices of one signal and block. */
+#define PHAST_LOMB_POWER 0
+#define PHAST_LOMB_NORMALIZE 1
+#define PHAST_LOMB_AMPLITUDE 2
+typedef struct phast_planner_lomb64 phast_planner_lomb64; /* PlannerLomb64 */
+int phast_planner_lomb64_new(const double *t, size_t m, const double *freqs, size_t k, const double *weights_or_null, int floating_mean, double eps,
+                              phast_planner_lomb64 **out);
+void phast_planner_lomb64_free(phast_planner_lomb64 *p);
+int phast_planner_lomb64_describe(const phast_planner_lomb64 *p, char *buf, size_t buf_len);
+size_t phast_planner_lomb64_device_bytes(const phast_planner_lomb64 *p);
+size_t phast_planner_lomb64_slab(const phast_planner_lomb64 *p); /* Q: the points per slab of the two reductions */
+size_t phast_planner_lomb64_grid_len(const phast_planner_lomb64 *p); /* n_f of the inner type-3 planner */
+size_t phast_planner_lomb64_workspace_len(const phast_planner_lomb64 *p, size_t batch);
+size_t phast_planner_lomb64_workspace_min(const phast_planner_lomb64 *p);
+int phast_lombscargle_f64(const double *t, size_t m, const double *freqs, size_t k, const double *weights_or_null, int floating_mean, double eps,
+                         const double *y, double *out_re, double *out_im, int normalize);
+int phast_lombscargle_f64_with_planner(const double *y, size_t m, double *out_re, size_t re_len, double *out_im, size_t im_len, int normalize,
+                                      const phast_planner_lomb64 *planner);
+int phast_lombscargle_f64_dev(const double *d_y, double *d_out_re, double *d_out_im, size_t m, size_t batch, size_t sig_dist, size_t out_dist, int normalize,
+                             const phast_planner_lomb64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/lomb_rate.py): stage_ms[3] = average milliseconds of the sweeps in front of the transform (partial,
+ * final, strength, final), of the type-3 call and of the post sweep over `reps` calls of `batch` signals at the natural
+ * distances in ONE chunk (work_len >= phast_planner_lomb*_workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_lomb64_time_stages(const phast_planner_lomb64 *p, const double *d_y, double *d_out_re, double *d_out_im, size_t batch, int normalize, double *d_work, size_t work_len,
+                                      int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_lomb32 phast_planner_lomb32; /* PlannerLomb32 */
+int phast_planner_lomb32_new(const double *t, size_t m, const double *freqs, size_t k, const double *weights_or_null, int floating_mean, double eps,
+                              phast_planner_lomb32 **out);
+void phast_planner_lomb32_free(phast_planner_lomb32 *p);
+int phast_planner_lomb32_describe(const phast_planner_lomb32 *p, char *buf, size_t buf_len);
+size_t phast_planner_lomb32_device_bytes(const phast_planner_lomb32 *p);
+size_t phast_planner_lomb32_slab(const phast_planner_lomb32 *p); /* Q: the points per slab of the two reductions */
+size_t phast_planner_lomb32_grid_len(const phast_planner_lomb32 *p); /* n_f of the inner type-3 planner */
+size_t phast_planner_lomb32_workspace_len(const phast_planner_lomb32 *p, size_t batch);
+size_t phast_planner_lomb32_workspace_min(const phast_planner_lomb32 *p);
+int phast_lombscargle_f32(const double *t, size_t m, const double *freqs, size_t k, const double *weights_or_null, int floating_mean, double eps,
+                         const float *y, float *out_re, float *out_im, int normalize);
+int phast_lombscargle_f32_with_planner(const float *y, size_t m, float *out_re, size_t re_len, float *out_im, size_t im_len, int normalize,
+                                      const phast_planner_lomb32 *planner);
+int phast_lombscargle_f32_dev(const float *d_y, float *d_out_re, float *d_out_im, size_t m, size_t batch, size_t sig_dist, size_t out_dist, int normalize,
+                             const phast_planner_lomb32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/lomb_rate.py): stage_ms[3] = average milliseconds of the sweeps in front of the transform (partial,
+ * final, strength, final), of the type-3 call and of the post sweep over `reps` calls of `batch` signals at the natural
+ * distances in ONE chunk (work_len >= phast_planner_lomb*_workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_lomb32_time_stages(const phast_planner_lomb32 *p, const float *d_y, float *d_out_re, float *d_out_im, size_t batch, int normalize, float *d_work, size_t work_len,
+                                      int reps, float *stage_ms, void *stream);
+
 /* ---- overlap-save FIR convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve /
  * correlate(x, h, mode, method="direct")).  Signal x of L samples, K taps h, both real:
  *     full[t] = sum_j g[j] x[t - j], t in [0, L + K - 1); g = h (flip = 0: convolution) or g[j] = h[K - 1 - j] (flip = 1:

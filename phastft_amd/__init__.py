@@ -30,6 +30,8 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
     (none: no spectral estimation)                  PlannerPsd64/32, psd_batched, csd_batched,
                                                     psd_f64/f32_with_planner, csd_f64/f32_with_planner, welch, csd,
                                                     spectrogram, periodogram, coherence
+    (none: no spectra of uneven samples)            PlannerLomb64/32, lombscargle_batched,
+                                                    lombscargle_f64/f32_with_planner, lombscargle
     (none: no convolution)                          PlannerConv64/32, conv_batched, conv_f64/f32_with_planner,
                                                     fftconvolve, correlate
     (none: no convolution)                          PlannerConvNd64/32, convnd_batched, convnd_f64/f32_with_planner,
@@ -95,6 +97,8 @@ __all__ = [
     "imdct_f64_with_planner", "imdct_f32_with_planner", "mdct", "imdct", "mdct_window",
     "PlannerPsd64", "PlannerPsd32", "psd_batched", "csd_batched", "psd_f64_with_planner", "psd_f32_with_planner",
     "csd_f64_with_planner", "csd_f32_with_planner", "welch", "csd", "spectrogram", "periodogram", "coherence",
+    "PlannerLomb64", "PlannerLomb32", "lombscargle_batched", "lombscargle_f64_with_planner", "lombscargle_f32_with_planner",
+    "lombscargle",
     "PlannerConv64", "PlannerConv32", "conv_batched", "conv_f64_with_planner", "conv_f32_with_planner", "fftconvolve",
     "correlate",
     "PlannerConvNd64", "PlannerConvNd32", "convnd_batched", "convnd_f64_with_planner", "convnd_f32_with_planner",
@@ -1641,6 +1645,166 @@ def periodogram(x, fs: float = 1.0, window="boxcar", nfft: int | None = None, de
     if not _is_torch(x) or x.dim() < 1:
         raise TypeError("need a float64 or float32 device tensor")
     return welch(x, fs, window, x.shape[-1], 0, nfft, detrend, scaling)
+
+
+# ---------------------------------------------------------------------------------------------
+# the Lomb-Scargle periodogram of unevenly spaced samples (no reference counterpart; scipy.signal.lombscargle)
+# ---------------------------------------------------------------------------------------------
+_LOMB_NORMS = {"power": 0, "normalize": 1, "amplitude": 2}
+
+
+def _lomb_norm(normalize) -> int:
+    """scipy's ``normalize``: False / "power", True / "normalize", or "amplitude" """
+    if normalize is False or normalize is True:
+        return 1 if normalize else 0
+    if isinstance(normalize, str) and normalize in _LOMB_NORMS:
+        return _LOMB_NORMS[normalize]
+    raise ValueError(f"normalize must be False, True, 'power', 'normalize' or 'amplitude', not {normalize!r}")
+
+
+class PlannerLomb64(_AnyHandle):
+    """f64 generalised Lomb-Scargle periodogram (scipy.signal.lombscargle's definitions) of signals sampled at the M
+    ``times`` (host doubles, any finite values, in any order) at the K ``freqs`` (host doubles, cycles per unit of time:
+    scipy's angular frequencies over 2 pi), with optional ``weights`` (M values >= 0, normalised to sum 1; None: equal) and
+    ``floating_mean``.  ``eps`` is the accuracy of the inner type-3 transform ([1e-14, 1e-1]).  Times, frequencies and weights
+    are fixed here: the tables that depend on them alone are built once, in double."""
+
+    _prefix = "lomb"
+    _eps = 1e-12
+
+    def __init__(self, times, freqs, weights=None, floating_mean: bool = False, eps: float | None = None):
+        t, f = _host_doubles(times), _host_doubles(freqs)
+        w = None if weights is None else _host_doubles(weights)
+        if w is not None and w.size != t.size:
+            raise ValueError(f"weights: {w.size} values for {t.size} times")
+        eps = self._eps if eps is None else float(eps)
+        self._new(t.ctypes.data_as(C.c_void_p), t.size, f.ctypes.data_as(C.c_void_p), f.size,
+                  None if w is None else w.ctypes.data_as(C.c_void_p), bool(floating_mean), eps)
+        self.n = self.m = self.m_points = t.size
+        self.k = self.k_freqs = f.size
+        self.eps, self.floating_mean = eps, bool(floating_mean)
+        self.slab = int(self._fn("slab")(self._h))
+        self.grid_len = int(self._fn("grid_len")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` signals works in.  A smaller workspace of at least ``workspace_min()``
+        runs the batch in chunks of whole signals, to the same bits."""
+        return self._workspace_len(batch)
+
+    def workspace_min(self) -> int:
+        return int(self._fn("workspace_min")(self._h))
+
+    def time_stages(self, y, out_re, out_im=None, batch: int = 1, normalize="power", workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (the sweeps in front of the transform, the type-3 call, the post sweep) of a call
+        of ``batch`` signals at the natural distances on device tensors (measurement hook)"""
+        bufs = [_Slice(y, self._dtype, "y"), _Slice(out_re, self._dtype, "out_re"),
+                _NULL if out_im is None else _Slice(out_im, self._dtype, "out_im")]
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 3)()
+        _check(self._fn("time_stages")(self._h, *(b.ptr for b in bufs), batch, _lomb_norm(normalize), ws.ptr, ws.len, reps, ms,
+                                       _stream()))
+        return [float(v) for v in ms]
+
+
+class PlannerLomb32(PlannerLomb64):
+    """f32 twin of :class:`PlannerLomb64`: eps in [1e-6, 1e-1]; times, frequencies and weights stay doubles, the tables are
+    built in f64 and rounded, the mean and the sums over the points stay in double"""
+
+    _sfx = "32"
+    _dtype = np.float32
+    _eps = 1e-6
+
+
+def lombscargle_batched(y, planner, normalize="power", out=None, work=None, stream=None):
+    """Device-resident batch of periodograms through one planner: ``y`` is a torch device tensor of shape ``(batch, M)`` or
+    ``(M,)`` of the planner's type whose last axis is contiguous; returns a tensor of shape ``(batch, K)`` or ``(K,)`` -- for
+    ``normalize="amplitude"`` a pair ``(re, im)`` of them.  ``out``: such a tensor (pair) to write into; ``work``: a device
+    tensor of at least ``planner.workspace_min()`` elements, by default one of ``planner.workspace_len(batch)`` from torch's
+    allocator; ``stream``: a ``torch.cuda.Stream``, by default the current one.  ``y`` is not written."""
+    import torch
+
+    want = torch.float64 if planner._dtype == np.float64 else torch.float32
+    norm = _lomb_norm(normalize)
+    amp = norm == 2
+    fs = "f64" if planner._dtype == np.float64 else "f32"
+
+    def plane(v, what, per):
+        if not _is_torch(v) or v.device.type != "cuda" or v.dtype != want:
+            raise TypeError(f"{what}: need a {want} device tensor")
+        if v.dim() not in (1, 2) or v.shape[-1] != per or (per > 1 and v.stride(-1) != 1):
+            raise ValueError(f"{what}: need shape (batch, {per}) or ({per},) with a contiguous last axis, not {tuple(v.shape)}")
+        rows = v.shape[0] if v.dim() == 2 else 1
+        dist = v.stride(0) if v.dim() == 2 and rows > 1 else per
+        if dist < per:
+            raise ValueError(f"{what}: rows overlap")
+        return rows, dist
+
+    batch, sig_dist = plane(y, "y", planner.m_points)
+    k = planner.k_freqs
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        shape = (batch, k) if y.dim() == 2 else (k,)
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=want, device=y.device) for _ in range(2)) if amp else torch.empty(
+                shape, dtype=want, device=y.device)
+        outs = tuple(out) if amp else (out,)
+        if len(outs) != (2 if amp else 1):
+            raise ValueError("out: need a pair (re, im) for amplitude, one tensor otherwise")
+        rows, out_dist = plane(outs[0], "out", k)
+        if rows != batch or outs[0].dim() != y.dim() or (amp and plane(outs[1], "out_im", k) != (batch, out_dist)):
+            raise ValueError("out: need (batch, K) tensors with equal strides")
+        ws = _any_workspace(planner, batch, work)
+        _check(_call(f"phast_lombscargle_{fs}_dev", y.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr() if amp else None,
+                     planner.m_points, batch, sig_dist, out_dist, norm, planner._h, ws.ptr, ws.len, _stream()))
+    return out
+
+
+def _lomb_host(fs, dtype, y, out_re, out_im, normalize, planner):
+    norm = _lomb_norm(normalize)
+    sy, so = _Slice(y, dtype, "y"), _Slice(out_re, dtype, "out_re")
+    si = None if out_im is None else _Slice(out_im, dtype, "out_im")
+    if _same_place(*(v for v in (sy, so, si) if v is not None)):
+        raise TypeError(f"lombscargle_{fs}_with_planner takes host arrays (lombscargle_batched takes device tensors)")
+    _check(_call(f"phast_lombscargle_{fs}_with_planner", sy.ptr, sy.len, so.ptr, so.len, None if si is None else si.ptr,
+                 0 if si is None else si.len, norm, planner._h))
+
+
+def lombscargle_f64_with_planner(y, out_re, planner: PlannerLomb64, normalize="power", out_im=None) -> None:
+    """f64 periodogram of one host signal of M values into a host array of K values (``normalize="amplitude"``: the real
+    parts, the imaginary parts into ``out_im``); blocking"""
+    _lomb_host("f64", np.float64, y, out_re, out_im, normalize, planner)
+
+
+def lombscargle_f32_with_planner(y, out_re, planner: PlannerLomb32, normalize="power", out_im=None) -> None:
+    """f32 twin of :func:`lombscargle_f64_with_planner`"""
+    _lomb_host("f32", np.float32, y, out_re, out_im, normalize, planner)
+
+
+def lombscargle(x, y, freqs, precenter: bool = False, normalize=False, *, weights=None, floating_mean: bool = False,
+                eps: float | None = None):
+    """scipy.signal.lombscargle over the last axis of a real device tensor ``y`` sampled at the times ``x``, at the ANGULAR
+    frequencies ``freqs`` (scipy's argument meanings), through a planner of its own: a new tensor of shape
+    ``y.shape[:-1] + (len(freqs),)``, complex for ``normalize="amplitude"``.  ``precenter`` (deprecated in scipy) takes the
+    plain mean of every signal off first.  float64 runs in f64 (eps defaults to 1e-12), float32 in f32 (1e-6)."""
+    import torch
+
+    if not _is_torch(y) or y.device.type != "cuda" or y.dtype not in (torch.float64, torch.float32) or y.dim() < 1:
+        raise TypeError("need a float64 or float32 device tensor of at least one axis")
+    norm = _lomb_norm(normalize)
+    t = _host_doubles(x)
+    f = _host_doubles(freqs) / (2 * np.pi)
+    if y.shape[-1] != t.size:
+        raise ValueError(f"the last axis holds {y.shape[-1]} values for {t.size} times")
+    planner = (PlannerLomb64 if y.dtype == torch.float64 else PlannerLomb32)(t, f, weights, floating_mean, eps)
+    rows = y.reshape(-1, t.size)
+    if precenter:
+        rows = rows - rows.mean(dim=-1, keepdim=True)
+    rows = rows.contiguous()
+    out = torch.empty((2, rows.shape[0], f.size), dtype=y.dtype, device=y.device)
+    if rows.shape[0]:
+        lombscargle_batched(rows, planner, ("power", "normalize", "amplitude")[norm], (out[0], out[1]) if norm == 2 else out[0])
+        torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+    res = torch.complex(out[0], out[1]) if norm == 2 else out[0]
+    return res.reshape(y.shape[:-1] + (f.size,))
 
 
 # ---------------------------------------------------------------------------------------------

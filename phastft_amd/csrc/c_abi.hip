@@ -19,6 +19,7 @@
 #include "planner_dct.hpp"
 #include "planner_mdct.hpp"
 #include "planner_psd.hpp"
+#include "planner_lomb.hpp"
 #include "planner_stft.hpp"
 #include "planner_conv.hpp"
 #include "planner_convnd.hpp"
@@ -49,6 +50,8 @@ struct phast_planner_mdct64 : MdctPlanner<double> {};
 struct phast_planner_mdct32 : MdctPlanner<float> {};
 struct phast_planner_psd64 : PsdPlanner<double> {};
 struct phast_planner_psd32 : PsdPlanner<float> {};
+struct phast_planner_lomb64 : LombPlanner<double> {};
+struct phast_planner_lomb32 : LombPlanner<float> {};
 struct phast_planner_conv64 : ConvPlanner<double> {};
 struct phast_planner_conv32 : ConvPlanner<float> {};
 struct phast_planner_convnd64 : ConvNdPlanner<double> {};
@@ -562,6 +565,7 @@ PHAST_HANDLE_API(nufft64) PHAST_HANDLE_API(nufft32) PHAST_HANDLE_API(nufft2d64) 
 PHAST_HANDLE_API(nufft3d64) PHAST_HANDLE_API(nufft3d32) PHAST_HANDLE_API(nufft_t3_64) PHAST_HANDLE_API(nufft_t3_32)
 PHAST_HANDLE_API(nd64) PHAST_HANDLE_API(nd32) PHAST_HANDLE_API(r2c_nd64) PHAST_HANDLE_API(r2c_nd32)
 PHAST_HANDLE_API(convnd64) PHAST_HANDLE_API(convnd32) PHAST_HANDLE_API(mdct64) PHAST_HANDLE_API(mdct32)
+PHAST_HANDLE_API(lomb64) PHAST_HANDLE_API(lomb32)
 
 // Arbitrary lengths (Bluestein, planner_any.hpp): arguments are checked before the device is touched
 #define PHAST_ANY_API(SFX, T)                                                                                           \
@@ -872,6 +876,52 @@ PHAST_MDCT_API(32, f32, float)
     } PHAST_CATCH_RC
 PHAST_PSD_API(64, f64, double)
 PHAST_PSD_API(32, f32, float)
+
+// The Lomb-Scargle periodogram (planner_lomb.hpp): the counts, the values, eps and both type-3 grids are checked before the
+// device is touched; the one-shot form builds a planner of its own for the call.
+#define PHAST_LOMB_API(SFX, FS, T)                                                                                      \
+    int phast_planner_lomb##SFX##_new(const double *t, size_t m, const double *freqs, size_t k, const double *weights,  \
+                                      int floating_mean, double eps, phast_planner_lomb##SFX **out) try {               \
+        return lomb_planner_new<T>(t, m, freqs, k, weights, floating_mean, eps, out);                                   \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_lomb##SFX##_workspace_min(const phast_planner_lomb##SFX *p) try {                              \
+        return p ? p->workspace_min() : 0;                                                                              \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_lomb##SFX##_slab(const phast_planner_lomb##SFX *p) try {                                       \
+        return p ? p->q : 0;                                                                                            \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_lomb##SFX##_grid_len(const phast_planner_lomb##SFX *p) try {                                   \
+        return p ? (size_t)p->t3.grid.nf : 0;                                                                           \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_lomb##SFX##_time_stages(const phast_planner_lomb##SFX *p, const T *d_y, T *d_out_re, T *d_out_im, \
+                                              size_t batch, int normalize, T *d_work, size_t work_len, int reps,        \
+                                              float *stage_ms, void *stream) try {                                      \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(d_y, d_out_re, d_out_im, batch, normalize, d_work, work_len, reps, stage_ms,              \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_lombscargle_##FS(const double *t, size_t m, const double *freqs, size_t k, const double *weights,         \
+                               int floating_mean, double eps, const T *y, T *out_re, T *out_im, int normalize) try {    \
+        phast_planner_lomb##SFX *p = nullptr;                                                                           \
+        int rc = lomb_planner_new<T>(t, m, freqs, k, weights, floating_mean, eps, &p);                                  \
+        if (rc) return rc;                                                                                              \
+        std::unique_ptr<phast_planner_lomb##SFX> own(p);                                                                \
+        return p->host(y, m, out_re, k, out_im, k, normalize);                                                          \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_lombscargle_##FS##_with_planner(const T *y, size_t m, T *out_re, size_t re_len, T *out_im, size_t im_len, \
+                                              int normalize, const phast_planner_lomb##SFX *p) try {                    \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(y, m, out_re, re_len, out_im, im_len, normalize);                                                \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_lombscargle_##FS##_dev(const T *d_y, T *d_out_re, T *d_out_im, size_t m, size_t batch, size_t sig_dist,   \
+                                     size_t out_dist, int normalize, const phast_planner_lomb##SFX *p, T *d_work,       \
+                                     size_t work_len, void *stream) try {                                               \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->run(d_y, d_out_re, d_out_im, m, batch, sig_dist, out_dist, normalize, d_work, work_len,               \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC
+PHAST_LOMB_API(64, f64, double)
+PHAST_LOMB_API(32, f32, float)
 
 // Overlap-save convolution and correlation of real signals (planner_conv.hpp): every argument rule and a wrong length come
 // back before the device is touched

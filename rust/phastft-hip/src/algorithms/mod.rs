@@ -8,6 +8,7 @@ pub mod czt;
 pub mod dit;
 pub mod mdct;
 pub mod psd;
+pub mod lomb;
 pub mod nufft;
 pub mod nufft2d;
 pub mod nufft3d;

@@ -237,6 +237,41 @@ extern "C" {
     pub(crate) fn phast_csd_f32_dev(x: *const f32, y: *const f32, out_re: *mut f32, out_im: *mut f32, pxx: *mut f32, pyy: *mut f32,
         signal_len: usize, batch: usize, sig_dist: usize, average: c_int, planner: *const Opaque, work: *mut f32, work_len: usize,
         stream: *mut c_void) -> c_int;
+    // the Lomb-Scargle periodogram (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/lomb.rs)
+    pub(crate) fn phast_planner_lomb64_new(t: *const f64, m: usize, freqs: *const f64, k: usize, weights: *const f64,
+        floating_mean: c_int, eps: f64, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_lomb64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_lomb64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_lomb64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_lomb64_slab(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_lomb64_grid_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_lomb64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_lomb64_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_lomb64_time_stages(p: *const Opaque, y: *const f64, out_re: *mut f64, out_im: *mut f64, batch: usize,
+        normalize: c_int, work: *mut f64, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_lombscargle_f64(t: *const f64, m: usize, freqs: *const f64, k: usize, weights: *const f64, floating_mean: c_int,
+        eps: f64, y: *const f64, out_re: *mut f64, out_im: *mut f64, normalize: c_int) -> c_int;
+    pub(crate) fn phast_lombscargle_f64_with_planner(y: *const f64, m: usize, out_re: *mut f64, re_len: usize, out_im: *mut f64,
+        im_len: usize, normalize: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_lombscargle_f64_dev(y: *const f64, out_re: *mut f64, out_im: *mut f64, m: usize, batch: usize, sig_dist: usize,
+        out_dist: usize, normalize: c_int, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_lomb32_new(t: *const f64, m: usize, freqs: *const f64, k: usize, weights: *const f64,
+        floating_mean: c_int, eps: f64, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_lomb32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_lomb32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_lomb32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_lomb32_slab(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_lomb32_grid_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_lomb32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_lomb32_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_lomb32_time_stages(p: *const Opaque, y: *const f32, out_re: *mut f32, out_im: *mut f32, batch: usize,
+        normalize: c_int, work: *mut f32, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_lombscargle_f32(t: *const f64, m: usize, freqs: *const f64, k: usize, weights: *const f64, floating_mean: c_int,
+        eps: f64, y: *const f32, out_re: *mut f32, out_im: *mut f32, normalize: c_int) -> c_int;
+    pub(crate) fn phast_lombscargle_f32_with_planner(y: *const f32, m: usize, out_re: *mut f32, re_len: usize, out_im: *mut f32,
+        im_len: usize, normalize: c_int, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_lombscargle_f32_dev(y: *const f32, out_re: *mut f32, out_im: *mut f32, m: usize, batch: usize, sig_dist: usize,
+        out_dist: usize, normalize: c_int, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // overlap-save convolution and correlation (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/conv.rs)
     pub(crate) fn phast_planner_conv64_new(signal_len: usize, taps: *const f64, num_taps: usize, mode: c_int, flip: c_int,
         block: usize, out: *mut *mut Opaque) -> c_int;

@@ -67,6 +67,12 @@ pub use algorithms::psd::{
     psd_f64_with_planner,
 };
 pub use planner::{Detrend, PlannerPsd32, PlannerPsd64, PsdScaling};
+// the Lomb-Scargle periodogram of unevenly spaced samples (an extension beyond PhastFT 0.3.0)
+pub use algorithms::lomb::{
+    lombscargle_f32, lombscargle_f32_dev, lombscargle_f32_with_planner, lombscargle_f64, lombscargle_f64_dev,
+    lombscargle_f64_with_planner,
+};
+pub use planner::{LombNorm, PlannerLomb32, PlannerLomb64};
 // overlap-save convolution and correlation of real signals (an extension beyond PhastFT 0.3.0)
 pub use algorithms::conv::{conv_f32_dev, conv_f32_with_planner, conv_f64_dev, conv_f64_with_planner};
 pub use planner::{ConvMode, PlannerConv32, PlannerConv64};

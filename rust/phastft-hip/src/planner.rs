@@ -449,6 +449,80 @@ impl_planner_psd!(PlannerPsd32, phast_planner_psd32_new, phast_planner_psd32_fre
                   phast_planner_psd32_bins, phast_planner_psd32_slab, phast_planner_psd32_workspace_len,
                   phast_planner_psd32_workspace_min);
 
+/// What a periodogram returns (PHAST_LOMB_* of the C ABI): scipy's legacy power P M / 4, the power over the signal's own
+/// (P / 2 YY, in [0, 1]), or the complex amplitude (a + i b) e^{i tau}
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum LombNorm {
+    Power = 0,
+    Normalize = 1,
+    Amplitude = 2,
+}
+
+macro_rules! impl_planner_lomb {
+    ($lomb:ident, $new:ident, $free:ident, $slab:ident, $grid:ident, $ws_len:ident, $ws_min:ident) => {
+        /// An extension beyond PhastFT 0.3.0: the generalised Lomb-Scargle periodogram (scipy.signal.lombscargle's
+        /// definitions) of signals sampled at `times` (any finite values, any order), at `freqs` in cycles per unit of
+        /// time, with optional weights and a floating mean.  One type-3 non-uniform transform per signal; the tables that
+        /// depend on the times, frequencies and weights alone are built at `new`, in double.  Immutable after `new`.
+        pub struct $lomb {
+            pub(crate) h: *mut Opaque,
+            pub(crate) points: usize,
+            pub(crate) freqs: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's workspace (device calls) or in
+        // device buffers of its own (host-slice calls)
+        unsafe impl Send for $lomb {}
+        unsafe impl Sync for $lomb {}
+        impl $lomb {
+            /// `weights`: one value >= 0 per time with a positive sum, or `None` for equal weights.  Panics with "invalid
+            /// argument" unless 1 <= M, K <= 2^30, every time, frequency and weight is finite, eps is in the type-3
+            /// planner's range for the type and the type-3 grids of (t, f) and of (t, 2 f) are within its limit
+            pub fn new(times: &[f64], freqs: &[f64], weights: Option<&[f64]>, floating_mean: bool, eps: f64) -> Self {
+                if let Some(w) = weights {
+                    assert_eq!(w.len(), times.len(), "invalid argument");
+                }
+                let mut h = std::ptr::null_mut();
+                let w = weights.map_or(std::ptr::null(), |w| w.as_ptr());
+                ffi::check(unsafe {
+                    ffi::$new(times.as_ptr(), times.len(), freqs.as_ptr(), freqs.len(), w, floating_mean as c_int, eps, &mut h)
+                });
+                Self { h, points: times.len(), freqs: freqs.len() }
+            }
+            pub fn points(&self) -> usize {
+                self.points
+            }
+            pub fn freqs(&self) -> usize {
+                self.freqs
+            }
+            /// points per slab of the two reductions: a function of `points()` alone
+            pub fn slab(&self) -> usize {
+                unsafe { ffi::$slab(self.h) }
+            }
+            /// n_f of the inner type-3 planner
+            pub fn grid_len(&self) -> usize {
+                unsafe { ffi::$grid(self.h) }
+            }
+            /// elements of the workspace a device call of `batch` signals works in
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+            /// the least workspace a call runs in: one signal
+            pub fn workspace_min(&self) -> usize {
+                unsafe { ffi::$ws_min(self.h) }
+            }
+        }
+        impl Drop for $lomb {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_lomb!(PlannerLomb64, phast_planner_lomb64_new, phast_planner_lomb64_free, phast_planner_lomb64_slab,
+                   phast_planner_lomb64_grid_len, phast_planner_lomb64_workspace_len, phast_planner_lomb64_workspace_min);
+impl_planner_lomb!(PlannerLomb32, phast_planner_lomb32_new, phast_planner_lomb32_free, phast_planner_lomb32_slab,
+                   phast_planner_lomb32_grid_len, phast_planner_lomb32_workspace_len, phast_planner_lomb32_workspace_min);
+
 /// Which part of the full convolution a planner yields (PHAST_CONV_* of the C ABI)
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum ConvMode {
