@@ -28,6 +28,9 @@
 //                                                            csd_f64/f32_with_planner
 //   (none: no spectra of uneven samples upstream)            class PlannerLomb64/32, lombscargle_f64/f32_with_planner,
 //                                                            enum LombNorm -- scipy.signal.lombscargle
+//   (none: no sample-rate conversion upstream)               class PlannerUpfirdn64/32, upfirdn_f64/f32_with_planner -- the polyphase
+//                                                            FIR of scipy.signal.upfirdn; class PlannerResample64/32,
+//                                                            resample_f64/f32_with_planner -- scipy.signal.resample
 //   (none: no convolution upstream)                          class PlannerConv64/32, conv_f64/f32_with_planner, enum ConvMode --
 //                                                            scipy.signal.convolve / correlate by overlap-save
 //   (none: no convolution upstream)                          class PlannerConvNd64/32, convnd_f64/f32_with_planner -- the same of
@@ -691,6 +694,87 @@ PHASTFT_PLANNER_LOMB(PlannerLomb32, phast_planner_lomb32, 32, float)
 PHASTFT_LOMB(f64, double, PlannerLomb64)
 PHASTFT_LOMB(f32, float, PlannerLomb32)
 #undef PHASTFT_LOMB
+
+// ---- sample-rate conversion (no reference counterpart; scipy.signal.upfirdn / resample_poly / decimate / resample) ----
+#define PHASTFT_PLANNER_UPFIRDN(NAME, CT, SFX, T)                                                                \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* upfirdn(taps, x, up, down) of signals of signal_len samples: the out_len samples from `first` on (out_len = 0: up to \
+           full_len; first + out_len may pass it: zeros).  up and down are used as given */                      \
+        NAME(std::size_t signal_len, Slice<const T> taps, std::size_t up = 1, std::size_t down = 1, std::size_t first = 0, \
+             std::size_t out_len = 0) {                                                                          \
+            check(phast_planner_upfirdn##SFX##_new(signal_len, taps.ptr, taps.len, up, down, first, out_len, &h_)); \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }                                                   \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_upfirdn##SFX##_free(h_);                                                       \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_upfirdn##SFX##_describe(h_, &s[0], s.size()));                                   \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_upfirdn##SFX##_device_bytes(h_); }               \
+        std::size_t out_len() const { return phast_planner_upfirdn##SFX##_out_len(h_); }                         \
+        std::size_t full_len() const { return phast_planner_upfirdn##SFX##_full_len(h_); }                       \
+        /* outputs per workgroup and taps of a phase per LDS chunk: functions of (K, up, down) alone */          \
+        std::size_t tile() const { return phast_planner_upfirdn##SFX##_tile(h_); }                               \
+        std::size_t chunk() const { return phast_planner_upfirdn##SFX##_chunk(h_); }                             \
+        /* 0: the kernel needs no workspace */                                                                   \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_upfirdn##SFX##_workspace_len(h_, batch); } \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+    };
+PHASTFT_PLANNER_UPFIRDN(PlannerUpfirdn64, phast_planner_upfirdn64, 64, double)
+PHASTFT_PLANNER_UPFIRDN(PlannerUpfirdn32, phast_planner_upfirdn32, 32, float)
+#undef PHASTFT_PLANNER_UPFIRDN
+#define PHASTFT_PLANNER_RESAMPLE(NAME, CT, SFX)                                                                  \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* scipy.signal.resample(x, num) of real signals of signal_len samples (Fourier method, no window) */    \
+        NAME(std::size_t signal_len, std::size_t num) : num_(num) { check(phast_planner_resample##SFX##_new(signal_len, num, &h_)); } \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_), num_(o.num_) { o.h_ = nullptr; }                                     \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_resample##SFX##_free(h_);                                                      \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_resample##SFX##_describe(h_, &s[0], s.size()));                                  \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_resample##SFX##_device_bytes(h_); }              \
+        std::size_t out_len() const { return num_; }                                                             \
+        /* elements of T a _dev call of `batch` signals works in; workspace_min: the least a call runs in */     \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_resample##SFX##_workspace_len(h_, batch); } \
+        std::size_t workspace_min() const { return phast_planner_resample##SFX##_workspace_min(h_); }            \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+        std::size_t num_ = 0;                                                                                    \
+    };
+PHASTFT_PLANNER_RESAMPLE(PlannerResample64, phast_planner_resample64, 64)
+PHASTFT_PLANNER_RESAMPLE(PlannerResample32, phast_planner_resample32, 32)
+#undef PHASTFT_PLANNER_RESAMPLE
+
+// one host signal of L samples -> its out_len() output samples; blocking
+#define PHASTFT_RESAMPLE(NAME, FS, T, P)                                                                         \
+    inline void NAME##_##FS##_with_planner(Slice<const T> signal, Slice<T> output, const P &planner) {           \
+        check(phast_##NAME##_##FS##_with_planner(signal.ptr, signal.len, output.ptr, output.len, planner.get())); \
+    }
+PHASTFT_RESAMPLE(upfirdn, f64, double, PlannerUpfirdn64)
+PHASTFT_RESAMPLE(upfirdn, f32, float, PlannerUpfirdn32)
+PHASTFT_RESAMPLE(resample, f64, double, PlannerResample64)
+PHASTFT_RESAMPLE(resample, f32, float, PlannerResample32)
+#undef PHASTFT_RESAMPLE
 
 // ---- overlap-save convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve / correlate) ----
 enum class ConvMode : int { Full = PHAST_CONV_FULL, Same = PHAST_CONV_SAME, Valid = PHAST_CONV_VALID };

@@ -734,6 +734,105 @@ int phast_lombscargle_f32_dev(const float *d_y, float *d_out_re, float *d_out_im
 int phast_planner_lomb32_time_stages(const phast_planner_lomb32 *p, const float *d_y, float *d_out_re, float *d_out_im, size_t batch, int normalize, float *d_work, size_t work_len,
                                       int reps, float *stage_ms, void *stream);
 
+/* ---- sample-rate conversion of real signals (no reference counterpart; scipy.signal.upfirdn / resample_poly / decimate and
+ * scipy.signal.resample, 1.15).
+ *
+ * Polyphase FIR: phast_planner_upfirdn*.  Signal x of L samples, K taps h (host values of T), up, down >= 1, used as given (not
+ * reduced by their gcd, as scipy.signal.upfirdn does not reduce them):
+ *     full[m] = sum_n h[m down - n up] x[n],  0 <= m < full_len = ((L - 1) up + K - 1) / down + 1;  full[m] = 0 above
+ *     out[i]  = full[first + i],              0 <= i < out_len     (out_len = 0 at _new: full_len - first)
+ * This is upfirdn(h, x, up, down) with mode "constant", windowed by (first, out_len); first + out_len may pass full_len (zeros).
+ * One direct kernel, no transform: the taps are kept phase-major on the device (up rows of Kp = ceil(K / up), zero-padded), a
+ * 256-thread workgroup owns a tile of consecutive outputs of one signal and walks the rows in tap chunks that share LDS with
+ * the run of the signal they meet.  An output is acc = fma(h[p + j up], x[q - j], acc) for j = 0 .. Kp - 1 ascending from 0
+ * (p = (m down) mod up, q = (m down) div up), in T: the result's bits depend on the values alone -- not on the batch, the
+ * distances, pointer alignment, the workspace, the stream or a graph replay.  No workspace is needed: _workspace_len is 0, and
+ * d_work / work_len of the _dev call are not read (NULL and 0 are fine).
+ * _new refuses with PHAST_ERR_INVALID_ARG, before the device is touched: NULL taps, L, K or the resulting out_len outside
+ * 1 .. 2^29, up or down outside 1 .. 2^20, first > full_len.  _dev: signal b at d_signal + b sig_dist (>= L), its out_len
+ * outputs at d_out + b out_dist (>= out_len); batch 1 ignores both; pointers need element alignment only; the signal is never
+ * written and nothing is written outside the out_len outputs of a signal.  A null pointer or a short dist is
+ * PHAST_ERR_INVALID_ARG, a signal_len that is not the planner's PHAST_ERR_PLANNER_SIZE, a wrong out_len of the host-slice form
+ * PHAST_ERR_LEN_MISMATCH -- all before the device is touched.  The *_with_planner forms take host slices of one signal and block. */
+typedef struct phast_planner_upfirdn64 phast_planner_upfirdn64; /* PlannerUpfirdn64 */
+int phast_planner_upfirdn64_new(size_t signal_len, const double *taps, size_t num_taps, size_t up, size_t down, size_t first, size_t out_len,
+                                 phast_planner_upfirdn64 **out);
+void phast_planner_upfirdn64_free(phast_planner_upfirdn64 *p);
+int phast_planner_upfirdn64_describe(const phast_planner_upfirdn64 *p, char *buf, size_t buf_len);
+size_t phast_planner_upfirdn64_device_bytes(const phast_planner_upfirdn64 *p);
+size_t phast_planner_upfirdn64_workspace_len(const phast_planner_upfirdn64 *p, size_t batch); /* 0 */
+size_t phast_planner_upfirdn64_out_len(const phast_planner_upfirdn64 *p);
+size_t phast_planner_upfirdn64_full_len(const phast_planner_upfirdn64 *p);
+size_t phast_planner_upfirdn64_tile(const phast_planner_upfirdn64 *p);  /* outputs per workgroup */
+size_t phast_planner_upfirdn64_chunk(const phast_planner_upfirdn64 *p); /* taps of a phase per LDS chunk */
+int phast_upfirdn_f64_with_planner(const double *signal, size_t signal_len, double *out, size_t out_len, const phast_planner_upfirdn64 *planner);
+int phast_upfirdn_f64_dev(const double *d_signal, double *d_out, size_t signal_len, size_t batch, size_t sig_dist, size_t out_dist,
+                         const phast_planner_upfirdn64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/resample_rate.py): stage_ms[1] = average milliseconds of the kernel over `reps` calls of `batch`
+ * signals at the natural distances.  Blocks until done. */
+int phast_planner_upfirdn64_time_stages(const phast_planner_upfirdn64 *p, const double *d_signal, double *d_out, size_t batch, int reps, float *stage_ms,
+                                         void *stream);
+typedef struct phast_planner_upfirdn32 phast_planner_upfirdn32; /* PlannerUpfirdn32 */
+int phast_planner_upfirdn32_new(size_t signal_len, const float *taps, size_t num_taps, size_t up, size_t down, size_t first, size_t out_len,
+                                 phast_planner_upfirdn32 **out);
+void phast_planner_upfirdn32_free(phast_planner_upfirdn32 *p);
+int phast_planner_upfirdn32_describe(const phast_planner_upfirdn32 *p, char *buf, size_t buf_len);
+size_t phast_planner_upfirdn32_device_bytes(const phast_planner_upfirdn32 *p);
+size_t phast_planner_upfirdn32_workspace_len(const phast_planner_upfirdn32 *p, size_t batch); /* 0 */
+size_t phast_planner_upfirdn32_out_len(const phast_planner_upfirdn32 *p);
+size_t phast_planner_upfirdn32_full_len(const phast_planner_upfirdn32 *p);
+size_t phast_planner_upfirdn32_tile(const phast_planner_upfirdn32 *p);  /* outputs per workgroup */
+size_t phast_planner_upfirdn32_chunk(const phast_planner_upfirdn32 *p); /* taps of a phase per LDS chunk */
+int phast_upfirdn_f32_with_planner(const float *signal, size_t signal_len, float *out, size_t out_len, const phast_planner_upfirdn32 *planner);
+int phast_upfirdn_f32_dev(const float *d_signal, float *d_out, size_t signal_len, size_t batch, size_t sig_dist, size_t out_dist,
+                         const phast_planner_upfirdn32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/resample_rate.py): stage_ms[1] = average milliseconds of the kernel over `reps` calls of `batch`
+ * signals at the natural distances.  Blocks until done. */
+int phast_planner_upfirdn32_time_stages(const phast_planner_upfirdn32 *p, const float *d_signal, float *d_out, size_t batch, int reps, float *stage_ms,
+                                         void *stream);
+/* Fourier method: phast_planner_resample*.  scipy.signal.resample(x, num) of a real signal of L samples (window None, domain
+ * "time"), 1 <= L, num <= 2^29:
+ *     X = rfft_L(x); N = min(L, num); Y[k] = X[k] for k <= N / 2, 0 for the other k <= num / 2;
+ *     N even and num < L: Y[N / 2] *= 2; N even and num > L: Y[N / 2] *= 1/2;  y = irfft_num(Y) num / L
+ * One R2C of L and one C2R of num on the any-length real path (phast_planner_r2c_any*; one planner serves both when
+ * num = L) around one new sweep, which copies, zero-fills and scales the two planes: num / L, the Nyquist factor, and the
+ * imaginary parts of Y[0] and (num even) Y[num / 2] set to 0, as irfft defines them.  The caller's device workspace holds
+ * _workspace_len(p, batch) elements of T: the planes of X and Y of all signals and the real planners' workspace in one chunk;
+ * any work_len >= _workspace_min(p) runs the batch in chunks of whole signals, to the same bits.  Signal b at d_signal +
+ * b sig_dist (>= L), its num outputs at d_out + b out_dist (>= num); batch 1 ignores both; pointers need element alignment
+ * only; as for phast_r2c_fft_*_any_dev, a power-of-two L >= 4 needs an even sig_dist in a batch and a power-of-two num >= 4 an
+ * even out_dist.  PHAST_ERR_INVALID_ARG (lengths out of range, null pointers, short dists, a null or short workspace),
+ * PHAST_ERR_PLANNER_SIZE (signal_len) and PHAST_ERR_LEN_MISMATCH (out_len of the host-slice form) come back before the device
+ * is touched.  Out of scope: complex signals, the window argument, automatic dispatch between the two methods. */
+typedef struct phast_planner_resample64 phast_planner_resample64; /* PlannerResample64 */
+int phast_planner_resample64_new(size_t signal_len, size_t num, phast_planner_resample64 **out);
+void phast_planner_resample64_free(phast_planner_resample64 *p);
+int phast_planner_resample64_describe(const phast_planner_resample64 *p, char *buf, size_t buf_len);
+size_t phast_planner_resample64_device_bytes(const phast_planner_resample64 *p);
+size_t phast_planner_resample64_workspace_len(const phast_planner_resample64 *p, size_t batch);
+size_t phast_planner_resample64_workspace_min(const phast_planner_resample64 *p);
+int phast_resample_f64_with_planner(const double *signal, size_t signal_len, double *out, size_t out_len, const phast_planner_resample64 *planner);
+int phast_resample_f64_dev(const double *d_signal, double *d_out, size_t signal_len, size_t batch, size_t sig_dist, size_t out_dist,
+                          const phast_planner_resample64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/resample_rate.py): stage_ms[3] = average milliseconds of the R2C, the spectrum sweep and the C2R over
+ * `reps` calls of `batch` signals at the natural distances in ONE chunk (work_len >= _workspace_len(p, batch)).  Blocks. */
+int phast_planner_resample64_time_stages(const phast_planner_resample64 *p, const double *d_signal, double *d_out, size_t batch, double *d_work, size_t work_len,
+                                          int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_resample32 phast_planner_resample32; /* PlannerResample32 */
+int phast_planner_resample32_new(size_t signal_len, size_t num, phast_planner_resample32 **out);
+void phast_planner_resample32_free(phast_planner_resample32 *p);
+int phast_planner_resample32_describe(const phast_planner_resample32 *p, char *buf, size_t buf_len);
+size_t phast_planner_resample32_device_bytes(const phast_planner_resample32 *p);
+size_t phast_planner_resample32_workspace_len(const phast_planner_resample32 *p, size_t batch);
+size_t phast_planner_resample32_workspace_min(const phast_planner_resample32 *p);
+int phast_resample_f32_with_planner(const float *signal, size_t signal_len, float *out, size_t out_len, const phast_planner_resample32 *planner);
+int phast_resample_f32_dev(const float *d_signal, float *d_out, size_t signal_len, size_t batch, size_t sig_dist, size_t out_dist,
+                          const phast_planner_resample32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/resample_rate.py): stage_ms[3] = average milliseconds of the R2C, the spectrum sweep and the C2R over
+ * `reps` calls of `batch` signals at the natural distances in ONE chunk (work_len >= _workspace_len(p, batch)).  Blocks. */
+int phast_planner_resample32_time_stages(const phast_planner_resample32 *p, const float *d_signal, float *d_out, size_t batch, float *d_work, size_t work_len,
+                                          int reps, float *stage_ms, void *stream);
+
 /* ---- overlap-save FIR convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve /
  * correlate(x, h, mode, method="direct")).  Signal x of L samples, K taps h, both real:
  *     full[t] = sum_j g[j] x[t - j], t in [0, L + K - 1); g = h (flip = 0: convolution) or g[j] = h[K - 1 - j] (flip = 1:

@@ -32,6 +32,10 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
                                                     spectrogram, periodogram, coherence
     (none: no spectra of uneven samples)            PlannerLomb64/32, lombscargle_batched,
                                                     lombscargle_f64/f32_with_planner, lombscargle
+    (none: no sample-rate conversion)               PlannerUpfirdn64/32, PlannerResample64/32, upfirdn_batched,
+                                                    resample_batched, upfirdn_64/32_with_planner,
+                                                    resample_64/32_with_planner, upfirdn, resample_poly, decimate,
+                                                    resample, firwin_lowpass
     (none: no convolution)                          PlannerConv64/32, conv_batched, conv_f64/f32_with_planner,
                                                     fftconvolve, correlate
     (none: no convolution)                          PlannerConvNd64/32, convnd_batched, convnd_f64/f32_with_planner,
@@ -99,6 +103,9 @@ __all__ = [
     "csd_f64_with_planner", "csd_f32_with_planner", "welch", "csd", "spectrogram", "periodogram", "coherence",
     "PlannerLomb64", "PlannerLomb32", "lombscargle_batched", "lombscargle_f64_with_planner", "lombscargle_f32_with_planner",
     "lombscargle",
+    "PlannerUpfirdn64", "PlannerUpfirdn32", "PlannerResample64", "PlannerResample32", "upfirdn_batched", "resample_batched",
+    "upfirdn_64_with_planner", "upfirdn_32_with_planner", "resample_64_with_planner", "resample_32_with_planner", "upfirdn",
+    "resample_poly", "decimate", "resample", "firwin_lowpass",
     "PlannerConv64", "PlannerConv32", "conv_batched", "conv_f64_with_planner", "conv_f32_with_planner", "fftconvolve",
     "correlate",
     "PlannerConvNd64", "PlannerConvNd32", "convnd_batched", "convnd_f64_with_planner", "convnd_f32_with_planner",
@@ -1805,6 +1812,270 @@ def lombscargle(x, y, freqs, precenter: bool = False, normalize=False, *, weight
         torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
     res = torch.complex(out[0], out[1]) if norm == 2 else out[0]
     return res.reshape(y.shape[:-1] + (f.size,))
+
+
+# ---------------------------------------------------------------------------------------------
+# sample-rate conversion (no reference counterpart; scipy.signal.upfirdn / resample_poly / decimate / resample)
+# ---------------------------------------------------------------------------------------------
+class PlannerUpfirdn64(_AnyHandle):
+    """f64 polyphase FIR of signals of ``signal_len`` samples: ``scipy.signal.upfirdn(h, x, up, down)`` (zero-stuff by ``up``,
+    filter with the taps ``h``, keep every ``down``-th sample), of which a call yields the ``out_len`` samples from ``first``
+    on (``out_len=None``: up to the end, ``full_len - first``).  ``first + out_len`` may pass ``full_len``: zeros there.
+    ``up`` and ``down`` are used as given.  One direct kernel; no workspace."""
+
+    _prefix = "upfirdn"
+
+    def __init__(self, signal_len: int, h, up: int = 1, down: int = 1, first: int = 0, out_len: int | None = None):
+        if _is_torch(h):
+            h = h.detach().cpu().numpy()
+        taps = np.ascontiguousarray(h, dtype=self._dtype).reshape(-1)
+        self._new(signal_len, taps.ctypes.data_as(C.c_void_p), taps.size, up, down, first, 0 if out_len is None else out_len)
+        self.n = self.signal_len = signal_len
+        self.num_taps, self.up, self.down, self.first = taps.size, up, down, first
+        self.out_len = int(self._fn("out_len")(self._h))
+        self.full_len = int(self._fn("full_len")(self._h))
+        self.tile = int(self._fn("tile")(self._h))
+        self.chunk = int(self._fn("chunk")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """0: the kernel works in LDS alone"""
+        return self._workspace_len(batch)
+
+    def workspace_min(self) -> int:
+        return 0
+
+    def time_stages(self, signal, out, batch: int = 1, reps: int = 10):
+        """Average HIP-event milliseconds of the kernel of a call of ``batch`` signals at distances L and out_len on device
+        tensors, as a list of one (measurement hook)"""
+        x, y = _Slice(signal, self._dtype, "signal"), _Slice(out, self._dtype, "out")
+        ms = (C.c_float * 1)()
+        _check(self._fn("time_stages")(self._h, x.ptr, y.ptr, batch, reps, ms, _stream()))
+        return [float(ms[0])]
+
+
+class PlannerUpfirdn32(PlannerUpfirdn64):
+    """f32 twin of :class:`PlannerUpfirdn64`: taps, products and sums in f32"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+class PlannerResample64(_AnyHandle):
+    """f64 Fourier-method resampling of real signals of ``signal_len`` samples to ``num``: ``scipy.signal.resample(x, num)``
+    (no window, time domain).  One R2C of L and one C2R of num on the any-length real path around one sweep."""
+
+    _prefix = "resample"
+
+    def __init__(self, signal_len: int, num: int):
+        self._new(signal_len, num)
+        self.n = self.signal_len = signal_len
+        self.num = self.out_len = num
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` signals works in.  A smaller workspace of at least ``workspace_min()``
+        runs the batch in chunks of whole signals, to the same bits."""
+        return self._workspace_len(batch)
+
+    def workspace_min(self) -> int:
+        return int(self._fn("workspace_min")(self._h))
+
+    def time_stages(self, signal, out, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (R2C, spectrum sweep, C2R) of a call of ``batch`` signals at distances L and
+        num on device tensors (measurement hook)"""
+        x, y = _Slice(signal, self._dtype, "signal"), _Slice(out, self._dtype, "out")
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 3)()
+        _check(self._fn("time_stages")(self._h, x.ptr, y.ptr, batch, ws.ptr, ws.len, reps, ms, _stream()))
+        return [float(v) for v in ms]
+
+
+class PlannerResample32(PlannerResample64):
+    """f32 twin of :class:`PlannerResample64`"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def _rate_batched(name, x, planner, out, work, stream):
+    """a batch of rows of ``planner.signal_len`` samples through ``phast_{name}_f*_dev`` into rows of ``planner.out_len``"""
+    import torch
+
+    want = torch.float64 if planner._dtype == np.float64 else torch.float32
+    fs = "f64" if planner._dtype == np.float64 else "f32"
+
+    def plane(v, what, per):
+        if not _is_torch(v) or v.device.type != "cuda" or v.dtype != want:
+            raise TypeError(f"{what}: need a {want} device tensor")
+        if v.dim() not in (1, 2) or v.shape[-1] != per or (per > 1 and v.stride(-1) != 1):
+            raise ValueError(f"{what}: need shape (batch, {per}) or ({per},) with a contiguous last axis, not {tuple(v.shape)}")
+        rows = v.shape[0] if v.dim() == 2 else 1
+        dist = v.stride(0) if v.dim() == 2 and rows > 1 else per
+        if dist < per:
+            raise ValueError(f"{what}: rows overlap")
+        return rows, dist
+
+    batch, sig_dist = plane(x, "x", planner.signal_len)
+    m = planner.out_len
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        if out is None:
+            out = torch.empty((batch, m) if x.dim() == 2 else (m,), dtype=want, device=x.device)
+        rows, out_dist = plane(out, "out", m)
+        if rows != batch or out.dim() != x.dim():
+            raise ValueError("out: need one row per signal")
+        if work is None and planner.workspace_len(batch) == 0:
+            ptr, length = None, 0
+        else:
+            ws = _any_workspace(planner, batch, work)
+            ptr, length = ws.ptr, ws.len
+        _check(_call(f"phast_{name}_{fs}_dev", x.data_ptr(), out.data_ptr(), planner.signal_len, batch, sig_dist, out_dist,
+                     planner._h, ptr, length, _stream()))
+    return out
+
+
+def upfirdn_batched(x, planner, out=None, work=None, stream=None):
+    """Device-resident batch through one polyphase planner: ``x`` is a torch device tensor of shape ``(batch, L)`` or ``(L,)``
+    of the planner's type whose last axis is contiguous (rows any distance >= L apart); returns a tensor of shape
+    ``(batch, out_len)`` or ``(out_len,)``.  ``out``: such a tensor to write into; ``work`` is accepted and not used (the
+    kernel needs no workspace); ``stream``: a ``torch.cuda.Stream``, by default the current one.  ``x`` is not written."""
+    return _rate_batched("upfirdn", x, planner, out, work, stream)
+
+
+def resample_batched(x, planner, out=None, work=None, stream=None):
+    """Device-resident batch through one Fourier-method planner: ``x`` of shape ``(batch, L)`` or ``(L,)`` as for
+    :func:`upfirdn_batched`; returns ``(batch, num)`` or ``(num,)``.  ``work``: a device tensor of at least
+    ``planner.workspace_min()`` elements, by default one of ``planner.workspace_len(batch)`` from torch's allocator."""
+    return _rate_batched("resample", x, planner, out, work, stream)
+
+
+def _rate_host(name, fs, dtype, signal, out, planner):
+    x, y = _Slice(signal, dtype, "signal"), _Slice(out, dtype, "out")
+    if _same_place(x, y):
+        raise TypeError(f"{name}_{fs}_with_planner takes host arrays ({name}_batched takes device tensors)")
+    _check(_call(f"phast_{name}_{fs}_with_planner", x.ptr, x.len, y.ptr, y.len, planner._h))
+
+
+def upfirdn_64_with_planner(signal, out, planner: PlannerUpfirdn64) -> None:
+    """f64 polyphase FIR of one host signal of L samples into a host array of ``planner.out_len`` (blocking)"""
+    _rate_host("upfirdn", "f64", np.float64, signal, out, planner)
+
+
+def upfirdn_32_with_planner(signal, out, planner: PlannerUpfirdn32) -> None:
+    """f32 twin of :func:`upfirdn_64_with_planner`"""
+    _rate_host("upfirdn", "f32", np.float32, signal, out, planner)
+
+
+def resample_64_with_planner(signal, out, planner: PlannerResample64) -> None:
+    """f64 Fourier-method resampling of one host signal of L samples into a host array of ``planner.num`` (blocking)"""
+    _rate_host("resample", "f64", np.float64, signal, out, planner)
+
+
+def resample_32_with_planner(signal, out, planner: PlannerResample32) -> None:
+    """f32 twin of :func:`resample_64_with_planner`"""
+    _rate_host("resample", "f32", np.float32, signal, out, planner)
+
+
+def _rate_rows(x):
+    import torch
+
+    if not _is_torch(x) or x.device.type != "cuda" or x.dtype not in (torch.float64, torch.float32) or x.dim() < 1:
+        raise TypeError("need a float64 or float32 device tensor of at least one axis")
+    return x.reshape(-1, x.shape[-1]).contiguous(), x.dtype == torch.float64
+
+
+def _rate_apply(x, rows, planner, batched):
+    import torch
+
+    out = torch.empty((rows.shape[0], planner.out_len), dtype=x.dtype, device=x.device)
+    if rows.shape[0]:
+        batched(rows, planner, out)
+        torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+    return out.reshape(x.shape[:-1] + (planner.out_len,))
+
+
+def upfirdn(h, x, up: int = 1, down: int = 1):
+    """``scipy.signal.upfirdn(h, x, up, down)`` (mode "constant") over the last axis of a real device tensor ``x`` with the
+    taps ``h`` (an array or a tensor), through a planner of its own: a new tensor whose last axis has
+    ``((L - 1) * up + len(h) - 1) // down + 1`` samples"""
+    rows, f64 = _rate_rows(x)
+    planner = (PlannerUpfirdn64 if f64 else PlannerUpfirdn32)(x.shape[-1], h, up, down)
+    return _rate_apply(x, rows, planner, upfirdn_batched)
+
+
+def _fir_window(window, n: int):
+    """the symmetric window of n points of a name or a (name, parameter) pair, in double, from numpy alone"""
+    name, args = (window, ()) if isinstance(window, str) else (window[0], tuple(window[1:]))
+    plain = {"boxcar": np.ones, "rectangular": np.ones, "hamming": np.hamming, "hann": np.hanning, "blackman": np.blackman,
+             "bartlett": np.bartlett}
+    if name == "kaiser" and len(args) == 1:
+        return np.kaiser(n, float(args[0]))
+    if name in plain and not args:
+        return np.asarray(plain[name](n), dtype=np.float64)
+    raise ValueError(f"window {window!r}: need ('kaiser', beta), 'hamming', 'hann', 'blackman', 'bartlett' or 'boxcar', or an "
+                     "array of taps")
+
+
+def firwin_lowpass(numtaps: int, cutoff: float, window=("kaiser", 5.0)):
+    """``scipy.signal.firwin(numtaps, cutoff, window=window)``: the windowed-sinc low-pass of ``numtaps`` taps with the cutoff
+    in units of the Nyquist frequency, scaled to unit sum; a host array of doubles"""
+    if numtaps < 1 or not 0 < cutoff < 1:
+        raise ValueError("need numtaps >= 1 and 0 < cutoff < 1")
+    m = np.arange(numtaps) - 0.5 * (numtaps - 1)
+    h = cutoff * np.sinc(cutoff * m) * _fir_window(window, numtaps)
+    return h / h.sum()
+
+
+def resample_poly(x, up: int, down: int, window=("kaiser", 5.0), padtype: str = "constant"):
+    """``scipy.signal.resample_poly(x, up, down, window=window)`` over the last axis of a real device tensor: the rate times
+    ``up / down`` through the polyphase kernel, ``ceil(L up / down)`` samples.  ``window``: a window for the low-pass design
+    (``firwin(20 max(up, down) + 1, 1 / max(up, down), window)``) or an array of taps.  Only ``padtype="constant"``."""
+    import math
+
+    if padtype != "constant":
+        raise ValueError("only padtype='constant' is supported")
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise ValueError("up and down must be >= 1")
+    g = math.gcd(up, down)
+    up, down = up // g, down // g
+    rows, f64 = _rate_rows(x)
+    if up == 1 and down == 1:
+        return x.clone()
+    n_in = x.shape[-1]
+    n_out = -(-n_in * up // down)
+    if isinstance(window, (list, np.ndarray)) or _is_torch(window):
+        taps = np.asarray(window.detach().cpu().numpy() if _is_torch(window) else window, dtype=np.float64).reshape(-1)
+        half = (taps.size - 1) // 2
+    else:
+        half = 10 * max(up, down)
+        taps = firwin_lowpass(2 * half + 1, 1.0 / max(up, down), window)
+    n_pre_pad = down - half % down
+    h = np.concatenate((np.zeros(n_pre_pad), taps * up))
+    planner = (PlannerUpfirdn64 if f64 else PlannerUpfirdn32)(n_in, h, up, down, (half + n_pre_pad) // down, n_out)
+    return _rate_apply(x, rows, planner, upfirdn_batched)
+
+
+def decimate(x, q: int, n: int | None = None, ftype: str = "fir", zero_phase: bool = True):
+    """``scipy.signal.decimate(x, q, n, ftype="fir", zero_phase=True)`` over the last axis of a real device tensor: a Hamming
+    low-pass of ``n + 1`` taps (``n = 20 q`` by default) and every ``q``-th sample, without delay.  IIR decimation and
+    ``zero_phase=False`` are not supported."""
+    if ftype != "fir":
+        raise ValueError("only ftype='fir' is supported")
+    if not zero_phase:
+        raise ValueError("only zero_phase=True is supported")
+    q = int(q)
+    if q < 1:
+        raise ValueError("q must be >= 1")
+    n = 20 * q if n is None else int(n)
+    b = firwin_lowpass(n + 1, 1.0 / q, "hamming") if q > 1 else np.ones(1)
+    return resample_poly(x, 1, q, window=b)
+
+
+def resample(x, num: int):
+    """``scipy.signal.resample(x, num)`` over the last axis of a real device tensor (Fourier method, no window), through a
+    planner of its own: a new tensor whose last axis has ``num`` samples"""
+    rows, f64 = _rate_rows(x)
+    planner = (PlannerResample64 if f64 else PlannerResample32)(x.shape[-1], int(num))
+    return _rate_apply(x, rows, planner, resample_batched)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@
 #include "planner_mdct.hpp"
 #include "planner_psd.hpp"
 #include "planner_lomb.hpp"
+#include "planner_resample.hpp"
 #include "planner_stft.hpp"
 #include "planner_conv.hpp"
 #include "planner_convnd.hpp"
@@ -52,6 +53,10 @@ struct phast_planner_psd64 : PsdPlanner<double> {};
 struct phast_planner_psd32 : PsdPlanner<float> {};
 struct phast_planner_lomb64 : LombPlanner<double> {};
 struct phast_planner_lomb32 : LombPlanner<float> {};
+struct phast_planner_upfirdn64 : UpfirdnPlanner<double> {};
+struct phast_planner_upfirdn32 : UpfirdnPlanner<float> {};
+struct phast_planner_resample64 : ResamplePlanner<double> {};
+struct phast_planner_resample32 : ResamplePlanner<float> {};
 struct phast_planner_conv64 : ConvPlanner<double> {};
 struct phast_planner_conv32 : ConvPlanner<float> {};
 struct phast_planner_convnd64 : ConvNdPlanner<double> {};
@@ -565,7 +570,8 @@ PHAST_HANDLE_API(nufft64) PHAST_HANDLE_API(nufft32) PHAST_HANDLE_API(nufft2d64) 
 PHAST_HANDLE_API(nufft3d64) PHAST_HANDLE_API(nufft3d32) PHAST_HANDLE_API(nufft_t3_64) PHAST_HANDLE_API(nufft_t3_32)
 PHAST_HANDLE_API(nd64) PHAST_HANDLE_API(nd32) PHAST_HANDLE_API(r2c_nd64) PHAST_HANDLE_API(r2c_nd32)
 PHAST_HANDLE_API(convnd64) PHAST_HANDLE_API(convnd32) PHAST_HANDLE_API(mdct64) PHAST_HANDLE_API(mdct32)
-PHAST_HANDLE_API(lomb64) PHAST_HANDLE_API(lomb32)
+PHAST_HANDLE_API(lomb64) PHAST_HANDLE_API(lomb32) PHAST_HANDLE_API(upfirdn64) PHAST_HANDLE_API(upfirdn32)
+PHAST_HANDLE_API(resample64) PHAST_HANDLE_API(resample32)
 
 // Arbitrary lengths (Bluestein, planner_any.hpp): arguments are checked before the device is touched
 #define PHAST_ANY_API(SFX, T)                                                                                           \
@@ -922,6 +928,68 @@ PHAST_PSD_API(32, f32, float)
     } PHAST_CATCH_RC
 PHAST_LOMB_API(64, f64, double)
 PHAST_LOMB_API(32, f32, float)
+
+// Sample-rate conversion (planner_resample.hpp): the polyphase FIR and the Fourier method; every argument rule and a wrong
+// length come back before the device is touched
+#define PHAST_RESAMPLE_API(SFX, FS, T)                                                                                  \
+    int phast_planner_upfirdn##SFX##_new(size_t signal_len, const T *taps, size_t num_taps, size_t up, size_t down,     \
+                                         size_t first, size_t out_len, phast_planner_upfirdn##SFX **out) try {          \
+        return upfirdn_planner_new<T>(signal_len, taps, num_taps, up, down, first, out_len, out);                       \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_upfirdn##SFX##_out_len(const phast_planner_upfirdn##SFX *p) try {                              \
+        return p ? p->out_len : 0;                                                                                      \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_upfirdn##SFX##_full_len(const phast_planner_upfirdn##SFX *p) try {                             \
+        return p ? p->full_len : 0;                                                                                     \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_upfirdn##SFX##_tile(const phast_planner_upfirdn##SFX *p) try {                                 \
+        return p ? p->geom.tile : 0;                                                                                    \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_upfirdn##SFX##_chunk(const phast_planner_upfirdn##SFX *p) try {                                \
+        return p ? p->geom.jc : 0;                                                                                      \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_upfirdn##SFX##_time_stages(const phast_planner_upfirdn##SFX *p, const T *d_signal, T *d_out,      \
+                                                 size_t batch, int reps, float *stage_ms, void *stream) try {           \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(d_signal, d_out, batch, reps, stage_ms, static_cast<hipStream_t>(stream));                \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_upfirdn_##FS##_with_planner(const T *signal, size_t signal_len, T *out, size_t out_len,                   \
+                                          const phast_planner_upfirdn##SFX *p) try {                                    \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(signal, signal_len, out, out_len);                                                               \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_upfirdn_##FS##_dev(const T *d_signal, T *d_out, size_t signal_len, size_t batch, size_t sig_dist,         \
+                                 size_t out_dist, const phast_planner_upfirdn##SFX *p, T *, size_t, void *stream) try { \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(d_signal, d_out, signal_len, batch, sig_dist, out_dist, static_cast<hipStream_t>(stream));        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_planner_resample##SFX##_new(size_t signal_len, size_t num, phast_planner_resample##SFX **out) try {       \
+        return resample_planner_new<T>(signal_len, num, out);                                                           \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_resample##SFX##_workspace_min(const phast_planner_resample##SFX *p) try {                      \
+        return p ? p->workspace_min() : 0;                                                                              \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_resample##SFX##_time_stages(const phast_planner_resample##SFX *p, const T *d_signal, T *d_out,    \
+                                                  size_t batch, T *d_work, size_t work_len, int reps, float *stage_ms,  \
+                                                  void *stream) try {                                                   \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(d_signal, d_out, batch, d_work, work_len, reps, stage_ms,                                 \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_resample_##FS##_with_planner(const T *signal, size_t signal_len, T *out, size_t out_len,                  \
+                                           const phast_planner_resample##SFX *p) try {                                  \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(signal, signal_len, out, out_len);                                                               \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_resample_##FS##_dev(const T *d_signal, T *d_out, size_t signal_len, size_t batch, size_t sig_dist,        \
+                                  size_t out_dist, const phast_planner_resample##SFX *p, T *d_work, size_t work_len,    \
+                                  void *stream) try {                                                                   \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(d_signal, d_out, signal_len, batch, sig_dist, out_dist, d_work, work_len,                         \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC
+PHAST_RESAMPLE_API(64, f64, double)
+PHAST_RESAMPLE_API(32, f32, float)
 
 // Overlap-save convolution and correlation of real signals (planner_conv.hpp): every argument rule and a wrong length come
 // back before the device is touched

@@ -8,6 +8,7 @@ pub mod czt;
 pub mod dit;
 pub mod mdct;
 pub mod psd;
+pub mod resample;
 pub mod lomb;
 pub mod nufft;
 pub mod nufft2d;

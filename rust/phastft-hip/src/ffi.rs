@@ -272,6 +272,63 @@ extern "C" {
         im_len: usize, normalize: c_int, planner: *const Opaque) -> c_int;
     pub(crate) fn phast_lombscargle_f32_dev(y: *const f32, out_re: *mut f32, out_im: *mut f32, m: usize, batch: usize, sig_dist: usize,
         out_dist: usize, normalize: c_int, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // sample-rate conversion (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/resample.rs)
+    pub(crate) fn phast_planner_upfirdn64_new(signal_len: usize, taps: *const f64, num_taps: usize, up: usize, down: usize, first: usize,
+        out_len: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_upfirdn64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_upfirdn64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_upfirdn64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_upfirdn64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_upfirdn64_out_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_upfirdn64_full_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_upfirdn64_tile(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_upfirdn64_chunk(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_upfirdn64_time_stages(p: *const Opaque, signal: *const f64, out: *mut f64, batch: usize, reps: c_int,
+        stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_upfirdn_f64_with_planner(signal: *const f64, signal_len: usize, out: *mut f64, out_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_upfirdn_f64_dev(signal: *const f64, out: *mut f64, signal_len: usize, batch: usize, sig_dist: usize, out_dist: usize,
+        planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_resample64_new(signal_len: usize, num: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_resample64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_resample64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_resample64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_resample64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_resample64_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_resample64_time_stages(p: *const Opaque, signal: *const f64, out: *mut f64, batch: usize, work: *mut f64,
+        work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_resample_f64_with_planner(signal: *const f64, signal_len: usize, out: *mut f64, out_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_resample_f64_dev(signal: *const f64, out: *mut f64, signal_len: usize, batch: usize, sig_dist: usize, out_dist: usize,
+        planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_upfirdn32_new(signal_len: usize, taps: *const f32, num_taps: usize, up: usize, down: usize, first: usize,
+        out_len: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_upfirdn32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_upfirdn32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_upfirdn32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_upfirdn32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_upfirdn32_out_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_upfirdn32_full_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_upfirdn32_tile(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_upfirdn32_chunk(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_upfirdn32_time_stages(p: *const Opaque, signal: *const f32, out: *mut f32, batch: usize, reps: c_int,
+        stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_upfirdn_f32_with_planner(signal: *const f32, signal_len: usize, out: *mut f32, out_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_upfirdn_f32_dev(signal: *const f32, out: *mut f32, signal_len: usize, batch: usize, sig_dist: usize, out_dist: usize,
+        planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_resample32_new(signal_len: usize, num: usize, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_resample32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_resample32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_resample32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_resample32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_resample32_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_resample32_time_stages(p: *const Opaque, signal: *const f32, out: *mut f32, batch: usize, work: *mut f32,
+        work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_resample_f32_with_planner(signal: *const f32, signal_len: usize, out: *mut f32, out_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_resample_f32_dev(signal: *const f32, out: *mut f32, signal_len: usize, batch: usize, sig_dist: usize, out_dist: usize,
+        planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // overlap-save convolution and correlation (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/conv.rs)
     pub(crate) fn phast_planner_conv64_new(signal_len: usize, taps: *const f64, num_taps: usize, mode: c_int, flip: c_int,
         block: usize, out: *mut *mut Opaque) -> c_int;

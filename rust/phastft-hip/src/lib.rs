@@ -73,6 +73,12 @@ pub use algorithms::lomb::{
     lombscargle_f64_with_planner,
 };
 pub use planner::{LombNorm, PlannerLomb32, PlannerLomb64};
+// sample-rate conversion: the polyphase FIR and the Fourier method (an extension beyond PhastFT 0.3.0)
+pub use algorithms::resample::{
+    resample_f32_dev, resample_f32_with_planner, resample_f64_dev, resample_f64_with_planner, upfirdn_f32_dev, upfirdn_f32_with_planner,
+    upfirdn_f64_dev, upfirdn_f64_with_planner,
+};
+pub use planner::{PlannerResample32, PlannerResample64, PlannerUpfirdn32, PlannerUpfirdn64};
 // overlap-save convolution and correlation of real signals (an extension beyond PhastFT 0.3.0)
 pub use algorithms::conv::{conv_f32_dev, conv_f32_with_planner, conv_f64_dev, conv_f64_with_planner};
 pub use planner::{ConvMode, PlannerConv32, PlannerConv64};

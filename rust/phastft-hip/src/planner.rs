@@ -523,6 +523,111 @@ impl_planner_lomb!(PlannerLomb64, phast_planner_lomb64_new, phast_planner_lomb64
 impl_planner_lomb!(PlannerLomb32, phast_planner_lomb32_new, phast_planner_lomb32_free, phast_planner_lomb32_slab,
                    phast_planner_lomb32_grid_len, phast_planner_lomb32_workspace_len, phast_planner_lomb32_workspace_min);
 
+macro_rules! impl_planner_upfirdn {
+    ($up:ident, $t:ty, $new:ident, $free:ident, $out_len:ident, $full_len:ident, $tile:ident, $chunk:ident) => {
+        /// An extension beyond PhastFT 0.3.0: the polyphase FIR of scipy.signal.upfirdn on real signals of `signal_len`
+        /// samples -- zero-stuff by `up`, filter with the planner's taps, keep every `down`-th sample -- of which a call
+        /// yields the `out_len` samples from `first` on.  One direct kernel, no workspace; the bits of an output depend on the
+        /// values alone.  Immutable after `new`.
+        pub struct $up {
+            pub(crate) h: *mut Opaque,
+            pub(crate) signal_len: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's buffers (device calls) or in device
+        // buffers of its own (host-slice calls)
+        unsafe impl Send for $up {}
+        unsafe impl Sync for $up {}
+        impl $up {
+            /// `out_len` = 0 stands for `full_len - first`; `first + out_len` may pass `full_len` (zeros there); `up` and
+            /// `down` are used as given.  Panics with "invalid argument" unless 1 <= signal_len, taps.len(), out_len <= 2^29,
+            /// 1 <= up, down <= 2^20 and first <= full_len
+            pub fn new(signal_len: usize, taps: &[$t], up: usize, down: usize, first: usize, out_len: usize) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe { ffi::$new(signal_len, taps.as_ptr(), taps.len(), up, down, first, out_len, &mut h) });
+                Self { h, signal_len }
+            }
+            pub fn signal_len(&self) -> usize {
+                self.signal_len
+            }
+            pub fn out_len(&self) -> usize {
+                unsafe { ffi::$out_len(self.h) }
+            }
+            /// ((signal_len - 1) up + taps - 1) / down + 1
+            pub fn full_len(&self) -> usize {
+                unsafe { ffi::$full_len(self.h) }
+            }
+            /// outputs per workgroup: a function of (taps, up, down) alone
+            pub fn tile(&self) -> usize {
+                unsafe { ffi::$tile(self.h) }
+            }
+            /// taps of a phase per LDS chunk
+            pub fn chunk(&self) -> usize {
+                unsafe { ffi::$chunk(self.h) }
+            }
+            /// 0: the kernel needs no workspace
+            pub fn workspace_min(&self) -> usize {
+                0
+            }
+        }
+        impl Drop for $up {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_upfirdn!(PlannerUpfirdn64, f64, phast_planner_upfirdn64_new, phast_planner_upfirdn64_free, phast_planner_upfirdn64_out_len,
+                      phast_planner_upfirdn64_full_len, phast_planner_upfirdn64_tile, phast_planner_upfirdn64_chunk);
+impl_planner_upfirdn!(PlannerUpfirdn32, f32, phast_planner_upfirdn32_new, phast_planner_upfirdn32_free, phast_planner_upfirdn32_out_len,
+                      phast_planner_upfirdn32_full_len, phast_planner_upfirdn32_tile, phast_planner_upfirdn32_chunk);
+
+macro_rules! impl_planner_resample {
+    ($rs:ident, $new:ident, $free:ident, $ws_len:ident, $ws_min:ident) => {
+        /// An extension beyond PhastFT 0.3.0: scipy.signal.resample(x, num) of real signals of `signal_len` samples (Fourier
+        /// method, no window): one R2C of `signal_len` and one C2R of `num` on the any-length real path around one sweep.
+        /// Immutable after `new`.
+        pub struct $rs {
+            pub(crate) h: *mut Opaque,
+            pub(crate) signal_len: usize,
+            num: usize,
+        }
+        // SAFETY: as for the polyphase planner
+        unsafe impl Send for $rs {}
+        unsafe impl Sync for $rs {}
+        impl $rs {
+            /// Panics with "invalid argument" unless 1 <= signal_len, num <= 2^29
+            pub fn new(signal_len: usize, num: usize) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe { ffi::$new(signal_len, num, &mut h) });
+                Self { h, signal_len, num }
+            }
+            pub fn signal_len(&self) -> usize {
+                self.signal_len
+            }
+            pub fn out_len(&self) -> usize {
+                self.num
+            }
+            /// elements of the workspace a device call of `batch` signals works in
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+            /// the least workspace a call runs in: one signal
+            pub fn workspace_min(&self) -> usize {
+                unsafe { ffi::$ws_min(self.h) }
+            }
+        }
+        impl Drop for $rs {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_resample!(PlannerResample64, phast_planner_resample64_new, phast_planner_resample64_free,
+                       phast_planner_resample64_workspace_len, phast_planner_resample64_workspace_min);
+impl_planner_resample!(PlannerResample32, phast_planner_resample32_new, phast_planner_resample32_free,
+                       phast_planner_resample32_workspace_len, phast_planner_resample32_workspace_min);
+
 /// Which part of the full convolution a planner yields (PHAST_CONV_* of the C ABI)
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum ConvMode {
