@@ -693,15 +693,21 @@ int run_part(const char *) {
     set_case("%s wave", Fp<TT>::name());
     if (!listed) fail("wave_fft_kernel", "enumerate_plans no longer lists %s", spec_to_string(spec).c_str());
     std::printf("  stagger setting %#x\n", wave_stagger_setting());
-    for (size_t pos = 0; pos < 2; ++pos) {
-        Plan<TT> pl(L, spec, 3);
+    // ... and eight transforms, whole: the workgroup count is a multiple of 8 (locate's remap for XCD affinity) with several
+    // transforms behind it -- what a composite planner's engine gives the kernel (tests/test_gpu_engine_batches.py)
+    for (size_t run = 0; run < 4; ++run) {
+        const size_t pos = run & 1;
+        const bool eight = run >= 2;
+        Plan<TT> pl(L, spec, eight ? 8 : 3);
         if (!pl.ok || !pl.ps[pos].wave || !pl.run_before(pos)) {
             fail("wave_fft_kernel", "the plan %s could not be set up", spec_to_string(spec).c_str());
             continue;
         }
         const State<TT> before = pl.st;
         const unsigned all = pl.args(pos).tiles_total;
+        if (eight && (all % (8 * WAVES) || all / WAVES < 8)) fail("wave_fft_kernel", "eight transforms: %u tiles are no multiple of 8 workgroups", all);
         for (unsigned tiles : {1u, WAVES, 2 * WAVES + 1, all}) {
+            if (eight && tiles != all) continue;
             if (tiles > all) {
                 fail("wave_fft_kernel", "%u tiles wanted, the batch has %u", tiles, all);
                 continue;
@@ -763,7 +769,9 @@ int run_part(const char *) {
     for (const PlanSpec &s : plans_of<TT>(L)) listed |= s == spec;
     set_case("%s quad", Fp<TT>::name());
     if (!listed) fail("quad_fft_kernel", "enumerate_plans no longer lists %s", spec_to_string(spec).c_str());
-    for (size_t batch : {(size_t)1, (size_t)3}) {
+    // (eight transforms: a tile count that is a multiple of 8 -- locate's remap for XCD affinity -- with several transforms in it,
+    //  as a composite planner's engine runs the pass: tests/test_gpu_engine_batches.py)
+    for (size_t batch : {(size_t)1, (size_t)3, (size_t)8}) {
         Plan<TT> pl(L, spec, batch);
         if (!pl.ok || !pl.ps[1].quad || !pl.run_before(1)) {
             fail("quad_fft_kernel", "the plan %s could not be set up", spec_to_string(spec).c_str());
