@@ -28,6 +28,8 @@
 //                                                            csd_f64/f32_with_planner
 //   (none: no spectra of uneven samples upstream)            class PlannerLomb64/32, lombscargle_f64/f32_with_planner,
 //                                                            enum LombNorm -- scipy.signal.lombscargle
+//   (none: no filter banks upstream)                         class PlannerChannelizer64/32, channelize_f64/f32_with_planner -- the
+//                                                            polyphase channelizer (uniform DFT analysis filter bank)
 //   (none: no sample-rate conversion upstream)               class PlannerUpfirdn64/32, upfirdn_f64/f32_with_planner -- the polyphase
 //                                                            FIR of scipy.signal.upfirdn; class PlannerResample64/32,
 //                                                            resample_f64/f32_with_planner -- scipy.signal.resample
@@ -775,6 +777,66 @@ PHASTFT_RESAMPLE(upfirdn, f32, float, PlannerUpfirdn32)
 PHASTFT_RESAMPLE(resample, f64, double, PlannerResample64)
 PHASTFT_RESAMPLE(resample, f32, float, PlannerResample32)
 #undef PHASTFT_RESAMPLE
+
+// ---- polyphase filter-bank channelizer (no reference counterpart; cuSignal's channelize_poly) ----
+#define PHASTFT_PLANNER_CHANNELIZER(NAME, CT, SFX, T)                                                            \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* `channels` equally spaced channels of signals of signal_len samples, each filtered with the real taps and \
+           decimated by `hop` (0: channels, critically sampled), zero extension: the out_frames frames from first_frame on \
+           (out_frames = 0: up to full_frames; the window may pass it: zeros).  complex_input: the signals are (re, im) \
+           planes and a frame has `channels` bins; real signals give channels / 2 + 1 */                        \
+        NAME(std::size_t signal_len, Slice<const T> taps, std::size_t channels, std::size_t hop = 0, std::size_t first_frame = 0, \
+             std::size_t out_frames = 0, bool complex_input = false) {                                           \
+            check(phast_planner_channelizer##SFX##_new(signal_len, taps.ptr, taps.len, channels, hop ? hop : channels, first_frame, \
+                                                       out_frames, complex_input ? 1 : 0, &h_));                 \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }                                                   \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_channelizer##SFX##_free(h_);                                                   \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_channelizer##SFX##_describe(h_, &s[0], s.size()));                               \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_channelizer##SFX##_device_bytes(h_); }           \
+        std::size_t out_frames() const { return phast_planner_channelizer##SFX##_out_frames(h_); }               \
+        std::size_t full_frames() const { return phast_planner_channelizer##SFX##_full_frames(h_); }             \
+        std::size_t bins() const { return phast_planner_channelizer##SFX##_bins(h_); }                           \
+        /* the fold's tile (frames x columns per workgroup), tap rows per LDS chunk and periods of the signal in LDS: \
+           functions of (K, channels, hop) alone */                                                              \
+        std::size_t tile_frames() const { return phast_planner_channelizer##SFX##_tile_frames(h_); }             \
+        std::size_t tile_cols() const { return phast_planner_channelizer##SFX##_tile_cols(h_); }                 \
+        std::size_t chunk() const { return phast_planner_channelizer##SFX##_chunk(h_); }                         \
+        std::size_t periods() const { return phast_planner_channelizer##SFX##_periods(h_); }                     \
+        /* elements of T a _dev call of `batch` signals works in; workspace_min: the least a call runs in */     \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_channelizer##SFX##_workspace_len(h_, batch); } \
+        std::size_t workspace_min() const { return phast_planner_channelizer##SFX##_workspace_min(h_); }         \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+    };
+PHASTFT_PLANNER_CHANNELIZER(PlannerChannelizer64, phast_planner_channelizer64, 64, double)
+PHASTFT_PLANNER_CHANNELIZER(PlannerChannelizer32, phast_planner_channelizer32, 32, float)
+#undef PHASTFT_PLANNER_CHANNELIZER
+
+// one host signal of L samples (signal_im: its imaginary plane for a complex planner, an empty slice for a real one) -> the
+// out_frames() x bins() points of both output planes, frame-major; blocking
+#define PHASTFT_CHANNELIZE(FS, T, P)                                                                             \
+    inline void channelize_##FS##_with_planner(Slice<const T> signal, Slice<const T> signal_im, Slice<T> out_re, Slice<T> out_im, \
+                                               const P &planner) {                                               \
+        if (out_re.len != out_im.len || (signal_im.ptr && signal_im.len != signal.len)) check(PHAST_ERR_LEN_MISMATCH); \
+        check(phast_channelize_##FS##_with_planner(signal.ptr, signal_im.ptr, signal.len, out_re.ptr, out_im.ptr, out_re.len, \
+                                                   planner.get()));                                              \
+    }
+PHASTFT_CHANNELIZE(f64, double, PlannerChannelizer64)
+PHASTFT_CHANNELIZE(f32, float, PlannerChannelizer32)
+#undef PHASTFT_CHANNELIZE
 
 // ---- overlap-save convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve / correlate) ----
 enum class ConvMode : int { Full = PHAST_CONV_FULL, Same = PHAST_CONV_SAME, Valid = PHAST_CONV_VALID };

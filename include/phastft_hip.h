@@ -833,6 +833,79 @@ int phast_resample_f32_dev(const float *d_signal, float *d_out, size_t signal_le
 int phast_planner_resample32_time_stages(const phast_planner_resample32 *p, const float *d_signal, float *d_out, size_t batch, float *d_work, size_t work_len,
                                           int reps, float *stage_ms, void *stream);
 
+/* ---- polyphase filter-bank channelizer: the analysis side of a uniform DFT filter bank (no reference counterpart; cuSignal's
+ * channelize_poly).  Signal x of L samples -- real: one plane; complex: planes re and im --, K real taps h (host
+ * values of T), M channels, hop D, zero extension as phast_planner_upfirdn*:
+ *     full_frames = (L + K - 2) / D + 1
+ *     y[m][k] = sum_n h[m D - n] x[n] exp(-2 pi i k n / M),  0 <= m < full_frames, 0 <= k < M;  y[m] = 0 above
+ *     out[i]  = y[first_frame + i],                          0 <= i < out_frames   (out_frames = 0 at _new: full_frames - first_frame)
+ * Channel k is upfirdn(h, x exp(-2 pi i k n / M), 1, D): the phase is referred to absolute sample time, so the channels are
+ * baseband streams for any D (D = M: critically sampled; D < M: oversampled; D > M is legal).  first_frame + out_frames may pass
+ * full_frames (zeros).  Output planes, dense and frame-major: element (b out_frames + i) bins + k, bins = M for a complex signal
+ * and M / 2 + 1 for a real one (y[m][M - k] = conj y[m][k]).
+ * Method: one fold kernel, u[m][p] = sum_{j < T} h[r0 + j M] x[m D - r0 - j M] with r0 = (m D - p) mod M and T = ceil(K / M), then
+ * one M-point transform per frame on the any-length path (phast_planner_any* / phast_planner_r2c_any*).  An element of the fold is
+ * acc = fma(h[r0 + j M], x[m D - r0 - j M], acc) for j = 0 .. T - 1 ascending from 0 in T, so the result's bits depend on the
+ * values alone -- not on the batch, the distances, pointer alignment, the workspace, the stream or a graph replay.
+ * Complex signals: the fold writes the caller's output planes and the transform runs in place; the workspace
+ * (_workspace_len(p, batch) elements of T) is the transform's alone, 0 for a power-of-two M.  Real signals: the fold goes into
+ * workspace rows and the R2C from there into the output; any work_len >= _workspace_min(p) (one frame) runs the frames in chunks,
+ * to the same bits.  Where _workspace_min is 0, d_work may be NULL.
+ * _new refuses with PHAST_ERR_INVALID_ARG, before the device is touched: NULL taps; L, K, M or D outside 1 .. 2^29; first_frame >
+ * full_frames; out_frames (resolved) < 1 or out_frames M > 2^30.  _dev: signal b at d_sig_re (d_sig_im) + b sig_dist (>= L; batch 1
+ * ignores it); d_sig_im must be NULL for a real planner and non-NULL for a complex one; pointers need element alignment only;
+ * the signal is never written; input and output must not overlap (identical pointers are refused).  A null pointer, the wrong
+ * d_sig_im, a short dist, a null or short workspace: PHAST_ERR_INVALID_ARG; a signal_len that is not the planner's:
+ * PHAST_ERR_PLANNER_SIZE; an out_len of the host-slice form that is not out_frames bins: PHAST_ERR_LEN_MISMATCH -- all before the
+ * device is touched.  The *_with_planner forms take host slices of one signal (sig_im NULL for a real planner) and block.
+ * Out of scope: the synthesis bank (the inverse), complex taps, subsets of the channels, any choice of method by size. */
+typedef struct phast_planner_channelizer64 phast_planner_channelizer64; /* PlannerChannelizer64 */
+int phast_planner_channelizer64_new(size_t signal_len, const double *taps, size_t num_taps, size_t channels, size_t hop, size_t first_frame, size_t out_frames,
+                                     int complex_input, phast_planner_channelizer64 **out);
+void phast_planner_channelizer64_free(phast_planner_channelizer64 *p);
+int phast_planner_channelizer64_describe(const phast_planner_channelizer64 *p, char *buf, size_t buf_len);
+size_t phast_planner_channelizer64_device_bytes(const phast_planner_channelizer64 *p);
+size_t phast_planner_channelizer64_workspace_len(const phast_planner_channelizer64 *p, size_t batch);
+size_t phast_planner_channelizer64_workspace_min(const phast_planner_channelizer64 *p);
+size_t phast_planner_channelizer64_out_frames(const phast_planner_channelizer64 *p);
+size_t phast_planner_channelizer64_full_frames(const phast_planner_channelizer64 *p);
+size_t phast_planner_channelizer64_bins(const phast_planner_channelizer64 *p);
+size_t phast_planner_channelizer64_tile_frames(const phast_planner_channelizer64 *p); /* frames per workgroup */
+size_t phast_planner_channelizer64_tile_cols(const phast_planner_channelizer64 *p);   /* columns per workgroup */
+size_t phast_planner_channelizer64_chunk(const phast_planner_channelizer64 *p);       /* tap rows per LDS chunk */
+size_t phast_planner_channelizer64_periods(const phast_planner_channelizer64 *p);     /* periods of the signal in LDS */
+int phast_channelize_f64_with_planner(const double *sig_re, const double *sig_im, size_t signal_len, double *out_re, double *out_im, size_t out_len,
+                                       const phast_planner_channelizer64 *planner);
+int phast_channelize_f64_dev(const double *d_sig_re, const double *d_sig_im, double *d_out_re, double *d_out_im, size_t signal_len, size_t batch, size_t sig_dist,
+                              const phast_planner_channelizer64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/channelizer_rate.py): stage_ms[2] = average milliseconds of the fold and of the transform over `reps`
+ * calls of `batch` signals at distance L in ONE chunk (work_len >= _workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_channelizer64_time_stages(const phast_planner_channelizer64 *p, const double *d_sig_re, const double *d_sig_im, double *d_out_re, double *d_out_im, size_t batch, double *d_work, size_t work_len,
+                                             int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_channelizer32 phast_planner_channelizer32; /* PlannerChannelizer32 */
+int phast_planner_channelizer32_new(size_t signal_len, const float *taps, size_t num_taps, size_t channels, size_t hop, size_t first_frame, size_t out_frames,
+                                     int complex_input, phast_planner_channelizer32 **out);
+void phast_planner_channelizer32_free(phast_planner_channelizer32 *p);
+int phast_planner_channelizer32_describe(const phast_planner_channelizer32 *p, char *buf, size_t buf_len);
+size_t phast_planner_channelizer32_device_bytes(const phast_planner_channelizer32 *p);
+size_t phast_planner_channelizer32_workspace_len(const phast_planner_channelizer32 *p, size_t batch);
+size_t phast_planner_channelizer32_workspace_min(const phast_planner_channelizer32 *p);
+size_t phast_planner_channelizer32_out_frames(const phast_planner_channelizer32 *p);
+size_t phast_planner_channelizer32_full_frames(const phast_planner_channelizer32 *p);
+size_t phast_planner_channelizer32_bins(const phast_planner_channelizer32 *p);
+size_t phast_planner_channelizer32_tile_frames(const phast_planner_channelizer32 *p); /* frames per workgroup */
+size_t phast_planner_channelizer32_tile_cols(const phast_planner_channelizer32 *p);   /* columns per workgroup */
+size_t phast_planner_channelizer32_chunk(const phast_planner_channelizer32 *p);       /* tap rows per LDS chunk */
+size_t phast_planner_channelizer32_periods(const phast_planner_channelizer32 *p);     /* periods of the signal in LDS */
+int phast_channelize_f32_with_planner(const float *sig_re, const float *sig_im, size_t signal_len, float *out_re, float *out_im, size_t out_len,
+                                       const phast_planner_channelizer32 *planner);
+int phast_channelize_f32_dev(const float *d_sig_re, const float *d_sig_im, float *d_out_re, float *d_out_im, size_t signal_len, size_t batch, size_t sig_dist,
+                              const phast_planner_channelizer32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/channelizer_rate.py): stage_ms[2] = average milliseconds of the fold and of the transform over `reps`
+ * calls of `batch` signals at distance L in ONE chunk (work_len >= _workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_channelizer32_time_stages(const phast_planner_channelizer32 *p, const float *d_sig_re, const float *d_sig_im, float *d_out_re, float *d_out_im, size_t batch, float *d_work, size_t work_len,
+                                             int reps, float *stage_ms, void *stream);
+
 /* ---- overlap-save FIR convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve /
  * correlate(x, h, mode, method="direct")).  Signal x of L samples, K taps h, both real:
  *     full[t] = sum_j g[j] x[t - j], t in [0, L + K - 1); g = h (flip = 0: convolution) or g[j] = h[K - 1 - j] (flip = 1:

@@ -36,6 +36,8 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
                                                     resample_batched, upfirdn_64/32_with_planner,
                                                     resample_64/32_with_planner, upfirdn, resample_poly, decimate,
                                                     resample, firwin_lowpass
+    (none: no filter banks)                         PlannerChannelizer64/32, channelize_batched,
+                                                    channelize_64/32_with_planner, channelize_poly, pfb_prototype
     (none: no convolution)                          PlannerConv64/32, conv_batched, conv_f64/f32_with_planner,
                                                     fftconvolve, correlate
     (none: no convolution)                          PlannerConvNd64/32, convnd_batched, convnd_f64/f32_with_planner,
@@ -106,6 +108,8 @@ __all__ = [
     "PlannerUpfirdn64", "PlannerUpfirdn32", "PlannerResample64", "PlannerResample32", "upfirdn_batched", "resample_batched",
     "upfirdn_64_with_planner", "upfirdn_32_with_planner", "resample_64_with_planner", "resample_32_with_planner", "upfirdn",
     "resample_poly", "decimate", "resample", "firwin_lowpass",
+    "PlannerChannelizer64", "PlannerChannelizer32", "channelize_batched", "channelize_64_with_planner",
+    "channelize_32_with_planner", "channelize_poly", "pfb_prototype",
     "PlannerConv64", "PlannerConv32", "conv_batched", "conv_f64_with_planner", "conv_f32_with_planner", "fftconvolve",
     "correlate",
     "PlannerConvNd64", "PlannerConvNd32", "convnd_batched", "convnd_f64_with_planner", "convnd_f32_with_planner",
@@ -2076,6 +2080,176 @@ def resample(x, num: int):
     rows, f64 = _rate_rows(x)
     planner = (PlannerResample64 if f64 else PlannerResample32)(x.shape[-1], int(num))
     return _rate_apply(x, rows, planner, resample_batched)
+
+
+# ---------------------------------------------------------------------------------------------
+# polyphase filter-bank channelizer (no reference counterpart; cuSignal's channelize_poly)
+# ---------------------------------------------------------------------------------------------
+class PlannerChannelizer64(_AnyHandle):
+    """f64 polyphase channelizer of signals of ``signal_len`` samples: ``n_chans`` equally spaced channels, each the signal
+    times ``exp(-2 pi i k n / n_chans)``, filtered with the real taps ``h`` and decimated by ``hop`` (default ``n_chans``:
+    critically sampled), with zero extension: channel k is ``scipy.signal.upfirdn(h, x * exp(-2j pi k n / n_chans), 1, hop)``.
+    A call yields the ``out_frames`` frames from ``first_frame`` on (``out_frames=None``: up to the end, ``full_frames -
+    first_frame``); the window may pass ``full_frames``: zeros there.  ``complex_input``: the signals are (re, im) plane pairs
+    and a frame has ``n_chans`` bins; real signals give the one-sided ``n_chans // 2 + 1``.  One fold kernel, then one
+    ``n_chans``-point transform per frame on the any-length path."""
+
+    _prefix = "channelizer"
+
+    def __init__(self, signal_len: int, h, n_chans: int, hop: int | None = None, first_frame: int = 0,
+                 out_frames: int | None = None, complex_input: bool = False):
+        if _is_torch(h):
+            h = h.detach().cpu().numpy()
+        taps = np.ascontiguousarray(h, dtype=self._dtype).reshape(-1)
+        hop = n_chans if hop is None else hop
+        self._new(signal_len, taps.ctypes.data_as(C.c_void_p), taps.size, n_chans, hop, first_frame,
+                  0 if out_frames is None else out_frames, 1 if complex_input else 0)
+        self.n = self.signal_len = signal_len
+        self.num_taps, self.n_chans, self.hop, self.first_frame = taps.size, n_chans, hop, first_frame
+        self.complex_input = bool(complex_input)
+        self.out_frames = int(self._fn("out_frames")(self._h))
+        self.full_frames = int(self._fn("full_frames")(self._h))
+        self.bins = int(self._fn("bins")(self._h))
+        self.tile_frames = int(self._fn("tile_frames")(self._h))
+        self.tile_cols = int(self._fn("tile_cols")(self._h))
+        self.chunk = int(self._fn("chunk")(self._h))
+        self.periods = int(self._fn("periods")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` signals works in (0 for complex signals and a power-of-two ``n_chans``).
+        A smaller workspace of at least ``workspace_min()`` runs the frames in chunks, to the same bits."""
+        return self._workspace_len(batch)
+
+    def workspace_min(self) -> int:
+        return int(self._fn("workspace_min")(self._h))
+
+    def time_stages(self, x_re, x_im, out_re, out_im, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (fold, transform) of a call of ``batch`` signals at distance L on device
+        tensors; ``x_im`` is None for a real planner (measurement hook)"""
+        xr = _Slice(x_re, self._dtype, "x_re")
+        xi = _NULL if x_im is None else _Slice(x_im, self._dtype, "x_im")
+        o_re, o_im = _Slice(out_re, self._dtype, "out_re"), _Slice(out_im, self._dtype, "out_im")
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 2)()
+        _check(self._fn("time_stages")(self._h, xr.ptr, xi.ptr, o_re.ptr, o_im.ptr, batch, ws.ptr, ws.len, reps, ms, _stream()))
+        return [float(v) for v in ms]
+
+
+class PlannerChannelizer32(PlannerChannelizer64):
+    """f32 twin of :class:`PlannerChannelizer64`: taps, products and sums in f32"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def channelize_batched(x, planner, out=None, work=None, stream=None):
+    """Device-resident batch through one channelizer planner.  ``x``: a real torch device tensor of shape ``(batch, L)`` or
+    ``(L,)`` of the planner's type whose last axis is contiguous (rows any distance >= L apart); for a complex planner a
+    complex tensor of such a shape (split into planes here) or a pair ``(x_re, x_im)`` of real planes with equal strides.
+    Returns a complex tensor of shape ``(batch, out_frames, bins)`` (``(out_frames, bins)`` for one unbatched signal).  ``out``:
+    a pair of contiguous real planes of ``batch * out_frames * bins`` elements to write into, returned in place of the
+    complex tensor; ``work``: a device tensor of at least ``planner.workspace_min()`` elements, by default one of
+    ``planner.workspace_len(batch)`` from torch's allocator; ``stream``: a ``torch.cuda.Stream``, by default the current one.
+    ``x`` is not written."""
+    import torch
+
+    want = torch.float64 if planner._dtype == np.float64 else torch.float32
+    fs = "f64" if planner._dtype == np.float64 else "f32"
+    n = planner.signal_len
+
+    def plane(v, what):
+        if not _is_torch(v) or v.device.type != "cuda" or v.dtype != want:
+            raise TypeError(f"{what}: need a {want} device tensor")
+        if v.dim() not in (1, 2) or v.shape[-1] != n or (n > 1 and v.stride(-1) != 1):
+            raise ValueError(f"{what}: need shape (batch, {n}) or ({n},) with a contiguous last axis, not {tuple(v.shape)}")
+        rows = v.shape[0] if v.dim() == 2 else 1
+        dist = v.stride(0) if v.dim() == 2 and rows > 1 else n
+        if dist < n:
+            raise ValueError(f"{what}: rows overlap")
+        return rows, dist
+
+    if isinstance(x, (tuple, list)):
+        x_re, x_im = x
+    elif _is_torch(x) and x.is_complex():
+        x_re, x_im = x.real.contiguous(), x.imag.contiguous()
+    else:
+        x_re, x_im = x, None
+    if (x_im is not None) != planner.complex_input:
+        raise TypeError("a complex planner takes complex signals and a real planner real ones")
+    batch, sig_dist = plane(x_re, "x")
+    if x_im is not None and (plane(x_im, "x_im") != (batch, sig_dist) or x_im.shape != x_re.shape):
+        raise ValueError("x_im: need the shape and the strides of x_re")
+    pts = batch * planner.out_frames * planner.bins
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        own = out is None
+        if own:
+            out = torch.empty((2, pts), dtype=want, device=x_re.device)
+        out_re, out_im = out[0], out[1]
+        for v, what in ((out_re, "out_re"), (out_im, "out_im")):
+            if not _is_torch(v) or v.device.type != "cuda" or v.dtype != want or v.numel() != pts or not v.is_contiguous():
+                raise ValueError(f"{what}: need a contiguous {want} device tensor of {pts} elements")
+        if work is None and planner.workspace_min() == 0:
+            ptr, length = None, 0
+        else:
+            ws = _any_workspace(planner, batch, work)
+            ptr, length = ws.ptr, ws.len
+        _check(_call(f"phast_channelize_{fs}_dev", x_re.data_ptr(), None if x_im is None else x_im.data_ptr(), out_re.data_ptr(),
+                     out_im.data_ptr(), n, batch, sig_dist, planner._h, ptr, length, _stream()))
+        if not own:
+            return out
+        shape = (planner.out_frames, planner.bins) if x_re.dim() == 1 else (batch, planner.out_frames, planner.bins)
+        return torch.complex(out_re, out_im).reshape(shape)
+
+
+def _channelize_host(fs, dtype, signal, signal_im, out_re, out_im, planner):
+    x = _Slice(signal, dtype, "signal")
+    xi = _NULL if signal_im is None else _Slice(signal_im, dtype, "signal_im")
+    o_re, o_im = _Slice(out_re, dtype, "out_re"), _Slice(out_im, dtype, "out_im")
+    if _same_place(x, o_re):
+        raise TypeError(f"channelize_{fs}_with_planner takes host arrays (channelize_batched takes device tensors)")
+    _check(_call(f"phast_channelize_{fs}_with_planner", x.ptr, xi.ptr, x.len, o_re.ptr, o_im.ptr, o_re.len, planner._h))
+
+
+def channelize_64_with_planner(signal, out_re, out_im, planner: PlannerChannelizer64, signal_im=None) -> None:
+    """f64 channelizer of one host signal of L samples (``signal_im``: its imaginary plane, for a complex planner) into two
+    host arrays of ``planner.out_frames * planner.bins`` (blocking)"""
+    _channelize_host("f64", np.float64, signal, signal_im, out_re, out_im, planner)
+
+
+def channelize_32_with_planner(signal, out_re, out_im, planner: PlannerChannelizer32, signal_im=None) -> None:
+    """f32 twin of :func:`channelize_64_with_planner`"""
+    _channelize_host("f32", np.float32, signal, signal_im, out_re, out_im, planner)
+
+
+def pfb_prototype(n_chans: int, taps_per_chan: int, window=("kaiser", 5.0)):
+    """The usual prototype of a polyphase filter bank: ``firwin_lowpass(n_chans * taps_per_chan, 1 / n_chans, window)``, the
+    windowed-sinc low-pass whose cutoff is half a channel spacing; a host array of doubles (``n_chans >= 2``)"""
+    n_chans, taps_per_chan = int(n_chans), int(taps_per_chan)
+    if n_chans < 2 or taps_per_chan < 1:
+        raise ValueError("need n_chans >= 2 and taps_per_chan >= 1")
+    return firwin_lowpass(n_chans * taps_per_chan, 1.0 / n_chans, window)
+
+
+def channelize_poly(x, h, n_chans: int, hop: int | None = None, first_frame: int = 0, out_frames: int | None = None):
+    """The polyphase channelizer over the last axis of a real or complex device tensor ``x`` with the real taps ``h`` (an
+    array or a tensor), through a planner of its own: a new complex tensor of shape ``x.shape[:-1] + (out_frames, bins)``,
+    ``bins = n_chans`` for complex ``x`` and ``n_chans // 2 + 1`` for real.  float64 / complex128 run in f64, float32 /
+    complex64 in f32.  See :class:`PlannerChannelizer64` for the definition."""
+    import torch
+
+    kinds = {torch.float64: PlannerChannelizer64, torch.complex128: PlannerChannelizer64,
+             torch.float32: PlannerChannelizer32, torch.complex64: PlannerChannelizer32}
+    if not _is_torch(x) or x.device.type != "cuda" or x.dtype not in kinds or x.dim() < 1:
+        raise TypeError("need a float64, float32, complex128 or complex64 device tensor of at least one axis")
+    planner = kinds[x.dtype](x.shape[-1], h, n_chans, hop, first_frame, out_frames, x.is_complex())
+    rows = x.reshape(-1, x.shape[-1]).contiguous()
+    tail = (planner.out_frames, planner.bins)
+    if not rows.shape[0]:
+        return torch.empty(x.shape[:-1] + tail, dtype=torch.complex128 if planner._dtype == np.float64 else torch.complex64,
+                           device=x.device)
+    out = channelize_batched(rows, planner)
+    torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+    return out.reshape(x.shape[:-1] + tail)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@
 #include "planner_mdct.hpp"
 #include "planner_psd.hpp"
 #include "planner_lomb.hpp"
+#include "planner_channelizer.hpp"
 #include "planner_resample.hpp"
 #include "planner_stft.hpp"
 #include "planner_conv.hpp"
@@ -57,6 +58,8 @@ struct phast_planner_upfirdn64 : UpfirdnPlanner<double> {};
 struct phast_planner_upfirdn32 : UpfirdnPlanner<float> {};
 struct phast_planner_resample64 : ResamplePlanner<double> {};
 struct phast_planner_resample32 : ResamplePlanner<float> {};
+struct phast_planner_channelizer64 : ChannelizerPlanner<double> {};
+struct phast_planner_channelizer32 : ChannelizerPlanner<float> {};
 struct phast_planner_conv64 : ConvPlanner<double> {};
 struct phast_planner_conv32 : ConvPlanner<float> {};
 struct phast_planner_convnd64 : ConvNdPlanner<double> {};
@@ -571,7 +574,7 @@ PHAST_HANDLE_API(nufft3d64) PHAST_HANDLE_API(nufft3d32) PHAST_HANDLE_API(nufft_t
 PHAST_HANDLE_API(nd64) PHAST_HANDLE_API(nd32) PHAST_HANDLE_API(r2c_nd64) PHAST_HANDLE_API(r2c_nd32)
 PHAST_HANDLE_API(convnd64) PHAST_HANDLE_API(convnd32) PHAST_HANDLE_API(mdct64) PHAST_HANDLE_API(mdct32)
 PHAST_HANDLE_API(lomb64) PHAST_HANDLE_API(lomb32) PHAST_HANDLE_API(upfirdn64) PHAST_HANDLE_API(upfirdn32)
-PHAST_HANDLE_API(resample64) PHAST_HANDLE_API(resample32)
+PHAST_HANDLE_API(resample64) PHAST_HANDLE_API(resample32) PHAST_HANDLE_API(channelizer64) PHAST_HANDLE_API(channelizer32)
 
 // Arbitrary lengths (Bluestein, planner_any.hpp): arguments are checked before the device is touched
 #define PHAST_ANY_API(SFX, T)                                                                                           \
@@ -990,6 +993,62 @@ PHAST_LOMB_API(32, f32, float)
     } PHAST_CATCH_RC
 PHAST_RESAMPLE_API(64, f64, double)
 PHAST_RESAMPLE_API(32, f32, float)
+
+// The polyphase filter-bank channelizer (planner_channelizer.hpp): every argument rule, a wrong length and a signal whose
+// planes do not match the planner come back before the device is touched
+#define PHAST_CHANNELIZER_API(SFX, FS, T)                                                                               \
+    int phast_planner_channelizer##SFX##_new(size_t signal_len, const T *taps, size_t num_taps, size_t channels,        \
+                                             size_t hop, size_t first_frame, size_t out_frames, int complex_input,      \
+                                             phast_planner_channelizer##SFX **out) try {                                \
+        return channelizer_planner_new<T>(signal_len, taps, num_taps, channels, hop, first_frame, out_frames,           \
+                                          complex_input, out);                                                          \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_channelizer##SFX##_workspace_min(const phast_planner_channelizer##SFX *p) try {                \
+        return p ? p->workspace_min() : 0;                                                                              \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_channelizer##SFX##_out_frames(const phast_planner_channelizer##SFX *p) try {                   \
+        return p ? p->out_frames : 0;                                                                                   \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_channelizer##SFX##_full_frames(const phast_planner_channelizer##SFX *p) try {                  \
+        return p ? p->full_frames : 0;                                                                                  \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_channelizer##SFX##_bins(const phast_planner_channelizer##SFX *p) try {                         \
+        return p ? p->bins : 0;                                                                                         \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_channelizer##SFX##_tile_frames(const phast_planner_channelizer##SFX *p) try {                  \
+        return p ? p->geom.frames : 0;                                                                                  \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_channelizer##SFX##_tile_cols(const phast_planner_channelizer##SFX *p) try {                    \
+        return p ? p->geom.cols : 0;                                                                                    \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_channelizer##SFX##_chunk(const phast_planner_channelizer##SFX *p) try {                        \
+        return p ? p->geom.jc : 0;                                                                                      \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_channelizer##SFX##_periods(const phast_planner_channelizer##SFX *p) try {                      \
+        return p ? p->geom.rows : 0;                                                                                    \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_channelizer##SFX##_time_stages(const phast_planner_channelizer##SFX *p, const T *d_sig_re,        \
+                                                     const T *d_sig_im, T *d_out_re, T *d_out_im, size_t batch,         \
+                                                     T *d_work, size_t work_len, int reps, float *stage_ms,             \
+                                                     void *stream) try {                                                \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(d_sig_re, d_sig_im, d_out_re, d_out_im, batch, d_work, work_len, reps, stage_ms,          \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_channelize_##FS##_with_planner(const T *sig_re, const T *sig_im, size_t signal_len, T *out_re, T *out_im, \
+                                             size_t out_len, const phast_planner_channelizer##SFX *p) try {             \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(sig_re, sig_im, signal_len, out_re, out_im, out_len);                                            \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_channelize_##FS##_dev(const T *d_sig_re, const T *d_sig_im, T *d_out_re, T *d_out_im, size_t signal_len,  \
+                                    size_t batch, size_t sig_dist, const phast_planner_channelizer##SFX *p, T *d_work,  \
+                                    size_t work_len, void *stream) try {                                                \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(d_sig_re, d_sig_im, d_out_re, d_out_im, signal_len, batch, sig_dist, d_work, work_len,            \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC
+PHAST_CHANNELIZER_API(64, f64, double)
+PHAST_CHANNELIZER_API(32, f32, float)
 
 // Overlap-save convolution and correlation of real signals (planner_conv.hpp): every argument rule and a wrong length come
 // back before the device is touched

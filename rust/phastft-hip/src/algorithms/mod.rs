@@ -9,6 +9,7 @@ pub mod dit;
 pub mod mdct;
 pub mod psd;
 pub mod resample;
+pub mod channelizer;
 pub mod lomb;
 pub mod nufft;
 pub mod nufft2d;

@@ -329,6 +329,47 @@ extern "C" {
         planner: *const Opaque) -> c_int;
     pub(crate) fn phast_resample_f32_dev(signal: *const f32, out: *mut f32, signal_len: usize, batch: usize, sig_dist: usize, out_dist: usize,
         planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // the polyphase channelizer (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/channelizer.rs)
+    pub(crate) fn phast_planner_channelizer64_new(signal_len: usize, taps: *const f64, num_taps: usize, channels: usize, hop: usize, first_frame: usize,
+        out_frames: usize, complex_input: c_int, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_channelizer64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_channelizer64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_channelizer64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_channelizer64_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer64_out_frames(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer64_full_frames(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer64_bins(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer64_tile_frames(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer64_tile_cols(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer64_chunk(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer64_periods(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer64_time_stages(p: *const Opaque, sig_re: *const f64, sig_im: *const f64, out_re: *mut f64, out_im: *mut f64,
+        batch: usize, work: *mut f64, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_channelize_f64_with_planner(sig_re: *const f64, sig_im: *const f64, signal_len: usize, out_re: *mut f64,
+        out_im: *mut f64, out_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_channelize_f64_dev(sig_re: *const f64, sig_im: *const f64, out_re: *mut f64, out_im: *mut f64, signal_len: usize,
+        batch: usize, sig_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_channelizer32_new(signal_len: usize, taps: *const f32, num_taps: usize, channels: usize, hop: usize, first_frame: usize,
+        out_frames: usize, complex_input: c_int, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_channelizer32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_channelizer32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_channelizer32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_channelizer32_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer32_out_frames(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer32_full_frames(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer32_bins(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer32_tile_frames(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer32_tile_cols(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer32_chunk(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer32_periods(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_channelizer32_time_stages(p: *const Opaque, sig_re: *const f32, sig_im: *const f32, out_re: *mut f32, out_im: *mut f32,
+        batch: usize, work: *mut f32, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_channelize_f32_with_planner(sig_re: *const f32, sig_im: *const f32, signal_len: usize, out_re: *mut f32,
+        out_im: *mut f32, out_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_channelize_f32_dev(sig_re: *const f32, sig_im: *const f32, out_re: *mut f32, out_im: *mut f32, signal_len: usize,
+        batch: usize, sig_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // overlap-save convolution and correlation (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/conv.rs)
     pub(crate) fn phast_planner_conv64_new(signal_len: usize, taps: *const f64, num_taps: usize, mode: c_int, flip: c_int,
         block: usize, out: *mut *mut Opaque) -> c_int;

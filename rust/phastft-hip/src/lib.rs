@@ -79,6 +79,9 @@ pub use algorithms::resample::{
     upfirdn_f64_dev, upfirdn_f64_with_planner,
 };
 pub use planner::{PlannerResample32, PlannerResample64, PlannerUpfirdn32, PlannerUpfirdn64};
+// the polyphase filter-bank channelizer (an extension beyond PhastFT 0.3.0)
+pub use algorithms::channelizer::{channelize_f32_dev, channelize_f32_with_planner, channelize_f64_dev, channelize_f64_with_planner};
+pub use planner::{PlannerChannelizer32, PlannerChannelizer64};
 // overlap-save convolution and correlation of real signals (an extension beyond PhastFT 0.3.0)
 pub use algorithms::conv::{conv_f32_dev, conv_f32_with_planner, conv_f64_dev, conv_f64_with_planner};
 pub use planner::{ConvMode, PlannerConv32, PlannerConv64};

@@ -628,6 +628,92 @@ impl_planner_resample!(PlannerResample64, phast_planner_resample64_new, phast_pl
 impl_planner_resample!(PlannerResample32, phast_planner_resample32_new, phast_planner_resample32_free,
                        phast_planner_resample32_workspace_len, phast_planner_resample32_workspace_min);
 
+macro_rules! impl_planner_channelizer {
+    ($ch:ident, $t:ty, $new:ident, $free:ident, $out_frames:ident, $full_frames:ident, $bins:ident, $tile_frames:ident, $tile_cols:ident,
+     $chunk:ident, $periods:ident, $ws_len:ident, $ws_min:ident) => {
+        /// An extension beyond PhastFT 0.3.0: the polyphase filter-bank channelizer (the analysis side of a uniform DFT filter
+        /// bank) of signals of `signal_len` samples -- `channels` equally spaced channels, each the signal times
+        /// exp(-2 pi i k n / channels), filtered with the planner's real taps and decimated by `hop`, with zero extension -- of
+        /// which a call yields the `out_frames` frames from `first_frame` on.  One fold kernel and one `channels`-point
+        /// transform per frame; the bits of an output depend on the values alone.  Immutable after `new`.
+        pub struct $ch {
+            pub(crate) h: *mut Opaque,
+            pub(crate) signal_len: usize,
+            complex_input: bool,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's buffers (device calls) or in device
+        // buffers of its own (host-slice calls)
+        unsafe impl Send for $ch {}
+        unsafe impl Sync for $ch {}
+        impl $ch {
+            /// `out_frames` = 0 stands for `full_frames - first_frame`; the window may pass `full_frames` (zeros there);
+            /// `complex_input`: the signals are (re, im) planes and a frame has `channels` bins, else `channels / 2 + 1`.
+            /// Panics with "invalid argument" unless 1 <= signal_len, taps.len(), channels, hop <= 2^29, first_frame <=
+            /// full_frames, out_frames >= 1 and out_frames * channels <= 2^30
+            pub fn new(signal_len: usize, taps: &[$t], channels: usize, hop: usize, first_frame: usize, out_frames: usize,
+                       complex_input: bool) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe {
+                    ffi::$new(signal_len, taps.as_ptr(), taps.len(), channels, hop, first_frame, out_frames, complex_input as c_int, &mut h)
+                });
+                Self { h, signal_len, complex_input }
+            }
+            pub fn signal_len(&self) -> usize {
+                self.signal_len
+            }
+            pub fn complex_input(&self) -> bool {
+                self.complex_input
+            }
+            pub fn out_frames(&self) -> usize {
+                unsafe { ffi::$out_frames(self.h) }
+            }
+            /// (signal_len + taps - 2) / hop + 1
+            pub fn full_frames(&self) -> usize {
+                unsafe { ffi::$full_frames(self.h) }
+            }
+            /// bins of a frame: channels (complex signals) or channels / 2 + 1 (real signals)
+            pub fn bins(&self) -> usize {
+                unsafe { ffi::$bins(self.h) }
+            }
+            /// the fold's tile: (frames, columns) per workgroup, a function of (taps, channels, hop) alone
+            pub fn tile(&self) -> (usize, usize) {
+                unsafe { (ffi::$tile_frames(self.h), ffi::$tile_cols(self.h)) }
+            }
+            /// tap rows per LDS chunk
+            pub fn chunk(&self) -> usize {
+                unsafe { ffi::$chunk(self.h) }
+            }
+            /// periods of the signal a tile stages in LDS per chunk
+            pub fn periods(&self) -> usize {
+                unsafe { ffi::$periods(self.h) }
+            }
+            /// elements of the workspace a device call of `batch` signals works in
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+            /// the least workspace a call runs in: one frame (0 for complex signals and a power-of-two `channels`)
+            pub fn workspace_min(&self) -> usize {
+                unsafe { ffi::$ws_min(self.h) }
+            }
+        }
+        impl Drop for $ch {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_channelizer!(PlannerChannelizer64, f64, phast_planner_channelizer64_new, phast_planner_channelizer64_free,
+                          phast_planner_channelizer64_out_frames, phast_planner_channelizer64_full_frames, phast_planner_channelizer64_bins,
+                          phast_planner_channelizer64_tile_frames, phast_planner_channelizer64_tile_cols, phast_planner_channelizer64_chunk,
+                          phast_planner_channelizer64_periods, phast_planner_channelizer64_workspace_len,
+                          phast_planner_channelizer64_workspace_min);
+impl_planner_channelizer!(PlannerChannelizer32, f32, phast_planner_channelizer32_new, phast_planner_channelizer32_free,
+                          phast_planner_channelizer32_out_frames, phast_planner_channelizer32_full_frames, phast_planner_channelizer32_bins,
+                          phast_planner_channelizer32_tile_frames, phast_planner_channelizer32_tile_cols, phast_planner_channelizer32_chunk,
+                          phast_planner_channelizer32_periods, phast_planner_channelizer32_workspace_len,
+                          phast_planner_channelizer32_workspace_min);
+
 /// Which part of the full convolution a planner yields (PHAST_CONV_* of the C ABI)
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum ConvMode {
