@@ -30,6 +30,8 @@
 //                                                            enum LombNorm -- scipy.signal.lombscargle
 //   (none: no filter banks upstream)                         class PlannerChannelizer64/32, channelize_f64/f32_with_planner -- the
 //                                                            polyphase channelizer (uniform DFT analysis filter bank)
+//   (none: no filter banks upstream)                         class PlannerSynthesizer64/32, synthesize_f64/f32_with_planner -- the
+//                                                            polyphase synthesis bank, the channelizer's inverse
 //   (none: no sample-rate conversion upstream)               class PlannerUpfirdn64/32, upfirdn_f64/f32_with_planner -- the polyphase
 //                                                            FIR of scipy.signal.upfirdn; class PlannerResample64/32,
 //                                                            resample_f64/f32_with_planner -- scipy.signal.resample
@@ -837,6 +839,64 @@ PHASTFT_PLANNER_CHANNELIZER(PlannerChannelizer32, phast_planner_channelizer32, 3
 PHASTFT_CHANNELIZE(f64, double, PlannerChannelizer64)
 PHASTFT_CHANNELIZE(f32, float, PlannerChannelizer32)
 #undef PHASTFT_CHANNELIZE
+
+// ---- polyphase synthesis filter bank, the channelizer's inverse (no reference counterpart) ----
+#define PHASTFT_PLANNER_SYNTHESIZER(NAME, CT, SFX, T)                                                            \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* `frames` frames of `channels` channels back into a signal: every channel raised by `hop` (0: channels), filtered \
+           with the real taps, brought back to its band, and the channels summed, zero extension: the out_len samples from \
+           `first` on (out_len = 0: up to full_len; the window may pass it: zeros).  complex_output: a frame has `channels` \
+           bins and the signal is (re, im) planes; otherwise channels / 2 + 1 bins and one plane.  The phases are in absolute \
+           time: the delay of an analysis / synthesis pair must be a multiple of `channels` (taps (0, h reversed)) */ \
+        NAME(std::size_t frames, Slice<const T> taps, std::size_t channels, std::size_t hop = 0, std::size_t first = 0, \
+             std::size_t out_len = 0, bool complex_output = false) {                                             \
+            check(phast_planner_synthesizer##SFX##_new(frames, taps.ptr, taps.len, channels, hop ? hop : channels, first, out_len, \
+                                                       complex_output ? 1 : 0, &h_));                            \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }                                                   \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_synthesizer##SFX##_free(h_);                                                   \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_synthesizer##SFX##_describe(h_, &s[0], s.size()));                               \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_synthesizer##SFX##_device_bytes(h_); }           \
+        std::size_t out_len() const { return phast_planner_synthesizer##SFX##_out_len(h_); }                     \
+        std::size_t full_len() const { return phast_planner_synthesizer##SFX##_full_len(h_); }                   \
+        std::size_t bins() const { return phast_planner_synthesizer##SFX##_bins(h_); }                           \
+        /* the unfold's tile (output samples per workgroup and per thread) and the terms of an output at most */ \
+        std::size_t tile_samples() const { return phast_planner_synthesizer##SFX##_tile_samples(h_); }           \
+        std::size_t per_thread() const { return phast_planner_synthesizer##SFX##_per_thread(h_); }               \
+        std::size_t max_terms() const { return phast_planner_synthesizer##SFX##_max_terms(h_); }                 \
+        /* elements of T a _dev call of `batch` signals works in; workspace_min: the least a call runs in */     \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_synthesizer##SFX##_workspace_len(h_, batch); } \
+        std::size_t workspace_min() const { return phast_planner_synthesizer##SFX##_workspace_min(h_); }         \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+    };
+PHASTFT_PLANNER_SYNTHESIZER(PlannerSynthesizer64, phast_planner_synthesizer64, 64, double)
+PHASTFT_PLANNER_SYNTHESIZER(PlannerSynthesizer32, phast_planner_synthesizer32, 32, float)
+#undef PHASTFT_PLANNER_SYNTHESIZER
+
+// one signal's frames from host planes of frames x bins() points -> out_len() samples (out_im: the imaginary plane for a complex
+// planner, an empty slice for a real one); blocking
+#define PHASTFT_SYNTHESIZE(FS, T, P)                                                                             \
+    inline void synthesize_##FS##_with_planner(Slice<const T> in_re, Slice<const T> in_im, Slice<T> out, Slice<T> out_im, \
+                                               const P &planner) {                                               \
+        if (in_re.len != in_im.len || (out_im.ptr && out_im.len != out.len)) check(PHAST_ERR_LEN_MISMATCH);      \
+        check(phast_synthesize_##FS##_with_planner(in_re.ptr, in_im.ptr, in_re.len, out.ptr, out_im.ptr, out.len, planner.get())); \
+    }
+PHASTFT_SYNTHESIZE(f64, double, PlannerSynthesizer64)
+PHASTFT_SYNTHESIZE(f32, float, PlannerSynthesizer32)
+#undef PHASTFT_SYNTHESIZE
 
 // ---- overlap-save convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve / correlate) ----
 enum class ConvMode : int { Full = PHAST_CONV_FULL, Same = PHAST_CONV_SAME, Valid = PHAST_CONV_VALID };

@@ -858,7 +858,8 @@ int phast_planner_resample32_time_stages(const phast_planner_resample32 *p, cons
  * d_sig_im, a short dist, a null or short workspace: PHAST_ERR_INVALID_ARG; a signal_len that is not the planner's:
  * PHAST_ERR_PLANNER_SIZE; an out_len of the host-slice form that is not out_frames bins: PHAST_ERR_LEN_MISMATCH -- all before the
  * device is touched.  The *_with_planner forms take host slices of one signal (sig_im NULL for a real planner) and block.
- * Out of scope: the synthesis bank (the inverse), complex taps, subsets of the channels, any choice of method by size. */
+ * The synthesis bank (the inverse) is phast_planner_synthesizer* below.  Out of scope: complex taps, subsets of the channels,
+ * any choice of method by size. */
 typedef struct phast_planner_channelizer64 phast_planner_channelizer64; /* PlannerChannelizer64 */
 int phast_planner_channelizer64_new(size_t signal_len, const double *taps, size_t num_taps, size_t channels, size_t hop, size_t first_frame, size_t out_frames,
                                      int complex_input, phast_planner_channelizer64 **out);
@@ -904,6 +905,87 @@ int phast_channelize_f32_dev(const float *d_sig_re, const float *d_sig_im, float
 /* measurement hook (tools/channelizer_rate.py): stage_ms[2] = average milliseconds of the fold and of the transform over `reps`
  * calls of `batch` signals at distance L in ONE chunk (work_len >= _workspace_len(p, batch)).  Blocks until done. */
 int phast_planner_channelizer32_time_stages(const phast_planner_channelizer32 *p, const float *d_sig_re, const float *d_sig_im, float *d_out_re, float *d_out_im, size_t batch, float *d_work, size_t work_len,
+                                             int reps, float *stage_ms, void *stream);
+
+/* ---- polyphase synthesis filter bank: the inverse side of the channelizer above (no reference counterpart).
+ * Channel data Y[m][k] of F frames by M channels, K real taps g (host values of T), hop D, zero extension as
+ * phast_planner_upfirdn*:
+ *     full_len = (F - 1) D + K
+ *     s[n]   = sum_m g[n - m D] sum_k Y[m][k] exp(+2 pi i k n / M),  0 <= n < full_len;  s[n] = 0 above
+ *     out[i] = s[first + i],                                         0 <= i < out_len   (out_len = 0 at _new: full_len - first)
+ * so s = sum_k exp(2 pi i k n / M) upfirdn(g, Y[:, k], D, 1): the phase is referred to absolute sample time, as on the analysis
+ * side, and the sum over k is unnormalised.  first + out_len may pass full_len (zeros).  Input planes, dense and frame-major as
+ * the channelizer writes them: element (b F + m) bins + k.  complex_output: bins = M and the signal is two planes; otherwise
+ * bins = M / 2 + 1, the Hermitian half, read by irfft's rules (the imaginary parts of bin 0 and, for even M, of bin M / 2 are
+ * ignored), and the signal is one plane.  Signal b lies at d_out_re (d_out_im) + b out_dist.
+ * Because the phases are in absolute time, the delay of an analysis / synthesis pair must be a multiple of M for the columns
+ * to line up: with analysis taps h of K = M T points, g = (0, h[K - 1], ..., h[0]) of K + 1 points gives the adjoint of the
+ * channelizer delayed by K, and with h[j] = sin(pi (j + 1/2) / M), K = M, D = M / 2 and that g divided by M the pair
+ * reconstructs the signal delayed by M.
+ * Method: one M-point inverse transform per frame on the any-length path (phast_planner_any* / phast_planner_c2r_any*) into
+ * workspace rows, v[m][p], then one gather kernel, the unfold: s[n] = sum_m tab[n - m D] v[m][n mod M] over the frames
+ * max(0, ceil((n - K + 1) / D)) .. min(F - 1, n / D).  (Complex output goes through a copy of both planes into those rows; real
+ * output of an even M >= 4 through a copy of the imaginary plane with bin 0 and bin M / 2 set to 0, which the engine's C2R
+ * would otherwise use.)  The transform carries 1 / M, so the planner keeps tab[j] = M g[j], the
+ * product in double, rounded once to T.  An output is acc = fma(tab[n - m D], v[m][n mod M], acc) for m ascending from 0 in T,
+ * so the result's bits depend on the values alone -- not on the batch, the distances, pointer alignment, the workspace, the
+ * stream or a graph replay.
+ * Workspace: _workspace_len(p, batch) elements of T hold every frame of the batch; any work_len >= _workspace_min(p) (one
+ * signal's frames: an output sample needs all of them) runs whole signals in chunks, to the same bits.  Complex output of one
+ * channel needs none, and d_work may then be NULL.
+ * _new refuses with PHAST_ERR_INVALID_ARG, before the device is touched: NULL taps; F, K, M or D outside 1 .. 2^29; F M > 2^30;
+ * first > full_len; out_len (resolved) < 1 or > 2^30.  _dev: d_out_im must be NULL for a real planner and non-NULL for a complex
+ * one; out_dist >= out_len (batch 1 ignores it); pointers need element alignment only; the input is never written; input and
+ * output must not overlap (identical pointers are refused).  A null pointer, the wrong d_out_im, a short dist, a null or short
+ * workspace: PHAST_ERR_INVALID_ARG; a `frames` that is not the planner's (host form: an in_len that is not F bins):
+ * PHAST_ERR_PLANNER_SIZE; an out_len of the host-slice form that is not the planner's: PHAST_ERR_LEN_MISMATCH -- all before the
+ * device is touched.  The *_with_planner forms take host slices of one signal's frames (out_im NULL for a real planner) and block.
+ * Out of scope: complex taps, subsets of the channels, fusing the unfold behind the transform's last pass. */
+typedef struct phast_planner_synthesizer64 phast_planner_synthesizer64; /* PlannerSynthesizer64 */
+int phast_planner_synthesizer64_new(size_t frames, const double *taps, size_t num_taps, size_t channels, size_t hop, size_t first, size_t out_len,
+                                     int complex_output, phast_planner_synthesizer64 **out);
+void phast_planner_synthesizer64_free(phast_planner_synthesizer64 *p);
+int phast_planner_synthesizer64_describe(const phast_planner_synthesizer64 *p, char *buf, size_t buf_len);
+size_t phast_planner_synthesizer64_device_bytes(const phast_planner_synthesizer64 *p);
+size_t phast_planner_synthesizer64_workspace_len(const phast_planner_synthesizer64 *p, size_t batch);
+size_t phast_planner_synthesizer64_workspace_min(const phast_planner_synthesizer64 *p);
+size_t phast_planner_synthesizer64_out_len(const phast_planner_synthesizer64 *p);
+size_t phast_planner_synthesizer64_full_len(const phast_planner_synthesizer64 *p);
+size_t phast_planner_synthesizer64_bins(const phast_planner_synthesizer64 *p);
+size_t phast_planner_synthesizer64_tile_samples(const phast_planner_synthesizer64 *p); /* output samples per workgroup */
+size_t phast_planner_synthesizer64_per_thread(const phast_planner_synthesizer64 *p);   /* output samples per thread */
+size_t phast_planner_synthesizer64_max_terms(const phast_planner_synthesizer64 *p);    /* terms of an output at most: ceil(K / D) */
+int phast_synthesize_f64_with_planner(const double *in_re, const double *in_im, size_t in_len, double *out_re, double *out_im, size_t out_len,
+                                       const phast_planner_synthesizer64 *planner);
+int phast_synthesize_f64_dev(const double *d_in_re, const double *d_in_im, double *d_out_re, double *d_out_im, size_t frames, size_t batch, size_t out_dist,
+                              const phast_planner_synthesizer64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/synthesizer_rate.py): stage_ms[2] = average milliseconds of the transform (with the copy sweep of
+ * complex output) and of the unfold over `reps` calls of `batch` signals at distance out_len in ONE chunk (work_len >=
+ * _workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_synthesizer64_time_stages(const phast_planner_synthesizer64 *p, const double *d_in_re, const double *d_in_im, double *d_out_re, double *d_out_im, size_t batch, double *d_work, size_t work_len,
+                                             int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_synthesizer32 phast_planner_synthesizer32; /* PlannerSynthesizer32 */
+int phast_planner_synthesizer32_new(size_t frames, const float *taps, size_t num_taps, size_t channels, size_t hop, size_t first, size_t out_len,
+                                     int complex_output, phast_planner_synthesizer32 **out);
+void phast_planner_synthesizer32_free(phast_planner_synthesizer32 *p);
+int phast_planner_synthesizer32_describe(const phast_planner_synthesizer32 *p, char *buf, size_t buf_len);
+size_t phast_planner_synthesizer32_device_bytes(const phast_planner_synthesizer32 *p);
+size_t phast_planner_synthesizer32_workspace_len(const phast_planner_synthesizer32 *p, size_t batch);
+size_t phast_planner_synthesizer32_workspace_min(const phast_planner_synthesizer32 *p);
+size_t phast_planner_synthesizer32_out_len(const phast_planner_synthesizer32 *p);
+size_t phast_planner_synthesizer32_full_len(const phast_planner_synthesizer32 *p);
+size_t phast_planner_synthesizer32_bins(const phast_planner_synthesizer32 *p);
+size_t phast_planner_synthesizer32_tile_samples(const phast_planner_synthesizer32 *p); /* output samples per workgroup */
+size_t phast_planner_synthesizer32_per_thread(const phast_planner_synthesizer32 *p);   /* output samples per thread */
+size_t phast_planner_synthesizer32_max_terms(const phast_planner_synthesizer32 *p);    /* terms of an output at most: ceil(K / D) */
+int phast_synthesize_f32_with_planner(const float *in_re, const float *in_im, size_t in_len, float *out_re, float *out_im, size_t out_len,
+                                       const phast_planner_synthesizer32 *planner);
+int phast_synthesize_f32_dev(const float *d_in_re, const float *d_in_im, float *d_out_re, float *d_out_im, size_t frames, size_t batch, size_t out_dist,
+                              const phast_planner_synthesizer32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/synthesizer_rate.py): stage_ms[2] = average milliseconds of the transform (with the copy sweep of
+ * complex output) and of the unfold over `reps` calls of `batch` signals at distance out_len in ONE chunk (work_len >=
+ * _workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_synthesizer32_time_stages(const phast_planner_synthesizer32 *p, const float *d_in_re, const float *d_in_im, float *d_out_re, float *d_out_im, size_t batch, float *d_work, size_t work_len,
                                              int reps, float *stage_ms, void *stream);
 
 /* ---- overlap-save FIR convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve /

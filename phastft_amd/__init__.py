@@ -38,6 +38,8 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
                                                     resample, firwin_lowpass
     (none: no filter banks)                         PlannerChannelizer64/32, channelize_batched,
                                                     channelize_64/32_with_planner, channelize_poly, pfb_prototype
+    (none: no filter banks)                         PlannerSynthesizer64/32, synthesize_batched,
+                                                    synthesize_64/32_with_planner, synthesize_poly
     (none: no convolution)                          PlannerConv64/32, conv_batched, conv_f64/f32_with_planner,
                                                     fftconvolve, correlate
     (none: no convolution)                          PlannerConvNd64/32, convnd_batched, convnd_f64/f32_with_planner,
@@ -110,6 +112,8 @@ __all__ = [
     "resample_poly", "decimate", "resample", "firwin_lowpass",
     "PlannerChannelizer64", "PlannerChannelizer32", "channelize_batched", "channelize_64_with_planner",
     "channelize_32_with_planner", "channelize_poly", "pfb_prototype",
+    "PlannerSynthesizer64", "PlannerSynthesizer32", "synthesize_batched", "synthesize_64_with_planner",
+    "synthesize_32_with_planner", "synthesize_poly",
     "PlannerConv64", "PlannerConv32", "conv_batched", "conv_f64_with_planner", "conv_f32_with_planner", "fftconvolve",
     "correlate",
     "PlannerConvNd64", "PlannerConvNd32", "convnd_batched", "convnd_f64_with_planner", "convnd_f32_with_planner",
@@ -2250,6 +2254,189 @@ def channelize_poly(x, h, n_chans: int, hop: int | None = None, first_frame: int
     out = channelize_batched(rows, planner)
     torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
     return out.reshape(x.shape[:-1] + tail)
+
+
+# ---------------------------------------------------------------------------------------------
+# polyphase synthesis filter bank, the channelizer's inverse (no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class PlannerSynthesizer64(_AnyHandle):
+    """f64 polyphase synthesis bank of ``frames`` frames of ``n_chans`` channels: channel k is raised by ``hop`` (default
+    ``n_chans``: critically sampled), filtered with the real taps ``g``, brought back to its band and the channels are summed,
+    ``s = sum_k exp(2j pi k n / n_chans) * scipy.signal.upfirdn(g, Y[:, k], hop, 1)`` -- the phase in absolute sample time, as
+    in :class:`PlannerChannelizer64`, the sum unnormalised.  A call yields the ``out_len`` samples from ``first`` on
+    (``out_len=None``: up to the end, ``full_len - first`` with ``full_len = (frames - 1) * hop + len(g)``); the window may
+    pass ``full_len``: zeros there.  ``complex_output``: a frame has ``n_chans`` bins and the signal is complex; otherwise a
+    frame is the one-sided ``n_chans // 2 + 1`` bins, read by ``irfft``'s rules, and the signal is real.  One
+    ``n_chans``-point inverse transform per frame on the any-length path, then one gather kernel.
+
+    The phases are in absolute time, so the delay of an analysis / synthesis pair must be a multiple of ``n_chans`` for the
+    columns to line up: for analysis taps ``h`` of ``n_chans * T`` points, ``g = concatenate(([0], h[::-1]))`` is the adjoint
+    of the channelizer delayed by ``len(h)``; with ``h[j] = sin(pi (j + 1/2) / n_chans)``, ``hop = n_chans / 2`` and that
+    ``g / n_chans`` the pair returns the signal delayed by ``n_chans``."""
+
+    _prefix = "synthesizer"
+
+    def __init__(self, frames: int, g, n_chans: int, hop: int | None = None, first: int = 0, out_len: int | None = None,
+                 complex_output: bool = False):
+        if _is_torch(g):
+            g = g.detach().cpu().numpy()
+        taps = np.ascontiguousarray(g, dtype=self._dtype).reshape(-1)
+        hop = n_chans if hop is None else hop
+        self._new(frames, taps.ctypes.data_as(C.c_void_p), taps.size, n_chans, hop, first, 0 if out_len is None else out_len,
+                  1 if complex_output else 0)
+        self.n = self.frames = frames
+        self.num_taps, self.n_chans, self.hop, self.first = taps.size, n_chans, hop, first
+        self.complex_output = bool(complex_output)
+        self.out_len = int(self._fn("out_len")(self._h))
+        self.full_len = int(self._fn("full_len")(self._h))
+        self.bins = int(self._fn("bins")(self._h))
+        self.tile_samples = int(self._fn("tile_samples")(self._h))
+        self.per_thread = int(self._fn("per_thread")(self._h))
+        self.max_terms = int(self._fn("max_terms")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` signals works in.  A smaller workspace of at least ``workspace_min()``
+        (one signal's frames) runs whole signals in chunks, to the same bits."""
+        return self._workspace_len(batch)
+
+    def workspace_min(self) -> int:
+        return int(self._fn("workspace_min")(self._h))
+
+    def time_stages(self, y_re, y_im, out_re, out_im, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (transform, unfold) of a call of ``batch`` signals at distance ``out_len`` on
+        device tensors; ``out_im`` is None for a real planner (measurement hook)"""
+        yr, yi = _Slice(y_re, self._dtype, "y_re"), _Slice(y_im, self._dtype, "y_im")
+        o_re = _Slice(out_re, self._dtype, "out_re")
+        o_im = _NULL if out_im is None else _Slice(out_im, self._dtype, "out_im")
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 2)()
+        _check(self._fn("time_stages")(self._h, yr.ptr, yi.ptr, o_re.ptr, o_im.ptr, batch, ws.ptr, ws.len, reps, ms, _stream()))
+        return [float(v) for v in ms]
+
+
+class PlannerSynthesizer32(PlannerSynthesizer64):
+    """f32 twin of :class:`PlannerSynthesizer64`: taps, products and sums in f32"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def synthesize_batched(y, planner, out=None, work=None, stream=None):
+    """Device-resident batch through one synthesizer planner.  ``y``: a complex torch device tensor of shape
+    ``(batch, frames, bins)`` or ``(frames, bins)`` (split into planes here) or a pair ``(y_re, y_im)`` of contiguous real
+    planes of such a shape, of the planner's type.  Returns a real tensor of shape ``(batch, out_len)`` (``(out_len,)`` for one
+    unbatched signal), complex for a complex planner.  ``out``: a real tensor of that shape to write into whose last axis is
+    contiguous (rows any distance >= out_len apart), for a complex planner a pair of such planes with equal strides; it is
+    returned in place of a new tensor.  ``work``: a device tensor of at least ``planner.workspace_min()`` elements, by default
+    one of ``planner.workspace_len(batch)`` from torch's allocator; ``stream``: a ``torch.cuda.Stream``, by default the current
+    one.  ``y`` is not written."""
+    import torch
+
+    want = torch.float64 if planner._dtype == np.float64 else torch.float32
+    fs = "f64" if planner._dtype == np.float64 else "f32"
+    f, bins, n = planner.frames, planner.bins, planner.out_len
+
+    if isinstance(y, (tuple, list)):
+        y_re, y_im = y
+    elif _is_torch(y) and y.is_complex():
+        y_re, y_im = y.real.contiguous(), y.imag.contiguous()
+    else:
+        raise TypeError("y: need a complex device tensor or a pair of real planes")
+    for v, what in ((y_re, "y_re"), (y_im, "y_im")):
+        if not _is_torch(v) or v.device.type != "cuda" or v.dtype != want or not v.is_contiguous():
+            raise TypeError(f"{what}: need a contiguous {want} device tensor")
+        if v.dim() not in (2, 3) or tuple(v.shape[-2:]) != (f, bins) or v.shape != y_re.shape:
+            raise ValueError(f"{what}: need shape (batch, {f}, {bins}) or ({f}, {bins}), not {tuple(v.shape)}")
+    unbatched = y_re.dim() == 2
+    batch = 1 if unbatched else y_re.shape[0]
+
+    def plane(v, what):
+        if not _is_torch(v) or v.device.type != "cuda" or v.dtype != want:
+            raise TypeError(f"{what}: need a {want} device tensor")
+        if v.dim() not in (1, 2) or v.shape[-1] != n or (n > 1 and v.stride(-1) != 1) or (v.shape[0] if v.dim() == 2 else 1) != batch:
+            raise ValueError(f"{what}: need shape ({batch}, {n}) or ({n},) with a contiguous last axis, not {tuple(v.shape)}")
+        dist = v.stride(0) if v.dim() == 2 and batch > 1 else n
+        if dist < n:
+            raise ValueError(f"{what}: rows overlap")
+        return dist
+
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        own = out is None
+        if own:
+            shape = (n,) if unbatched else (batch, n)
+            out = tuple(torch.empty(shape, dtype=want, device=y_re.device) for _ in range(2 if planner.complex_output else 1))
+            if not planner.complex_output:
+                out = out[0]
+        if planner.complex_output:
+            if not isinstance(out, (tuple, list)) or len(out) != 2:
+                raise TypeError("out: a complex planner writes a pair of real planes")
+            out_re, out_im = out
+            out_dist = plane(out_re, "out_re")
+            if plane(out_im, "out_im") != out_dist:
+                raise ValueError("out_im: need the strides of out_re")
+        else:
+            if isinstance(out, (tuple, list)):
+                raise TypeError("out: a real planner writes one real plane")
+            out_re, out_im = out, None
+            out_dist = plane(out_re, "out")
+        if batch == 0:
+            return out if not (own and planner.complex_output) else torch.complex(out_re, out_im)
+        if work is None and planner.workspace_min() == 0:
+            ptr, length = None, 0
+        else:
+            ws = _any_workspace(planner, batch, work)
+            ptr, length = ws.ptr, ws.len
+        _check(_call(f"phast_synthesize_{fs}_dev", y_re.data_ptr(), y_im.data_ptr(), out_re.data_ptr(),
+                     None if out_im is None else out_im.data_ptr(), f, batch, out_dist, planner._h, ptr, length, _stream()))
+        if own and planner.complex_output:
+            return torch.complex(out_re, out_im)
+        return out
+
+
+def _synthesize_host(fs, dtype, in_re, in_im, out_re, out_im, planner):
+    y_re, y_im = _Slice(in_re, dtype, "in_re"), _Slice(in_im, dtype, "in_im")
+    o_re = _Slice(out_re, dtype, "out_re")
+    o_im = _NULL if out_im is None else _Slice(out_im, dtype, "out_im")
+    if y_re.len != y_im.len:
+        raise ValueError("in_re and in_im differ in length")
+    if _same_place(y_re, o_re):
+        raise TypeError(f"synthesize_{fs}_with_planner takes host arrays (synthesize_batched takes device tensors)")
+    _check(_call(f"phast_synthesize_{fs}_with_planner", y_re.ptr, y_im.ptr, y_re.len, o_re.ptr, o_im.ptr, o_re.len, planner._h))
+
+
+def synthesize_64_with_planner(in_re, in_im, out_re, planner: PlannerSynthesizer64, out_im=None) -> None:
+    """f64 synthesis of one signal from host planes of ``planner.frames * planner.bins`` points into a host array of
+    ``planner.out_len`` samples (``out_im``: its imaginary plane, for a complex planner); blocking"""
+    _synthesize_host("f64", np.float64, in_re, in_im, out_re, out_im, planner)
+
+
+def synthesize_32_with_planner(in_re, in_im, out_re, planner: PlannerSynthesizer32, out_im=None) -> None:
+    """f32 twin of :func:`synthesize_64_with_planner`"""
+    _synthesize_host("f32", np.float32, in_re, in_im, out_re, out_im, planner)
+
+
+def synthesize_poly(y, g, n_chans: int, hop: int | None = None, first: int = 0, out_len: int | None = None, real: bool = False):
+    """The polyphase synthesis bank over the last two axes ``(frames, bins)`` of a complex device tensor ``y`` with the real
+    taps ``g`` (an array or a tensor), through a planner of its own: a new tensor of shape ``y.shape[:-2] + (out_len,)``.
+    ``real=False``: ``bins = n_chans`` and the result is complex; ``real=True``: ``bins = n_chans // 2 + 1``, the one-sided
+    frames of a real signal as :func:`channelize_poly` writes them, and the result is real.  complex128 runs in f64, complex64
+    in f32.  See :class:`PlannerSynthesizer64` for the definition and for the taps that invert a channelizer."""
+    import torch
+
+    kinds = {torch.complex128: PlannerSynthesizer64, torch.complex64: PlannerSynthesizer32}
+    if not _is_torch(y) or y.device.type != "cuda" or y.dtype not in kinds or y.dim() < 2:
+        raise TypeError("need a complex128 or complex64 device tensor of at least two axes (frames, bins)")
+    bins = n_chans // 2 + 1 if real else n_chans
+    if y.shape[-1] != bins:
+        raise ValueError(f"the last axis must have {bins} bins, not {y.shape[-1]}")
+    planner = kinds[y.dtype](y.shape[-2], g, n_chans, hop, first, out_len, not real)
+    rows = y.reshape((-1,) + tuple(y.shape[-2:]))
+    if not rows.shape[0]:
+        dt = y.real.dtype if real else y.dtype
+        return torch.empty(y.shape[:-2] + (planner.out_len,), dtype=dt, device=y.device)
+    out = synthesize_batched(rows, planner)
+    torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+    return out.reshape(y.shape[:-2] + (planner.out_len,))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -21,6 +21,7 @@
 #include "planner_psd.hpp"
 #include "planner_lomb.hpp"
 #include "planner_channelizer.hpp"
+#include "planner_synthesizer.hpp"
 #include "planner_resample.hpp"
 #include "planner_stft.hpp"
 #include "planner_conv.hpp"
@@ -60,6 +61,8 @@ struct phast_planner_resample64 : ResamplePlanner<double> {};
 struct phast_planner_resample32 : ResamplePlanner<float> {};
 struct phast_planner_channelizer64 : ChannelizerPlanner<double> {};
 struct phast_planner_channelizer32 : ChannelizerPlanner<float> {};
+struct phast_planner_synthesizer64 : SynthesizerPlanner<double> {};
+struct phast_planner_synthesizer32 : SynthesizerPlanner<float> {};
 struct phast_planner_conv64 : ConvPlanner<double> {};
 struct phast_planner_conv32 : ConvPlanner<float> {};
 struct phast_planner_convnd64 : ConvNdPlanner<double> {};
@@ -575,6 +578,7 @@ PHAST_HANDLE_API(nd64) PHAST_HANDLE_API(nd32) PHAST_HANDLE_API(r2c_nd64) PHAST_H
 PHAST_HANDLE_API(convnd64) PHAST_HANDLE_API(convnd32) PHAST_HANDLE_API(mdct64) PHAST_HANDLE_API(mdct32)
 PHAST_HANDLE_API(lomb64) PHAST_HANDLE_API(lomb32) PHAST_HANDLE_API(upfirdn64) PHAST_HANDLE_API(upfirdn32)
 PHAST_HANDLE_API(resample64) PHAST_HANDLE_API(resample32) PHAST_HANDLE_API(channelizer64) PHAST_HANDLE_API(channelizer32)
+PHAST_HANDLE_API(synthesizer64) PHAST_HANDLE_API(synthesizer32)
 
 // Arbitrary lengths (Bluestein, planner_any.hpp): arguments are checked before the device is touched
 #define PHAST_ANY_API(SFX, T)                                                                                           \
@@ -1049,6 +1053,58 @@ PHAST_RESAMPLE_API(32, f32, float)
     } PHAST_CATCH_RC
 PHAST_CHANNELIZER_API(64, f64, double)
 PHAST_CHANNELIZER_API(32, f32, float)
+
+// The polyphase synthesis filter bank (planner_synthesizer.hpp): every argument rule, a wrong length and an output whose
+// planes do not match the planner come back before the device is touched
+#define PHAST_SYNTHESIZER_API(SFX, FS, T)                                                                               \
+    int phast_planner_synthesizer##SFX##_new(size_t frames, const T *taps, size_t num_taps, size_t channels, size_t hop, \
+                                             size_t first, size_t out_len, int complex_output,                          \
+                                             phast_planner_synthesizer##SFX **out) try {                                \
+        return synthesizer_planner_new<T>(frames, taps, num_taps, channels, hop, first, out_len, complex_output, out);  \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_synthesizer##SFX##_workspace_min(const phast_planner_synthesizer##SFX *p) try {                \
+        return p ? p->workspace_min() : 0;                                                                              \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_synthesizer##SFX##_out_len(const phast_planner_synthesizer##SFX *p) try {                      \
+        return p ? p->out_len : 0;                                                                                      \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_synthesizer##SFX##_full_len(const phast_planner_synthesizer##SFX *p) try {                     \
+        return p ? p->full_len : 0;                                                                                     \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_synthesizer##SFX##_bins(const phast_planner_synthesizer##SFX *p) try {                         \
+        return p ? p->bins : 0;                                                                                         \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_synthesizer##SFX##_tile_samples(const phast_planner_synthesizer##SFX *p) try {                 \
+        return p ? p->geom.tile : 0;                                                                                    \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_synthesizer##SFX##_per_thread(const phast_planner_synthesizer##SFX *p) try {                   \
+        return p ? p->geom.per : 0;                                                                                     \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_synthesizer##SFX##_max_terms(const phast_planner_synthesizer##SFX *p) try {                    \
+        return p ? p->geom.terms : 0;                                                                                   \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_synthesizer##SFX##_time_stages(const phast_planner_synthesizer##SFX *p, const T *d_in_re,         \
+                                                     const T *d_in_im, T *d_out_re, T *d_out_im, size_t batch,          \
+                                                     T *d_work, size_t work_len, int reps, float *stage_ms,             \
+                                                     void *stream) try {                                                \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(d_in_re, d_in_im, d_out_re, d_out_im, batch, d_work, work_len, reps, stage_ms,            \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_synthesize_##FS##_with_planner(const T *in_re, const T *in_im, size_t in_len, T *out_re, T *out_im,       \
+                                             size_t out_len, const phast_planner_synthesizer##SFX *p) try {             \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(in_re, in_im, in_len, out_re, out_im, out_len);                                                  \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_synthesize_##FS##_dev(const T *d_in_re, const T *d_in_im, T *d_out_re, T *d_out_im, size_t frames,        \
+                                    size_t batch, size_t out_dist, const phast_planner_synthesizer##SFX *p, T *d_work,  \
+                                    size_t work_len, void *stream) try {                                                \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(d_in_re, d_in_im, d_out_re, d_out_im, frames, batch, out_dist, d_work, work_len,                  \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC
+PHAST_SYNTHESIZER_API(64, f64, double)
+PHAST_SYNTHESIZER_API(32, f32, float)
 
 // Overlap-save convolution and correlation of real signals (planner_conv.hpp): every argument rule and a wrong length come
 // back before the device is touched

@@ -25,7 +25,8 @@
 // and zero samples included: its bits depend on (K, M, D) and the values alone -- not on the batch, the distances, the
 // workspace, alignment, the stream or a graph replay.  No atomics; a workgroup talks to no other.
 //
-// Out of scope: the synthesis bank (the inverse), complex taps, subsets of the channels, any choice of method by size.
+// The synthesis bank (the inverse) is synthesizer.hpp.  Out of scope: complex taps, subsets of the channels,
+// any choice of method by size.
 //
 // The top of this header (argument rules, geometry) has no HIP dependency: tests/test_channelizer_cpu.py compiles it with g++.
 #pragma once

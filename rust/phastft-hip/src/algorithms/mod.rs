@@ -10,6 +10,7 @@ pub mod mdct;
 pub mod psd;
 pub mod resample;
 pub mod channelizer;
+pub mod synthesizer;
 pub mod lomb;
 pub mod nufft;
 pub mod nufft2d;

@@ -370,6 +370,45 @@ extern "C" {
         out_im: *mut f32, out_len: usize, planner: *const Opaque) -> c_int;
     pub(crate) fn phast_channelize_f32_dev(sig_re: *const f32, sig_im: *const f32, out_re: *mut f32, out_im: *mut f32, signal_len: usize,
         batch: usize, sig_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // the polyphase synthesis bank (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/synthesizer.rs)
+    pub(crate) fn phast_planner_synthesizer64_new(frames: usize, taps: *const f64, num_taps: usize, channels: usize, hop: usize, first: usize,
+        out_len: usize, complex_output: c_int, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_synthesizer64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_synthesizer64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_synthesizer64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_synthesizer64_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer64_out_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer64_full_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer64_bins(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer64_tile_samples(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer64_per_thread(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer64_max_terms(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer64_time_stages(p: *const Opaque, in_re: *const f64, in_im: *const f64, out_re: *mut f64, out_im: *mut f64,
+        batch: usize, work: *mut f64, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_synthesize_f64_with_planner(in_re: *const f64, in_im: *const f64, in_len: usize, out_re: *mut f64,
+        out_im: *mut f64, out_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_synthesize_f64_dev(in_re: *const f64, in_im: *const f64, out_re: *mut f64, out_im: *mut f64, frames: usize,
+        batch: usize, out_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_synthesizer32_new(frames: usize, taps: *const f32, num_taps: usize, channels: usize, hop: usize, first: usize,
+        out_len: usize, complex_output: c_int, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_synthesizer32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_synthesizer32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_synthesizer32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_synthesizer32_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer32_out_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer32_full_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer32_bins(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer32_tile_samples(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer32_per_thread(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer32_max_terms(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_synthesizer32_time_stages(p: *const Opaque, in_re: *const f32, in_im: *const f32, out_re: *mut f32, out_im: *mut f32,
+        batch: usize, work: *mut f32, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_synthesize_f32_with_planner(in_re: *const f32, in_im: *const f32, in_len: usize, out_re: *mut f32,
+        out_im: *mut f32, out_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_synthesize_f32_dev(in_re: *const f32, in_im: *const f32, out_re: *mut f32, out_im: *mut f32, frames: usize,
+        batch: usize, out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // overlap-save convolution and correlation (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/conv.rs)
     pub(crate) fn phast_planner_conv64_new(signal_len: usize, taps: *const f64, num_taps: usize, mode: c_int, flip: c_int,
         block: usize, out: *mut *mut Opaque) -> c_int;

@@ -82,6 +82,9 @@ pub use planner::{PlannerResample32, PlannerResample64, PlannerUpfirdn32, Planne
 // the polyphase filter-bank channelizer (an extension beyond PhastFT 0.3.0)
 pub use algorithms::channelizer::{channelize_f32_dev, channelize_f32_with_planner, channelize_f64_dev, channelize_f64_with_planner};
 pub use planner::{PlannerChannelizer32, PlannerChannelizer64};
+// the polyphase synthesis filter bank, the channelizer's inverse (an extension beyond PhastFT 0.3.0)
+pub use algorithms::synthesizer::{synthesize_f32_dev, synthesize_f32_with_planner, synthesize_f64_dev, synthesize_f64_with_planner};
+pub use planner::{PlannerSynthesizer32, PlannerSynthesizer64};
 // overlap-save convolution and correlation of real signals (an extension beyond PhastFT 0.3.0)
 pub use algorithms::conv::{conv_f32_dev, conv_f32_with_planner, conv_f64_dev, conv_f64_with_planner};
 pub use planner::{ConvMode, PlannerConv32, PlannerConv64};

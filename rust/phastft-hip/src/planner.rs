@@ -714,6 +714,89 @@ impl_planner_channelizer!(PlannerChannelizer32, f32, phast_planner_channelizer32
                           phast_planner_channelizer32_periods, phast_planner_channelizer32_workspace_len,
                           phast_planner_channelizer32_workspace_min);
 
+macro_rules! impl_planner_synthesizer {
+    ($sy:ident, $t:ty, $new:ident, $free:ident, $out_len:ident, $full_len:ident, $bins:ident, $tile:ident, $per:ident, $terms:ident,
+     $ws_len:ident, $ws_min:ident) => {
+        /// An extension beyond PhastFT 0.3.0: the polyphase synthesis filter bank, the inverse side of the channelizer -- from
+        /// `frames` frames of `channels` channels, s[n] = sum_m g[n - m hop] sum_k Y[m][k] exp(2 pi i k n / channels) with the
+        /// planner's real taps g and zero extension, of which a call yields the `out_len` samples from `first` on.  One
+        /// `channels`-point inverse transform per frame and one gather kernel; the bits of an output depend on the values alone.
+        /// The phases are in absolute time, so the delay of an analysis / synthesis pair must be a multiple of `channels`: for
+        /// analysis taps h of channels * T points, g = (0, h reversed) is the channelizer's adjoint delayed by h.len().
+        /// Immutable after `new`.
+        pub struct $sy {
+            pub(crate) h: *mut Opaque,
+            pub(crate) frames: usize,
+            complex_output: bool,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's buffers (device calls) or in device
+        // buffers of its own (host-slice calls)
+        unsafe impl Send for $sy {}
+        unsafe impl Sync for $sy {}
+        impl $sy {
+            /// `out_len` = 0 stands for `full_len - first`; the window may pass `full_len` (zeros there); `complex_output`: a
+            /// frame has `channels` bins and the signal is (re, im) planes, else `channels / 2 + 1` bins and one plane.
+            /// Panics with "invalid argument" unless 1 <= frames, taps.len(), channels, hop <= 2^29, frames * channels <= 2^30,
+            /// first <= full_len and 1 <= out_len <= 2^30
+            pub fn new(frames: usize, taps: &[$t], channels: usize, hop: usize, first: usize, out_len: usize, complex_output: bool) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe {
+                    ffi::$new(frames, taps.as_ptr(), taps.len(), channels, hop, first, out_len, complex_output as c_int, &mut h)
+                });
+                Self { h, frames, complex_output }
+            }
+            pub fn frames(&self) -> usize {
+                self.frames
+            }
+            pub fn complex_output(&self) -> bool {
+                self.complex_output
+            }
+            pub fn out_len(&self) -> usize {
+                unsafe { ffi::$out_len(self.h) }
+            }
+            /// (frames - 1) * hop + taps
+            pub fn full_len(&self) -> usize {
+                unsafe { ffi::$full_len(self.h) }
+            }
+            /// bins of a frame: channels (complex output) or channels / 2 + 1 (real output)
+            pub fn bins(&self) -> usize {
+                unsafe { ffi::$bins(self.h) }
+            }
+            /// the unfold's tile: (output samples per workgroup, per thread)
+            pub fn tile(&self) -> (usize, usize) {
+                unsafe { (ffi::$tile(self.h), ffi::$per(self.h)) }
+            }
+            /// terms of an output sample at most: ceil(taps / hop)
+            pub fn max_terms(&self) -> usize {
+                unsafe { ffi::$terms(self.h) }
+            }
+            /// elements of the workspace a device call of `batch` signals works in
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+            /// the least workspace a call runs in: one signal's frames (0 for complex output of one channel)
+            pub fn workspace_min(&self) -> usize {
+                unsafe { ffi::$ws_min(self.h) }
+            }
+        }
+        impl Drop for $sy {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_synthesizer!(PlannerSynthesizer64, f64, phast_planner_synthesizer64_new, phast_planner_synthesizer64_free,
+                          phast_planner_synthesizer64_out_len, phast_planner_synthesizer64_full_len, phast_planner_synthesizer64_bins,
+                          phast_planner_synthesizer64_tile_samples, phast_planner_synthesizer64_per_thread,
+                          phast_planner_synthesizer64_max_terms, phast_planner_synthesizer64_workspace_len,
+                          phast_planner_synthesizer64_workspace_min);
+impl_planner_synthesizer!(PlannerSynthesizer32, f32, phast_planner_synthesizer32_new, phast_planner_synthesizer32_free,
+                          phast_planner_synthesizer32_out_len, phast_planner_synthesizer32_full_len, phast_planner_synthesizer32_bins,
+                          phast_planner_synthesizer32_tile_samples, phast_planner_synthesizer32_per_thread,
+                          phast_planner_synthesizer32_max_terms, phast_planner_synthesizer32_workspace_len,
+                          phast_planner_synthesizer32_workspace_min);
+
 /// Which part of the full convolution a planner yields (PHAST_CONV_* of the C ABI)
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum ConvMode {
