@@ -32,6 +32,8 @@
 //                                                            polyphase channelizer (uniform DFT analysis filter bank)
 //   (none: no filter banks upstream)                         class PlannerSynthesizer64/32, synthesize_f64/f32_with_planner -- the
 //                                                            polyphase synthesis bank, the channelizer's inverse
+//   (none: no wavelets upstream)                             class PlannerCwt64/32, cwt_64/32_with_planner, enum CwtFamily, CwtNorm --
+//                                                            the continuous wavelet transform and the analytic signal
 //   (none: no sample-rate conversion upstream)               class PlannerUpfirdn64/32, upfirdn_f64/f32_with_planner -- the polyphase
 //                                                            FIR of scipy.signal.upfirdn; class PlannerResample64/32,
 //                                                            resample_f64/f32_with_planner -- scipy.signal.resample
@@ -897,6 +899,67 @@ PHASTFT_PLANNER_SYNTHESIZER(PlannerSynthesizer32, phast_planner_synthesizer32, 3
 PHASTFT_SYNTHESIZE(f64, double, PlannerSynthesizer64)
 PHASTFT_SYNTHESIZE(f32, float, PlannerSynthesizer32)
 #undef PHASTFT_SYNTHESIZE
+
+// ---- continuous wavelet transform and analytic signal (no reference counterpart; Torrence & Compo 1998) ----
+enum class CwtFamily : int { Morlet = PHAST_CWT_MORLET, Paul = PHAST_CWT_PAUL, Dog = PHAST_CWT_DOG, Step = PHAST_CWT_STEP };
+enum class CwtNorm : int { L2 = PHAST_CWT_L2, Peak = PHAST_CWT_PEAK };
+#define PHASTFT_PLANNER_CWT(NAME, CT, SFX, T)                                                                    \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* signals of `signal_len` points at the scales `scales` (in samples: finite, > 0), through a periodic convolution of \
+           `pad_len` >= signal_len points (0: signal_len; the signal is zero-extended): W[j][n] = ifft(fft(x) conj(c_j \
+           psi0^(s_j w)))[n], n < signal_len.  `param`: w0 of Morlet (customarily 6), the integer m of Paul (<= 85) and DOG \
+           (<= 170); Step (the analytic-signal filter) ignores it, the scales' values and the norm.  real_input: one input \
+           plane and the one-sided spectrum; otherwise (re, im) planes */ \
+        NAME(std::size_t signal_len, Slice<const double> scales, CwtFamily family = CwtFamily::Morlet, double param = 6.0, \
+             CwtNorm norm = CwtNorm::L2, std::size_t pad_len = 0, bool real_input = true)                        \
+            : signal_len_(signal_len) {                                                                          \
+            check(phast_planner_cwt##SFX##_new(signal_len, pad_len, scales.ptr, scales.len, static_cast<int>(family), param, \
+                                               static_cast<int>(norm), real_input ? 1 : 0, &h_));                \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_), signal_len_(o.signal_len_) { o.h_ = nullptr; }                       \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_cwt##SFX##_free(h_);                                                           \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_cwt##SFX##_describe(h_, &s[0], s.size()));                                       \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_cwt##SFX##_device_bytes(h_); }                   \
+        std::size_t signal_len() const { return signal_len_; }                                                   \
+        std::size_t pad_len() const { return phast_planner_cwt##SFX##_pad_len(h_); }                             \
+        std::size_t num_scales() const { return phast_planner_cwt##SFX##_num_scales(h_); }                       \
+        /* the bank's tile: bins and scales per workgroup */                                                     \
+        std::size_t tile_bins() const { return phast_planner_cwt##SFX##_tile_bins(h_); }                         \
+        std::size_t scale_group() const { return phast_planner_cwt##SFX##_scale_group(h_); }                     \
+        /* elements of T a _dev call of `batch` signals works in; workspace_min: the least a call runs in */     \
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_cwt##SFX##_workspace_len(h_, batch); } \
+        std::size_t workspace_min() const { return phast_planner_cwt##SFX##_workspace_min(h_); }                 \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+        std::size_t signal_len_ = 0;                                                                             \
+    };
+PHASTFT_PLANNER_CWT(PlannerCwt64, phast_planner_cwt64, 64, double)
+PHASTFT_PLANNER_CWT(PlannerCwt32, phast_planner_cwt32, 32, float)
+#undef PHASTFT_PLANNER_CWT
+
+// one signal from a host slice of signal_len() points (x_im: the imaginary plane for a complex planner, an empty slice for a
+// real one) -> host planes of num_scales() * signal_len() points, scale-major; blocking
+#define PHASTFT_CWT(FS, T, P)                                                                                    \
+    inline void cwt_##FS##_with_planner(Slice<const T> x, Slice<const T> x_im, Slice<T> out_re, Slice<T> out_im, \
+                                        const P &planner) {                                                      \
+        if ((x_im.ptr && x_im.len != x.len) || out_re.len != out_im.len) check(PHAST_ERR_LEN_MISMATCH);          \
+        check(phast_cwt_##FS##_with_planner(x.ptr, x_im.ptr, x.len, out_re.ptr, out_im.ptr, out_re.len, planner.get())); \
+    }
+PHASTFT_CWT(64, double, PlannerCwt64)
+PHASTFT_CWT(32, float, PlannerCwt32)
+#undef PHASTFT_CWT
 
 // ---- overlap-save convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve / correlate) ----
 enum class ConvMode : int { Full = PHAST_CONV_FULL, Same = PHAST_CONV_SAME, Valid = PHAST_CONV_VALID };

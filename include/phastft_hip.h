@@ -988,6 +988,92 @@ int phast_synthesize_f32_dev(const float *d_in_re, const float *d_in_im, float *
 int phast_planner_synthesizer32_time_stages(const phast_planner_synthesizer32 *p, const float *d_in_re, const float *d_in_im, float *d_out_re, float *d_out_im, size_t batch, float *d_work, size_t work_len,
                                              int reps, float *stage_ms, void *stream);
 
+/* ---- continuous wavelet transform and analytic signal (no reference counterpart; Torrence & Compo 1998, scipy.signal.hilbert;
+ * DESIGN.md §30).  Samples at unit spacing, scales in samples (a caller with a sampling interval dt passes s / dt).  A real or
+ * complex signal x of L points is zero-extended to P points, L <= P <= 2^29 (pad_len = 0 at _new: P = L); padding is how a
+ * caller pushes the wrap-around of the periodic convolution out of the window.  With X = fft_P(x) (numpy's convention) and
+ * w_k = 2 pi k / P for k <= P div 2, 2 pi (k - P) / P above (for even P the bin P / 2 counts as positive), for S scales s_j
+ * (finite doubles > 0, any order, repeats allowed, at most 2^20):
+ *     W[j][n] = ifft_P( X[k] conj( c_j psi0^(s_j w_k) ) )[n],  n < L
+ * in two planes: row (b, j) lies at d_out_re (d_out_im) + b out_dist + j L.  Families (Torrence & Compo's table 1 by its
+ * frequency-domain column; H(x) = 1 for x > 0, else 0); `param` is w0 or m:
+ *     PHAST_CWT_MORLET (w0 > 0, customarily 6)    pi^(-1/4) H(x) exp(-(x - w0)^2 / 2)
+ *     PHAST_CWT_PAUL (integer m, 1 .. 85)         2^m / sqrt(m (2m - 1)!) H(x) x^m exp(-x)
+ *     PHAST_CWT_DOG (integer m, 1 .. 170)         -(i^m) / sqrt(Gamma(m + 1/2)) x^m exp(-x^2 / 2)     (m = 2: the Mexican hat)
+ *     PHAST_CWT_STEP                              1 at k = 0 and at k = P / 2 (even P), 2 for 0 < k < P / 2, 0 above
+ * (the caps on m: where (2m - 1)! and Gamma(m + 1/2) stay finite in double).  The transform is defined by these
+ * frequency-domain formulas; for odd m of DOG the paper's time-domain column differs by a sign.  STEP does not depend on the
+ * scale and ignores `norm` and `param`: with one scale it is the analytic signal, scipy.signal.hilbert(x, N=P)[:L].  Norms:
+ *     PHAST_CWT_L2     c_j = sqrt(2 pi s_j)          (Torrence & Compo eq. 6 at dt = 1: unit energy)
+ *     PHAST_CWT_PEAK   c_j = 2 / max_x |psi0^(x)|    (a unit sinusoid at the centre frequency has |W| = 1 for Morlet and Paul)
+ * Method: one forward transform of P per signal on the any-length path (R2C for a real planner) into workspace planes, one
+ * bank kernel that evaluates the filters in registers and writes the S rows, one batched inverse transform in place in the
+ * rows.  When P = L the rows are the output planes; when P > L they live in the workspace and a crop copies the first L of
+ * each.  s_j w_k, the exponent and the exponential are formed in double in both types, the filter value rounded once to T; the gains
+ * c_j are built at _new in double.  Every element of a row is a function of its signal's spectrum, its scale and P alone, so
+ * the result's bits do not depend on the batch, the distances, pointer alignment, the workspace, the stream or a graph replay.
+ * Workspace: _workspace_len(p, batch) elements of T hold the whole call; any work_len >= _workspace_min(p) (one signal's
+ * spectrum and one row) runs chunks of whole rows, to the same bits.
+ * _new refuses with PHAST_ERR_INVALID_ARG, before the device is touched: NULL scales; L < 1; P < L or P > 2^29; S < 1 or
+ * S > 2^20; a scale that is not finite or is <= 0; an unknown family or norm; a param outside the family's range or not an
+ * integer where m is one.  _dev: d_x_im must be NULL for a real planner (real_input != 0 at _new) and non-NULL for a complex
+ * one; sig_dist >= L and out_dist >= S L (batch 1 ignores both); pointers need element alignment only; the signal is never
+ * written; signal and output must not overlap (identical pointers are refused).  The engine's distance rules are inherited:
+ * a real planner with P = L a power of two >= 4 and batch > 1 needs an even sig_dist.  A null pointer, the wrong d_x_im, a
+ * short or refused dist, a null or short workspace: PHAST_ERR_INVALID_ARG; a signal_len that is not the planner's:
+ * PHAST_ERR_PLANNER_SIZE; an out_len of the host-slice form that is not S L: PHAST_ERR_LEN_MISMATCH -- all before the device
+ * is touched.  The *_with_planner forms take host slices of one signal (x_im NULL for a real planner) and block.
+ * Out of scope: the inverse transform, real output by C2R for real wavelets of real signals, a fused |W|^2, pruning rows of
+ * narrow support, other families, padding other than zeros. */
+#define PHAST_CWT_MORLET 0
+#define PHAST_CWT_PAUL 1
+#define PHAST_CWT_DOG 2
+#define PHAST_CWT_STEP 3
+#define PHAST_CWT_L2 0
+#define PHAST_CWT_PEAK 1
+typedef struct phast_planner_cwt64 phast_planner_cwt64; /* PlannerCwt64 */
+int phast_planner_cwt64_new(size_t signal_len, size_t pad_len, const double *scales, size_t num_scales, int family, double param, int norm,
+                             int real_input, phast_planner_cwt64 **out);
+void phast_planner_cwt64_free(phast_planner_cwt64 *p);
+int phast_planner_cwt64_describe(const phast_planner_cwt64 *p, char *buf, size_t buf_len);
+size_t phast_planner_cwt64_device_bytes(const phast_planner_cwt64 *p);
+size_t phast_planner_cwt64_workspace_len(const phast_planner_cwt64 *p, size_t batch);
+size_t phast_planner_cwt64_workspace_min(const phast_planner_cwt64 *p);
+size_t phast_planner_cwt64_pad_len(const phast_planner_cwt64 *p);     /* P */
+size_t phast_planner_cwt64_num_scales(const phast_planner_cwt64 *p);  /* S */
+size_t phast_planner_cwt64_tile_bins(const phast_planner_cwt64 *p);   /* bins per workgroup of the bank */
+size_t phast_planner_cwt64_scale_group(const phast_planner_cwt64 *p); /* scales per workgroup of the bank at most */
+int phast_cwt_64_with_planner(const double *x_re, const double *x_im, size_t x_len, double *out_re, double *out_im, size_t out_len,
+                               const phast_planner_cwt64 *planner);
+int phast_cwt_64_dev(const double *d_x_re, const double *d_x_im, double *d_out_re, double *d_out_im, size_t signal_len, size_t batch, size_t sig_dist,
+                      size_t out_dist, const phast_planner_cwt64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/cwt_rate.py): stage_ms[4] = average milliseconds of the forward transform (with its copy), the bank,
+ * the inverse transform and the crop over `reps` calls of `batch` signals at distances L and S L in ONE chunk (work_len >=
+ * _workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_cwt64_time_stages(const phast_planner_cwt64 *p, const double *d_x_re, const double *d_x_im, double *d_out_re, double *d_out_im, size_t batch, double *d_work, size_t work_len,
+                                     int reps, float *stage_ms, void *stream);
+typedef struct phast_planner_cwt32 phast_planner_cwt32; /* PlannerCwt32 */
+int phast_planner_cwt32_new(size_t signal_len, size_t pad_len, const double *scales, size_t num_scales, int family, double param, int norm,
+                             int real_input, phast_planner_cwt32 **out);
+void phast_planner_cwt32_free(phast_planner_cwt32 *p);
+int phast_planner_cwt32_describe(const phast_planner_cwt32 *p, char *buf, size_t buf_len);
+size_t phast_planner_cwt32_device_bytes(const phast_planner_cwt32 *p);
+size_t phast_planner_cwt32_workspace_len(const phast_planner_cwt32 *p, size_t batch);
+size_t phast_planner_cwt32_workspace_min(const phast_planner_cwt32 *p);
+size_t phast_planner_cwt32_pad_len(const phast_planner_cwt32 *p);     /* P */
+size_t phast_planner_cwt32_num_scales(const phast_planner_cwt32 *p);  /* S */
+size_t phast_planner_cwt32_tile_bins(const phast_planner_cwt32 *p);   /* bins per workgroup of the bank */
+size_t phast_planner_cwt32_scale_group(const phast_planner_cwt32 *p); /* scales per workgroup of the bank at most */
+int phast_cwt_32_with_planner(const float *x_re, const float *x_im, size_t x_len, float *out_re, float *out_im, size_t out_len,
+                               const phast_planner_cwt32 *planner);
+int phast_cwt_32_dev(const float *d_x_re, const float *d_x_im, float *d_out_re, float *d_out_im, size_t signal_len, size_t batch, size_t sig_dist,
+                      size_t out_dist, const phast_planner_cwt32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/cwt_rate.py): stage_ms[4] = average milliseconds of the forward transform (with its copy), the bank,
+ * the inverse transform and the crop over `reps` calls of `batch` signals at distances L and S L in ONE chunk (work_len >=
+ * _workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_cwt32_time_stages(const phast_planner_cwt32 *p, const float *d_x_re, const float *d_x_im, float *d_out_re, float *d_out_im, size_t batch, float *d_work, size_t work_len,
+                                     int reps, float *stage_ms, void *stream);
+
 /* ---- overlap-save FIR convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve /
  * correlate(x, h, mode, method="direct")).  Signal x of L samples, K taps h, both real:
  *     full[t] = sum_j g[j] x[t - j], t in [0, L + K - 1); g = h (flip = 0: convolution) or g[j] = h[K - 1 - j] (flip = 1:

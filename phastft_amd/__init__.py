@@ -40,6 +40,8 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
                                                     channelize_64/32_with_planner, channelize_poly, pfb_prototype
     (none: no filter banks)                         PlannerSynthesizer64/32, synthesize_batched,
                                                     synthesize_64/32_with_planner, synthesize_poly
+    (none: no wavelets)                             PlannerCwt64/32, cwt_batched, cwt_64/32_with_planner, cwt, hilbert,
+                                                    cwt_scales, cwt_fourier_period
     (none: no convolution)                          PlannerConv64/32, conv_batched, conv_f64/f32_with_planner,
                                                     fftconvolve, correlate
     (none: no convolution)                          PlannerConvNd64/32, convnd_batched, convnd_f64/f32_with_planner,
@@ -74,6 +76,7 @@ import contextlib
 import ctypes as C
 import enum
 import functools
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -114,6 +117,8 @@ __all__ = [
     "channelize_32_with_planner", "channelize_poly", "pfb_prototype",
     "PlannerSynthesizer64", "PlannerSynthesizer32", "synthesize_batched", "synthesize_64_with_planner",
     "synthesize_32_with_planner", "synthesize_poly",
+    "PlannerCwt64", "PlannerCwt32", "cwt_batched", "cwt_64_with_planner", "cwt_32_with_planner", "cwt", "hilbert",
+    "cwt_scales", "cwt_fourier_period",
     "PlannerConv64", "PlannerConv32", "conv_batched", "conv_f64_with_planner", "conv_f32_with_planner", "fftconvolve",
     "correlate",
     "PlannerConvNd64", "PlannerConvNd32", "convnd_batched", "convnd_f64_with_planner", "convnd_f32_with_planner",
@@ -2437,6 +2442,223 @@ def synthesize_poly(y, g, n_chans: int, hop: int | None = None, first: int = 0, 
     out = synthesize_batched(rows, planner)
     torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
     return out.reshape(y.shape[:-2] + (planner.out_len,))
+
+
+# ---------------------------------------------------------------------------------------------
+# continuous wavelet transform and analytic signal (no reference counterpart; Torrence & Compo 1998, scipy.signal.hilbert)
+# ---------------------------------------------------------------------------------------------
+_CWT_FAMILIES = {"morlet": 0, "paul": 1, "dog": 2, "step": 3}
+_CWT_NORMS = {"l2": 0, "peak": 1}
+_CWT_DEFAULTS = {"morlet": 6.0, "paul": 4.0, "dog": 2.0, "step": 0.0}
+
+
+def _cwt_family(wavelet: str, param):
+    if wavelet not in _CWT_FAMILIES:
+        raise ValueError(f"wavelet: one of {sorted(_CWT_FAMILIES)}, not {wavelet!r}")
+    return _CWT_FAMILIES[wavelet], float(_CWT_DEFAULTS[wavelet] if param is None else param)
+
+
+class PlannerCwt64(_AnyHandle):
+    """f64 continuous wavelet transform of signals of ``signal_len`` points at the scales ``scales`` (in samples: finite,
+    > 0, any order), through a periodic convolution of ``pad_len`` >= ``signal_len`` points (default ``signal_len``; the
+    signal is zero-extended, which pushes the wrap-around out of the window):
+    ``W[j, n] = ifft(fft(x, pad_len) * conj(c_j * psi_hat(s_j * w)))[n]``, ``n < signal_len``, with Torrence & Compo's (1998)
+    frequency-domain wavelets ``"morlet"`` (``param`` = w0, default 6), ``"paul"`` (integer order m <= 85, default 4),
+    ``"dog"`` (integer derivative m <= 170, default 2: the Mexican hat) and ``"step"`` (the analytic-signal filter of
+    ``scipy.signal.hilbert``; it ignores scale, ``param`` and ``norm``).  ``norm="l2"``: ``c_j = sqrt(2 pi s_j)`` (unit energy,
+    Torrence & Compo eq. 6 at dt = 1); ``norm="peak"``: ``c_j = 2 / max |psi_hat|`` (a unit sinusoid at the centre frequency
+    has ``|W| = 1`` for Morlet and Paul).  ``real_input`` is a property of the planner: a real planner takes one plane and keeps
+    the one-sided spectrum.  One forward transform per signal, one bank kernel, one inverse transform per row.  Not here:
+    the inverse transform, real output for real wavelets, ``|W|**2``, other families, other paddings."""
+
+    _prefix = "cwt"
+
+    def __init__(self, signal_len: int, scales, wavelet: str = "morlet", param=None, norm: str = "l2", pad_len: int | None = None,
+                 real_input: bool = True):
+        family, par = _cwt_family(wavelet, param)
+        if norm not in _CWT_NORMS:
+            raise ValueError(f"norm: one of {sorted(_CWT_NORMS)}, not {norm!r}")
+        if _is_torch(scales):
+            scales = scales.detach().cpu().numpy()
+        sc = np.ascontiguousarray(scales, dtype=np.float64).reshape(-1)
+        self._new(signal_len, 0 if pad_len is None else pad_len, sc.ctypes.data_as(C.c_void_p), sc.size, family, par,
+                  _CWT_NORMS[norm], 1 if real_input else 0)
+        self.n = self.signal_len = signal_len
+        self.scales, self.wavelet, self.param, self.norm = sc.copy(), wavelet, par, norm
+        self.real_input = bool(real_input)
+        self.pad_len = int(self._fn("pad_len")(self._h))
+        self.num_scales = int(self._fn("num_scales")(self._h))
+        self.tile_bins = int(self._fn("tile_bins")(self._h))
+        self.scale_group = int(self._fn("scale_group")(self._h))
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` signals works in.  A smaller workspace of at least ``workspace_min()`` (one
+        signal's spectrum and one row) runs chunks of whole rows, to the same bits."""
+        return self._workspace_len(batch)
+
+    def workspace_min(self) -> int:
+        return int(self._fn("workspace_min")(self._h))
+
+    def time_stages(self, x_re, x_im, out_re, out_im, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (forward, bank, inverse, crop) of a call of ``batch`` signals at distances
+        ``signal_len`` and ``num_scales * signal_len`` on device tensors; ``x_im`` is None for a real planner (measurement hook)"""
+        xr = _Slice(x_re, self._dtype, "x_re")
+        xi = _NULL if x_im is None else _Slice(x_im, self._dtype, "x_im")
+        o_re, o_im = _Slice(out_re, self._dtype, "out_re"), _Slice(out_im, self._dtype, "out_im")
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 4)()
+        _check(self._fn("time_stages")(self._h, xr.ptr, xi.ptr, o_re.ptr, o_im.ptr, batch, ws.ptr, ws.len, reps, ms, _stream()))
+        return [float(v) for v in ms]
+
+
+class PlannerCwt32(PlannerCwt64):
+    """f32 twin of :class:`PlannerCwt64`: the scales and gains stay in f64 and the filter is evaluated in f64 and rounded once;
+    the transforms and the product are f32"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def cwt_batched(x, planner, out=None, work=None, stream=None):
+    """Device-resident batch through one CWT planner.  ``x``: for a real planner a real torch device tensor of shape
+    ``(batch, signal_len)`` or ``(signal_len,)`` whose last axis is contiguous (rows any distance >= signal_len apart); for a
+    complex planner a complex tensor of such a shape (split into planes here) or a pair ``(x_re, x_im)`` of such real planes
+    with equal strides.  Returns a complex tensor of shape ``(batch, S, signal_len)`` (``(S, signal_len)`` for one unbatched
+    signal).  ``out``: a pair ``(out_re, out_im)`` of real tensors of that shape to write into, their last two axes dense
+    (signals any distance >= S * signal_len apart), equal strides; it is returned in place of a new tensor.  ``work``: a device
+    tensor of at least ``planner.workspace_min()`` elements, by default one of ``planner.workspace_len(batch)`` from torch's
+    allocator; ``stream``: a ``torch.cuda.Stream``, by default the current one.  ``x`` is not written."""
+    import torch
+
+    want = torch.float64 if planner._dtype == np.float64 else torch.float32
+    l, s = planner.signal_len, planner.num_scales
+
+    if planner.real_input:
+        if isinstance(x, (tuple, list)) or not _is_torch(x) or x.is_complex():
+            raise TypeError("x: a real planner takes one real device tensor")
+        x_re, x_im = x, None
+    elif isinstance(x, (tuple, list)):
+        x_re, x_im = x
+    elif _is_torch(x) and x.is_complex():
+        x_re, x_im = x.real.contiguous(), x.imag.contiguous()
+    else:
+        raise TypeError("x: a complex planner takes a complex device tensor or a pair of real planes")
+
+    def plane(v, what, n, lead):
+        """the distance of the leading axis of a plane whose trailing axes are dense"""
+        if not _is_torch(v) or v.device.type != "cuda" or v.dtype != want:
+            raise TypeError(f"{what}: need a {want} device tensor")
+        tail = (s, n) if lead == 2 else (n,)
+        if v.dim() not in (lead, lead + 1) or tuple(v.shape[-lead:]) != tail:
+            raise ValueError(f"{what}: need shape (batch,) + {tail} or {tail}, not {tuple(v.shape)}")
+        dense = 1
+        for ax in range(v.dim() - 1, v.dim() - 1 - lead, -1):
+            if v.shape[ax] > 1 and v.stride(ax) != dense:
+                raise ValueError(f"{what}: the last {lead} axes must be dense")
+            dense *= v.shape[ax]
+        count = v.shape[0] if v.dim() == lead + 1 else 1
+        dist = v.stride(0) if v.dim() == lead + 1 and count > 1 else dense
+        if dist < dense:
+            raise ValueError(f"{what}: rows overlap")
+        return count, dist
+
+    batch, sig_dist = plane(x_re, "x", l, 1)
+    if x_im is not None and plane(x_im, "x_im", l, 1) != (batch, sig_dist):
+        raise ValueError("x_im: need the shape and strides of x_re")
+    unbatched = x_re.dim() == 1
+
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        own = out is None
+        if own:
+            shape = (s, l) if unbatched else (batch, s, l)
+            out = tuple(torch.empty(shape, dtype=want, device=x_re.device) for _ in range(2))
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError("out: a pair of real planes (out_re, out_im)")
+        out_re, out_im = out
+        n_out, out_dist = plane(out_re, "out_re", l, 2)
+        if plane(out_im, "out_im", l, 2) != (n_out, out_dist) or n_out != batch:
+            raise ValueError("out: need two planes of the batch's shape with equal strides")
+        if batch:
+            ws = _any_workspace(planner, batch, work)
+            _check(_call(f"phast_cwt_{planner._sfx}_dev", x_re.data_ptr(), None if x_im is None else x_im.data_ptr(),
+                         out_re.data_ptr(), out_im.data_ptr(), l, batch, sig_dist, out_dist, planner._h, ws.ptr, ws.len, _stream()))
+        return torch.complex(out_re, out_im) if own else out
+
+
+def _cwt_host(sfx, dtype, x_re, x_im, out_re, out_im, planner):
+    xr = _Slice(x_re, dtype, "x_re")
+    xi = _NULL if x_im is None else _Slice(x_im, dtype, "x_im")
+    o_re, o_im = _Slice(out_re, dtype, "out_re"), _Slice(out_im, dtype, "out_im")
+    if o_re.len != o_im.len:
+        raise ValueError("out_re and out_im differ in length")
+    if _same_place(xr, o_re, o_im):
+        raise TypeError(f"cwt_{sfx}_with_planner takes host arrays (cwt_batched takes device tensors)")
+    _check(_call(f"phast_cwt_{sfx}_with_planner", xr.ptr, xi.ptr, xr.len, o_re.ptr, o_im.ptr, o_re.len, planner._h))
+
+
+def cwt_64_with_planner(x_re, out_re, out_im, planner: PlannerCwt64, x_im=None) -> None:
+    """f64 transform of one signal from a host array of ``planner.signal_len`` points (``x_im``: its imaginary plane, for a
+    complex planner) into host planes of ``planner.num_scales * planner.signal_len`` points, scale-major; blocking"""
+    _cwt_host("64", np.float64, x_re, x_im, out_re, out_im, planner)
+
+
+def cwt_32_with_planner(x_re, out_re, out_im, planner: PlannerCwt32, x_im=None) -> None:
+    """f32 twin of :func:`cwt_64_with_planner`"""
+    _cwt_host("32", np.float32, x_re, x_im, out_re, out_im, planner)
+
+
+def cwt(x, scales, wavelet: str = "morlet", param=None, norm: str = "l2", pad_len: int | None = None):
+    """The continuous wavelet transform over the last axis of a real or complex device tensor ``x`` at the scales ``scales``
+    (an array or a tensor, in samples), through a planner of its own: a new complex tensor of shape
+    ``x.shape[:-1] + (len(scales), x.shape[-1])``.  float64 / complex128 run in f64, float32 / complex64 in f32.  See
+    :class:`PlannerCwt64` for the definition; :func:`cwt_scales` makes the customary dyadic scales and
+    :func:`cwt_fourier_period` turns a scale into a Fourier period.  Not here: the inverse transform."""
+    import torch
+
+    kinds = {torch.float64: (PlannerCwt64, True), torch.float32: (PlannerCwt32, True),
+             torch.complex128: (PlannerCwt64, False), torch.complex64: (PlannerCwt32, False)}
+    if not _is_torch(x) or x.device.type != "cuda" or x.dtype not in kinds or x.dim() < 1:
+        raise TypeError("need a float64, float32, complex128 or complex64 device tensor of at least one axis")
+    kind, real = kinds[x.dtype]
+    planner = kind(x.shape[-1], scales, wavelet, param, norm, pad_len, real)
+    rows = x.reshape(-1, x.shape[-1]).contiguous()
+    tail = (planner.num_scales, x.shape[-1])
+    if not rows.shape[0]:
+        return torch.empty(x.shape[:-1] + tail, dtype=torch.complex128 if kind is PlannerCwt64 else torch.complex64, device=x.device)
+    out = cwt_batched(rows, planner)
+    torch.cuda.current_stream().synchronize()  # the temporary planner's tables die with it
+    return out.reshape(x.shape[:-1] + tail)
+
+
+def hilbert(x, pad_len: int | None = None):
+    """The analytic signal over the last axis of a real or complex device tensor, ``scipy.signal.hilbert(x, N=pad_len)`` cut
+    to the first ``x.shape[-1]`` points: the ``"step"`` filter of :func:`cwt` with one scale.  A complex tensor of ``x``'s shape."""
+    return cwt(x, [1.0], "step", pad_len=pad_len).squeeze(-2)
+
+
+def cwt_scales(L: int, s0: float = 2.0, dj: float = 0.25, J: int | None = None):
+    """Torrence & Compo's eqs. 9-10: the scales ``s0 * 2**(j * dj)``, ``j = 0 .. J``, with ``J = floor(log2(L / s0) / dj)`` by
+    default, as a float64 array.  A negative default ``J`` (``L < s0``) has no scales and is a :class:`ValueError`."""
+    if not (s0 > 0 and dj > 0 and L >= 1):
+        raise ValueError("need L >= 1, s0 > 0 and dj > 0")
+    if J is None:
+        J = int(math.floor(math.log2(L / s0) / dj))
+    if J < 0:
+        raise ValueError(f"J = {J}: no scales (give J, or an s0 <= L)")
+    return s0 * 2.0 ** (dj * np.arange(J + 1, dtype=np.float64))
+
+
+def cwt_fourier_period(wavelet: str = "morlet", param=None) -> float:
+    """The Fourier period of scale 1 (Torrence & Compo's table 1): ``4 pi / (w0 + sqrt(2 + w0**2))`` for Morlet,
+    ``4 pi / (2 m + 1)`` for Paul, ``2 pi / sqrt(m + 1/2)`` for DOG; multiply by a scale.  ``"step"`` has no scale."""
+    family, par = _cwt_family(wavelet, param)
+    if family == 0:
+        return 4 * math.pi / (par + math.sqrt(2 + par * par))
+    if family == 1:
+        return 4 * math.pi / (2 * par + 1)
+    if family == 2:
+        return 2 * math.pi / math.sqrt(par + 0.5)
+    raise ValueError("the step filter has no scale")
 
 
 # ---------------------------------------------------------------------------------------------

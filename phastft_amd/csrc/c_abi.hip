@@ -22,6 +22,7 @@
 #include "planner_lomb.hpp"
 #include "planner_channelizer.hpp"
 #include "planner_synthesizer.hpp"
+#include "planner_cwt.hpp"
 #include "planner_resample.hpp"
 #include "planner_stft.hpp"
 #include "planner_conv.hpp"
@@ -63,6 +64,8 @@ struct phast_planner_channelizer64 : ChannelizerPlanner<double> {};
 struct phast_planner_channelizer32 : ChannelizerPlanner<float> {};
 struct phast_planner_synthesizer64 : SynthesizerPlanner<double> {};
 struct phast_planner_synthesizer32 : SynthesizerPlanner<float> {};
+struct phast_planner_cwt64 : CwtPlanner<double> {};
+struct phast_planner_cwt32 : CwtPlanner<float> {};
 struct phast_planner_conv64 : ConvPlanner<double> {};
 struct phast_planner_conv32 : ConvPlanner<float> {};
 struct phast_planner_convnd64 : ConvNdPlanner<double> {};
@@ -578,7 +581,7 @@ PHAST_HANDLE_API(nd64) PHAST_HANDLE_API(nd32) PHAST_HANDLE_API(r2c_nd64) PHAST_H
 PHAST_HANDLE_API(convnd64) PHAST_HANDLE_API(convnd32) PHAST_HANDLE_API(mdct64) PHAST_HANDLE_API(mdct32)
 PHAST_HANDLE_API(lomb64) PHAST_HANDLE_API(lomb32) PHAST_HANDLE_API(upfirdn64) PHAST_HANDLE_API(upfirdn32)
 PHAST_HANDLE_API(resample64) PHAST_HANDLE_API(resample32) PHAST_HANDLE_API(channelizer64) PHAST_HANDLE_API(channelizer32)
-PHAST_HANDLE_API(synthesizer64) PHAST_HANDLE_API(synthesizer32)
+PHAST_HANDLE_API(synthesizer64) PHAST_HANDLE_API(synthesizer32) PHAST_HANDLE_API(cwt64) PHAST_HANDLE_API(cwt32)
 
 // Arbitrary lengths (Bluestein, planner_any.hpp): arguments are checked before the device is touched
 #define PHAST_ANY_API(SFX, T)                                                                                           \
@@ -1105,6 +1108,51 @@ PHAST_CHANNELIZER_API(32, f32, float)
     } PHAST_CATCH_RC
 PHAST_SYNTHESIZER_API(64, f64, double)
 PHAST_SYNTHESIZER_API(32, f32, float)
+
+// The continuous wavelet transform (planner_cwt.hpp): every argument rule, a wrong length and planes that do not match the
+// planner come back before the device is touched
+#define PHAST_CWT_API(SFX, T)                                                                                           \
+    int phast_planner_cwt##SFX##_new(size_t signal_len, size_t pad_len, const double *scales, size_t num_scales,        \
+                                     int family, double param, int norm, int real_input,                                \
+                                     phast_planner_cwt##SFX **out) try {                                                \
+        return cwt_planner_new<T>(signal_len, pad_len, scales, num_scales, family, param, norm, real_input, out);       \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_cwt##SFX##_workspace_min(const phast_planner_cwt##SFX *p) try {                                \
+        return p ? p->workspace_min() : 0;                                                                              \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_cwt##SFX##_pad_len(const phast_planner_cwt##SFX *p) try {                                      \
+        return p ? p->p : 0;                                                                                            \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_cwt##SFX##_num_scales(const phast_planner_cwt##SFX *p) try {                                   \
+        return p ? p->s : 0;                                                                                            \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_cwt##SFX##_tile_bins(const phast_planner_cwt##SFX *p) try {                                    \
+        return p ? p->geom.tile : 0;                                                                                    \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_cwt##SFX##_scale_group(const phast_planner_cwt##SFX *p) try {                                  \
+        return p ? p->geom.group : 0;                                                                                   \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_cwt##SFX##_time_stages(const phast_planner_cwt##SFX *p, const T *d_x_re, const T *d_x_im,         \
+                                             T *d_out_re, T *d_out_im, size_t batch, T *d_work, size_t work_len,        \
+                                             int reps, float *stage_ms, void *stream) try {                             \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(d_x_re, d_x_im, d_out_re, d_out_im, batch, d_work, work_len, reps, stage_ms,              \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_cwt_##SFX##_with_planner(const T *x_re, const T *x_im, size_t x_len, T *out_re, T *out_im,                \
+                                       size_t out_len, const phast_planner_cwt##SFX *p) try {                           \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(x_re, x_im, x_len, out_re, out_im, out_len);                                                     \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_cwt_##SFX##_dev(const T *d_x_re, const T *d_x_im, T *d_out_re, T *d_out_im, size_t signal_len,            \
+                              size_t batch, size_t sig_dist, size_t out_dist, const phast_planner_cwt##SFX *p,          \
+                              T *d_work, size_t work_len, void *stream) try {                                           \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(d_x_re, d_x_im, d_out_re, d_out_im, signal_len, batch, sig_dist, out_dist, d_work, work_len,      \
+                      static_cast<hipStream_t>(stream));                                                                \
+    } PHAST_CATCH_RC
+PHAST_CWT_API(64, double)
+PHAST_CWT_API(32, float)
 
 // Overlap-save convolution and correlation of real signals (planner_conv.hpp): every argument rule and a wrong length come
 // back before the device is touched

@@ -11,6 +11,7 @@ pub mod psd;
 pub mod resample;
 pub mod channelizer;
 pub mod synthesizer;
+pub mod cwt;
 pub mod lomb;
 pub mod nufft;
 pub mod nufft2d;

@@ -409,6 +409,41 @@ extern "C" {
         out_im: *mut f32, out_len: usize, planner: *const Opaque) -> c_int;
     pub(crate) fn phast_synthesize_f32_dev(in_re: *const f32, in_im: *const f32, out_re: *mut f32, out_im: *mut f32, frames: usize,
         batch: usize, out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // the continuous wavelet transform (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/cwt.rs)
+    pub(crate) fn phast_planner_cwt64_new(signal_len: usize, pad_len: usize, scales: *const f64, num_scales: usize, family: c_int, param: f64,
+        norm: c_int, real_input: c_int, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_cwt64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_cwt64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_cwt64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_cwt64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_cwt64_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_cwt64_pad_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_cwt64_num_scales(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_cwt64_tile_bins(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_cwt64_scale_group(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_cwt64_time_stages(p: *const Opaque, x_re: *const f64, x_im: *const f64, out_re: *mut f64, out_im: *mut f64,
+        batch: usize, work: *mut f64, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_cwt_64_with_planner(x_re: *const f64, x_im: *const f64, x_len: usize, out_re: *mut f64, out_im: *mut f64,
+        out_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_cwt_64_dev(x_re: *const f64, x_im: *const f64, out_re: *mut f64, out_im: *mut f64, signal_len: usize, batch: usize,
+        sig_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_cwt32_new(signal_len: usize, pad_len: usize, scales: *const f64, num_scales: usize, family: c_int, param: f64,
+        norm: c_int, real_input: c_int, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_cwt32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_cwt32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_cwt32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_cwt32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_cwt32_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_cwt32_pad_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_cwt32_num_scales(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_cwt32_tile_bins(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_cwt32_scale_group(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_cwt32_time_stages(p: *const Opaque, x_re: *const f32, x_im: *const f32, out_re: *mut f32, out_im: *mut f32,
+        batch: usize, work: *mut f32, work_len: usize, reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_cwt_32_with_planner(x_re: *const f32, x_im: *const f32, x_len: usize, out_re: *mut f32, out_im: *mut f32,
+        out_len: usize, planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_cwt_32_dev(x_re: *const f32, x_im: *const f32, out_re: *mut f32, out_im: *mut f32, signal_len: usize, batch: usize,
+        sig_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
     // overlap-save convolution and correlation (an extension beyond PhastFT 0.3.0: planner.rs / algorithms/conv.rs)
     pub(crate) fn phast_planner_conv64_new(signal_len: usize, taps: *const f64, num_taps: usize, mode: c_int, flip: c_int,
         block: usize, out: *mut *mut Opaque) -> c_int;

@@ -85,6 +85,9 @@ pub use planner::{PlannerChannelizer32, PlannerChannelizer64};
 // the polyphase synthesis filter bank, the channelizer's inverse (an extension beyond PhastFT 0.3.0)
 pub use algorithms::synthesizer::{synthesize_f32_dev, synthesize_f32_with_planner, synthesize_f64_dev, synthesize_f64_with_planner};
 pub use planner::{PlannerSynthesizer32, PlannerSynthesizer64};
+// the continuous wavelet transform and the analytic signal (an extension beyond PhastFT 0.3.0)
+pub use algorithms::cwt::{cwt_32_dev, cwt_32_with_planner, cwt_64_dev, cwt_64_with_planner};
+pub use planner::{CwtFamily, CwtNorm, PlannerCwt32, PlannerCwt64};
 // overlap-save convolution and correlation of real signals (an extension beyond PhastFT 0.3.0)
 pub use algorithms::conv::{conv_f32_dev, conv_f32_with_planner, conv_f64_dev, conv_f64_with_planner};
 pub use planner::{ConvMode, PlannerConv32, PlannerConv64};

@@ -797,6 +797,88 @@ impl_planner_synthesizer!(PlannerSynthesizer32, f32, phast_planner_synthesizer32
                           phast_planner_synthesizer32_max_terms, phast_planner_synthesizer32_workspace_len,
                           phast_planner_synthesizer32_workspace_min);
 
+/// The wavelet family of a CWT planner (PHAST_CWT_* of the C ABI; Torrence & Compo 1998, table 1); `Step`: the analytic-signal filter
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum CwtFamily {
+    Morlet = 0,
+    Paul = 1,
+    Dog = 2,
+    Step = 3,
+}
+
+/// The normalisation of a CWT planner: `L2` c = sqrt(2 pi s) (unit energy), `Peak` c = 2 / max |psi^|
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum CwtNorm {
+    L2 = 0,
+    Peak = 1,
+}
+
+macro_rules! impl_planner_cwt {
+    ($cw:ident, $t:ty, $new:ident, $free:ident, $pad_len:ident, $scales:ident, $tile:ident, $group:ident, $ws_len:ident, $ws_min:ident) => {
+        /// An extension beyond PhastFT 0.3.0: the continuous wavelet transform of signals of `signal_len` points at the given
+        /// scales (in samples), W[j][n] = ifft_P(fft_P(x) conj(c_j psi^(s_j w)))[n] for n < signal_len with the signal
+        /// zero-extended to `pad_len` points, and with `CwtFamily::Step` and one scale the analytic signal.  One forward
+        /// transform per signal, one bank kernel, one inverse transform per scale; the bits of a row depend on its signal and
+        /// scale alone.  Immutable after `new`.
+        pub struct $cw {
+            pub(crate) h: *mut Opaque,
+            pub(crate) signal_len: usize,
+            real_input: bool,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's buffers (device calls) or in device
+        // buffers of its own (host-slice calls)
+        unsafe impl Send for $cw {}
+        unsafe impl Sync for $cw {}
+        impl $cw {
+            /// `pad_len` = 0 stands for `signal_len`; `param`: w0 of Morlet, the integer m of Paul (<= 85) and DOG (<= 170),
+            /// ignored by Step; `real_input`: one input plane, else (re, im) planes.  Panics with "invalid argument" unless
+            /// 1 <= signal_len <= pad_len <= 2^29, 1 <= scales.len() <= 2^20, every scale is finite and > 0 and `param` is legal
+            pub fn new(signal_len: usize, scales: &[f64], family: CwtFamily, param: f64, norm: CwtNorm, pad_len: usize, real_input: bool) -> Self {
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe {
+                    ffi::$new(signal_len, pad_len, scales.as_ptr(), scales.len(), family as c_int, param, norm as c_int, real_input as c_int, &mut h)
+                });
+                Self { h, signal_len, real_input }
+            }
+            pub fn signal_len(&self) -> usize {
+                self.signal_len
+            }
+            pub fn real_input(&self) -> bool {
+                self.real_input
+            }
+            pub fn pad_len(&self) -> usize {
+                unsafe { ffi::$pad_len(self.h) }
+            }
+            pub fn num_scales(&self) -> usize {
+                unsafe { ffi::$scales(self.h) }
+            }
+            /// the bank's tile: (bins per workgroup, scales per workgroup at most)
+            pub fn tile(&self) -> (usize, usize) {
+                unsafe { (ffi::$tile(self.h), ffi::$group(self.h)) }
+            }
+            /// elements of the workspace a device call of `batch` signals works in
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+            /// the least workspace a call runs in: one signal's spectrum and one row
+            pub fn workspace_min(&self) -> usize {
+                unsafe { ffi::$ws_min(self.h) }
+            }
+        }
+        impl Drop for $cw {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_cwt!(PlannerCwt64, f64, phast_planner_cwt64_new, phast_planner_cwt64_free, phast_planner_cwt64_pad_len,
+                  phast_planner_cwt64_num_scales, phast_planner_cwt64_tile_bins, phast_planner_cwt64_scale_group,
+                  phast_planner_cwt64_workspace_len, phast_planner_cwt64_workspace_min);
+impl_planner_cwt!(PlannerCwt32, f32, phast_planner_cwt32_new, phast_planner_cwt32_free, phast_planner_cwt32_pad_len,
+                  phast_planner_cwt32_num_scales, phast_planner_cwt32_tile_bins, phast_planner_cwt32_scale_group,
+                  phast_planner_cwt32_workspace_len, phast_planner_cwt32_workspace_min);
+
 /// Which part of the full convolution a planner yields (PHAST_CONV_* of the C ABI)
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum ConvMode {
