@@ -34,6 +34,9 @@
 //                                                            polyphase synthesis bank, the channelizer's inverse
 //   (none: no wavelets upstream)                             class PlannerCwt64/32, cwt_64/32_with_planner, enum CwtFamily, CwtNorm --
 //                                                            the continuous wavelet transform and the analytic signal
+//   (none: no wavelets upstream)                             class PlannerDwt64/32, wavedec_f64/f32_with_planner,
+//                                                            waverec_f64/f32_with_planner, enum DwtMode -- the discrete wavelet
+//                                                            transform and its inverse (pywt.wavedec / waverec)
 //   (none: no sample-rate conversion upstream)               class PlannerUpfirdn64/32, upfirdn_f64/f32_with_planner -- the polyphase
 //                                                            FIR of scipy.signal.upfirdn; class PlannerResample64/32,
 //                                                            resample_f64/f32_with_planner -- scipy.signal.resample
@@ -781,6 +784,63 @@ PHASTFT_RESAMPLE(upfirdn, f32, float, PlannerUpfirdn32)
 PHASTFT_RESAMPLE(resample, f64, double, PlannerResample64)
 PHASTFT_RESAMPLE(resample, f32, float, PlannerResample32)
 #undef PHASTFT_RESAMPLE
+
+// ---- discrete wavelet transform and its inverse (no reference counterpart; pywt.dwt / idwt / wavedec / waverec) ----
+// the extension modes of include/phastft_hip.h (PHAST_DWT_*): PyWavelets' definitions
+enum class DwtMode : int { Zero = 0, Constant = 1, Symmetric = 2, Reflect = 3, Periodic = 4, Periodization = 5 };
+#define PHASTFT_PLANNER_DWT(NAME, CT, SFX, T)                                                                    \
+    class NAME {                                                                                                 \
+      public:                                                                                                    \
+        /* pywt.wavedec / waverec of real signals of signal_len samples with `level` levels (1 .. 32): the four filters of one\
+           even length 2 .. 256, used as given.  A signal's result is the packed row [cA_J | cD_J | .. | cD_1] */\
+        NAME(std::size_t signal_len, Slice<const T> dec_lo, Slice<const T> dec_hi, Slice<const T> rec_lo,        \
+             Slice<const T> rec_hi, std::size_t level = 1, DwtMode mode = DwtMode::Symmetric) {                  \
+            if (dec_hi.len != dec_lo.len || rec_lo.len != dec_lo.len || rec_hi.len != dec_lo.len) check(PHAST_ERR_INVALID_ARG);\
+            check(phast_planner_dwt##SFX##_new(signal_len, dec_lo.ptr, dec_hi.ptr, rec_lo.ptr, rec_hi.ptr, dec_lo.len, level,\
+                                               static_cast<int>(mode), &h_));                                    \
+        }                                                                                                        \
+        NAME(const NAME &) = delete;                                                                             \
+        NAME &operator=(const NAME &) = delete;                                                                  \
+        NAME(NAME &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }                                                   \
+        ~NAME() {                                                                                                \
+            if (h_) phast_planner_dwt##SFX##_free(h_);                                                           \
+        }                                                                                                        \
+        const CT *get() const { return h_; }                                                                     \
+        std::string describe() const {                                                                           \
+            std::string s(4096, '\0');                                                                           \
+            check(phast_planner_dwt##SFX##_describe(h_, &s[0], s.size()));                                       \
+            s.resize(s.find('\0'));                                                                              \
+            return s;                                                                                            \
+        }                                                                                                        \
+        std::size_t device_bytes() const { return phast_planner_dwt##SFX##_device_bytes(h_); }                   \
+        /* elements of a packed row; n_l for 0 <= l <= J; where cD_l starts in the row for 1 <= l <= J (cA_J starts at 0) */\
+        std::size_t coeff_len() const { return phast_planner_dwt##SFX##_coeff_len(h_); }                         \
+        std::size_t level_len(std::size_t l) const { return phast_planner_dwt##SFX##_level_len(h_, l); }         \
+        std::size_t level_offset(std::size_t l) const { return phast_planner_dwt##SFX##_level_offset(h_, l); }   \
+        /* coefficient indices / output pairs per workgroup */                                                   \
+        std::size_t tile() const { return phast_planner_dwt##SFX##_tile(h_); }                                   \
+        /* elements of T a _dev call of `batch` signals works in (0 for one level); workspace_min: the least a call runs in */\
+        std::size_t workspace_len(std::size_t batch = 1) const { return phast_planner_dwt##SFX##_workspace_len(h_, batch); }\
+        std::size_t workspace_min() const { return phast_planner_dwt##SFX##_workspace_min(h_); }                 \
+                                                                                                                 \
+      private:                                                                                                   \
+        CT *h_ = nullptr;                                                                                        \
+    };
+PHASTFT_PLANNER_DWT(PlannerDwt64, phast_planner_dwt64, 64, double)
+PHASTFT_PLANNER_DWT(PlannerDwt32, phast_planner_dwt32, 32, float)
+#undef PHASTFT_PLANNER_DWT
+
+// one host signal of L samples -> its packed row of coeff_len() coefficients, and back; blocking
+#define PHASTFT_DWT(FS, T, P)                                                                                    \
+    inline void wavedec_##FS##_with_planner(Slice<const T> signal, Slice<T> coeffs, const P &planner) {          \
+        check(phast_wavedec_##FS##_with_planner(signal.ptr, signal.len, coeffs.ptr, coeffs.len, planner.get())); \
+    }                                                                                                            \
+    inline void waverec_##FS##_with_planner(Slice<const T> coeffs, Slice<T> signal, const P &planner) {          \
+        check(phast_waverec_##FS##_with_planner(coeffs.ptr, coeffs.len, signal.ptr, signal.len, planner.get())); \
+    }
+PHASTFT_DWT(f64, double, PlannerDwt64)
+PHASTFT_DWT(f32, float, PlannerDwt32)
+#undef PHASTFT_DWT
 
 // ---- polyphase filter-bank channelizer (no reference counterpart; cuSignal's channelize_poly) ----
 #define PHASTFT_PLANNER_CHANNELIZER(NAME, CT, SFX, T)                                                            \

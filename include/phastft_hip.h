@@ -1074,6 +1074,104 @@ int phast_cwt_32_dev(const float *d_x_re, const float *d_x_im, float *d_out_re, 
 int phast_planner_cwt32_time_stages(const phast_planner_cwt32 *p, const float *d_x_re, const float *d_x_im, float *d_out_re, float *d_out_im, size_t batch, float *d_work, size_t work_len,
                                      int reps, float *stage_ms, void *stream);
 
+/* ---- discrete wavelet transform and its inverse (no reference counterpart; pywt.dwt / idwt / wavedec / waverec; DESIGN.md
+ * §31).  PyWavelets' definitions; the formulas here are the authority.  Real signals of L samples, 1 <= L <= 2^29, batches.
+ * Filter bank: four real filters of one even length F, 2 <= F <= 256 -- dec_lo, dec_hi, rec_lo, rec_hi --, host values of T used
+ * as given (pad an odd-length biorthogonal filter with a zero).  Extension ext(x, t) of a signal of n samples, any integer t:
+ *     PHAST_DWT_ZERO            0 outside [0, n)
+ *     PHAST_DWT_CONSTANT        x[clamp(t, 0, n - 1)]
+ *     PHAST_DWT_SYMMETRIC       u = t mod 2n;        x[u] if u < n, else x[2n - 1 - u]
+ *     PHAST_DWT_REFLECT         u = t mod (2n - 2);  x[u] if u < n, else x[2n - 2 - u];  n = 1: x[0]
+ *     PHAST_DWT_PERIODIC        x[t mod n]
+ *     PHAST_DWT_PERIODIZATION   below
+ * (the modulus makes F > n legal: the extension wraps more than once).  One analysis level on n samples:
+ *     the five extension modes: m = (n + F - 1) div 2,  cA[i] = sum_{j=0}^{F-1} dec_lo[j] ext(x, 2i + 1 - j),  0 <= i < m
+ *     periodization:            n' = n + (n mod 2), x[n] := x[n - 1] for odd n, m = n' / 2,
+ *                               cA[i] = sum_j dec_lo[j] x[(2i + F/2 - j) mod n']
+ * and cD the same with dec_hi.  One synthesis level from m coefficients of each band:
+ *     extension modes:          N = 2m - F + 2,  y[r] = sum_k rec_lo[r + F - 2 - 2k] cA[k] + rec_hi[r + F - 2 - 2k] cD[k] over the k
+ *                               whose tap index lies in [0, F)
+ *     periodization:            N = 2m,  the tap indices are all t in [0, F) with t = (r + F/2 - 1 - 2k) mod N (more than one
+ *                               t per k when F > N)
+ * Multi-level, `level` = J, 1 <= J <= 32 (J above floor(log2(L / (F - 1))), pywt.dwt_max_level, is legal): n_0 = L, n_l the m
+ * of n_{l-1}.  The packed result of one signal is [cA_J | cD_J | cD_{J-1} | ... | cD_1], _coeff_len = n_J + sum_l n_l elements:
+ * pywt.wavedec's list, concatenated; _level_len(p, l) = n_l for 0 <= l <= J, _level_offset(p, l) = where cD_l starts for
+ * 1 <= l <= J (cA_J starts at 0).  waverec undoes the levels from J down and keeps, at each, the first n_{l-1} of the N
+ * reconstructed samples (N is n_{l-1} or n_{l-1} + 1; PyWavelets drops the extra sample, too).
+ * Method: one launch per level.  A 256-thread workgroup owns _tile consecutive coefficient indices (analysis) or output pairs
+ * (synthesis) of one signal, stages the run of the input it meets through the extension map into LDS (split by parity, so
+ * that lanes read consecutive elements; no padded signal exists in memory and a batch neighbour is never read) and feeds every
+ * staged value to both bands.  One order per sum, in T: analysis acc = fma(dec[j], ext(x, 2i + 1 - j), acc), j ascending from
+ * 0, one chain per band; synthesis tap index descending (k ascending), per tap acc = fma(rec_lo[t], cA[k], acc), then
+ * acc = fma(rec_hi[t], cD[k], acc).  The bits depend on the filters, the mode and the values alone: not on the batch, the
+ * distances, pointer alignment (element alignment is all that is needed), the workspace's chunks, the stream or a graph replay.
+ * Workspace: two ping-pong rows per signal for the approximations between the levels, n_1 + n_2 elements (the longest of the
+ * later levels where a signal shorter than the filter grows); _workspace_len(p, batch) holds the batch in one chunk, any
+ * work_len >= _workspace_min(p) (one signal's) runs chunks of whole signals.  For J = 1 both are 0 and d_work is not read.
+ * _new refuses with PHAST_ERR_INVALID_ARG, before the device is touched: a NULL filter; L < 1 or L > 2^29; F odd, < 2 or > 256;
+ * level < 1 or > 32; an unknown mode (PyWavelets' smooth, antisymmetric and antireflect are out of scope).  _dev: asynchronous
+ * on `stream`; signal b at d_signal + b sig_dist, its packed row at d_coeffs + b coeff_dist; sig_dist >= L and coeff_dist >=
+ * _coeff_len (batch 1 ignores both); the input is never written; signal and coefficients must not overlap (identical pointers
+ * are refused).  A null pointer, a short dist, a null or short workspace where one is needed: PHAST_ERR_INVALID_ARG; a
+ * signal_len that is not the planner's: PHAST_ERR_PLANNER_SIZE; a coeff_len of the host-slice form that is not _coeff_len:
+ * PHAST_ERR_LEN_MISMATCH -- all before any launch.  The *_with_planner forms take host slices of one signal and block.
+ * Out of scope, refused rather than approximated: complex signals, a missing band in the inverse, the stationary transform,
+ * wavelet packets, 2-D transforms, an axis argument. */
+typedef enum {
+    PHAST_DWT_ZERO = 0,
+    PHAST_DWT_CONSTANT = 1,
+    PHAST_DWT_SYMMETRIC = 2,
+    PHAST_DWT_REFLECT = 3,
+    PHAST_DWT_PERIODIC = 4,
+    PHAST_DWT_PERIODIZATION = 5
+} phast_dwt_mode;
+typedef struct phast_planner_dwt64 phast_planner_dwt64; /* PlannerDwt64 */
+int phast_planner_dwt64_new(size_t signal_len, const double *dec_lo, const double *dec_hi, const double *rec_lo, const double *rec_hi, size_t filter_len, size_t level, int mode,
+                             phast_planner_dwt64 **out);
+void phast_planner_dwt64_free(phast_planner_dwt64 *p);
+int phast_planner_dwt64_describe(const phast_planner_dwt64 *p, char *buf, size_t buf_len);
+size_t phast_planner_dwt64_device_bytes(const phast_planner_dwt64 *p);
+size_t phast_planner_dwt64_workspace_len(const phast_planner_dwt64 *p, size_t batch);
+size_t phast_planner_dwt64_workspace_min(const phast_planner_dwt64 *p);
+size_t phast_planner_dwt64_coeff_len(const phast_planner_dwt64 *p);                  /* elements of a packed row */
+size_t phast_planner_dwt64_level_len(const phast_planner_dwt64 *p, size_t level);    /* n_level, 0 <= level <= J */
+size_t phast_planner_dwt64_level_offset(const phast_planner_dwt64 *p, size_t level); /* where cD_level starts in the packed row, 1 <= level <= J */
+size_t phast_planner_dwt64_tile(const phast_planner_dwt64 *p);                       /* coefficient indices / output pairs per workgroup */
+int phast_wavedec_f64_with_planner(const double *signal, size_t signal_len, double *coeffs, size_t coeff_len, const phast_planner_dwt64 *planner);
+int phast_waverec_f64_with_planner(const double *coeffs, size_t coeff_len, double *signal, size_t signal_len, const phast_planner_dwt64 *planner);
+int phast_wavedec_f64_dev(const double *d_signal, double *d_coeffs, size_t signal_len, size_t batch, size_t sig_dist, size_t coeff_dist,
+                         const phast_planner_dwt64 *planner, double *d_work, size_t work_len, void *stream);
+int phast_waverec_f64_dev(const double *d_coeffs, double *d_signal, size_t signal_len, size_t batch, size_t coeff_dist, size_t sig_dist,
+                         const phast_planner_dwt64 *planner, double *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/dwt_rate.py): stage_ms[2] = average milliseconds of wavedec of the signals into the packed rows and of
+ * waverec of the packed rows back into the signals (which it overwrites with their reconstruction) over `reps` calls of `batch`
+ * signals at distances L and _coeff_len in ONE chunk (work_len >= _workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_dwt64_time_stages(const phast_planner_dwt64 *p, double *d_signal, double *d_coeffs, size_t batch, double *d_work, size_t work_len, int reps, float *stage_ms,
+                                     void *stream);
+typedef struct phast_planner_dwt32 phast_planner_dwt32; /* PlannerDwt32 */
+int phast_planner_dwt32_new(size_t signal_len, const float *dec_lo, const float *dec_hi, const float *rec_lo, const float *rec_hi, size_t filter_len, size_t level, int mode,
+                             phast_planner_dwt32 **out);
+void phast_planner_dwt32_free(phast_planner_dwt32 *p);
+int phast_planner_dwt32_describe(const phast_planner_dwt32 *p, char *buf, size_t buf_len);
+size_t phast_planner_dwt32_device_bytes(const phast_planner_dwt32 *p);
+size_t phast_planner_dwt32_workspace_len(const phast_planner_dwt32 *p, size_t batch);
+size_t phast_planner_dwt32_workspace_min(const phast_planner_dwt32 *p);
+size_t phast_planner_dwt32_coeff_len(const phast_planner_dwt32 *p);                  /* elements of a packed row */
+size_t phast_planner_dwt32_level_len(const phast_planner_dwt32 *p, size_t level);    /* n_level, 0 <= level <= J */
+size_t phast_planner_dwt32_level_offset(const phast_planner_dwt32 *p, size_t level); /* where cD_level starts in the packed row, 1 <= level <= J */
+size_t phast_planner_dwt32_tile(const phast_planner_dwt32 *p);                       /* coefficient indices / output pairs per workgroup */
+int phast_wavedec_f32_with_planner(const float *signal, size_t signal_len, float *coeffs, size_t coeff_len, const phast_planner_dwt32 *planner);
+int phast_waverec_f32_with_planner(const float *coeffs, size_t coeff_len, float *signal, size_t signal_len, const phast_planner_dwt32 *planner);
+int phast_wavedec_f32_dev(const float *d_signal, float *d_coeffs, size_t signal_len, size_t batch, size_t sig_dist, size_t coeff_dist,
+                         const phast_planner_dwt32 *planner, float *d_work, size_t work_len, void *stream);
+int phast_waverec_f32_dev(const float *d_coeffs, float *d_signal, size_t signal_len, size_t batch, size_t coeff_dist, size_t sig_dist,
+                         const phast_planner_dwt32 *planner, float *d_work, size_t work_len, void *stream);
+/* measurement hook (tools/dwt_rate.py): stage_ms[2] = average milliseconds of wavedec of the signals into the packed rows and of
+ * waverec of the packed rows back into the signals (which it overwrites with their reconstruction) over `reps` calls of `batch`
+ * signals at distances L and _coeff_len in ONE chunk (work_len >= _workspace_len(p, batch)).  Blocks until done. */
+int phast_planner_dwt32_time_stages(const phast_planner_dwt32 *p, float *d_signal, float *d_coeffs, size_t batch, float *d_work, size_t work_len, int reps, float *stage_ms,
+                                     void *stream);
+
 /* ---- overlap-save FIR convolution and correlation of real signals (no reference counterpart; scipy.signal.convolve /
  * correlate(x, h, mode, method="direct")).  Signal x of L samples, K taps h, both real:
  *     full[t] = sum_j g[j] x[t - j], t in [0, L + K - 1); g = h (flip = 0: convolution) or g[j] = h[K - 1 - j] (flip = 1:

@@ -42,6 +42,9 @@ the reference tree) over the C ABI of ``include/phastft_hip.h``:
                                                     synthesize_64/32_with_planner, synthesize_poly
     (none: no wavelets)                             PlannerCwt64/32, cwt_batched, cwt_64/32_with_planner, cwt, hilbert,
                                                     cwt_scales, cwt_fourier_period
+    (none: no wavelets)                             PlannerDwt64/32, wavedec_batched, waverec_batched,
+                                                    wavedec_64/32_with_planner, waverec_64/32_with_planner, dwt, idwt,
+                                                    wavedec, waverec, wavelet_filters, dwt_max_level, dwt_coeff_lens
     (none: no convolution)                          PlannerConv64/32, conv_batched, conv_f64/f32_with_planner,
                                                     fftconvolve, correlate
     (none: no convolution)                          PlannerConvNd64/32, convnd_batched, convnd_f64/f32_with_planner,
@@ -119,6 +122,9 @@ __all__ = [
     "synthesize_32_with_planner", "synthesize_poly",
     "PlannerCwt64", "PlannerCwt32", "cwt_batched", "cwt_64_with_planner", "cwt_32_with_planner", "cwt", "hilbert",
     "cwt_scales", "cwt_fourier_period",
+    "PlannerDwt64", "PlannerDwt32", "wavedec_batched", "waverec_batched", "wavedec_64_with_planner", "wavedec_32_with_planner",
+    "waverec_64_with_planner", "waverec_32_with_planner", "dwt", "idwt", "wavedec", "waverec", "wavelet_filters",
+    "dwt_max_level", "dwt_coeff_lens",
     "PlannerConv64", "PlannerConv32", "conv_batched", "conv_f64_with_planner", "conv_f32_with_planner", "fftconvolve",
     "correlate",
     "PlannerConvNd64", "PlannerConvNd32", "convnd_batched", "convnd_f64_with_planner", "convnd_f32_with_planner",
@@ -2659,6 +2665,284 @@ def cwt_fourier_period(wavelet: str = "morlet", param=None) -> float:
     if family == 2:
         return 2 * math.pi / math.sqrt(par + 0.5)
     raise ValueError("the step filter has no scale")
+
+
+# ---------------------------------------------------------------------------------------------
+# discrete wavelet transform and its inverse (no reference counterpart; pywt.dwt / idwt / wavedec / waverec)
+# ---------------------------------------------------------------------------------------------
+_DWT_MODES = {"zero": 0, "constant": 1, "symmetric": 2, "reflect": 3, "periodic": 4, "periodization": 5}
+_DWT_REFUSED = ("smooth", "antisymmetric", "antireflect")
+
+
+def _dwt_mode(mode) -> int:
+    if isinstance(mode, str):
+        if mode in _DWT_REFUSED:
+            raise ValueError(f"mode {mode!r} is out of scope: one of {sorted(_DWT_MODES)}")
+        if mode in _DWT_MODES:
+            return _DWT_MODES[mode]
+    raise ValueError(f"mode: one of {sorted(_DWT_MODES)}, not {mode!r}")
+
+
+@functools.lru_cache(maxsize=None)
+def _daubechies(n: int):
+    """rec_lo of dbN, 2N taps, by spectral factorisation: with y = (2 - z - 1/z) / 4 the half-band product filter is
+    ((1 + z)(1 + 1/z) / 4)^N P(y), P(y) = sum_{k<N} C(N - 1 + k, k) y^k; each root of P gives a pair (z, 1/z) of which the one
+    inside the unit circle is kept (minimum phase); h = (1 + z)^N prod (z - z_k), scaled to sum sqrt(2)"""
+    roots = np.roots([math.comb(n - 1 + k, k) for k in range(n - 1, -1, -1)]) if n > 1 else np.zeros(0)
+    zs = []
+    for y in roots:
+        b = 1 - 2 * y
+        d = np.sqrt(b * b - 1 + 0j)
+        z = b + d
+        zs.append(z if abs(z) < 1 else b - d)
+    h = np.real(np.poly(zs)) if zs else np.ones(1)
+    for _ in range(n):
+        h = np.convolve(h, [1.0, 1.0])
+    return h * (math.sqrt(2.0) / h.sum())
+
+
+def wavelet_filters(name: str):
+    """``(dec_lo, dec_hi, rec_lo, rec_hi)`` of a built-in orthogonal wavelet as float64 arrays, in PyWavelets' order and sign:
+    ``"haar"`` and ``"db1"`` .. ``"db10"``, computed by spectral factorisation (no tables).  ``rec_lo = h``, ``dec_lo`` is
+    ``rec_lo`` reversed, ``rec_hi[k] = (-1)**k rec_lo[F - 1 - k]``, ``dec_hi`` is ``rec_hi`` reversed."""
+    order = 1 if name == "haar" else int(name[2:]) if isinstance(name, str) and name[:2] == "db" and name[2:].isdigit() else 0
+    if not 1 <= order <= 10:
+        raise ValueError(f"wavelet {name!r}: 'haar' or 'db1' .. 'db10' (pass the four filters for any other bank)")
+    rec_lo = _daubechies(order).copy()
+    rec_hi = rec_lo[::-1] * (-1.0) ** np.arange(rec_lo.size)
+    return rec_lo[::-1].copy(), rec_hi[::-1].copy(), rec_lo, rec_hi
+
+
+def _dwt_bank(wavelet):
+    """the four filters of a name or a 4-tuple of tap arrays, as float64 arrays of one even length"""
+    if isinstance(wavelet, str):
+        return wavelet_filters(wavelet)
+    bank = tuple(wavelet)
+    if len(bank) != 4:
+        raise ValueError("wavelet: a name or the 4-tuple (dec_lo, dec_hi, rec_lo, rec_hi)")
+    bank = tuple(np.asarray(f.detach().cpu().numpy() if _is_torch(f) else f, dtype=np.float64).reshape(-1) for f in bank)
+    f = bank[0].size
+    if any(b.size != f for b in bank) or f < 2 or f > 256 or f % 2:
+        raise ValueError("wavelet: four filters of one even length 2 .. 256 (pad an odd-length filter with a zero)")
+    return bank
+
+
+def _dwt_filter_len(wavelet) -> int:
+    return int(wavelet) if isinstance(wavelet, (int, np.integer)) else _dwt_bank(wavelet)[0].size
+
+
+def dwt_max_level(signal_len: int, wavelet) -> int:
+    """``pywt.dwt_max_level``: ``floor(log2(L / (F - 1)))``, 0 for ``L < F - 1``; ``wavelet``: a name, a filter bank or F"""
+    f = _dwt_filter_len(wavelet)
+    if signal_len < 1 or f < 2:
+        raise ValueError("need L >= 1 and F >= 2")
+    j = 0
+    while (signal_len >> (j + 1)) >= f - 1:
+        j += 1
+    return j
+
+
+def dwt_coeff_lens(signal_len: int, wavelet, level: int = 1, mode="symmetric"):
+    """The lengths of ``pywt.wavedec``'s list ``[cA_J, cD_J, .., cD_1]`` for a signal of ``signal_len`` samples"""
+    f, m = _dwt_filter_len(wavelet), _dwt_mode(mode)
+    if signal_len < 1 or f < 2 or f % 2 or not 1 <= level <= 32:
+        raise ValueError("need L >= 1, an even F >= 2 and 1 <= level <= 32")
+    lens, n = [], signal_len
+    for _ in range(level):
+        n = (n + (n & 1)) // 2 if m == 5 else (n + f - 1) // 2
+        lens.append(n)
+    return [lens[-1]] + lens[::-1]
+
+
+class PlannerDwt64(_AnyHandle):
+    """f64 discrete wavelet transform of real signals of ``signal_len`` samples and its inverse: ``pywt.wavedec`` /
+    ``pywt.waverec`` with ``level`` levels (1 .. 32; more than ``dwt_max_level`` is legal) in one of the modes ``zero``,
+    ``constant``, ``symmetric``, ``reflect``, ``periodic``, ``periodization``.  ``filters``: a built-in name
+    (:func:`wavelet_filters`) or the 4-tuple ``(dec_lo, dec_hi, rec_lo, rec_hi)`` of one even length 2 .. 256.  A signal's
+    result is the packed row ``[cA_J | cD_J | .. | cD_1]`` of ``coeff_len`` elements.  One direct kernel launch per level."""
+
+    _prefix = "dwt"
+
+    def __init__(self, signal_len: int, filters, level: int = 1, mode="symmetric"):
+        bank = [np.ascontiguousarray(f, dtype=self._dtype) for f in _dwt_bank(filters)]
+        self.mode = mode
+        self._new(signal_len, *(f.ctypes.data_as(C.c_void_p) for f in bank), bank[0].size, level, _dwt_mode(mode))
+        self.n = self.signal_len = signal_len
+        self.filter_len, self.level = bank[0].size, level
+        self.coeff_len = int(self._fn("coeff_len")(self._h))
+        self.tile = int(self._fn("tile")(self._h))
+        self.level_lens = [int(self._fn("level_len")(self._h, l)) for l in range(level + 1)]          # n_0 .. n_J
+        self.level_offsets = [0] + [int(self._fn("level_offset")(self._h, l)) for l in range(1, level + 1)]  # [0]: cA_J
+
+    def bands(self):
+        """``[(offset, length)]`` of ``cA_J, cD_J, .., cD_1`` in a packed row"""
+        return [(0, self.level_lens[-1])] + [(self.level_offsets[l], self.level_lens[l]) for l in range(self.level, 0, -1)]
+
+    def workspace_len(self, batch: int = 1) -> int:
+        """Elements of T a device call of ``batch`` signals works in (0 for one level).  A smaller workspace of at least
+        ``workspace_min()`` runs the batch in chunks of whole signals, to the same bits."""
+        return self._workspace_len(batch)
+
+    def workspace_min(self) -> int:
+        return int(self._fn("workspace_min")(self._h))
+
+    def time_stages(self, signal, coeffs, batch: int = 1, workspace=None, reps: int = 10):
+        """Average HIP-event milliseconds of (wavedec, waverec) of ``batch`` signals at distances L and coeff_len on device
+        tensors; the second overwrites ``signal`` with its reconstruction (measurement hook)"""
+        x, y = _Slice(signal, self._dtype, "signal"), _Slice(coeffs, self._dtype, "coeffs")
+        ws = _any_workspace(self, batch, workspace)
+        ms = (C.c_float * 2)()
+        _check(self._fn("time_stages")(self._h, x.ptr, y.ptr, batch, ws.ptr, ws.len, reps, ms, _stream()))
+        return [float(v) for v in ms]
+
+
+class PlannerDwt32(PlannerDwt64):
+    """f32 twin of :class:`PlannerDwt64`: taps, products and sums in f32"""
+
+    _sfx = "32"
+    _dtype = np.float32
+
+
+def _dwt_batched(name, x, planner, out, work, stream, per_in, per_out):
+    """rows of ``per_in`` elements through ``phast_{name}_f*_dev`` into rows of ``per_out``"""
+    import torch
+
+    want = torch.float64 if planner._dtype == np.float64 else torch.float32
+    fs = "f64" if planner._dtype == np.float64 else "f32"
+
+    def plane(v, what, per):
+        if not _is_torch(v) or v.device.type != "cuda" or v.dtype != want:
+            raise TypeError(f"{what}: need a {want} device tensor")
+        if v.dim() not in (1, 2) or v.shape[-1] != per or (per > 1 and v.stride(-1) != 1):
+            raise ValueError(f"{what}: need shape (batch, {per}) or ({per},) with a contiguous last axis, not {tuple(v.shape)}")
+        rows = v.shape[0] if v.dim() == 2 else 1
+        dist = v.stride(0) if v.dim() == 2 and rows > 1 else per
+        if dist < per:
+            raise ValueError(f"{what}: rows overlap")
+        return rows, dist
+
+    batch, in_dist = plane(x, "input", per_in)
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        if out is None:
+            out = torch.empty((batch, per_out) if x.dim() == 2 else (per_out,), dtype=want, device=x.device)
+        rows, out_dist = plane(out, "out", per_out)
+        if rows != batch or out.dim() != x.dim():
+            raise ValueError("out: need one row per signal")
+        if work is None and planner.workspace_len(batch) == 0:
+            ptr, length = None, 0
+        else:
+            ws = _any_workspace(planner, batch, work)
+            ptr, length = ws.ptr, ws.len
+        _check(_call(f"phast_{name}_{fs}_dev", x.data_ptr(), out.data_ptr(), planner.signal_len, batch, in_dist, out_dist,
+                     planner._h, ptr, length, _stream()))
+    return out
+
+
+def wavedec_batched(x, planner, out=None, work=None, stream=None):
+    """Device-resident batch through one wavelet planner: ``x`` is a torch device tensor of shape ``(batch, L)`` or ``(L,)`` of
+    the planner's type whose last axis is contiguous (rows any distance >= L apart); returns the packed rows, shape
+    ``(batch, coeff_len)`` or ``(coeff_len,)``.  ``out``: such a tensor to write into; ``work``: a device tensor of at least
+    ``planner.workspace_min()`` elements, by default one of ``planner.workspace_len(batch)`` from torch's allocator (none is
+    needed for one level); ``stream``: a ``torch.cuda.Stream``, by default the current one.  ``x`` is not written."""
+    return _dwt_batched("wavedec", x, planner, out, work, stream, planner.signal_len, planner.coeff_len)
+
+
+def waverec_batched(coeffs, planner, out=None, work=None, stream=None):
+    """The inverse of :func:`wavedec_batched`: packed rows ``(batch, coeff_len)`` or ``(coeff_len,)`` into signals
+    ``(batch, L)`` or ``(L,)``.  ``coeffs`` is not written."""
+    return _dwt_batched("waverec", coeffs, planner, out, work, stream, planner.coeff_len, planner.signal_len)
+
+
+def _dwt_host(name, fs, dtype, a, b, planner):
+    x, y = _Slice(a, dtype, "input"), _Slice(b, dtype, "out")
+    if _same_place(x, y):
+        raise TypeError(f"{name}_{fs[1:]}_with_planner takes host arrays ({name}_batched takes device tensors)")
+    _check(_call(f"phast_{name}_{fs}_with_planner", x.ptr, x.len, y.ptr, y.len, planner._h))
+
+
+def wavedec_64_with_planner(signal, coeffs, planner: PlannerDwt64) -> None:
+    """f64 transform of one host signal of L samples into a host array of ``planner.coeff_len`` (blocking)"""
+    _dwt_host("wavedec", "f64", np.float64, signal, coeffs, planner)
+
+
+def wavedec_32_with_planner(signal, coeffs, planner: PlannerDwt32) -> None:
+    """f32 twin of :func:`wavedec_64_with_planner`"""
+    _dwt_host("wavedec", "f32", np.float32, signal, coeffs, planner)
+
+
+def waverec_64_with_planner(coeffs, signal, planner: PlannerDwt64) -> None:
+    """f64 inverse of one host packed row of ``planner.coeff_len`` into a host array of L samples (blocking)"""
+    _dwt_host("waverec", "f64", np.float64, coeffs, signal, planner)
+
+
+def waverec_32_with_planner(coeffs, signal, planner: PlannerDwt32) -> None:
+    """f32 twin of :func:`waverec_64_with_planner`"""
+    _dwt_host("waverec", "f32", np.float32, coeffs, signal, planner)
+
+
+def _dwt_planner(f64, signal_len, wavelet, level, mode):
+    return (PlannerDwt64 if f64 else PlannerDwt32)(signal_len, wavelet, level, mode)
+
+
+def _dwt_apply(x, rows, planner, batched, per_out):
+    import torch
+
+    out = torch.empty((rows.shape[0], per_out), dtype=x.dtype, device=x.device)
+    if rows.shape[0]:
+        batched(rows, planner, out)
+        torch.cuda.current_stream().synchronize()  # the temporary planner's table dies with it
+    return out.reshape(x.shape[:-1] + (per_out,))
+
+
+def wavedec(x, wavelet, mode="symmetric", level: int | None = None):
+    """``pywt.wavedec(x, wavelet, mode, level)`` over the last axis of a real device tensor: the list of views
+    ``[cA_J, cD_J, .., cD_1]`` into one new packed tensor.  ``level=None``: ``dwt_max_level`` (at least 1)."""
+    rows, f64 = _rate_rows(x)
+    if level is None:
+        level = max(1, dwt_max_level(x.shape[-1], wavelet))
+    planner = _dwt_planner(f64, x.shape[-1], wavelet, level, mode)
+    packed = _dwt_apply(x, rows, planner, wavedec_batched, planner.coeff_len)
+    return [packed[..., o:o + n] for o, n in planner.bands()]
+
+
+def waverec(coeffs, wavelet, mode="symmetric"):
+    """``pywt.waverec(coeffs, wavelet, mode)`` over the last axis of the real device tensors ``[cA_J, cD_J, .., cD_1]``: a new
+    tensor.  As in PyWavelets the lengths of the list fix the signal's length up to one sample, and the longer one is
+    returned; lengths that no signal gives are a :class:`ValueError`."""
+    import torch
+
+    coeffs = list(coeffs)
+    if len(coeffs) < 2 or any(c is None for c in coeffs):
+        raise ValueError("coeffs: [cA_J, cD_J, .., cD_1] without missing bands")
+    lens = [c.shape[-1] for c in coeffs]
+    f, m = _dwt_filter_len(wavelet), _dwt_mode(mode)
+    top = 2 * lens[-1] if m == 5 else 2 * lens[-1] - f + 2
+    level = len(coeffs) - 1
+    for signal_len in (top, top - 1):
+        if signal_len >= 1 and dwt_coeff_lens(signal_len, f, level, mode) == lens:
+            break
+    else:
+        raise ValueError(f"coeffs: no signal has bands of the lengths {lens} with F = {f} in mode {mode!r}")
+    packed = torch.cat(coeffs, dim=-1)
+    rows, f64 = _rate_rows(packed)
+    planner = _dwt_planner(f64, signal_len, wavelet, level, mode)
+    return _dwt_apply(packed, rows, planner, waverec_batched, signal_len)
+
+
+def dwt(x, wavelet, mode="symmetric"):
+    """``pywt.dwt(x, wavelet, mode)`` over the last axis of a real device tensor: ``(cA, cD)``"""
+    cA, cD = wavedec(x, wavelet, mode, 1)
+    return cA, cD
+
+
+def idwt(cA, cD, wavelet, mode="symmetric"):
+    """``pywt.idwt(cA, cD, wavelet, mode)`` over the last axis of two real device tensors of one shape (a ``None`` band is
+    out of scope): ``2 m - F + 2`` samples, ``2 m`` in periodization"""
+    if cA is None or cD is None:
+        raise ValueError("idwt: a None band is out of scope")
+    if cA.shape != cD.shape:
+        raise ValueError("idwt: cA and cD must have one shape")
+    return waverec([cA, cD], wavelet, mode)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -23,6 +23,7 @@
 #include "planner_channelizer.hpp"
 #include "planner_synthesizer.hpp"
 #include "planner_cwt.hpp"
+#include "planner_dwt.hpp"
 #include "planner_resample.hpp"
 #include "planner_stft.hpp"
 #include "planner_conv.hpp"
@@ -58,6 +59,8 @@ struct phast_planner_lomb64 : LombPlanner<double> {};
 struct phast_planner_lomb32 : LombPlanner<float> {};
 struct phast_planner_upfirdn64 : UpfirdnPlanner<double> {};
 struct phast_planner_upfirdn32 : UpfirdnPlanner<float> {};
+struct phast_planner_dwt64 : DwtPlanner<double> {};
+struct phast_planner_dwt32 : DwtPlanner<float> {};
 struct phast_planner_resample64 : ResamplePlanner<double> {};
 struct phast_planner_resample32 : ResamplePlanner<float> {};
 struct phast_planner_channelizer64 : ChannelizerPlanner<double> {};
@@ -582,6 +585,7 @@ PHAST_HANDLE_API(convnd64) PHAST_HANDLE_API(convnd32) PHAST_HANDLE_API(mdct64) P
 PHAST_HANDLE_API(lomb64) PHAST_HANDLE_API(lomb32) PHAST_HANDLE_API(upfirdn64) PHAST_HANDLE_API(upfirdn32)
 PHAST_HANDLE_API(resample64) PHAST_HANDLE_API(resample32) PHAST_HANDLE_API(channelizer64) PHAST_HANDLE_API(channelizer32)
 PHAST_HANDLE_API(synthesizer64) PHAST_HANDLE_API(synthesizer32) PHAST_HANDLE_API(cwt64) PHAST_HANDLE_API(cwt32)
+PHAST_HANDLE_API(dwt64) PHAST_HANDLE_API(dwt32)
 
 // Arbitrary lengths (Bluestein, planner_any.hpp): arguments are checked before the device is touched
 #define PHAST_ANY_API(SFX, T)                                                                                           \
@@ -1000,6 +1004,62 @@ PHAST_LOMB_API(32, f32, float)
     } PHAST_CATCH_RC
 PHAST_RESAMPLE_API(64, f64, double)
 PHAST_RESAMPLE_API(32, f32, float)
+
+// The discrete wavelet transform (planner_dwt.hpp): every argument rule, a wrong length, a short distance or workspace come
+// back before the device is touched
+#define PHAST_DWT_API(SFX, FS, T)                                                                                       \
+    int phast_planner_dwt##SFX##_new(size_t signal_len, const T *dec_lo, const T *dec_hi, const T *rec_lo,              \
+                                     const T *rec_hi, size_t filter_len, size_t level, int mode,                        \
+                                     phast_planner_dwt##SFX **out) try {                                                \
+        return dwt_planner_new<T>(signal_len, dec_lo, dec_hi, rec_lo, rec_hi, filter_len, level, mode, out);            \
+    } PHAST_CATCH_RC                                                                                                    \
+    size_t phast_planner_dwt##SFX##_workspace_min(const phast_planner_dwt##SFX *p) try {                                \
+        return p ? p->workspace_min() : 0;                                                                              \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_dwt##SFX##_coeff_len(const phast_planner_dwt##SFX *p) try {                                    \
+        return p ? p->coeff_len() : 0;                                                                                  \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_dwt##SFX##_level_len(const phast_planner_dwt##SFX *p, size_t level) try {                      \
+        return p ? p->level_len(level) : 0;                                                                             \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_dwt##SFX##_level_offset(const phast_planner_dwt##SFX *p, size_t level) try {                   \
+        return p ? p->level_offset(level) : 0;                                                                          \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    size_t phast_planner_dwt##SFX##_tile(const phast_planner_dwt##SFX *p) try {                                         \
+        return p ? p->geom.tile : 0;                                                                                    \
+    } PHAST_CATCH_ZERO                                                                                                  \
+    int phast_planner_dwt##SFX##_time_stages(const phast_planner_dwt##SFX *p, T *d_signal, T *d_coeffs, size_t batch,   \
+                                             T *d_work, size_t work_len, int reps, float *stage_ms, void *stream) try { \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->time_stages(d_signal, d_coeffs, batch, d_work, work_len, reps, stage_ms,                              \
+                              static_cast<hipStream_t>(stream));                                                        \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_wavedec_##FS##_with_planner(const T *signal, size_t signal_len, T *coeffs, size_t coeff_len,              \
+                                          const phast_planner_dwt##SFX *p) try {                                        \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(false, signal, signal_len, coeffs, coeff_len);                                                   \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_waverec_##FS##_with_planner(const T *coeffs, size_t coeff_len, T *signal, size_t signal_len,              \
+                                          const phast_planner_dwt##SFX *p) try {                                        \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->host(true, coeffs, coeff_len, signal, signal_len);                                                    \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_wavedec_##FS##_dev(const T *d_signal, T *d_coeffs, size_t signal_len, size_t batch, size_t sig_dist,      \
+                                 size_t coeff_dist, const phast_planner_dwt##SFX *p, T *d_work, size_t work_len,        \
+                                 void *stream) try {                                                                    \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(false, const_cast<T *>(d_signal), d_coeffs, signal_len, batch, sig_dist, coeff_dist, d_work,      \
+                      work_len, static_cast<hipStream_t>(stream));                                                      \
+    } PHAST_CATCH_RC                                                                                                    \
+    int phast_waverec_##FS##_dev(const T *d_coeffs, T *d_signal, size_t signal_len, size_t batch, size_t coeff_dist,    \
+                                 size_t sig_dist, const phast_planner_dwt##SFX *p, T *d_work, size_t work_len,          \
+                                 void *stream) try {                                                                    \
+        if (!p) return PHAST_ERR_INVALID_ARG;                                                                           \
+        return p->dev(true, d_signal, const_cast<T *>(d_coeffs), signal_len, batch, sig_dist, coeff_dist, d_work,       \
+                      work_len, static_cast<hipStream_t>(stream));                                                      \
+    } PHAST_CATCH_RC
+PHAST_DWT_API(64, f64, double)
+PHAST_DWT_API(32, f32, float)
 
 // The polyphase filter-bank channelizer (planner_channelizer.hpp): every argument rule, a wrong length and a signal whose
 // planes do not match the planner come back before the device is touched

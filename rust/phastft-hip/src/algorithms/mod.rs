@@ -12,6 +12,7 @@ pub mod resample;
 pub mod channelizer;
 pub mod synthesizer;
 pub mod cwt;
+pub mod dwt;
 pub mod lomb;
 pub mod nufft;
 pub mod nufft2d;

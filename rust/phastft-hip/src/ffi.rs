@@ -795,6 +795,49 @@ extern "C" {
         in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
     pub(crate) fn phast_c2r_fft_f32_nd_dev(ire: *const f32, iim: *const f32, out: *mut f32, n_total: usize, batch: usize,
         in_dist: usize, out_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    // the discrete wavelet transform and its inverse
+    pub(crate) fn phast_planner_dwt64_new(signal_len: usize, dec_lo: *const f64, dec_hi: *const f64, rec_lo: *const f64, rec_hi: *const f64,
+        filter_len: usize, level: usize, mode: c_int, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_dwt64_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_dwt64_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_dwt64_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_dwt64_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_dwt64_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_dwt64_coeff_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_dwt64_level_len(p: *const Opaque, level: usize) -> usize;
+    pub(crate) fn phast_planner_dwt64_level_offset(p: *const Opaque, level: usize) -> usize;
+    pub(crate) fn phast_planner_dwt64_tile(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_dwt64_time_stages(p: *const Opaque, signal: *mut f64, coeffs: *mut f64, batch: usize, work: *mut f64, work_len: usize,
+        reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_wavedec_f64_with_planner(signal: *const f64, signal_len: usize, coeffs: *mut f64, coeff_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_waverec_f64_with_planner(coeffs: *const f64, coeff_len: usize, signal: *mut f64, signal_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_wavedec_f64_dev(signal: *const f64, coeffs: *mut f64, signal_len: usize, batch: usize, sig_dist: usize,
+        coeff_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_waverec_f64_dev(coeffs: *const f64, signal: *mut f64, signal_len: usize, batch: usize, coeff_dist: usize,
+        sig_dist: usize, planner: *const Opaque, work: *mut f64, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_planner_dwt32_new(signal_len: usize, dec_lo: *const f32, dec_hi: *const f32, rec_lo: *const f32, rec_hi: *const f32,
+        filter_len: usize, level: usize, mode: c_int, out: *mut *mut Opaque) -> c_int;
+    pub(crate) fn phast_planner_dwt32_free(p: *mut Opaque);
+    pub(crate) fn phast_planner_dwt32_describe(p: *const Opaque, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub(crate) fn phast_planner_dwt32_device_bytes(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_dwt32_workspace_len(p: *const Opaque, batch: usize) -> usize;
+    pub(crate) fn phast_planner_dwt32_workspace_min(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_dwt32_coeff_len(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_dwt32_level_len(p: *const Opaque, level: usize) -> usize;
+    pub(crate) fn phast_planner_dwt32_level_offset(p: *const Opaque, level: usize) -> usize;
+    pub(crate) fn phast_planner_dwt32_tile(p: *const Opaque) -> usize;
+    pub(crate) fn phast_planner_dwt32_time_stages(p: *const Opaque, signal: *mut f32, coeffs: *mut f32, batch: usize, work: *mut f32, work_len: usize,
+        reps: c_int, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_wavedec_f32_with_planner(signal: *const f32, signal_len: usize, coeffs: *mut f32, coeff_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_waverec_f32_with_planner(coeffs: *const f32, coeff_len: usize, signal: *mut f32, signal_len: usize,
+        planner: *const Opaque) -> c_int;
+    pub(crate) fn phast_wavedec_f32_dev(signal: *const f32, coeffs: *mut f32, signal_len: usize, batch: usize, sig_dist: usize,
+        coeff_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn phast_waverec_f32_dev(coeffs: *const f32, signal: *mut f32, signal_len: usize, batch: usize, coeff_dist: usize,
+        sig_dist: usize, planner: *const Opaque, work: *mut f32, work_len: usize, stream: *mut c_void) -> c_int;
 }
 
 /// Re-raises a library status as the reference's panic: `phast_strerror` returns the exact text of the

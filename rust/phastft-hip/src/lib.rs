@@ -88,6 +88,12 @@ pub use planner::{PlannerSynthesizer32, PlannerSynthesizer64};
 // the continuous wavelet transform and the analytic signal (an extension beyond PhastFT 0.3.0)
 pub use algorithms::cwt::{cwt_32_dev, cwt_32_with_planner, cwt_64_dev, cwt_64_with_planner};
 pub use planner::{CwtFamily, CwtNorm, PlannerCwt32, PlannerCwt64};
+// the discrete wavelet transform and its inverse (an extension beyond PhastFT 0.3.0)
+pub use algorithms::dwt::{
+    wavedec_f32_dev, wavedec_f32_with_planner, wavedec_f64_dev, wavedec_f64_with_planner, waverec_f32_dev, waverec_f32_with_planner,
+    waverec_f64_dev, waverec_f64_with_planner,
+};
+pub use planner::{DwtMode, PlannerDwt32, PlannerDwt64};
 // overlap-save convolution and correlation of real signals (an extension beyond PhastFT 0.3.0)
 pub use algorithms::conv::{conv_f32_dev, conv_f32_with_planner, conv_f64_dev, conv_f64_with_planner};
 pub use planner::{ConvMode, PlannerConv32, PlannerConv64};

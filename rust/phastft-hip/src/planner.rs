@@ -581,6 +581,86 @@ impl_planner_upfirdn!(PlannerUpfirdn64, f64, phast_planner_upfirdn64_new, phast_
 impl_planner_upfirdn!(PlannerUpfirdn32, f32, phast_planner_upfirdn32_new, phast_planner_upfirdn32_free, phast_planner_upfirdn32_out_len,
                       phast_planner_upfirdn32_full_len, phast_planner_upfirdn32_tile, phast_planner_upfirdn32_chunk);
 
+/// The extension of a discrete wavelet planner (PyWavelets' modes of the same names; `smooth`, `antisymmetric` and
+/// `antireflect` are out of scope)
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum DwtMode {
+    Zero = 0,
+    Constant = 1,
+    Symmetric = 2,
+    Reflect = 3,
+    Periodic = 4,
+    Periodization = 5,
+}
+
+macro_rules! impl_planner_dwt {
+    ($dw:ident, $t:ty, $new:ident, $free:ident, $coeff_len:ident, $level_len:ident, $level_offset:ident, $tile:ident, $ws_len:ident,
+     $ws_min:ident) => {
+        /// An extension beyond PhastFT 0.3.0: the discrete wavelet transform of real signals of `signal_len` samples and its
+        /// inverse (pywt.wavedec / waverec) with `level` levels: four filters of one even length 2 ..= 256, used as given.  A
+        /// signal's result is the packed row [cA_J | cD_J | .. | cD_1] of `coeff_len()` elements.  One direct kernel launch per
+        /// level; the bits of a coefficient depend on the filters, the mode and the values alone.  Immutable after `new`.
+        pub struct $dw {
+            pub(crate) h: *mut Opaque,
+            pub(crate) signal_len: usize,
+        }
+        // SAFETY: the handle is immutable after creation; a call works in the caller's buffers (device calls) or in device
+        // buffers of its own (host-slice calls)
+        unsafe impl Send for $dw {}
+        unsafe impl Sync for $dw {}
+        impl $dw {
+            /// Panics with "invalid argument" unless 1 <= signal_len <= 2^29, the four filters have one even length 2 ..= 256
+            /// and 1 <= level <= 32 (more levels than floor(log2(signal_len / (F - 1))) are legal)
+            pub fn new(signal_len: usize, dec_lo: &[$t], dec_hi: &[$t], rec_lo: &[$t], rec_hi: &[$t], level: usize, mode: DwtMode) -> Self {
+                assert!(dec_hi.len() == dec_lo.len() && rec_lo.len() == dec_lo.len() && rec_hi.len() == dec_lo.len(), "invalid argument");
+                let mut h = std::ptr::null_mut();
+                ffi::check(unsafe {
+                    ffi::$new(signal_len, dec_lo.as_ptr(), dec_hi.as_ptr(), rec_lo.as_ptr(), rec_hi.as_ptr(), dec_lo.len(), level, mode as c_int, &mut h)
+                });
+                Self { h, signal_len }
+            }
+            pub fn signal_len(&self) -> usize {
+                self.signal_len
+            }
+            /// elements of a packed row: n_J + the sum of n_l
+            pub fn coeff_len(&self) -> usize {
+                unsafe { ffi::$coeff_len(self.h) }
+            }
+            /// n_l for 0 <= l <= J (n_0 = signal_len)
+            pub fn level_len(&self, level: usize) -> usize {
+                unsafe { ffi::$level_len(self.h, level) }
+            }
+            /// where cD_l starts in the packed row, 1 <= l <= J (cA_J starts at 0)
+            pub fn level_offset(&self, level: usize) -> usize {
+                unsafe { ffi::$level_offset(self.h, level) }
+            }
+            /// coefficient indices / output pairs per workgroup
+            pub fn tile(&self) -> usize {
+                unsafe { ffi::$tile(self.h) }
+            }
+            /// elements of T a device call of `batch` signals works in: two ping-pong rows per signal, 0 for one level
+            pub fn workspace_len(&self, batch: usize) -> usize {
+                unsafe { ffi::$ws_len(self.h, batch) }
+            }
+            /// the least a device call runs in (one signal's rows)
+            pub fn workspace_min(&self) -> usize {
+                unsafe { ffi::$ws_min(self.h) }
+            }
+        }
+        impl Drop for $dw {
+            fn drop(&mut self) {
+                unsafe { ffi::$free(self.h) }
+            }
+        }
+    };
+}
+impl_planner_dwt!(PlannerDwt64, f64, phast_planner_dwt64_new, phast_planner_dwt64_free, phast_planner_dwt64_coeff_len,
+                  phast_planner_dwt64_level_len, phast_planner_dwt64_level_offset, phast_planner_dwt64_tile,
+                  phast_planner_dwt64_workspace_len, phast_planner_dwt64_workspace_min);
+impl_planner_dwt!(PlannerDwt32, f32, phast_planner_dwt32_new, phast_planner_dwt32_free, phast_planner_dwt32_coeff_len,
+                  phast_planner_dwt32_level_len, phast_planner_dwt32_level_offset, phast_planner_dwt32_tile,
+                  phast_planner_dwt32_workspace_len, phast_planner_dwt32_workspace_min);
+
 macro_rules! impl_planner_resample {
     ($rs:ident, $new:ident, $free:ident, $ws_len:ident, $ws_min:ident) => {
         /// An extension beyond PhastFT 0.3.0: scipy.signal.resample(x, num) of real signals of `signal_len` samples (Fourier
